@@ -7,12 +7,16 @@ HBM: 1,048,576 Gaussians rendered to 1024x1024, 5 channels. With N>1 GPUs each r
 view of the same Gaussians (view-sharded data parallelism) and a step additionally
 all-reduces the 56 B/Gaussian parameter-gradient buffer over RCCL. value = views/s over the whole job.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times exactly --steps steps and prints the line: value, ms_per_step, config, pipeline
+(algorithmic bytes over the step time), host (per-step host intervals of the timed region) and, with N ranks, exchange.
+--dump-outputs DIR writes what the last timed step returned to its caller (see dump_outputs).
+
+Extra objects in the JSON line, measured only with --full:
   roofline      — dominant kernel (render_bwd): algorithmic bytes (52 B/pair + 32 B/pixel)
                   / its mean HIP-event duration on the launch stream, vs the 8 TB/s HBM peak; `traffic` = its HBM bytes per
                   launch counted IN THIS RUN by two `rocprofv3 --pmc` child runs (live_traffic; --no-live-traffic skips them,
                   the committed profile of the same kernel sources is the fallback)
-  host          — kernel sum against step time, and the per-step host intervals of the timed region (median / min / max)
+  host          — kernel sum against step time (the per-step host intervals of the timed region are in every run)
   regimes       — the same step at trained opacities, opacity 0.1, 2048^2 and 2 M Gaussians (median of three 20-step windows)
   train_iter*   — the synthetic 3-render training iteration (torch ops / fused / graphs / parallel branches / altitude-only sun)
   train_example — examples/train_synthetic.py at this size: the reference's whole iteration with its shipped configuration
@@ -65,6 +69,11 @@ def parse():
     ap.add_argument("--gaussians", type=int, default=1 << 20)
     ap.add_argument("--size", type=int, default=1024)
     ap.add_argument("--opacity", default="init", help="init (0.01, gs_config/train.yaml:55) | trained | float | surface (the trained-scene shape, synthetic.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel groups and rooflines, the training "
+                         "iterations, graph replays, regimes, the other workloads' comparisons and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (image, radii, gradients) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-iter", action="store_true", help="skip the extra synthetic training-iteration measurement")
     ap.add_argument("--force-dist", action="store_true",
@@ -88,7 +97,10 @@ def parse():
                     help="N ranks: also report the training iteration with its compute recorded into a HIP graph (opt-in)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher self-test: ranks rendezvous over gloo, all-reduce one number and exit before any GPU call")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def graph_extras(a):
@@ -1036,6 +1048,42 @@ def train_example_bench(P, S, iters=24):
     return out
 
 
+DUMP_ROWS = 1 << 18     # per-Gaussian arrays: at most this many rows (20 floats each over the six arrays)
+DUMP_PIXELS = 1 << 20   # images: at most this many pixels per channel (1024 x 1024 whole)
+
+
+def _dump_sample(n, k, seed):
+    """Sorted indices of a fixed, seeded sample of k of range(n) (all of it when n <= k)."""
+    if n <= k:
+        return None
+    return torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+
+
+def dump_outputs(path, color, radii, invdepth, grads):
+    """--dump-outputs: what the caller of the timed step received from its last step, as float32 .npy files: the image
+    [5, H, W], the inverse-depth image [1, H, W], radii [P] and the gradients of the six inputs (means2D included). At
+    most 44 MiB in all: beyond DUMP_PIXELS pixels the images keep a fixed, seeded sample of pixel positions ([C, DUMP_PIXELS],
+    the same positions in every channel), beyond DUMP_ROWS Gaussians the per-Gaussian arrays a fixed, seeded sample of
+    rows (the same rows in every array). The inputs are seeded, so two runs with the same arguments can be compared."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    P = radii.shape[0]
+    rows = _dump_sample(P, DUMP_ROWS, 1)
+    pix = _dump_sample(color.shape[-2] * color.shape[-1], DUMP_PIXELS, 2)
+    out = {"color": color, "invdepth": invdepth, "radii": radii}
+    out.update({"grad_" + k: g for k, g in grads.items()})
+    for name, t in out.items():
+        if t is None:
+            continue
+        t = t.detach().to("cpu", torch.float32)
+        if t.dim() == 3 and pix is not None:  # an image
+            t = t.reshape(t.shape[0], -1)[:, pix]
+        elif t.dim() != 3 and rows is not None:  # per Gaussian
+            t = t[rows]
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
+
+
 def main():
     a = parse()
     # read by the HSA runtime when it initialises: must be in the environment before the first torch.cuda call
@@ -1099,12 +1147,12 @@ def main():
         else:
             for p in params.values():
                 p.grad = None
-        color, radii, _ = rast(params["means3D"], means2D, params["opacities"], colors_precomp=params["colors"],
-                               scales=params["scales"], rotations=params["rotations"])
+        color, radii, invdepth = rast(params["means3D"], means2D, params["opacities"], colors_precomp=params["colors"],
+                                      scales=params["scales"], rotations=params["rotations"])
         torch.autograd.backward([color], [dL])  # the loss gradient dL/dcolor is an input of the path
         if use_dist and exchange:
             bucket.finish()
-        return color
+        return color, radii, invdepth
 
     def fence():
         if use_dist:
@@ -1126,15 +1174,16 @@ def main():
         dist.all_reduce(ones)
         exchange = {"rccl_ranks": int(ones.item()), "bytes": int(bucket.flat.numel() * 4),
                     "bytes_per_gaussian": bucket.bytes_per_gaussian, "ipc_mode_legacy": os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY")}
-        # the collective alone (not overlapped with anything), max over ranks
-        fence()
-        t0 = time.perf_counter()
-        for _ in range(10):
-            dist.all_reduce(bucket.flat)
-        fence()
-        tt = torch.tensor([(time.perf_counter() - t0) / 10], device=dev, dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        exchange["allreduce_ms"] = float(tt.item()) * 1e3
+        if a.full:
+            # the collective alone (not overlapped with anything), max over ranks
+            fence()
+            t0 = time.perf_counter()
+            for _ in range(10):
+                dist.all_reduce(bucket.flat)
+            fence()
+            tt = torch.tensor([(time.perf_counter() - t0) / 10], device=dev, dtype=torch.float64)
+            dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+            exchange["allreduce_ms"] = float(tt.item()) * 1e3
         # How the exchange is issued is measured, not guessed: {all-reduce, reduce-scatter + all-gather} x Gaussian ranges
         # {1, 4} of the overlapped backward (ranges only with the all-reduce). Every rank times every candidate, the
         # clocks are combined with MAX over the ranks, so every rank picks the same one.
@@ -1173,40 +1222,47 @@ def main():
     for _ in range(a.warmup):
         step()
     fence()
-    # Timed region: EXACTLY a.steps steps. HIP events (inside the library, on the launch stream) bracket only the
+    # Timed region: EXACTLY a.steps steps. With --full, HIP events (inside the library, on the launch stream) bracket the
     # dominant kernel here — every bracket costs two event records of ~3.4 us of queue time, and bracketing all six
     # kernel groups slows the step by 5 %. The per-group breakdown is taken right after, outside the timed region.
-    slots = abi.profile_slot_names()
-    abi.profile_select(1 << slots.index("render_bwd"))
-    abi.profile_reset()
-    abi.profile_enable(1)
+    if a.full:
+        slots = abi.profile_slot_names()
+        abi.profile_select(1 << slots.index("render_bwd"))
+        abi.profile_reset()
+        abi.profile_enable(1)
     stamps = [0.0] * (a.steps + 1)  # host clock after each step's calls returned (no synchronisation: diagnostics only)
+    last = None
     t0 = stamps[0] = time.perf_counter()
     for i in range(a.steps):
-        step()
+        last = None  # (the previous step's outputs are released before the next step starts)
+        last = step()
         stamps[i + 1] = time.perf_counter()
     fence()
     dt = time.perf_counter() - t0
-    abi.profile_enable(0)
-    prof_timed = abi.profile()
-    abi.profile_select(0xFFFFFFFF)
-    abi.profile_reset()
-    abi.profile_enable(1)
-    for _ in range(a.steps):
-        step()
-    fence()
-    abi.profile_enable(0)
-    prof = abi.profile()
-    if prof_timed.get("render_bwd", (0, 0))[1]:
-        prof["render_bwd"] = prof_timed["render_bwd"]  # the live measurement over the timed region
+    color, radii, invdepth = last
+    if a.dump_outputs and rank == 0:
+        grads = {k: params[k].grad for k in names}
+        grads["means2D"] = means2D.grad
+        dump_outputs(a.dump_outputs, color, radii, invdepth, grads)
+    if a.full:
+        abi.profile_enable(0)
+        prof_timed = abi.profile()
+        abi.profile_select(0xFFFFFFFF)
+        abi.profile_reset()
+        abi.profile_enable(1)
+        for _ in range(a.steps):
+            step()
+        fence()
+        abi.profile_enable(0)
+        prof = abi.profile()
+        if prof_timed.get("render_bwd", (0, 0))[1]:
+            prof["render_bwd"] = prof_timed["render_bwd"]  # the live measurement over the timed region
     if use_dist:
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
 
-    # num_rendered of this rank's view, straight from the API's own bookkeeping
-    color = step()
-    torch.cuda.synchronize()
+    # num_rendered of this rank's view (the last timed step's), straight from the API's own bookkeeping
     # (num_rendered_exact: this forward's own counts; num_rendered may name a workspace sized from the previous forward)
     nr = int(getattr(color.grad_fn, "num_rendered_exact", getattr(color.grad_fn, "num_rendered", -1)))
     # the API's num_rendered packs both counts: (tile, Gaussian) record slots below, (32-px block, Gaussian) list entries
@@ -1214,79 +1270,80 @@ def main():
     R, R_entries = (nr & 0x7FFFFFFF, (nr >> 32) & 0x07FFFFFF) if nr >= 0 else (-1, -1)
 
     ti_dist = None
-    if use_dist and not a.no_train_iter:
+    if use_dist and a.full and not a.no_train_iter:
         # the iteration that can actually scale: three renders, ONE exchange, the optimizer step
         ti_dist = train_iteration(sc, P, H, W, dev, fused=True, dist=dist, view_seed=rank, algo=bucket.algo)
     ti_dist_graphed = None
-    if use_dist and not a.no_train_iter and a.graph_train_iter:
+    if use_dist and a.full and not a.no_train_iter and a.graph_train_iter:
         # opt-in (never part of the driver's line): the same iteration with its three renders, loss and backward passes
         # recorded into a HIP graph per rank; the exchange and the optimizer step stay outside
         ti_dist_graphed = train_iteration(sc, P, H, W, dev, fused=True, dist=dist, view_seed=rank, algo=bucket.algo, graphed=True)
     if rank == 0:
         ms_step = dt / a.steps * 1e3
-        kern = {k: ms / a.steps for k, (ms, n) in prof.items() if n}  # device ms per step of each kernel group
-        dom = max(kern, key=kern.get) if kern else None
         npx = H * W
-        # algorithmic bytes per launch group. Since round 3 the groups "binning" (count scan, entry expand,
-        # block sort) and "depth_sort" (per-block depth order + split into tile lists) together do the job the survey
-        # prices at 12 R + 2 x 24 R + 8 R (keys written, a two-pass sort of 12-byte pairs, ranges) and 64 P (the depth
-        # order): the figures stay the survey's, the split between the two groups follows what each kernel moves
-        # (16-byte entries: write + one sort pass; then 8-byte list items written once).
-        alg = {
-            "render_bwd": 52 * R + 32 * npx,
-            "render_fwd": 52 * R + 32 * npx,
-            "binning": 12 * R + 24 * R * 2 + 8 * R,
-            "preprocess_fwd": 104 * P,
-            "depth_sort": 4 * 16 * P,
-            "gaussian_bwd": 300 * P,
-        }
-        roof = None
-        live = {}
-        if dom:
-            ach = alg[dom] / (kern[dom] * 1e-3) / 1e9
-            # observed in this run (rocprofv3 --pmc children) where the profiler is there; else the committed profile of the
-            # same kernel sources; else null
-            live, live_note = ({}, "disabled") if (a.no_live_traffic or use_dist) else live_traffic(a)
-            traffic, tsrc = (live[dom], live_note) if dom in live else measured_traffic(dom, a)
-            roof = {"kernel": dom, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
-                    "algorithmic_bytes": alg[dom], "kernel_ms": kern[dom]}
-            valu = measured_valu(dom, a)
-            if valu:
-                # the bound this kernel really runs at: VALU issue. 1024 SIMDs x 2.4 GHz; a wave64 VALU instruction
-                # occupies its SIMD for 2.4 (all-VGPR fma/mul/add) to 4.2 cycles (SGPR operand, cmp, cndmask, DPP) and
-                # 8.5 for v_exp/v_rcp (tools/ubench.hip)
-                cyc = kern[dom] * 1e-3 * 2.4e9 * 1024 / valu
-                roof["valu_issue"] = {"valu_wave_insts": valu, "simd_cycles_per_valu_inst": cyc,
-                                      "floor_simd_cycles_per_inst": [2.4, 4.2],
-                                      "insts_per_pair": valu / max(R, 1)}
-                # the same kernel against the fp32 vector peak (157.3 TFLOP/s = 1024 SIMDs x 64 FLOP/clk x 2.4 GHz): every
-                # VALU wave-instruction counted as 64 lanes x 2 FLOP, i.e. an upper bound on useful work. The headline
-                # `frac` stays the HBM one, as the task prescribes.
-                tf = valu * 64 * 2 / (kern[dom] * 1e-3) / 1e12
-                # ... and against what the kernel's own instruction mix can issue at best: its trips timed as bare instruction
-                # SEQUENCES (tools/ubench.hip, profiles/r02_ubench.txt: 105 cycles per wave for the backward trip's 32 VALU
-                # + 2 SALU at 8 waves per SIMD, LDS traffic overlapped) = 3.3 SIMD-cycles per VALU instruction
-                floor_cyc = 105.0 / 32.0
-                roof["valu"] = {"bound": "valu", "achieved": tf, "peak": 157.3, "unit": "TFLOP/s", "frac": tf / 157.3,
-                                "issue_floor_simd_cycles_per_inst": floor_cyc, "frac_of_issue_floor": floor_cyc / cyc}
-                # the second pipe this kernel keeps busy: the LDS array (one per CU, 256 B per clock). SQ_LDS_IDX_ACTIVE = its
-                # active cycles summed over the CUs; against 256 CUs x the launch's duration at the nominal 2.4 GHz (the
-                # clock under this load is lower, DESIGN.md 2.8: the true share is higher). Round 5 found the backward at
-                # 0.65 of that (0.8 of its real clock) beside a VALU that never idles: its ds_read_b96 and ds_read2_b32 forms
-                # were costing twice their bytes.
-                lds_active, lds_conf = measured_valu(dom, a, "SQ_LDS_IDX_ACTIVE"), measured_valu(dom, a, "SQ_LDS_BANK_CONFLICT")
-                if lds_active:
-                    cu_cycles = 256 * kern[dom] * 1e-3 * 2.4e9
-                    roof["lds"] = {"lds_array_active_cycles": lds_active, "cu_cycles_at_2.4GHz": cu_cycles,
-                                   "frac_of_cu_cycles": lds_active / cu_cycles, "bank_conflict_cycles": lds_conf}
-        # every kernel group against the HBM roofline (the render kernels are VALU-issue-bound: DESIGN.md §4)
-        per_kernel = {}
-        for k, ms in kern.items():
-            if k in alg and ms > 0:
-                tr = live[k] if (dom and k in live) else measured_traffic(k, a)[0]
-                per_kernel[k] = {"algorithmic_bytes": alg[k], "achieved": alg[k] / (ms * 1e-3) / 1e9,
-                                 "frac": alg[k] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": tr}
+        if a.full:
+            kern = {k: ms / a.steps for k, (ms, n) in prof.items() if n}  # device ms per step of each kernel group
+            dom = max(kern, key=kern.get) if kern else None
+            # algorithmic bytes per launch group. Since round 3 the groups "binning" (count scan, entry expand,
+            # block sort) and "depth_sort" (per-block depth order + split into tile lists) together do the job the survey
+            # prices at 12 R + 2 x 24 R + 8 R (keys written, a two-pass sort of 12-byte pairs, ranges) and 64 P (the depth
+            # order): the figures stay the survey's, the split between the two groups follows what each kernel moves
+            # (16-byte entries: write + one sort pass; then 8-byte list items written once).
+            alg = {
+                "render_bwd": 52 * R + 32 * npx,
+                "render_fwd": 52 * R + 32 * npx,
+                "binning": 12 * R + 24 * R * 2 + 8 * R,
+                "preprocess_fwd": 104 * P,
+                "depth_sort": 4 * 16 * P,
+                "gaussian_bwd": 300 * P,
+            }
+            roof = None
+            live = {}
+            if dom:
+                ach = alg[dom] / (kern[dom] * 1e-3) / 1e9
+                # observed in this run (rocprofv3 --pmc children) where the profiler is there; else the committed profile of the
+                # same kernel sources; else null
+                live, live_note = ({}, "disabled") if (a.no_live_traffic or use_dist) else live_traffic(a)
+                traffic, tsrc = (live[dom], live_note) if dom in live else measured_traffic(dom, a)
+                roof = {"kernel": dom, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": ach / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
+                        "algorithmic_bytes": alg[dom], "kernel_ms": kern[dom]}
+                valu = measured_valu(dom, a)
+                if valu:
+                    # the bound this kernel really runs at: VALU issue. 1024 SIMDs x 2.4 GHz; a wave64 VALU instruction
+                    # occupies its SIMD for 2.4 (all-VGPR fma/mul/add) to 4.2 cycles (SGPR operand, cmp, cndmask, DPP) and
+                    # 8.5 for v_exp/v_rcp (tools/ubench.hip)
+                    cyc = kern[dom] * 1e-3 * 2.4e9 * 1024 / valu
+                    roof["valu_issue"] = {"valu_wave_insts": valu, "simd_cycles_per_valu_inst": cyc,
+                                          "floor_simd_cycles_per_inst": [2.4, 4.2],
+                                          "insts_per_pair": valu / max(R, 1)}
+                    # the same kernel against the fp32 vector peak (157.3 TFLOP/s = 1024 SIMDs x 64 FLOP/clk x 2.4 GHz): every
+                    # VALU wave-instruction counted as 64 lanes x 2 FLOP, i.e. an upper bound on useful work. The headline
+                    # `frac` stays the HBM one, as BASELINE.md prescribes.
+                    tf = valu * 64 * 2 / (kern[dom] * 1e-3) / 1e12
+                    # ... and against what the kernel's own instruction mix can issue at best: its trips timed as bare instruction
+                    # SEQUENCES (tools/ubench.hip, profiles/r02_ubench.txt: 105 cycles per wave for the backward trip's 32 VALU
+                    # + 2 SALU at 8 waves per SIMD, LDS traffic overlapped) = 3.3 SIMD-cycles per VALU instruction
+                    floor_cyc = 105.0 / 32.0
+                    roof["valu"] = {"bound": "valu", "achieved": tf, "peak": 157.3, "unit": "TFLOP/s", "frac": tf / 157.3,
+                                    "issue_floor_simd_cycles_per_inst": floor_cyc, "frac_of_issue_floor": floor_cyc / cyc}
+                    # the second pipe this kernel keeps busy: the LDS array (one per CU, 256 B per clock). SQ_LDS_IDX_ACTIVE = its
+                    # active cycles summed over the CUs; against 256 CUs x the launch's duration at the nominal 2.4 GHz (the
+                    # clock under this load is lower, DESIGN.md 2.8: the true share is higher). Round 5 found the backward at
+                    # 0.65 of that (0.8 of its real clock) beside a VALU that never idles: its ds_read_b96 and ds_read2_b32 forms
+                    # were costing twice their bytes.
+                    lds_active, lds_conf = measured_valu(dom, a, "SQ_LDS_IDX_ACTIVE"), measured_valu(dom, a, "SQ_LDS_BANK_CONFLICT")
+                    if lds_active:
+                        cu_cycles = 256 * kern[dom] * 1e-3 * 2.4e9
+                        roof["lds"] = {"lds_array_active_cycles": lds_active, "cu_cycles_at_2.4GHz": cu_cycles,
+                                       "frac_of_cu_cycles": lds_active / cu_cycles, "bank_conflict_cycles": lds_conf}
+            # every kernel group against the HBM roofline (the render kernels are VALU-issue-bound: DESIGN.md §4)
+            per_kernel = {}
+            for k, ms in kern.items():
+                if k in alg and ms > 0:
+                    tr = live[k] if (dom and k in live) else measured_traffic(k, a)[0]
+                    per_kernel[k] = {"algorithmic_bytes": alg[k], "achieved": alg[k] / (ms * 1e-3) / 1e9,
+                                     "frac": alg[k] / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": tr}
         pipe_bytes = 432 * P + 268 * R + 64 * npx
         pipe = {"algorithmic_bytes": pipe_bytes, "achieved": pipe_bytes / (ms_step * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                 "achievable_stream_GBps": HBM_ACHIEVABLE_GBS,
@@ -1302,30 +1359,34 @@ def main():
                        "gaussians": P, "height": H, "width": W, "num_rendered": R, "list_entries": R_entries,
                        "list_block_px": 32 if nr >= 0 and (nr >> 62) & 1 else 8,
                        "parallelism": f"view-dp{world}"},
-            "roofline": roof, "pipeline": pipe, "kernels_ms": kern, "kernel_rooflines": per_kernel,
+            "pipeline": pipe,
             "ramp_s": ramp_s,  # untimed clock ramp before the contract's warmup (a fresh box starts at idle clocks)
         }
-        # how much of the step the host adds on top of the kernels (launch gaps, the count readback), and how the forwards
-        # of the run obtained their counts (eogs2_amd/rasterizer.py: "hit" = queued whole on the previous forward's counts)
+        # how the forwards of the run obtained their counts (eogs2_amd/rasterizer.py: "hit" = queued whole on the previous
+        # forward's counts)
         from eogs2_amd import rasterizer as _rz
-        ksum = float(sum(kern.values()))
         # An eager forward blocks on its count readback (as the reference's does, rasterizer_impl.cu:284), so the host is never
         # more than one step ahead and a stall of the host idles the GPU: the per-step host intervals of the timed region say
         # whether `ms_per_step` is the steady state (median = mean) or carries a hiccup (max >> median).
         iv = sorted((stamps[i + 1] - stamps[i]) * 1e3 for i in range(a.steps))
-        line["host"] = {"kernel_sum_ms": ksum, "step_over_kernel_sum": ms_step / ksum if ksum > 0 else None,
-                        "count_readback": _rz.speculation_stats(),
+        line["host"] = {"count_readback": _rz.speculation_stats(),
                         "timed_step_intervals_ms": {"median": iv[len(iv) // 2], "min": iv[0], "max": iv[-1]} if iv else None}
+        if a.full:
+            line.update(roofline=roof, kernels_ms=kern, kernel_rooflines=per_kernel)
+            # how much of the step the host adds on top of the kernels (launch gaps, the count readback)
+            ksum = float(sum(kern.values()))
+            line["host"].update(kernel_sum_ms=ksum, step_over_kernel_sum=ms_step / ksum if ksum > 0 else None)
         if exchange is not None:
             exchange["backend"] = a.backend + (" (rehearsal: ranks share one GPU)" if a.share_gpu else "")
             line["exchange"] = exchange
             line["rccl_ranks"] = exchange["rccl_ranks"]
-            line["allreduce_ms"] = exchange["allreduce_ms"]
-        if use_dist and not a.no_train_iter:
+            if "allreduce_ms" in exchange:
+                line["allreduce_ms"] = exchange["allreduce_ms"]
+        if use_dist and a.full and not a.no_train_iter:
             line["train_iter_fused"] = ti_dist
             if ti_dist_graphed is not None:
                 line["train_iter_fused_graphed"] = ti_dist_graphed
-        if world == 1 and not use_dist and not a.no_train_iter:
+        if a.full and world == 1 and not use_dist and not a.no_train_iter:
             line["train_iter"] = train_iteration(sc, P, H, W, dev, fused=False)
             line["train_iter_fused"] = train_iteration(sc, P, H, W, dev, fused=True)
             line["train_iter_fused_sun_altitude_only"] = train_iteration(sc, P, H, W, dev, fused=True, sun_altitude_only=True)
@@ -1344,7 +1405,7 @@ def main():
             line["resample"] = resample_bench(abi, dev, H, W)
             line["shade"] = shade_bench(abi, dev, H, W)
             line["tsdf"] = tsdf_bench(abi, dev)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(P, H)
         print(json.dumps(line), flush=True)
     if use_dist:

@@ -11,14 +11,18 @@ constructors and every statement of `RangeImageEOGS.__init__ / reconstruct_norma
 (tsdf.py:186-368) and `TSDFVolume.__init__ / integrate / update_tsdf` (:374-520) run unmodified, in fp32, as the reference
 runs them. Stored per case: the volume's constructor results (voxel counts, the three axes), per view the affine model, the
 altitude image and the weights `get_weights()` returned, `sample_sdf` at the voxel centres, and both volumes after every view.
+MKL runs its CPU-independent code path (MKL_CBWR=COMPATIBLE, as tests/test_tsdf_oracle.py does): otherwise the fp32 F.linear /
+linalg.inv results depend on the instruction set MKL picks for the host (AVX-512 and AVX2 round them differently).
 """
 import importlib.util
 import os
 import sys
 import types
 
-import numpy as np
-import torch
+os.environ["MKL_CBWR"] = "COMPATIBLE"  # before torch loads MKL
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 REFROOT = "/root/reference/src/gaussiansplatting"
 OUT = os.path.dirname(os.path.abspath(__file__))

@@ -19,7 +19,7 @@ def test_two_rank_bench_rehearsal():
         pytest.skip("needs a GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
-                        "--steps", "4", "--warmup", "1", "--gaussians", "30000", "--size", "160"],
+                        "--steps", "4", "--warmup", "1", "--gaussians", "30000", "--size", "160", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -75,13 +75,13 @@ def test_two_rank_bench_under_torchrun():
 
 
 def test_one_gpu_bench_line_and_its_graph_extras():
-    """The driver's own command at a small size: ONE JSON line with the contract's keys, `roofline` and `host`, and — from
-    the child process bench.py starts after its own measurements — the graph-replay figures beside the eager ones."""
+    """The driver's own command at a small size with --full: ONE JSON line with the contract's keys, `roofline` and `host`,
+    and — from the child process bench.py starts after its own measurements — the graph-replay figures beside the eager ones."""
     if not torch.cuda.is_available():
         pytest.skip("needs a GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-                        "--gaussians", "30000", "--size", "160", "--no-cpu-baseline"], env=env, capture_output=True,
+                        "--gaussians", "30000", "--size", "160", "--no-cpu-baseline", "--full"], env=env, capture_output=True,
                        text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -117,7 +117,7 @@ def test_two_rank_training_iteration_with_the_compute_as_a_graph():
         pytest.skip("needs a GPU")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
-                        "--steps", "4", "--warmup", "1", "--gaussians", "30000", "--size", "160", "--graph-train-iter"],
+                        "--steps", "4", "--warmup", "1", "--gaussians", "30000", "--size", "160", "--graph-train-iter", "--full"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

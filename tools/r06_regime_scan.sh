@@ -4,7 +4,7 @@
 # Output: gpurun_out/r06_regime_scan.txt
 OUT=gpurun_out/r06_regime_scan.txt; mkdir -p gpurun_out; : > $OUT
 run() {  # $1 = env assignments, $2 = bench args
-  env $1 python bench.py --no-cpu-baseline --no-train-iter --no-live-traffic --steps 60 $2 2>/dev/null | python -c "
+  env $1 python bench.py --full --no-cpu-baseline --no-train-iter --no-live-traffic --steps 60 $2 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d['config']; k=d['kernels_ms']
 print('%.3f blk %d tiles/G %.2f bl %.3f fwd %.3f bwd %.3f gb %.3f' % (d['ms_per_step'], c['list_block_px'], c['num_rendered']/c['gaussians'], k['depth_sort'], k['render_fwd'], k['render_bwd'], k['gaussian_bwd']))"
