@@ -730,7 +730,7 @@ __device__ inline uint32_t eighth_of(uint32_t a, uint32_t b) {
 template <int ST>
 __device__ __forceinline__ void tile_sched_body(const uint32_t* __restrict__ bpairs, const uint32_t* __restrict__ bcount,
                                                 const uint32_t* __restrict__ misc,
-                                                uint32_t nblocks, uint32_t lg, uint32_t flags, uint32_t* __restrict__ sched,
+                                                uint32_t nblocks, uint32_t lg, uint32_t* __restrict__ sched,
                                                 uint32_t* __restrict__ where) {
   constexpr int SCHED_ITEMS = (int)SCHED_MAX_BLOCKS / ST;
   __shared__ uint4 s_w[ST / 64];
@@ -770,7 +770,7 @@ __device__ __forceinline__ void tile_sched_body(const uint32_t* __restrict__ bpa
   // pairs of a block beyond which its tiles have saturated: 16 tiles x SCHED_K / (mean pair opacity), the mean pair opacity
   // being sum(round(64 opacity)) / (64 pairs) over the listed pairs (misc[MISC_OPW], written by the count scan)
   const float opw = (float)misc[MISC_OPW_LO] + 4294967296.0f * (float)misc[MISC_OPW_HI];
-  const float capf = (opw > 0.f && !(flags & 0x20u)) ? 16.0f * 64.0f * SCHED_K * (float)tot.x / opw : 4.0e9f;
+  const float capf = opw > 0.f ? 16.0f * 64.0f * SCHED_K * (float)tot.x / opw : 4.0e9f;
   const uint32_t cap = capf < 4.0e9f ? (uint32_t)capf : 0xFFFFFFFFu;
   // raw[] keeps the pairs; wk[] becomes the block's WORK: its pairs up to the cap
   uint32_t raw[SCHED_ITEMS];
@@ -800,7 +800,7 @@ __device__ __forceinline__ void tile_sched_body(const uint32_t* __restrict__ bpa
   // scene does not reach never saturate, its tiles walk their whole lists, and they are the launch's stragglers (wave traces
   // at trained opacities: tiles of 90-130 us among a mean of 37, profiles/r04_wave_trace.txt). They start FIRST, dealt one by one.
   const unsigned long long heavy_pairs = tot.x, heavy_n = tot.y;
-  const bool saturating = !(flags & 0x40u) && (unsigned long long)cap * heavy_n < heavy_pairs;
+  const bool saturating = (unsigned long long)cap * heavy_n < heavy_pairs;
   bool edge[SCHED_ITEMS];
   v = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
@@ -912,7 +912,7 @@ __global__ __launch_bounds__(T_, (NBITS <= 10 && T_ == 1024 ? ES_WAVES : 1)) voi
   constexpr uint32_t nb = 1u << NBITS, mask = nb - 1u;
   if constexpr (T_ == 1024 || T_ == 512) {
     if (sched_blocks && blockIdx.x == gridDim.x - 1) {  // the launch's extra workgroup: the tile schedule
-      tile_sched_body<T_>(bpairs, dtotal, misc, sched_blocks, sched_lg & 0xFFFFFFu, sched_lg >> 24, sched, where);  // (one pass: dtotal IS the per-block entry count)
+      tile_sched_body<T_>(bpairs, dtotal, misc, sched_blocks, sched_lg, sched, where);  // (one pass: dtotal IS the per-block entry count)
       return;
     }
   }
@@ -1055,7 +1055,7 @@ __global__ __launch_bounds__(SCHED_T) void tile_sched_kernel(const uint32_t* __r
                                                              const uint32_t* __restrict__ misc,
                                                              uint32_t nblocks, uint32_t lg, uint32_t* __restrict__ sched,
                                                              uint32_t* __restrict__ where) {
-  tile_sched_body<SCHED_T>(bpairs, bcount, misc, nblocks, lg & 0xFFFFFFu, lg >> 24, sched, where);
+  tile_sched_body<SCHED_T>(bpairs, bcount, misc, nblocks, lg, sched, where);
 }
 template <int NBITS>
 static void launch_entry_scatter_n(uint32_t nblk, hipStream_t s, const uint4* in, uint4* out, const uint32_t* misc, uint32_t cap,
@@ -1093,8 +1093,7 @@ void launch_entry_sort(const GeomWS& g, const SortWS& w, int P, int H, int W, hi
     hipLaunchKernelGGL(entry_colscan_kernel, dim3((mask + 64u) / 64u), dim3(ES_T), 0, s, w.hist, histp, g.misc, w.cap, mask + 1u,
                        passes == 1 ? g.bcount : w.dtotal, g.bpairs);
     // (one pass <=> at most SCHED_MAX_BLOCKS blocks) the render launches' tile schedule goes with this launch
-    // (lg travels with the experiment switches in its top byte)
-    const SchedArgs sa{g.bpairs, (passes == 1 && sched_enabled()) ? nblocks : 0u, sched_capacity(nblocks) | (sched_flags() << 24), g.sched, g.where};
+    const SchedArgs sa{g.bpairs, (passes == 1 && sched_enabled()) ? nblocks : 0u, sched_capacity(nblocks), g.sched, g.where};
     launch_entry_scatter(bits, w.nblk, s, in, out, g.misc, w.cap, shift, w.hist, passes == 1 ? g.bcount : w.dtotal, sa);
     const uint4* t = in; in = out; out = const_cast<uint4*>(t);
   }
@@ -1579,10 +1578,8 @@ void launch_block_lists(const GeomWS& g, const SortWS& w, const BinWS& b, const 
   // few hundred entries per block — large images: 4096 blocks at 2048^2 — sixteen waves mostly wait at barriers for one or two
   // busy ones, and only two such workgroups fit a CU. Lists longer than 4 x the workgroup stream through global memory (any
   // length is handled), so the thresholds leave room for the spread between blocks.
-  static const int forced = [] { const char* e = getenv("EOGS_BL_T"); return e ? atoi(e) : 0; }();  // tuning aid: 256 / 512 / 1024
   const double per_block = (double)nr_entries(R) / (double)nblocks;
-  int T = wide ? 1024 : per_block <= BL_NARROW_256 ? 256 : per_block <= BL_NARROW_512 ? 512 : 1024;
-  if (!wide && (forced == 256 || forced == 512 || forced == 1024)) T = forced;
+  const int T = wide ? 1024 : per_block <= BL_NARROW_256 ? 256 : per_block <= BL_NARROW_512 ? 512 : 1024;
   // (Round 6 tried eight entries per thread in workgroups of 256 / 512 threads — a quarter / half of the waves per barrier, four /
   // two blocks per CU at once, ids in LDS: 61 / 50 us against 48 at the headline, 139 / 66 against 64 at trained opacities:
   // profiles/r06_ab_block_lists_small_workgroups.txt. Not kept.)

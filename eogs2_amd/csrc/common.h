@@ -32,16 +32,8 @@
                                 // (64-byte slots with zero padding in rounds 1-2: a quarter of the backward's record traffic)
 static_assert(REC == 12, "record quarters");
 // Where quarter q (16 bytes) of the record in slot `slot` lives, in float4 units: record-major (a record's 48 bytes side by
-// side). -DEOGS_REC_SOA=1 builds the quarter-major alternative — three planes of `plane` = capacity slots — tried in round 4 on
-// the idea that gaussian_bwd's lanes (one Gaussian each, its records 48 x tiles-per-Gaussian bytes from the neighbour lane's)
-// would coalesce better 16 x tiles apart: measured WORSE (gaussian_bwd 0.094 -> 0.111 ms, render_bwd 0.288 -> 0.300: a lane's
-// three quarters then sit in three cache lines instead of one or two; profiles/r04_experiments/ab_rec_soa.txt). Kept as a switch.
-#ifndef EOGS_REC_SOA
-#define EOGS_REC_SOA 0
-#endif
-__host__ __device__ inline size_t rec_q(size_t slot, int q, size_t plane, int quarters) {
-  return EOGS_REC_SOA ? (size_t)q * plane + slot : slot * (size_t)quarters + (size_t)q;
-}
+// side). Quarter-major planes measured worse in round 4: profiles/r04_experiments/ab_rec_soa.txt.
+__host__ __device__ inline size_t rec_q(size_t slot, int q, int quarters) { return slot * (size_t)quarters + (size_t)q; }
 
 // ---- misc[] slots (u32) in the geometry workspace ----
 // Inclusive prefix sum over the 64 lanes of a wave on the DPP path: row_shr 1, 2, 4, 8 inside each row of 16 lanes, then the
@@ -118,13 +110,6 @@ __host__ __device__ inline bool noflag_scene(uint32_t opw_lo, uint32_t opw_hi, i
 // An XCD's sequence holds up to 1.25 x its fair share of the blocks (+1): the equal-work cut gives an XCD whose blocks are
 // light more of them; what exceeds the capacity spills into the other XCDs' free places.
 static inline uint32_t sched_capacity(uint32_t nblocks) { return (nblocks + 7u) / 8u + (nblocks + 31u) / 32u + 1u; }
-static inline uint32_t sched_flags() {  // EOGS_SCHED_FLAGS: experiment switch of tile_sched_body (0x20 = no saturation cap), default 0
-  static const uint32_t v = [] {
-    const char* e = getenv("EOGS_SCHED_FLAGS");
-    return (uint32_t)(e ? strtoul(e, nullptr, 0) : 0ul) & 0xE0u;
-  }();
-  return v;
-}
 // EOGS_TILE_SCHED=0 switches the schedule off (A/B: the XCD band mapping of rounds 1-3)
 static inline bool sched_enabled() {
   static const bool v = [] {

@@ -575,10 +575,10 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
         const uint32_t q = q0 + (uint32_t)lane;
         const bool lv = q < n && (noflag || live[s0 + q] != 0);
         const uint32_t qq = q < n ? q : 0u;  // a valid address either way
-        const float4 ra = r4c[rec_q((size_t)s0 + qq, 0, cap_slots, RQc)];
-        const float4 rb = r4c[rec_q((size_t)s0 + qq, 1, cap_slots, RQc)];
+        const float4 ra = r4c[rec_q((size_t)s0 + qq, 0, RQc)];
+        const float4 rb = r4c[rec_q((size_t)s0 + qq, 1, RQc)];
         float3 rc = make_float3(0.f, 0.f, 0.f);
-        if (!ALT) rc = reinterpret_cast<const float3*>(r4c + rec_q((size_t)s0 + qq, 2, cap_slots, RQc))[0];
+        if (!ALT) rc = reinterpret_cast<const float3*>(r4c + rec_q((size_t)s0 + qq, 2, RQc))[0];
         if (lv) {  // (a dead pair's record is never-written memory: read, selected away)
           part[0] += ra.x; part[1] += ra.y; part[2] += ra.z; part[5] += ra.w;
           part[3] += rb.x; part[4] += rb.y;
@@ -603,7 +603,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
       // fixed-order sum of this Gaussian's (tile,Gaussian) records: deterministic, no atomics
       const uint32_t n = is_big ? 0u : n_all;
       const size_t s0 = (size_t)pb + bi1.y;  // Gaussian-id order: a wave reads one contiguous region
-      constexpr int RQ = (ALT ? REC_ALT : REC) / 4;  // quarters per record (common.h rec_q: quarter-major planes of cap_slots)
+      constexpr int RQ = (ALT ? REC_ALT : REC) / 4;  // quarters per record (common.h rec_q)
       const float4* r4 = reinterpret_cast<const float4*>(records);
       uint32_t q_first = 0;
       if (n <= dlim) {
@@ -622,9 +622,9 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
           lv[u] = false;
           if (u < n) {
             lv[u] = ((uint32_t)(fl4 >> (8u * u)) & 0xFFu) != 0u;
-            ra[u] = r4[rec_q(s0 + qq, 0, cap_slots, RQ)];
-            rb[u] = r4[rec_q(s0 + qq, 1, cap_slots, RQ)];
-            if (!ALT) rc[u] = reinterpret_cast<const float3*>(r4 + rec_q(s0 + qq, 2, cap_slots, RQ))[0];
+            ra[u] = r4[rec_q(s0 + qq, 0, RQ)];
+            rb[u] = r4[rec_q(s0 + qq, 1, RQ)];
+            if (!ALT) rc[u] = reinterpret_cast<const float3*>(r4 + rec_q(s0 + qq, 2, RQ))[0];
           }
         }
 #pragma unroll
@@ -678,16 +678,16 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
           for (int u = 0; u < NW; u++) {
             if (NW > 4 && u >= 4) {  // the wide trip's second half: only the lanes that have that many
               if (have[u]) {
-                ra[u] = r4[rec_q(s0 + q[u], 0, cap_slots, RQ)];
-                rb[u] = r4[rec_q(s0 + q[u], 1, cap_slots, RQ)];
-                if (!ALT) rc[u] = reinterpret_cast<const float3*>(r4 + rec_q(s0 + q[u], 2, cap_slots, RQ))[0];
+                ra[u] = r4[rec_q(s0 + q[u], 0, RQ)];
+                rb[u] = r4[rec_q(s0 + q[u], 1, RQ)];
+                if (!ALT) rc[u] = reinterpret_cast<const float3*>(r4 + rec_q(s0 + q[u], 2, RQ))[0];
               }
               continue;
             }
             const uint32_t qq = have[u] ? q[u] : q[0];  // a valid address either way
-            ra[u] = r4[rec_q(s0 + qq, 0, cap_slots, RQ)];
-            rb[u] = r4[rec_q(s0 + qq, 1, cap_slots, RQ)];
-            if (!ALT) rc[u] = reinterpret_cast<const float3*>(r4 + rec_q(s0 + qq, 2, cap_slots, RQ))[0];
+            ra[u] = r4[rec_q(s0 + qq, 0, RQ)];
+            rb[u] = r4[rec_q(s0 + qq, 1, RQ)];
+            if (!ALT) rc[u] = reinterpret_cast<const float3*>(r4 + rec_q(s0 + qq, 2, RQ))[0];
           }
 #pragma unroll
           for (int u = 0; u < NW; u++) {

@@ -46,14 +46,7 @@
 
 #pragma clang fp contract(fast)
 
-// Threads per render workgroup. A workgroup is nothing but RBLK / 64 independent tiles (no barriers, no shared data), and its
-// LDS and wave slots are only released when its LAST wave ends, while tiles have uneven lists: one tile = one wave = one
-// workgroup measured render_bwd 0.355 -> 0.329 ms, render_fwd 0.151 -> 0.144 ms, the block-list kernels -10 % / -3 %
-// against four tiles per workgroup. Every LDS address is a compile-time constant as well.
-#ifndef EOGS_RENDER_BLK
-#define EOGS_RENDER_BLK 64
-#endif
-#define RBLK EOGS_RENDER_BLK
+// One tile = one wave = one 64-thread workgroup: four tiles per workgroup measured slower (profiles/r02_v18).
 static_assert(SUBX == 8 && SUBY == 8 && PPL == 1, "render kernels are written for 8x8 internal tiles, one pixel per lane");
 
 namespace {
@@ -116,10 +109,10 @@ __device__ inline void wave_lds_sync() {
 //     last; the 16 tiles of a block are 16 consecutive workgroups of its XCD. The workgroup's descriptor — written by
 //     block_lists_kernel at the block's place in the schedule — holds the tile AND its list range: one 16-byte load where
 //     rounds 1-3 computed the tile and loaded ranges[tile]. Workgroups past an XCD's count, or on tiles outside the image, leave.
-//   * without one (images beyond 4096 blocks, or a forward that lists nothing): XCD x gets the contiguous run of tile groups
+//   * without one (images beyond 4096 blocks, or a forward that lists nothing): XCD x gets the contiguous run of tiles
 //     [x*per, (x+1)*per); gridDim.x is a multiple of 8; `range` is left for the caller to load.
 __device__ inline int tile_of_wave(const uint4* __restrict__ desc, const uint32_t* __restrict__ sched, int lg16, int gsx, uint2& range) {
-  if (RBLK == 64 && desc != nullptr) {
+  if (desc != nullptr) {
     const uint32_t x = blockIdx.x & 7u, i = blockIdx.x >> 3;
     const uint32_t cnt = sched[x];                          // (independent loads: one round trip)
     const uint4 d = desc[(size_t)x * (uint32_t)lg16 + i];
@@ -128,9 +121,7 @@ __device__ inline int tile_of_wave(const uint4* __restrict__ desc, const uint32_
     return (int)(d.x >> 16) * gsx + (int)(d.x & 0xFFFFu);
   }
   const int per = gridDim.x >> 3;
-  const int grp = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  // the wave index is uniform across the wave: tell the compiler, so tile, list range and loop control live in SGPRs
-  return grp * (RBLK / 64) + (RBLK == 64 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
+  return (blockIdx.x & 7) * per + (blockIdx.x >> 3);
 }
 
 // -DEOGS_WAVE_TRACE: per tile {start, end} of its wave on the constant-rate clock, the shader-clock ticks between them, and where
@@ -268,19 +259,19 @@ __device__ inline Ent fetch(const float* slab, int j) {
 }  // namespace
 
 template <int MACRO>
-__global__ __launch_bounds__(RBLK) void render_fwd_kernel(
+__global__ __launch_bounds__(64) void render_fwd_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ keys, const uint2* __restrict__ point_list, int W, int H, int gsx, int ntiles, int gmx, const uint4* __restrict__ desc, const uint32_t* __restrict__ sched, int lg16,
     const float4* __restrict__ packed, const float* __restrict__ bg,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
     float* __restrict__ out_invdepth, int opts) {
-  __shared__ __attribute__((aligned(16))) float s_slab[RBLK / 64][FWD_CAP * ENT];
-  __shared__ uint32_t s_pos[RBLK / 64][FWD_CAP];  // list position of every slab entry (what n_contrib counts)
+  __shared__ __attribute__((aligned(16))) float s_slab[FWD_CAP * ENT];
+  __shared__ uint32_t s_pos[FWD_CAP];  // list position of every slab entry (what n_contrib counts)
   const int lane = threadIdx.x & 63;
   uint2 range = make_uint2(0u, 0u);
   const int tile = tile_of_wave(desc, sched, lg16, gsx, range);
   if (tile >= ntiles) return;  // wave-uniform; waves never synchronise with each other
-  float* slab = s_slab[RBLK == 64 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
-  uint32_t* spos = s_pos[RBLK == 64 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))];
+  float* slab = s_slab;
+  uint32_t* spos = s_pos;
   const int px = (tile % gsx) * SUBX + (lane & 7), py = (tile / gsx) * SUBY + (lane >> 3);
   const bool inside = px < W && py < H;
   const uint32_t pix_id = (uint32_t)py * (uint32_t)W + (uint32_t)px;
@@ -429,7 +420,7 @@ __device__ inline void quad_append(uint32_t* sidx, int lane, bool hit, int pos, 
 // INVD = false: the caller passed no inverse-depth image (out_invdepth == NULL: the reference's render() drops that output,
 // gaussian_renderer/renderer.py:101,126) — its multiply-add per evaluated (pixel, entry) is left out, one of 22.
 template <int MACRO, bool ALT, bool INVD = true>
-__global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_FW, EOGS_FW))) void render_fwd_quad_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EOGS_FW, EOGS_FW))) void render_fwd_quad_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ keys, const uint2* __restrict__ point_list, int W, int H, int gsx, int ntiles, int gmx, const uint4* __restrict__ desc, const uint32_t* __restrict__ sched, int lg16,
     const float4* __restrict__ packed, const float* __restrict__ bg,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ out_color,
@@ -437,16 +428,15 @@ __global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_FW, E
   static_assert(MACRO == 1, "quad sub-lists run on per-tile lists: every chunk of 64 list entries is processed at once");
   // slab position FQ_CAP holds a DUMMY entry (opacity 0: alpha = 0 fails the 1/255 test at every pixel); sub-lists
   // shorter than the longest one are padded with it, so the hot loop needs no "is my quad still active" test
-  __shared__ __attribute__((aligned(16))) float s_slab[RBLK / 64][(FQ_CAP + 1) * ENT];
-  __shared__ __attribute__((aligned(16))) uint32_t s_idx[RBLK / 64][4 * QCAP];
+  __shared__ __attribute__((aligned(16))) float s_slab[(FQ_CAP + 1) * ENT];
+  __shared__ __attribute__((aligned(16))) uint32_t s_idx[4 * QCAP];
   const int lane = threadIdx.x & 63;
   uint2 range = make_uint2(0u, 0u);
   const int tile = tile_of_wave(desc, sched, lg16, gsx, range);
   if (tile >= ntiles) return;  // wave-uniform; waves never synchronise with each other
   WTRACE_BEGIN;
-  const int w = RBLK == 64 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  float* slab = s_slab[w];
-  uint32_t* sidx = s_idx[w];
+  float* slab = s_slab;
+  uint32_t* sidx = s_idx;
   if (lane < ENT) slab[FQ_CAP * ENT + lane] = 0.f;
   int ox, oy;
   quad_pixel(lane, ox, oy);
@@ -651,11 +641,10 @@ static double quad_switch() {
 
 // grid of a render launch: with a tile schedule 8 XCD sequences x lg blocks x 16 tiles, else the tiles rounded up to a multiple of 8
 // (a forward that lists nothing has built no descriptors: launch_block_lists returned before its kernel)
-static inline const uint4* render_desc(const ImgWS& im, int64_t R) { return (RBLK == 64 && nr_entries(R) > 0) ? im.desc : nullptr; }
+static inline const uint4* render_desc(const ImgWS& im, int64_t R) { return nr_entries(R) > 0 ? im.desc : nullptr; }
 static inline uint32_t render_grid(int ntiles, const ImgWS& im, int64_t R) {
   if (render_desc(im, R)) return 8u * 16u * im.sched_lg;
-  const uint32_t groups = ceil_div_u32((uint64_t)ntiles, RBLK / 64);
-  return ((groups + 7u) / 8u) * 8u;  // multiple of 8 for the XCD band mapping
+  return ((uint32_t)ntiles + 7u) / 8u * 8u;  // multiple of 8 for the XCD band mapping
 }
 
 int render_fwd_variant(int block, int64_t R, int P) {
@@ -671,7 +660,7 @@ void launch_render_fwd(const GeomWS& g, const BinWS& b, const ImgWS& im, int P, 
   auto* kern = variant == 1 ? render_fwd_kernel<BLOCK_BIG> : (variant == 2 ? (nr_alt(R) ? render_fwd_quad_kernel<1, true> : (out_invdepth ? render_fwd_quad_kernel<1, false> : render_fwd_quad_kernel<1, false, false>)) : render_fwd_kernel<1>);
   // (the quad forward leaves its quad masks for the backward in BinWS::qmask, handed over in place of the keys it does not read)
   const uint32_t* keys = variant == 2 ? reinterpret_cast<const uint32_t*>(b.qmask) : b.sorted_keys;
-  hipLaunchKernelGGL(kern, dim3(render_grid(ntiles, im, R)), dim3(RBLK), 0, s, im.ranges, keys, b.point_list, W, H, gsx,
+  hipLaunchKernelGGL(kern, dim3(render_grid(ntiles, im, R)), dim3(64), 0, s, im.ranges, keys, b.point_list, W, H, gsx,
                      ntiles, (int)macro_grid_x(W, b.block), render_desc(im, R), g.sched, (int)(16u * im.sched_lg), g.packed, bg, im.final_T, im.n_contrib,
                      out_color, out_invdepth, render_opts());
 }
@@ -745,7 +734,7 @@ __device__ inline void group8_sum11(float (&c)[11]) {
 // survived), so a round may span several list chunks.
 __device__ inline void transpose_round(int nsurv, int lane, const float* rb, const float* s_u, const float* s_v,
                                        const float* s_pix, float bx0, float by0, float kx, float ky,
-                                       float* __restrict__ records, uint8_t* __restrict__ live_flag, uint32_t rec_plane) {
+                                       float* __restrict__ records, uint8_t* __restrict__ live_flag) {
   const int k = lane >> 3, o = lane & 7;
   const bool live = k < nsurv;
   const float4 q0 = *reinterpret_cast<const float4*>(rb + k * 8);      // gx gy A B
@@ -779,9 +768,9 @@ __device__ inline void transpose_round(int nsurv, int lane, const float* rb, con
     const float ho = -0.5f * op;
     const uint32_t slot = __float_as_uint(q1.z);
     float4* r4 = reinterpret_cast<float4*>(records);  // layout: common.h REC, rec_q
-    r4[rec_q(slot, 0, rec_plane, REC / 4)] = make_float4(m2x, m2y, ho * acc[3], acc[0]);
-    r4[rec_q(slot, 1, rec_plane, REC / 4)] = make_float4(ho * acc[4], ho * acc[5], acc[6], acc[7]);
-    reinterpret_cast<float3*>(r4 + rec_q(slot, 2, rec_plane, REC / 4))[0] = make_float3(acc[8], acc[9], acc[10]);
+    r4[rec_q(slot, 0, REC / 4)] = make_float4(m2x, m2y, ho * acc[3], acc[0]);
+    r4[rec_q(slot, 1, REC / 4)] = make_float4(ho * acc[4], ho * acc[5], acc[6], acc[7]);
+    reinterpret_cast<float3*>(r4 + rec_q(slot, 2, REC / 4))[0] = make_float3(acc[8], acc[9], acc[10]);
     live_flag[slot] = 1;  // pairs that never get here keep the 0 of the memset and are skipped by gaussian_bwd
   }
 }
@@ -802,28 +791,27 @@ __device__ inline Peek peek_cand_r(uint32_t k, uint32_t begin, uint32_t end, con
 // positions of the list the wave walks, render_fwd_kernel — and every eight surviving entries are transposed (transpose_round);
 // a round may span chunks.
 template <int MACRO, bool HAVE_INV>
-__global__ __launch_bounds__(RBLK) void render_bwd_kernel(
+__global__ __launch_bounds__(64) void render_bwd_kernel(
     const uint2* __restrict__ ranges, const uint32_t* __restrict__ keys, const uint2* __restrict__ point_list, int W, int H, int gsx, int ntiles, int gmx, const uint4* __restrict__ desc, const uint32_t* __restrict__ sched, int lg16,
     const float4* __restrict__ packed, const uint32_t* __restrict__ n_contrib, const float* __restrict__ final_T,
     const float* __restrict__ bg, const float* __restrict__ dL_dpix, const float* __restrict__ dL_dinv,
-    float* __restrict__ records, uint8_t* __restrict__ live_flag, uint32_t rec_plane) {
-  __shared__ __attribute__((aligned(16))) float s_slab[RBLK / 64][64 * ENT];
-  __shared__ __attribute__((aligned(16))) float s_round[RBLK / 64][KSURV * 8];
+    float* __restrict__ records, uint8_t* __restrict__ live_flag) {
+  __shared__ __attribute__((aligned(16))) float s_slab[64 * ENT];
+  __shared__ __attribute__((aligned(16))) float s_round[KSURV * 8];
   // u and v matrices of a wave sit UV_PITCH floats (a multiple of 64 dwords) apart: one ds_write2st64_b32 stores both
-  __shared__ __attribute__((aligned(16))) float s_uv[RBLK / 64][UV_PITCH + UV_SIZE];
-  __shared__ __attribute__((aligned(16))) float s_pix[RBLK / 64][64 * 8 + 32];
-  __shared__ uint32_t s_slot[RBLK / 64][64];
+  __shared__ __attribute__((aligned(16))) float s_uv[UV_PITCH + UV_SIZE];
+  __shared__ __attribute__((aligned(16))) float s_pix[64 * 8 + 32];
+  __shared__ uint32_t s_slot[64];
   const int lane = threadIdx.x & 63;
   uint2 range = make_uint2(0u, 0u);
   const int tile = tile_of_wave(desc, sched, lg16, gsx, range);
   if (tile >= ntiles) return;
-  const int w = RBLK == 64 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  float* slab = s_slab[w];
-  float* su = s_uv[w];
-  float* sv = s_uv[w] + UV_PITCH;
-  float* spix = s_pix[w];
-  uint32_t* sslot = s_slot[w];
-  float* rb = s_round[w];
+  float* slab = s_slab;
+  float* su = s_uv;
+  float* sv = s_uv + UV_PITCH;
+  float* spix = s_pix;
+  uint32_t* sslot = s_slot;
+  float* rb = s_round;
   const int tx0 = (tile % gsx) * SUBX, ty0 = (tile / gsx) * SUBY;
   const int px = tx0 + (lane & 7), py = ty0 + (lane >> 3);
   const bool inside = px < W && py < H;
@@ -930,7 +918,7 @@ __global__ __launch_bounds__(RBLK) void render_bwd_kernel(
       if (++k == KSURV) {
         stash(kstashed, KSURV);
         wave_lds_sync();
-        transpose_round(KSURV, lane, rb, su, sv, spix, bx0, by0, kx, ky, records, live_flag, rec_plane);
+        transpose_round(KSURV, lane, rb, su, sv, spix, bx0, by0, kx, ky, records, live_flag);
         wave_lds_sync();
         k = 0;
         kstashed = 0;
@@ -953,7 +941,7 @@ __global__ __launch_bounds__(RBLK) void render_bwd_kernel(
   }
   if (k) {  // the last, partial round
     wave_lds_sync();
-    transpose_round(k, lane, rb, su, sv, spix, bx0, by0, kx, ky, records, live_flag, rec_plane);
+    transpose_round(k, lane, rb, su, sv, spix, bx0, by0, kx, ky, records, live_flag);
   }
 }
 
@@ -981,31 +969,18 @@ namespace {
                   // against bank conflicts) in floats [0, 288), channel 4 at PIXB + pixel (read eight at a time: two ds_read_b128)
 #define STG 12    // floats per staged (trip, quad) partial: 11 used
 
-// Transposition of one round of `nk` trips (trips 8 r .. 8 r + nk - 1 of the chunk). ALT (altitude-only render): the one
+// Transposition of the `nk` trips of one round (the u / v matrices hold them). ALT (altitude-only render): the one
 // colour sum of channel 3, whose pixel gradients sit in the single plane at s_pix + PIXB; 7 partials per (trip, quad).
-// ORG (round 5, EOGS_ORIGIN_MOMENTS): the six moments of v are taken in TILE-LOCAL pixel coordinates {1, X, Y, X^2, XY, Y^2}
-// instead of about the Gaussian's centre: a row of four pixels costs three sums with constant weights (v1 + 2 v2 + 3 v3,
-// v1 + 4 v2 + 9 v3) instead of a subtraction, a product and two multiply-adds per pixel, the lane needs neither the entry's
-// centre nor its sub-list element (two LDS reads per round), and the four quads' partials add up in the owner as they are; the
-// owner shifts the sums to the centre once per entry and chunk (sum v (g - X) = g S0 - SX, ...), as the MFMA variant always did.
-#ifndef EOGS_ORIGIN_MOMENTS
-#define EOGS_ORIGIN_MOMENTS 1
-#endif
+// The six moments of v are taken in TILE-LOCAL pixel coordinates {1, X, Y, X^2, XY, Y^2}: a row of four pixels costs three sums
+// with constant weights (v1 + 2 v2 + 3 v3, v1 + 4 v2 + 9 v3), and the four quads' partials add up in the owner as they are; the
+// owner shifts the sums to the Gaussian's centre once per entry and chunk (sum v (g - X) = g S0 - SX, ...).
+// Moments about the centre, per pixel, measured slower: profiles/r05_ab_origin_moments.txt.
 // NOC4 (raw-parameter renders, EOGS_FLAG_RAW_PARAMS): the fifth feature is the constant 1 (renderer.py:88-95), so nobody consumes its
 // gradient: ten sums instead of eleven, no reads of the fifth channel's pixel gradients.
-template <bool ALT, bool ORG, bool NOC4>
-__device__ inline void transpose_round_quad(int nk, int r, int lane, const uint32_t* sidx, const float* slab, float* s_u,
-                                            const float* s_v, const float* s_pix, float bx0, float by0) {
+template <bool ALT, bool NOC4>
+__device__ inline void transpose_round_quad(int nk, int lane, float* s_u, const float* s_v, const float* s_pix) {
   const int k = lane >> 3, o = lane & 7, q = o >> 1, h = o & 1;
-  float gxr = 0.f, dy0 = 0.f, dy1 = 0.f;
-  if (!ORG) {
-    const uint32_t off = sidx[q * QB + 8 * r + k];  // the entry quad q evaluated in trip k (any staged value is a valid offset)
-    const float2 gxy = *reinterpret_cast<const float2*>(reinterpret_cast<const char*>(slab) + off);
-    gxr = gxy.x - (bx0 + (float)(4 * (q & 1)));  // centre relative to the quad's first column
-    dy0 = gxy.y - (by0 + (float)(4 * (q >> 1) + 2 * h));
-    dy1 = dy0 - 1.f;
-  }
-  // !ORG: S0 / Sx / Sxx = sum v {1, dx, dx^2} of a row (dx = centre - pixel); ORG: s0 / s1 / s2 = sum v {1, x, x^2}, x = 0..3
+  // S0 / Sx / Sxx = sum v {1, x, x^2} of a row, x = 0..3
   float S0a = 0.f, Sxa = 0.f, Sxxa = 0.f, S0b = 0.f, Sxb = 0.f, Sxxb = 0.f;
   float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
   const float* urow = s_u + uv_index(k, 8 * o);
@@ -1020,23 +995,15 @@ __device__ inline void transpose_round_quad(int nk, int r, int lane, const uint3
     float4 gb4 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (!NOC4) gb4 = *reinterpret_cast<const float4*>(s_pix + PIXB + 8 * o + 4 * hrow);
     const float uu[4] = {u4.x, u4.y, u4.z, u4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w}, gg[4] = {gb4.x, gb4.y, gb4.z, gb4.w};
-    if (ORG) {
-      const float s0 = (vv[0] + vv[1]) + (vv[2] + vv[3]);
-      const float s1 = __builtin_fmaf(3.f, vv[3], __builtin_fmaf(2.f, vv[2], vv[1]));
-      const float s2 = __builtin_fmaf(9.f, vv[3], __builtin_fmaf(4.f, vv[2], vv[1]));
-      if (hrow == 0) { S0a = s0; Sxa = s1; Sxxa = s2; }
-      else { S0b = s0; Sxb = s1; Sxxb = s2; }
-    }
+    const float s0 = (vv[0] + vv[1]) + (vv[2] + vv[3]);
+    const float s1 = __builtin_fmaf(3.f, vv[3], __builtin_fmaf(2.f, vv[2], vv[1]));
+    const float s2 = __builtin_fmaf(9.f, vv[3], __builtin_fmaf(4.f, vv[2], vv[1]));
+    if (hrow == 0) { S0a = s0; Sxa = s1; Sxxa = s2; }
+    else { S0b = s0; Sxb = s1; Sxxb = s2; }
 #pragma unroll
     for (int x = 0; x < 4; x++) {
       const int i = 4 * hrow + x;
-      const float u = uu[x], v = vv[x];
-      if (!ORG) {
-        const float dx = gxr - (float)x;
-        const float t1 = v * dx;
-        if (hrow == 0) { S0a += v; Sxa += t1; Sxxa += t1 * dx; }
-        else { S0b += v; Sxb += t1; Sxxb += t1 * dx; }
-      }
+      const float u = uu[x];
       if (!ALT) {
         const float4 ga = *reinterpret_cast<const float4*>(pa + i * 4);
         c0 += u * ga.x; c1 += u * ga.y; c2 += u * ga.z; c3 += u * ga.w;
@@ -1045,21 +1012,17 @@ __device__ inline void transpose_round_quad(int nk, int r, int lane, const uint3
     }
     if (hrow == 0) __builtin_amdgcn_sched_barrier(0);
   }
+  // rows Ya, Ya + 1 and columns X0 .. X0 + 3 of the tile: X = X0 + x
+  const float X0 = (float)(4 * (q & 1)), Ya = (float)(4 * (q >> 1) + 2 * h), Yb = Ya + 1.f;
+  const float s1 = Sxa + Sxb;
+  const float xa = __builtin_fmaf(X0, S0a, Sxa), xb = __builtin_fmaf(X0, S0b, Sxb);  // sum v X of each row
   float m[6];
-  if (ORG) {  // rows Ya, Ya + 1 and columns X0 .. X0 + 3 of the tile: X = X0 + x
-    const float X0 = (float)(4 * (q & 1)), Ya = (float)(4 * (q >> 1) + 2 * h), Yb = Ya + 1.f;
-    const float s1 = Sxa + Sxb;
-    const float xa = __builtin_fmaf(X0, S0a, Sxa), xb = __builtin_fmaf(X0, S0b, Sxb);  // sum v X of each row
-    m[0] = S0a + S0b;
-    m[1] = xa + xb;
-    m[2] = __builtin_fmaf(Ya, S0a, Yb * S0b);
-    m[3] = __builtin_fmaf(X0, m[1] + s1, Sxxa + Sxxb);  // sum v X^2 = s2 + 2 X0 s1 + X0^2 s0 = s2 + X0 (s1 + (s1 + X0 s0))
-    m[4] = __builtin_fmaf(Ya, xa, Yb * xb);
-    m[5] = __builtin_fmaf(Ya * Ya, S0a, (Yb * Yb) * S0b);
-  } else {
-    m[0] = S0a + S0b; m[1] = Sxa + Sxb; m[2] = dy0 * S0a + dy1 * S0b; m[3] = Sxxa + Sxxb; m[4] = dy0 * Sxa + dy1 * Sxb;
-    m[5] = dy0 * dy0 * S0a + dy1 * dy1 * S0b;
-  }
+  m[0] = S0a + S0b;
+  m[1] = xa + xb;
+  m[2] = __builtin_fmaf(Ya, S0a, Yb * S0b);
+  m[3] = __builtin_fmaf(X0, m[1] + s1, Sxxa + Sxxb);  // sum v X^2 = s2 + 2 X0 s1 + X0^2 s0 = s2 + X0 (s1 + (s1 + X0 s0))
+  m[4] = __builtin_fmaf(Ya, xa, Yb * xb);
+  m[5] = __builtin_fmaf(Ya * Ya, S0a, (Yb * Yb) * S0b);
   if (ALT) {
     float c[7] = {m[0], m[1], m[2], m[3], m[4], m[5], c4};
     DPP_STEP7("row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1");  // lane h = 1 += lane h = 0
@@ -1110,18 +1073,18 @@ __device__ unsigned long long g_bwd_phase[PHASE_TILES][6];  // per tile (wave): 
 // head, and inside a chunk every quad walks its sub-list from the end. Trip j of a chunk is still slot j & 7 of round j >> 3, so
 // the transposition, the staging area and the owner pull do not know the direction; the chunk's partial round comes first.
 template <bool HAVE_INV, bool ALT, bool NOC4 = false>
-__global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_BW, EOGS_BW))) void render_bwd_quad_kernel(
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EOGS_BW, EOGS_BW))) void render_bwd_quad_kernel(
     const uint2* __restrict__ ranges, const uint8_t* __restrict__ qmask, const uint2* __restrict__ point_list, int W, int H, int gsx, int ntiles, const uint4* __restrict__ desc, const uint32_t* __restrict__ sched, int lg16,
     const float4* __restrict__ packed, const uint32_t* __restrict__ n_contrib, const float* __restrict__ final_T,
     const float* __restrict__ bg, const float* __restrict__ dL_dpix,
-    const float* __restrict__ dL_dinv, float* __restrict__ records, uint8_t* __restrict__ live_flag, uint32_t rec_plane,
+    const float* __restrict__ dL_dinv, float* __restrict__ records, uint8_t* __restrict__ live_flag,
     const uint32_t* __restrict__ misc, int opts) {
   // slab position 64 holds a DUMMY entry (opacity 0 -> alpha = 0 -> never valid): shorter sub-lists are padded with it
-  __shared__ __attribute__((aligned(16))) float s_slab[RBLK / 64][65 * ENT];
-  __shared__ __attribute__((aligned(16))) float s_uv[RBLK / 64][UV_PITCH + UV_SIZE];
+  __shared__ __attribute__((aligned(16))) float s_slab[65 * ENT];
+  __shared__ __attribute__((aligned(16))) float s_uv[UV_PITCH + UV_SIZE];
   // 8 floats per pixel (+ padding) for the transposition
-  __shared__ __attribute__((aligned(16))) float s_pix[RBLK / 64][6 * 64];
-  __shared__ __attribute__((aligned(16))) uint32_t s_idx[RBLK / 64][4 * QB];
+  __shared__ __attribute__((aligned(16))) float s_pix[6 * 64];
+  __shared__ __attribute__((aligned(16))) uint32_t s_idx[4 * QB];
   static_assert(PIXB + 72 <= 6 * 64, "both pixel-gradient planes fit");
   static_assert(32 * STG <= UV_SIZE, "the staging area lives inside the u matrix");
   const int lane = threadIdx.x & 63;
@@ -1129,12 +1092,11 @@ __global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_BW, E
   const int tile = tile_of_wave(desc, sched, lg16, gsx, range);
   if (tile >= ntiles) return;
   WTRACE_BEGIN;
-  const int w = RBLK == 64 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  float* slab = s_slab[w];
-  float* su = s_uv[w];
-  float* sv = s_uv[w] + UV_PITCH;
-  float* spix = s_pix[w];
-  uint32_t* sidx = s_idx[w];
+  float* slab = s_slab;
+  float* su = s_uv;
+  float* sv = s_uv + UV_PITCH;
+  float* spix = s_pix;
+  uint32_t* sidx = s_idx;
   int ox, oy;
   quad_pixel(lane, ox, oy);
   const int tx0 = (tile % gsx) * SUBX, ty0 = (tile / gsx) * SUBY;
@@ -1154,7 +1116,6 @@ __global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_BW, E
   uint32_t ncontrib = 0;
   static_assert(!ALT || !HAVE_INV, "the altitude-only variant has no inverse-depth output");
   static_assert(!NOC4 || !ALT, "ten sums: a five-channel render");
-  constexpr bool ORG = EOGS_ORIGIN_MOMENTS != 0;  // tile-local moments in the transposition (transpose_round_quad)
   if (inside) {
     ncontrib = n_contrib[pix_id];
     Tfin = final_T[pix_id];
@@ -1270,7 +1231,7 @@ __global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_BW, E
     auto round = [&](int r, int nk) {
       PHASE(1);
       wave_lds_sync();
-      transpose_round_quad<ALT, ORG, NOC4>(nk, r, lane, sidx + QLEAD, slab, su, sv, spix, bx0, by0);
+      transpose_round_quad<ALT, NOC4>(nk, lane, su, sv, spix);
       wave_lds_sync();
       PHASE(2);
 #pragma unroll
@@ -1394,16 +1355,15 @@ __global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_BW, E
         const float4 q0 = *reinterpret_cast<const float4*>(slab + lane * ENT);
         const float2 q1 = *reinterpret_cast<const float2*>(slab + lane * ENT + 4);
         const float A = q0.z, B = q0.w, Cq = q1.x, op = q1.y;
-        if (ORG) {  // moments about the tile origin -> about the Gaussian centre: sum v (gx - x) = gx S0 - Sx, ...
-          const float gxr = q0.x - bx0, gyr = q0.y - by0;
-          const float S0 = acc[0], Sx = acc[1], Sy = acc[2], Sxx = acc[3], Sxy = acc[4], Syy = acc[5];
-          const float Sdx = gxr * S0 - Sx, Sdy = gyr * S0 - Sy;
-          acc[1] = Sdx;
-          acc[2] = Sdy;
-          acc[3] = gxr * (Sdx - Sx) + Sxx;
-          acc[4] = gxr * Sdy - gyr * Sx + Sxy;
-          acc[5] = gyr * (Sdy - Sy) + Syy;
-        }
+        // moments about the tile origin -> about the Gaussian centre: sum v (gx - x) = gx S0 - Sx, ...
+        const float gxr = q0.x - bx0, gyr = q0.y - by0;
+        const float S0 = acc[0], Sx = acc[1], Sy = acc[2], Sxx = acc[3], Sxy = acc[4], Syy = acc[5];
+        const float Sdx = gxr * S0 - Sx, Sdy = gyr * S0 - Sy;
+        acc[1] = Sdx;
+        acc[2] = Sdy;
+        acc[3] = gxr * (Sdx - Sx) + Sxx;
+        acc[4] = gxr * Sdy - gyr * Sx + Sxy;
+        acc[5] = gyr * (Sdy - Sy) + Syy;
         float opq = op;
         asm volatile("" : "+v"(opq));  // (kx, ky formed here, once per chunk, not kept in registers across the trips)
         const float m2x = opq * (LN2 * 0.5f * W) * (2.f * A * acc[1] - B * acc[2]);
@@ -1411,12 +1371,12 @@ __global__ __launch_bounds__(RBLK) __attribute__((amdgpu_waves_per_eu(EOGS_BW, E
         const float ho = -0.5f * op;
         constexpr int RQ = (ALT ? REC_ALT : REC) / 4;  // layout: common.h REC / REC_ALT, rec_q
         float4* r4 = reinterpret_cast<float4*>(records);
-        r4[rec_q(cur_slot, 0, rec_plane, RQ)] = make_float4(m2x, m2y, ho * acc[3], acc[0]);
+        r4[rec_q(cur_slot, 0, RQ)] = make_float4(m2x, m2y, ho * acc[3], acc[0]);
         if (ALT) {
-          reinterpret_cast<float3*>(r4 + rec_q(cur_slot, 1, rec_plane, RQ))[0] = make_float3(ho * acc[4], ho * acc[5], acc[6]);
+          reinterpret_cast<float3*>(r4 + rec_q(cur_slot, 1, RQ))[0] = make_float3(ho * acc[4], ho * acc[5], acc[6]);
         } else {
-          r4[rec_q(cur_slot, 1, rec_plane, RQ)] = make_float4(ho * acc[4], ho * acc[5], acc[6], acc[7]);
-          reinterpret_cast<float3*>(r4 + rec_q(cur_slot, 2, rec_plane, RQ))[0] = make_float3(acc[8], acc[9], acc[10]);
+          r4[rec_q(cur_slot, 1, RQ)] = make_float4(ho * acc[4], ho * acc[5], acc[6], acc[7]);
+          reinterpret_cast<float3*>(r4 + rec_q(cur_slot, 2, RQ))[0] = make_float3(acc[8], acc[9], acc[10]);
         }
         if (!noflag) live_flag[cur_slot] = 1;
       }
@@ -1475,16 +1435,16 @@ void launch_render_bwd(const GeomWS& g, const BinWS& b, const ImgWS& im, int P, 
     if (variant == 2 && raw) kq = dL_dinvdepth ? render_bwd_quad_kernel<true, false, true> : render_bwd_quad_kernel<false, false, true>;
     if (variant == 6) kq = render_bwd_quad_kernel<false, true>;
     const bool fwd_quad = render_fwd_variant(b.block, R, P) == 2 && b.qmask != nullptr && fwd_masks_on();
-    hipLaunchKernelGGL(kq, dim3(render_grid(ntiles, im, R)), dim3(RBLK), 0, s, im.ranges, b.qmask, b.point_list, W, H, gsx,
+    hipLaunchKernelGGL(kq, dim3(render_grid(ntiles, im, R)), dim3(64), 0, s, im.ranges, b.qmask, b.point_list, W, H, gsx,
                        ntiles, render_desc(im, R), g.sched, (int)(16u * im.sched_lg), g.packed, im.n_contrib, im.final_T, bg,
-                       dL_dcolor, dL_dinvdepth, b.records, b.live, b.cap_slots, g.misc, render_bwd_opts(b.block, R, P) | (fwd_quad ? 8 : 0));
+                       dL_dcolor, dL_dinvdepth, b.records, b.live, g.misc, render_bwd_opts(b.block, R, P) | (fwd_quad ? 8 : 0));
     return;
   }
   auto* kern = variant == 1 ? (dL_dinvdepth ? render_bwd_kernel<BLOCK_BIG, true> : render_bwd_kernel<BLOCK_BIG, false>)
                             : (dL_dinvdepth ? render_bwd_kernel<1, true> : render_bwd_kernel<1, false>);
-  hipLaunchKernelGGL(kern, dim3(render_grid(ntiles, im, R)), dim3(RBLK), 0, s, im.ranges, b.sorted_keys, b.point_list, W, H, gsx,
+  hipLaunchKernelGGL(kern, dim3(render_grid(ntiles, im, R)), dim3(64), 0, s, im.ranges, b.sorted_keys, b.point_list, W, H, gsx,
                      ntiles, (int)macro_grid_x(W, b.block), render_desc(im, R), g.sched, (int)(16u * im.sched_lg), g.packed, im.n_contrib,
-                     im.final_T, bg, dL_dcolor, dL_dinvdepth, b.records, b.live, b.cap_slots);
+                     im.final_T, bg, dL_dcolor, dL_dinvdepth, b.records, b.live);
 }
 
 #ifdef EOGS_BWD_PHASES

@@ -19,9 +19,7 @@ What a recorded forward freezes besides its capacities is the list granularity (
 DESIGN.md §2.3) of the last eager forward of that shape: an eager loop re-decides it per forward, so near the switch the two
 loops take different — equally valid, individually oracle-tested — kernel variants and their gradients differ at the
 level of threshold flips (examples/train_synthetic.py at 200 k / 512²: identical loss curves with the switch disabled,
-0.00815 against 0.00844 after 200 iterations with it). The choice of the back-to-front backward (image-sized opaque
-Gaussians) is frozen the same way, with a guard: a replay whose forward asks for it while the graph was
-recorded without it counts as not fitting (`CapturedForward.fits`) and is recorded again.
+0.00815 against 0.00844 after 200 iterations with it).
 
 When the tensors `fn` reads are REPLACED (a prune gives every parameter a new shape and address) the step has to be recorded
 again: `step.record_again()` does it inside the step's own memory pool — recording often then neither grows the process nor pays

@@ -370,8 +370,7 @@ def _run_forward(rs, viewmat, means3D, colors, opacities, scales, rotations, cov
             # previous one's counts plus slack and queue the whole forward before asking for the counts
             # (EOGS_FLAG_DEFER_COUNTS): the device builds no lists when the guess does not hold them, and the forward is then
             # repeated with the exact counts. Which way a forward went changes the kernel variants it runs (a capacity token
-            # keeps the earlier forward's list granularity), never what it computes, with one guarded exception: a forward
-            # that needs the back-to-front backward does not fit a token counted without it and is redone.
+            # keeps the earlier forward's list granularity), never what it computes.
             key = (dev, P, H, W, bool(raw), bool(alt_only))
             hs = lambda: int(scratch is not None) | (2 if alt_only else 0)  # `have_scratch` of the token-building calls
             last = _spec.get(key) if (_speculate and abi.backend != "cpu-oracle") else None
