@@ -33,6 +33,12 @@ FORCED = {  # (the default switches run in-process: tests/test_gpu_parity.py, sa
              "EOGS_NOFLAG": "0"},
     "quad_noflag": {"EOGS_BLOCK_SWITCH": "1000", "EOGS_DEPTH_SWITCH": "0", "EOGS_QUAD_SWITCH": "1000", "EOGS_QUAD_BWD_SWITCH": "1000",
                     "EOGS_NOFLAG": "2", "EOGS_PLAIN_TRIPS": "0"},
+    # A forward of one per-tile kernel with the backward of the other: the two read separate switches (EOGS_QUAD_SWITCH,
+    # EOGS_QUAD_BWD_SWITCH), and n_contrib means something different per kernel — 1 + the last blended position (tile forward),
+    # the position of the stop entry or 0xFFFFFFFF (quad forward); both backwards read it as "positions >= n_contrib take no part",
+    # which both values satisfy (csrc/render.hip). The quad backward after a tile forward finds its quad masks itself.
+    "tile_fwd_quad_bwd": {"EOGS_BLOCK_SWITCH": "1000", "EOGS_DEPTH_SWITCH": "0", "EOGS_QUAD_SWITCH": "0", "EOGS_QUAD_BWD_SWITCH": "1000"},
+    "quad_fwd_tile_bwd": {"EOGS_BLOCK_SWITCH": "1000", "EOGS_DEPTH_SWITCH": "0", "EOGS_QUAD_SWITCH": "1000", "EOGS_QUAD_BWD_SWITCH": "0"},
 }
 # (Rounds 2-5 also forced two matrix-pipe variants of the quad backward and, for image-sized Gaussians, a separate back-to-front
 # kernel; since round 6 every backward kernel walks back to front — the reference's recursion — and the variants are gone.)
@@ -84,7 +90,7 @@ def case_dir(tmp_path_factory):
 def test_every_kernel_path_matches_oracle(dev, case_dir, tmp_path):
     d, ncases = case_dir
     seen_fwd, seen_bwd, report = set(), set(), {}
-    # One child first, then the other three together (each is one process on the card and mostly CPU-side comparison; the GPU box
+    # One child first, then the others together (each is one process on the card and mostly CPU-side comparison; the GPU box
     # allows six processes on its card and has 16 cores): what the float64 arbiter needs for a case depends on the case alone
     # and is cached in files the children share, so the first child pays for it and the others read it (all four at once
     # computed it four times: 95 s against 78 s two by two). Exactly the processes started here are waited for.
@@ -120,6 +126,10 @@ def test_every_kernel_path_matches_oracle(dev, case_dir, tmp_path):
             assert sum(p[0] == 32 for p in paths) >= len(paths) * 0.8, report[tag]
         if tag in ("quad", "quad_noflag"):  # (quad_noflag also switches the forward's plain chunks off: its general loop on every case)
             assert all(p == (8, 2, 2) for p in paths), report[tag]
+        if tag == "tile_fwd_quad_bwd":
+            assert all(p == (8, 0, 2) for p in paths), report[tag]
+        if tag == "quad_fwd_tile_bwd":
+            assert all(p == (8, 2, 0) for p in paths), report[tag]
         seen_fwd |= {p[1] for p in paths}
         seen_bwd |= {p[2] for p in paths}
     print("kernel paths compared with the oracle:", json.dumps(report))
