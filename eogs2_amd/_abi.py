@@ -119,12 +119,17 @@ SIGNATURES = {
     "eogs_tshadow_backward": (_i, [_i64, _p, _p, _p, _p]),
     # include/eogs_tsdf.h
     "eogs_tsdf_integrate": (_i, [_i, _i, _i, _p, _p, _p, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p]),
+    "eogs_tsdf_normals": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "eogs_tsdf_prior_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+    "eogs_tsdf_prior": (_i, [_i, _i, _i, _p, _p, _p, _z, _p]),
+    "eogs_tsdf_surface": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
 }
 # symbols only the HIP library exports (the CPU oracle of the loss is oracle/loss_oracle.py, not a C-ABI twin)
 HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
             "eogs_compact_plan", "eogs_compact_apply", "eogs_resample_forward", "eogs_resample_bytes", "eogs_resample_backward", "eogs_knn_bytes",
             "eogs_knn_mean_dist2", "eogs_shade_bytes", "eogs_shade_forward", "eogs_shade_backward", "eogs_mloss_forward",
-            "eogs_mloss_backward", "eogs_tshadow_forward", "eogs_tshadow_backward", "eogs_tsdf_integrate")
+            "eogs_mloss_backward", "eogs_tshadow_forward", "eogs_tshadow_backward", "eogs_tsdf_integrate", "eogs_tsdf_normals",
+            "eogs_tsdf_prior_bytes", "eogs_tsdf_prior", "eogs_tsdf_surface")
 
 
 class PackTensor(C.Structure):

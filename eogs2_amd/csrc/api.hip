@@ -63,10 +63,13 @@ int check_launch(hipStream_t s, bool debug, const char* what) {
 }
 // ---- optional per-kernel-group timing with hipEvents on the launch stream ----
 enum { PS_PREPROCESS, PS_DEPTH_SORT, PS_BINNING, PS_RENDER_FWD, PS_RENDER_BWD, PS_GAUSS_BWD, PS_LOSS_FWD, PS_LOSS_BWD, PS_ADAM,
-       PS_COMPACT, PS_RESAMPLE_FWD, PS_RESAMPLE_BWD, PS_KNN, PS_SHADE_FWD, PS_SHADE_BWD, PS_MLOSS_FWD, PS_MLOSS_BWD, PS_TSDF, PS_COUNT };
+       PS_COMPACT, PS_RESAMPLE_FWD, PS_RESAMPLE_BWD, PS_KNN, PS_SHADE_FWD, PS_SHADE_BWD, PS_MLOSS_FWD, PS_MLOSS_BWD, PS_TSDF,
+       PS_TSDF_NORMALS, PS_TSDF_PRIOR, PS_TSDF_SURFACE, PS_COUNT };
+static_assert(PS_COUNT <= 32, "eogs_rast_profile_select takes a 32-bit slot mask");
 const char* const kSlotNames[PS_COUNT] = {"preprocess_fwd", "depth_sort", "binning", "render_fwd", "render_bwd", "gaussian_bwd",
                                           "loss_fwd", "loss_bwd", "adam", "compact", "resample_fwd", "resample_bwd", "knn",
-                                          "shade_fwd", "shade_bwd", "mloss_fwd", "mloss_bwd", "tsdf"};
+                                          "shade_fwd", "shade_bwd", "mloss_fwd", "mloss_bwd", "tsdf",
+                                          "tsdf_normals", "tsdf_prior", "tsdf_surface"};
 struct Pending { int slot; hipEvent_t a, b; };
 // process-wide (autograd runs backward on its own thread), guarded by g_prof_mu
 std::mutex g_prof_mu;
@@ -911,6 +914,50 @@ int eogs_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay
   { ProfScope ps(PS_TSDF, s);
     launch_tsdf_integrate(nx, ny, nz, ax, ay, az, affine, model_scale, trunc_margin, H, W, altitude, weight, tsdf_vol, weight_vol, s); }
   LAUNCH_TRY(s, false, "tsdf_integrate");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_normals(int H, int W, const float* altitude, const float* affine, const float* view_dir, float* normals, float* angle,
+                      float* weights, void* stream) {
+  g_err[0] = 0;
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "tsdf_normals: bad sizes");
+  if (!altitude || !affine || !view_dir || !angle) return fail(EOGS_ERR_INVALID_ARG, "tsdf_normals: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_TSDF_NORMALS, s); launch_tsdf_normals(H, W, altitude, affine, view_dir, normals, angle, weights, s); }
+  LAUNCH_TRY(s, false, "tsdf_normals");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_prior_bytes(int nx, int ny, int nz, size_t* bytes) {
+  g_err[0] = 0;
+  if (nx < 0 || ny < 0 || nz < 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "tsdf_prior_bytes: bad argument");
+  if ((uint64_t)nx * ny * nz > ((uint64_t)1 << 40)) return fail(EOGS_ERR_OVERFLOW, "tsdf_prior_bytes: volume too large");
+  *bytes = tsdf_prior_ws_bytes(nx, ny, nz);
+  return EOGS_OK;
+}
+
+int eogs_tsdf_prior(int nx, int ny, int nz, float* tsdf_vol, float* weight_vol, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (nx < 0 || ny < 0 || nz < 0) return fail(EOGS_ERR_INVALID_ARG, "tsdf_prior: bad sizes");
+  if ((size_t)nx * ny * nz == 0) return EOGS_OK;
+  if ((uint64_t)nx * ny * nz > ((uint64_t)1 << 40)) return fail(EOGS_ERR_OVERFLOW, "tsdf_prior: volume too large");
+  if (!tsdf_vol || !weight_vol || !ws) return fail(EOGS_ERR_INVALID_ARG, "tsdf_prior: NULL argument");
+  if (ws_bytes < tsdf_prior_ws_bytes(nx, ny, nz)) return fail(EOGS_ERR_WORKSPACE, "tsdf_prior: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_TSDF_PRIOR, s); launch_tsdf_prior(nx, ny, nz, tsdf_vol, weight_vol, ws, s); }
+  LAUNCH_TRY(s, false, "tsdf_prior");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_surface(int nx, int ny, int nz, const float* tsdf_vol, const float* az, int64_t* index, float* height, void* stream) {
+  g_err[0] = 0;
+  if (nx < 0 || ny < 0 || nz <= 0) return fail(EOGS_ERR_INVALID_ARG, "tsdf_surface: bad sizes");
+  if ((size_t)nx * ny == 0) return EOGS_OK;
+  if ((uint64_t)nx * ny * nz > ((uint64_t)1 << 40)) return fail(EOGS_ERR_OVERFLOW, "tsdf_surface: volume too large");
+  if (!tsdf_vol || !az || !index) return fail(EOGS_ERR_INVALID_ARG, "tsdf_surface: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_TSDF_SURFACE, s); launch_tsdf_surface(nx, ny, nz, tsdf_vol, az, index, height, s); }
+  LAUNCH_TRY(s, false, "tsdf_surface");
   return EOGS_OK;
 }
 

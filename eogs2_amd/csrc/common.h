@@ -642,6 +642,11 @@ void launch_tshadow_bwd(int64_t n, const float* a, const float* upstream, float*
 void launch_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,
                            float scale, float trunc, int H, int W, const float* alt, const float* wgt, float* tsdf,
                            float* wvol, hipStream_t s);
+void launch_tsdf_normals(int H, int W, const float* alt, const float* affine, const float* view_dir, float* normals, float* angle,
+                         float* weights, hipStream_t s);
+size_t tsdf_prior_ws_bytes(int nx, int ny, int nz);
+void launch_tsdf_prior(int nx, int ny, int nz, float* tsdf, float* wvol, void* ws, hipStream_t s);
+void launch_tsdf_surface(int nx, int ny, int nz, const float* tsdf, const float* az, int64_t* index, float* height, hipStream_t s);
 
 // ---- 3-nearest-neighbour statistic (knn.hip, include/eogs_knn.h) ----
 struct KnnWS {

@@ -1,14 +1,24 @@
-"""TSDF volume integration over the C-ABI of include/eogs_tsdf.h (second piece).
+"""TSDF fusion over the C-ABI of include/eogs_tsdf.h (second piece).
 
 `TSDFVolume(vol_bounds, vox_size, trunc_margin_fact)` has the reference's constructor arithmetic and attributes
 (src/gaussiansplatting/tsdf.py:374-456: `num_voxels_per_dimension`, `axes`, `_tsdf_vol` = ones, `_weight_vol` = zeros)
 and `integrate(rangeimage)` (:459-498) runs ONE HIP kernel per range image instead of the reference's ~25 voxel-sized
 PyTorch temporaries. `rangeimage` is duck-typed like `RangeImageEOGS` (:186-368): `affine_model = (coef[3,3],
-intercept[3])`, `model_scale`, `altitude_img [1,1,H,W]`, `get_weights() [1,1,H,W]` (the normal estimation that produces
-the weights stays PyTorch: it runs once per image on H x W pixels). No CPU / eager fallback.
+intercept[3])`, `model_scale`, `altitude_img [1,1,H,W]`, `get_weights() [1,1,H,W]`.
+
+The stages around integrate are HIP as well:
+  RangeImage (alias RangeImageEOGS)  the reference's RangeImageEOGS (:186-323): normals, view angle and weights of one
+                                     altitude image in one kernel, without the 5x5 unfold of the world-position image
+  TSDFVolume.apply_prior()           tsdf.py:602-638, in place (two kernels, no voxel-sized index tensors)
+  TSDFVolume.surface()               tsdf.py:530-536: the top-most voxel with t < 0 per column and its height
+  TSDFVolume.surface_cloud(sp)       tsdf.py:538-556: the float64 point cloud the reference hands to plyflatten
+No CPU / eager fallback: CPU tensors raise.
 """
+import ctypes
+
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from . import _lib
 from .rasterizer import _Ctx, _ptr
@@ -41,6 +51,131 @@ class TSDFVolume:
                   float(rangeimage.model_scale), float(self._trunc_margin), rangeimage.altitude_img,
                   rangeimage.get_weights())
 
+    def apply_prior(self):
+        """tsdf.py:602-638, in place."""
+        apply_prior(self._tsdf_vol, self._weight_vol)
+
+    def surface(self):
+        """tsdf.py:530-536: (index int64 [nx, ny] = the top-most z with t < 0, 0 if none; height f32 [nx, ny] = axes[2][index])."""
+        return surface(self._tsdf_vol, self.axes[2])
+
+    def surface_cloud(self, scene_params):
+        """tsdf.py:538-556: the array the reference's extract_dsm hands to plyflatten, float64 [nx * ny, 3]
+        (x, y, height in fp32 on the device, then `+ scene_params[0]` on the host)."""
+        _, height = self.surface()
+        xy = torch.stack(torch.meshgrid([self.axes[0], self.axes[1]], indexing="ij"), dim=-1)
+        cloud = torch.cat([xy, height.unsqueeze(-1)], dim=-1).detach().cpu().reshape(-1, 3).numpy()
+        return cloud + scene_params[0]
+
+
+class RangeImage:
+    """The reference's RangeImageEOGS (tsdf.py:186-323) on the GPU: `metadata` is its dict (`img`, `model.scale`,
+    `model.coef_`, `model.intercept_`), `altitude_img` a numpy array or a tensor, [H, W] or [1, 1, H, W]. Attributes as in
+    the reference: img_name, model_scale, affine_model, view_direction, altitude_img [1,1,H,W], height, width,
+    pixels_normals [1,3,H,W], pixels_angle [1,1,H,W]. The weights come out of the same kernel: get_weights() returns
+    clamp(pixels_angle, 0, 1) as computed at construction."""
+
+    def __init__(self, metadata, altitude_img, device="cuda:0"):
+        self.device = altitude_img.device if torch.is_tensor(altitude_img) else torch.device(device)
+        self.img_name = metadata["img"]
+        self.model_scale = metadata["model"]["scale"]
+        self.affine_model = (torch.tensor(metadata["model"]["coef_"], dtype=torch.float32, device=self.device),
+                             torch.tensor(metadata["model"]["intercept_"], dtype=torch.float32, device=self.device))
+        self.view_direction = view_direction(self.affine_model[0])
+        alt = torch.as_tensor(altitude_img).to(device=self.device, dtype=torch.float32)
+        if alt.ndim == 2:
+            alt = alt[None, None]
+        if alt.ndim != 4 or alt.shape[:2] != (1, 1):
+            raise RuntimeError("RangeImage: altitude_img must be [H, W] or [1, 1, H, W]")
+        self.altitude_img = alt.contiguous()
+        _, _, self.height, self.width = self.altitude_img.shape
+        self.pixels_normals, self.pixels_angle, self._weights = normals(self.altitude_img, *self.affine_model,
+                                                                        view_dir=self.view_direction)
+
+    def get_weights(self):
+        return self._weights
+
+
+RangeImageEOGS = RangeImage
+
+
+def _affine24(coef, intercept, dev):
+    """f32[24] = coef, intercept, inv(coef), inv(coef) @ intercept (tsdf.py:234, :238-240): the layout of include/eogs_tsdf.h."""
+    f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    A, b = f(coef).reshape(3, 3), f(intercept).reshape(3)
+    Ainv = torch.linalg.inv(A)
+    return torch.cat([A.reshape(-1), b, Ainv.reshape(-1), Ainv @ b])
+
+
+def view_direction(coef):
+    """tsdf.py:213-218: normalize(solve(coef, e3), eps=1e-6)."""
+    v = torch.linalg.solve(coef, torch.tensor([0, 0, 1.0], device=coef.device))
+    return F.normalize(v, dim=0, eps=1e-6)
+
+
+def _on_device(t, what):
+    if t.device.type != "cuda":
+        raise RuntimeError(f"tsdf {what}: tensors live on '{t.device.type}'; the TSDF stages run on the GPU only, there is no "
+                           "CPU fallback")
+
+
+def normals(altitude_img, coef, intercept, view_dir=None, with_normals=True, with_weights=True):
+    """tsdf.py:213-231, 243-323 in one kernel: (pixels_normals [1,3,H,W] or None, pixels_angle [1,1,H,W],
+    weights [1,1,H,W] = clamp(angle, 0, 1) or None) of an altitude image [H, W] or [1, 1, H, W]."""
+    _on_device(altitude_img, "normals")
+    abi = _lib.get()
+    dev = altitude_img.device
+    alt = altitude_img.detach().to(dtype=torch.float32).contiguous()
+    H, W = alt.shape[-2:]
+    if alt.numel() != H * W or H * W == 0:
+        raise RuntimeError("tsdf normals: the altitude image must be a non-empty single-channel H x W")
+    affine = _affine24(coef, intercept, dev)
+    vd = (view_direction(coef.detach().to(device=dev, dtype=torch.float32).reshape(3, 3)) if view_dir is None else view_dir)
+    vd = vd.detach().to(device=dev, dtype=torch.float32).contiguous()
+    n = torch.empty((1, 3, H, W), device=dev, dtype=torch.float32) if with_normals else None
+    angle = torch.empty((1, 1, H, W), device=dev, dtype=torch.float32)
+    wgt = torch.empty((1, 1, H, W), device=dev, dtype=torch.float32) if with_weights else None
+    with _Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_normals(H, W, _ptr(alt), _ptr(affine), _ptr(vd), _ptr(n), _ptr(angle), _ptr(wgt), cx.stream))
+    return n, angle, wgt
+
+
+def _check_volume(t, what):
+    _on_device(t, what)
+    if t.dtype != torch.float32 or not t.is_contiguous() or t.ndim != 3:
+        raise RuntimeError(f"tsdf {what}: volumes must be contiguous float32 [nx, ny, nz]")
+
+
+def apply_prior(tsdf_vol, weight_vol):
+    """tsdf.py:602-638 in place on `tsdf_vol` / `weight_vol` (f32[nx,ny,nz], contiguous)."""
+    for t in (tsdf_vol, weight_vol):
+        _check_volume(t, "apply_prior")
+    abi = _lib.get()
+    if tsdf_vol.shape != weight_vol.shape or tsdf_vol.device != weight_vol.device:
+        raise RuntimeError("tsdf apply_prior: the volumes differ in shape or device")
+    nx, ny, nz = tsdf_vol.shape
+    n = ctypes.c_size_t()
+    abi.check(abi.tsdf_prior_bytes(nx, ny, nz, ctypes.byref(n)))
+    ws = torch.empty(max(n.value, 1), dtype=torch.uint8, device=tsdf_vol.device)
+    with _Ctx(abi, tsdf_vol.device) as cx:
+        abi.check(abi.tsdf_prior(nx, ny, nz, _ptr(tsdf_vol), _ptr(weight_vol), _ptr(ws), n.value, cx.stream))
+
+
+def surface(tsdf_vol, z_axis):
+    """tsdf.py:530-536: (index int64 [nx, ny], height f32 [nx, ny]) with index = argmax((t < 0) * arange(nz)) (the
+    top-most voxel with t < 0; 0 if the column has none) and height = z_axis[index]."""
+    _check_volume(tsdf_vol, "surface")
+    abi = _lib.get()
+    nx, ny, nz = tsdf_vol.shape
+    az = z_axis.detach().to(device=tsdf_vol.device, dtype=torch.float32).contiguous()
+    if az.numel() != nz:
+        raise RuntimeError("tsdf surface: the z axis does not match the volume")
+    index = torch.empty((nx, ny), dtype=torch.int64, device=tsdf_vol.device)
+    height = torch.empty((nx, ny), dtype=torch.float32, device=tsdf_vol.device)
+    with _Ctx(abi, tsdf_vol.device) as cx:
+        abi.check(abi.tsdf_surface(nx, ny, nz, _ptr(tsdf_vol), _ptr(az), _ptr(index), _ptr(height), cx.stream))
+    return index, height
+
 
 def integrate(tsdf_vol, weight_vol, axes, coef, intercept, model_scale, trunc_margin, altitude_img, weight_img):
     """In place on `tsdf_vol` / `weight_vol` (f32[nx,ny,nz], contiguous)."""
@@ -56,9 +191,7 @@ def integrate(tsdf_vol, weight_vol, axes, coef, intercept, model_scale, trunc_ma
     ax, ay, az = (f(a) for a in axes)
     if (ax.numel(), ay.numel(), az.numel()) != (nx, ny, nz):
         raise RuntimeError("tsdf integrate: axes do not match the volume")
-    A, b = f(coef).reshape(3, 3), f(intercept).reshape(3)
-    Ainv = torch.linalg.inv(A)  # tsdf.py:238-239
-    affine = torch.cat([A.reshape(-1), b, Ainv.reshape(-1), Ainv @ b])
+    affine = _affine24(coef, intercept, dev)  # tsdf.py:238-239
     alt, wgt = f(altitude_img), f(weight_img)
     H, W = alt.shape[-2:]
     if alt.numel() != H * W or wgt.numel() != H * W:
@@ -68,4 +201,5 @@ def integrate(tsdf_vol, weight_vol, axes, coef, intercept, model_scale, trunc_ma
                                      H, W, _ptr(alt), _ptr(wgt), _ptr(tsdf_vol), _ptr(weight_vol), cx.stream))
 
 
-__all__ = ["TSDFVolume", "integrate", "volume_axes"]
+__all__ = ["RangeImage", "RangeImageEOGS", "TSDFVolume", "apply_prior", "integrate", "normals", "surface", "view_direction",
+           "volume_axes"]
