@@ -101,11 +101,13 @@ constexpr float SH_C0 = 0.28209479177387814f;  // utils/sh_utils.py:25
 
 __device__ inline float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
-// scaling_activation = exp (gaussian_model.py:41), rotation_activation = F.normalize, eps 1e-12 (gaussian_model.py:52)
-__device__ inline float raw_activate(float s[3], float q[4]) {
+// scaling_activation = exp (gaussian_model.py:41), rotation_activation = F.normalize, eps 1e-12 (gaussian_model.py:52).
+// `clamped`: the norm is below eps, where x / clamp_min(|x|, eps) passes no gradient to |x| (no projection in the backward)
+__device__ inline float raw_activate(float s[3], float q[4], bool* clamped = nullptr) {
 #pragma unroll
   for (int k = 0; k < 3; k++) s[k] = expf(s[k]);
   const float n = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (clamped) *clamped = n < 1e-12f;
   const float inv = 1.f / fmaxf(n, 1e-12f);
 #pragma unroll
   for (int k = 0; k < 4; k++) q[k] *= inv;
@@ -732,6 +734,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
       float q[4] = {1.f, 0.f, 0.f, 0.f};
       float s3[3] = {0.f, 0.f, 0.f};
       float q_inv = 1.f, op_in = 0.f;
+      bool q_clamped = false;
       if (RAW || antialiasing) op_in = RAW ? sigmoidf(op_raw) : op_raw;
       if (cov3D_precomp) {
         const float2* c2 = reinterpret_cast<const float2*>(cov3D_precomp + 6 * idx);
@@ -741,7 +744,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
         const float4 qq = rot_in;
         q[0] = qq.x; q[1] = qq.y; q[2] = qq.z; q[3] = qq.w;
         s3[0] = s_s[3 * t]; s3[1] = s_s[3 * t + 1]; s3[2] = s_s[3 * t + 2];
-        if (RAW) q_inv = raw_activate(s3, q);
+        if (RAW) q_inv = raw_activate(s3, q, &q_clamped);
         cov3d_from_scale_rot(s3, scale_modifier, q, c6);  // recomputed instead of stored: saves 48 B/Gaussian of HBM traffic
       }
       float T[2][3];
@@ -842,7 +845,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
         // chain through the activations: exp, normalize, sigmoid, and the altitude feature's dependence on xyz
 #pragma unroll
         for (int k = 0; k < 3; k++) dscale[k] *= s3[k];
-        const float dot = q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3];
+        const float dot = q_clamped ? 0.f : q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3];
 #pragma unroll
         for (int k = 0; k < 4; k++) dq[k] = (dq[k] - q[k] * dot) * q_inv;
         dop *= op_in * (1.f - op_in);

@@ -1276,8 +1276,11 @@ static int backward_full(
       const float* r = rotations + 4 * i;
       const double nr = sqrt((double)r[0] * r[0] + (double)r[1] * r[1] + (double)r[2] * r[2] + (double)r[3] * r[3]);
       const double den = nr > 1e-12 ? nr : 1e-12;
+      /* F.normalize is x / clamp_min(|x|, eps): below eps (the fp32 norm, as activate_raw computes it) the clamp passes no
+       * gradient to |x|, so dL/dx = dL/dq / eps, without the projection */
+      const int clamped = sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]) < 1e-12f;
       double dot = 0;
-      for (int k = 0; k < 4; k++) dot += (double)a.rotations[4 * i + k] * dL_drotations[4 * i + k];
+      for (int k = 0; k < 4 && !clamped; k++) dot += (double)a.rotations[4 * i + k] * dL_drotations[4 * i + k];
       for (int k = 0; k < 4; k++)
         dL_drotations[4 * i + k] = (float)(((double)dL_drotations[4 * i + k] - a.rotations[4 * i + k] * dot) / den);
     }

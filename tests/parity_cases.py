@@ -88,16 +88,20 @@ def sweep_case(seed):
 
 
 def oracle_run(case, backend=None):
-    """The case through the same host wrapper over the CPU oracle (checker library; tests only)."""
+    """The case through the same host wrapper over the CPU oracle (checker library; tests only). A raw-parameter case goes
+    through the front end it names (`entry`), so the oracle runs in its RAW mode (EOGS_FLAG_RAW_PARAMS)."""
     import oracle
-    from util import run_case
+    from util import run_case, run_raw_case, run_render_case
 
     from eogs2_amd import GaussianRasterizationSettings, GaussianRasterizer, _lib
 
     hip = _lib.get
     _lib.get = backend or oracle.abi
     try:
-        ref = run_case(case, torch.device("cpu"), GaussianRasterizer, GaussianRasterizationSettings)
+        # a raw-parameter case (util.load_render / util.raw_case) through the same front end, over the oracle's RAW mode
+        raw = {"render": run_render_case, "rasterize_raw": run_raw_case}.get(str(case.get("entry", "")))
+        ref = raw(case, torch.device("cpu")) if raw else run_case(case, torch.device("cpu"), GaussianRasterizer,
+                                                                   GaussianRasterizationSettings)
     finally:
         _lib.get = hip
     return {k: v.cpu().numpy() for k, v in ref.items() if not k.startswith("_")}
@@ -201,6 +205,23 @@ def fp32_variants(case):
 
 COUNT_RTOL = 1e-4  # the tolerance at which arbiter() counts the fp32 evaluations' own out-of-tolerance elements
 
+# the inputs arbiter() perturbs by SENS_ULPS ulp: relatively, except the raw log-scales and opacity logits, which move by SENS_ULPS
+# ulp absolutely (that is SENS_ULPS ulp relative of exp(s), and at most that of sigmoid(x))
+PERTURBED = ("means3D", "scales", "rotations", "opacities", "colors", "cov3D_precomp", "f_dc", "opacity_logit", "log_scaling",
+             "raw_rotation", "dL_dcolor", "dL_dinvdepth")
+PERTURBED_ABS = ("opacity_logit", "log_scaling")
+
+
+def perturbed(case, keys, g):
+    """`case` with the inputs `keys` moved by SENS_ULPS ulp (normal draws from the numpy Generator `g`, in the order of `keys`)."""
+    pert = dict(case)
+    for k in keys:
+        if k in case:
+            v = np.asarray(case[k])
+            d = SENS_ULPS * ULP * g.standard_normal(v.shape)
+            pert[k] = (v + d if k in PERTURBED_ABS else v * (1.0 + d)).astype(np.float32)
+    return pert
+
 
 def arbiter(case, base=None):
     """({output: the arbiter's value}, {output: spread}, {output: count}, {output: same-input spread}) for the gradients of `case`.
@@ -252,15 +273,9 @@ def arbiter(case, base=None):
     for res in fp32_variants(case).values():
         widen(res, counted=True)
     for draw in range(SENS_DRAWS):
-        g = np.random.default_rng(1000 + draw)
-        pert = dict(case)
         # the Gaussians' parameters (each moves all of a Gaussian's pixel terms together) AND the upstream gradient (moves
         # every pixel's term independently: what the rounding of the individual terms of a cancelling per-Gaussian sum does)
-        for k in ("means3D", "scales", "rotations", "opacities", "colors", "cov3D_precomp", "dL_dcolor", "dL_dinvdepth"):
-            if k in case:
-                v = np.asarray(case[k])
-                pert[k] = (v * (1.0 + SENS_ULPS * ULP * g.standard_normal(v.shape))).astype(np.float32)
-        widen(oracle_run(pert))
+        widen(oracle_run(perturbed(case, PERTURBED, np.random.default_rng(1000 + draw))))
     return {k: np.asarray(f64[k], dtype=np.float64) for k in keys}, spread, count, same
 
 
@@ -368,18 +383,39 @@ class Attribution:
     """Lazily evaluated explanations of one case's out-of-tolerance elements: the nudged oracle runs (only computed when
     some element is out of tolerance) and the arbiter with the spread of the fp32 evaluations around it (only when the nudges
     do not explain them). `cache`: a file prefix for the arbiter's arrays, which depend on the case alone, so
-    processes that replay the same case (tests/path_child.py) share them."""
+    processes that replay the same case (tests/path_child.py) share them.
+    `ref_is_oracle=False`: `ref` is not the oracle's own output (the reference's vectors, or another HIP path). Every oracle
+    run then explains only the way it moves away from the oracle's PLAIN run on the same inputs: its difference from that run
+    is added to `ref` (the arbiter's value likewise), and the arbiter's spread is measured around the plain run. An oracle that
+    itself differs from `ref` can then not excuse the same difference in the output under test."""
 
-    def __init__(self, case, out, ref, cache=None):
+    def __init__(self, case, out, ref, cache=None, ref_is_oracle=True):
         self.case = case
         self.out = out    # HIP outputs (torch tensors)
         self.ref = ref    # oracle outputs (numpy)
         self.cache = cache
+        self.ref_is_oracle = ref_is_oracle
+        self._plain = None
         self._matched = None
         self._hull = None
         self._arb = None
         self._nudged = None
         self.flipped_pixels = 0
+
+    def plain(self):
+        """The oracle's own run of the case (the reference outputs themselves when they are the oracle's)."""
+        if self._plain is None:
+            self._plain = self.ref if self.ref_is_oracle else oracle_run(self.case)
+        return self._plain
+
+    def shifted(self, run):
+        """An oracle run moved into the frame of `ref`: run + (ref - plain run), per output (the run itself when ref is the
+        oracle's output)."""
+        if self.ref_is_oracle:
+            return run
+        p = self.plain()
+        return {k: (np.asarray(v, dtype=np.float64) + (np.asarray(self.ref[k], dtype=np.float64) - np.asarray(p[k], dtype=np.float64))
+                    if k != "out_radii" and k in self.ref and k in p else v) for k, v in run.items()}
 
     def matched(self):
         """(oracle outputs with per-pixel threshold nudges chosen to reproduce the HIP image, {key: (lo, hi)} over the four
@@ -389,8 +425,8 @@ class Attribution:
         if self._matched is None:
             t0 = time.perf_counter()
             pre = _take_prefetched(self.case)
-            runs = {-1: pre[-1] if pre else nudged_run(self.case, uniform=-1), 0: self.ref,
-                    1: pre[1] if pre else nudged_run(self.case, uniform=1)}
+            nudged = {-1: pre[-1] if pre else nudged_run(self.case, uniform=-1), 1: pre[1] if pre else nudged_run(self.case, uniform=1)}
+            runs = {-1: self.shifted(nudged[-1]), 0: self.ref, 1: self.shifted(nudged[1])}
             H, W = int(self.case["H"]), int(self.case["W"])
             err = {}
             for sgn, r in runs.items():
@@ -408,7 +444,7 @@ class Attribution:
             sign[off & better_p & (err[1] <= err[-1])] = 1
             sign[off & better_m & (err[-1] < err[1])] = -1
             self.flipped_pixels = int((sign != 0).sum())
-            m = nudged_run(self.case, sign_map=sign) if self.flipped_pixels else self.ref
+            m = self.shifted(nudged_run(self.case, sign_map=sign)) if self.flipped_pixels else self.ref
             hull = {}
             for k in self.ref:
                 if k == "out_radii":
@@ -416,7 +452,7 @@ class Attribution:
                 stack = np.stack([np.asarray(r[k], dtype=np.float64) for r in (runs[-1], runs[0], runs[1], m)])
                 hull[k] = (stack.min(0), stack.max(0))
             self._matched, self._hull = m, hull
-            self._nudged = (runs[-1], runs[1])
+            self._nudged = (nudged[-1], nudged[1])  # (the oracle's own frame: support, and spread around the arbiter)
             print(f"threshold nudges: {self.flipped_pixels} pixels re-decided, {time.perf_counter() - t0:.1f} s of oracle")
         return self._matched, self._hull
 
@@ -437,7 +473,10 @@ class Attribution:
             # per-Gaussian chain still amplifies it into a visible difference of that Gaussian's gradient
             for r in self._nudged:
                 spread = np.maximum(spread, np.abs(np.asarray(r[key], dtype=np.float64) - self._arb[0][key]))
-        return torch.from_numpy(self._arb[0][key]), torch.from_numpy(spread), torch.from_numpy(self._arb[3][key])
+        f64 = self._arb[0][key]
+        if not self.ref_is_oracle:  # (the arbiter's value in the frame of ref: shifted)
+            f64 = f64 + (np.asarray(self.ref[key], dtype=np.float64) - np.asarray(self.plain()[key], dtype=np.float64))
+        return torch.from_numpy(f64), torch.from_numpy(spread), torch.from_numpy(self._arb[3][key])
 
     def _load_arbiter(self):
         import os
@@ -451,7 +490,7 @@ class Attribution:
                              {k[6:]: int(z[k]) for k in z.files if k.startswith("count_")}, {k[5:]: z[k] for k in z.files if k.startswith("same_")})
             else:
                 t0 = time.perf_counter()
-                self._arb = arbiter(self.case, self.ref)
+                self._arb = arbiter(self.case, self.plain())
                 print(f"arbiter (double) + {2 + PAIR_NOISE_DRAWS + SENS_DRAWS} fp32 evaluations: {time.perf_counter() - t0:.1f} s")
                 if f:  # (written whole, then renamed: the path children run two at a time and share this cache)
                     os.makedirs(os.path.dirname(f), exist_ok=True)
@@ -566,21 +605,22 @@ def check_close(got, ref, what, rtol, attribution=None, key=None, scale=None):
     return float(err.max()), nbad
 
 
-def compare(out, ref, name, case, stats=None, cache=None):
+def compare(out, ref, name, case, stats=None, cache=None, ref_is_oracle=True):
+    """`ref_is_oracle=False` where `ref` is not the oracle's output on `case` (Attribution)."""
     try:
-        return _compare(out, ref, name, case, stats, cache)
+        return _compare(out, ref, name, case, stats, cache, ref_is_oracle)
     finally:  # prefetched nudged runs nobody collected (every element within tolerance, or an assertion on the way): stop the workers
         leftover = _PREFETCH.pop(id(case), None)
         if leftover is not None:
             leftover[0].terminate()
 
 
-def _compare(out, ref, name, case, stats=None, cache=None):
+def _compare(out, ref, name, case, stats=None, cache=None, ref_is_oracle=True):
     """HIP outputs + gradients of one case against the oracle's. radii bit-exact; images and per-Gaussian gradients to
     RTOL (GRAD_RTOL for the stress fixtures); out-of-tolerance elements only where explained (check_close)."""
     assert np.array_equal(out["out_radii"].cpu().numpy(), np.asarray(ref["out_radii"])), f"{name}: radii differ"
     refs = {k: v for k, v in ref.items() if k.startswith(("out_", "g_"))}
-    att = Attribution(case, out, refs, cache=cache)
+    att = Attribution(case, out, refs, cache=cache, ref_is_oracle=ref_is_oracle)
     flips = 0
     # images first: gradients are only ever explained through decisions the images show
     keys = [k for k in out if k != "out_radii" and not k.startswith("_") and k != "g_viewmatrix"]
@@ -633,7 +673,7 @@ def _compare(out, ref, name, case, stats=None, cache=None):
               f"(magnitude sum / value = {scale / max(float(rt.abs().max()), 1e-30):.1f})")
         if err > lim and flips:
             # decisions moved somewhere in the image move these 16 global sums: the matched oracle run is the reference then
-            mt = torch.as_tensor(np.asarray(att.matched()[0]["g_viewmatrix"])).double()
+            mt = torch.as_tensor(np.asarray(att.matched()[0]["g_viewmatrix"], dtype=np.float64))
             err = min(err, float((v.cpu().double() - mt).abs().max()) / scale)
         if err > lim:
             # the [:3,:2] block comes from the covariance backward, the worst-conditioned part: the arbiter decides (check_close's

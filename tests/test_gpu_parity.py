@@ -532,25 +532,17 @@ def test_non_default_stream_and_strided_inputs(dev):
 
 
 # ---- raw-parameter front end (activations fused into the per-Gaussian kernels) ----
-def _close_all(a, b, name, means3D, rtol=1e-4):
-    assert torch.equal(a["out_radii"].cpu(), b["out_radii"].cpu()), f"{name}: radii differ"
-    for k in a:
-        if k == "out_radii":
-            continue
-        if k == "g_viewmatrix":
-            g2 = b["g_means2D"].abs().double().cpu()
-            m = means3D.abs().double().cpu()
-            scale = max(float((m.t() @ g2).max()), float(g2.sum(0).max()), 1e-30)
-            err = float((a[k].double().cpu() - b[k].double().cpu()).abs().max()) / scale
-            assert err <= 1e-4, f"{name}:{k}: {err:.3e} of the magnitude sum"
-            continue
-        assert_close(a[k], b[k], f"{name}:{k}", rtol=rtol, flip_floor=4)
+# Held to the same bar as every other path (parity_cases.compare: column check, support check, per-Gaussian pass; attribution
+# re-runs the oracle's RAW mode on the same inputs). `ref_is_oracle=False` where the reference side is another HIP path.
+def _np_out(res):
+    return {k: v.detach().cpu().numpy() for k, v in res.items() if torch.is_tensor(v) and not k.startswith("_")}
 
 
 @pytest.mark.parametrize("aa", [False, True])
 def test_fused_matches_unfused(dev, aa):
     """HIP raw-parameter path == the reference's PyTorch activation ops + the drop-in rasterizer (autograd chain)."""
-    from util import raw_params_from_scene, run_raw
+    from parity_cases import compare
+    from util import raw_case, raw_params_from_scene, run_raw_case
 
     from eogs2_amd.synthetic import make_scene
 
@@ -558,62 +550,58 @@ def test_fused_matches_unfused(dev, aa):
     scene = make_scene(P, H, W, seed=31, opacity="trained", device=dev, scale_mult=1.5)
     raw, alt = raw_params_from_scene(scene)
     dinv = torch.randn(1, H, W, device=dev) / (H * W)
-    a = run_raw(raw, alt, scene, H, W, aa, fused=True, dL_dinvdepth=dinv)
-    b = run_raw(raw, alt, scene, H, W, aa, fused=False, dL_dinvdepth=dinv)
-    _close_all(a, b, f"fused_vs_unfused_aa{int(aa)}", scene["means3D"])
+    case = raw_case(scene, raw, alt, H, W, aa, dL_dinvdepth=dinv)
+    a = run_raw_case(case, dev, fused=True)
+    b = run_raw_case(case, dev, fused=False)
+    compare(a, _np_out(b), f"fused_vs_unfused_aa{int(aa)}", case, ref_is_oracle=False)
     assert float(a["g_raw_rotation"].abs().max()) > 0 and float(a["g_log_scaling"].abs().max()) > 0
 
 
 def test_fused_matches_oracle(dev, monkeypatch):
     """HIP raw-parameter path == the oracle's restatement of the same front end (C, double-precision chain)."""
-    import oracle
-    from util import raw_params_from_scene, run_raw
+    from parity_cases import compare, oracle_run
+    from util import raw_case, raw_params_from_scene, run_raw_case
 
-    from eogs2_amd import _lib
     from eogs2_amd.synthetic import make_scene
 
     H, W, P = 96, 80, 3000
     scene = make_scene(P, H, W, seed=32, opacity="trained", scale_mult=2.0)
     raw, alt = raw_params_from_scene(scene)
-    to = lambda d: {k: v.to(dev) for k, v in d.items()}
-    a = run_raw(to(raw), alt.to(dev), to(scene), H, W, True, fused=True)
-    oabi = oracle.abi()
-    monkeypatch.setattr(_lib, "get", lambda: oabi)
-    b = run_raw(raw, alt, scene, H, W, True, fused=True)
-    monkeypatch.undo()
-    _close_all(a, b, "fused_vs_oracle", scene["means3D"])
+    case = raw_case(scene, raw, alt, H, W, True)
+    a = run_raw_case(case, dev, fused=True)
+    compare(a, oracle_run(case), "fused_vs_oracle", case)
 
 
 def test_render_entry_point(dev):
     """eogs2_amd.render.render (the reference's renderer.py signature): the fused path agrees with the unfused ops + drop-in rasterizer built in the test."""
-    import types
+    import numpy as np
 
-    from test_fused_cpu import _Cam, _Model
-    from util import raw_params_from_scene, render_unfused
+    from parity_cases import compare
+    from util import raw_params_from_scene, run_render_case
 
-    from eogs2_amd.render import render
     from eogs2_amd.synthetic import make_scene
 
     H, W, P = 200, 168, 20000
-    scene = make_scene(P, H, W, seed=33, opacity="trained", device=dev, scale_mult=1.5)
+    scene = make_scene(P, H, W, seed=33, opacity="trained", scale_mult=1.5)
     raw, _ = raw_params_from_scene(scene)
-    pipe = types.SimpleNamespace(debug=False, antialiasing=True, compute_cov3D_python=False, require_radii=True)
-    res = {}
-    for fused in (True, False):
-        cam, pc = _Cam(scene["viewmatrix"], H, W), _Model(raw)
-        cam.last_row = cam.last_row.detach().to(dev).requires_grad_(True)
-        cam.camera_center = cam.camera_center.to(dev)
-        out = render(cam, pc, pipe, scene["bg"]) if fused else render_unfused(cam, pc, pipe, scene["bg"])
-        (out["render"] * scene["dL_dcolor"]).sum().backward()
-        res[fused] = dict(render=out["render"].detach(), vsp=out["viewspace_points"].grad, last_row=cam.last_row.grad,
-                          **{k: v.grad for k, v in pc.params().items()})
-        assert torch.equal(out["visibility_filter"], (out["radii"] > 0).nonzero())
-    for k in res[True]:
-        if k == "last_row":
-            scale = float(res[False]["vsp"].abs().sum(0).max())
-            assert float((res[True][k] - res[False][k]).abs().max()) <= 1e-4 * scale
-        else:
-            assert_close(res[True][k], res[False][k], k, flip_floor=4)
+    # the camera of test_fused_cpu._Cam: affine = world_view_transform = full_proj_transform, a learned last row
+    n = lambda v: v.detach().cpu().numpy()
+    case = dict(H=H, W=W, antialiasing=True, learn_wv_only_lastparam=True, scaling_modifier=np.float32(1.0), FoVx=np.float32(1.0),
+                FoVy=np.float32(1.0), means3D=n(raw["xyz"]), f_dc=n(raw["f_dc"]), opacity_logit=n(raw["opacity_logit"]),
+                log_scaling=n(raw["log_scaling"]), raw_rotation=n(raw["raw_rotation"]), viewmatrix=n(scene["viewmatrix"]),
+                affine=n(scene["viewmatrix"]), last_row=np.array([0.01, -0.02, 0.03, 0.0], np.float32), bg=n(scene["bg"]),
+                dL_dcolor=n(scene["dL_dcolor"]), entry="render")
+    res = {fused: run_render_case(case, dev, fused=fused) for fused in (True, False)}
+    for r in res.values():
+        assert torch.equal(r["_visibility_filter"], (r["out_radii"] > 0).nonzero())
+        assert torch.equal(r["_g_last_row"], r["g_viewmatrix"][3])
+    # (the two paths take exp() of the log-scales differently — v_exp_f32 in the kernel, torch.exp —: a radius that sits on an
+    # integer may come out 1 px apart; seed 33 has one such Gaussian. Every other output goes through the bar.)
+    ref = _np_out(res[False])
+    dr = (res[True]["out_radii"] - res[False]["out_radii"]).abs()
+    assert int((dr != 0).sum()) <= 4 and int(dr.max()) <= 1, f"radii: {int((dr != 0).sum())} differ, by up to {int(dr.max())}"
+    ref["out_radii"] = res[True]["out_radii"].cpu().numpy()
+    compare(res[True], ref, "render_entry_point", case, ref_is_oracle=False)
 
 
 @pytest.mark.parametrize("P,H,W", [(1, 1, 1), (2, 1, 7), (70, 5, 3), (300, 8, 8), (65, 2, 33), (1, 40, 1)])

@@ -13,14 +13,17 @@ import pytest
 import torch
 
 from parity_cases import (ARB_ABS, ARB_FACTOR, PAIR_NOISE_DRAWS, SENS_ULPS, ULP, VIEW_ABS, arbiter, compare, fp32_variants, gaussian_grad_keys,
-                          oracle_run, quantity_scale, row_magnitude, seeded_case, sweep_case)
-from util import load_golden
+                          oracle_run, perturbed, quantity_scale, row_magnitude, seeded_case, sweep_case)
+from util import load_golden, load_render
 
 CASES = {
     "seed12": lambda: seeded_case(3000, 64, 64, 12, 0.7, 8.0, False, False)[0],
     "dense_termination": lambda: {k: v for k, v in load_golden("dense_termination").items() if not k.startswith(("out_", "g_"))},
     "seed11_aa_depth": lambda: seeded_case(5000, 160, 208, 11, "trained", 2.0, True, True)[0],
     "sweep4249": lambda: sweep_case(4249)[0],
+    # raw-parameter cases (the inputs of tests/golden/render/*.npz through eogs2_amd.render.render over the oracle's RAW mode)
+    "raw_aa_learn": lambda: load_render("aa_learn_61x83")[0],
+    "raw_edges": lambda: load_render("edges_41x53")[0],
 }
 _STATE = {}
 
@@ -171,21 +174,75 @@ def test_valid_fp32_evaluations_pass(cache_dir, name):
 # 68 elements — the column check without the row pass rejects that too; arbiter() counts only evaluations of the SAME inputs. There
 # the upstream gradient alone is perturbed: what the rounding of every pixel's term of a cancelling per-Gaussian sum does.)
 GAUSSIAN_INPUTS = ("means3D", "scales", "rotations", "opacities", "colors", "cov3D_precomp")
+RAW_INPUTS = ("means3D", "f_dc", "opacity_logit", "log_scaling", "raw_rotation")
 UPSTREAM = ("dL_dcolor", "dL_dinvdepth")
 
 
 @pytest.mark.parametrize("name,keys", [("seed12", GAUSSIAN_INPUTS + UPSTREAM), ("dense_termination", GAUSSIAN_INPUTS + UPSTREAM),
-                                       ("seed11_aa_depth", GAUSSIAN_INPUTS + UPSTREAM), ("sweep4249", UPSTREAM)], ids=lambda v: v if isinstance(v, str) else len(v))
+                                       ("seed11_aa_depth", GAUSSIAN_INPUTS + UPSTREAM), ("sweep4249", UPSTREAM),
+                                       ("raw_aa_learn", RAW_INPUTS + UPSTREAM), ("raw_edges", RAW_INPUTS + UPSTREAM)],
+                         ids=lambda v: v if isinstance(v, str) else len(v))
 def test_oracle_on_perturbed_inputs_passes(cache_dir, name, keys):
     """The oracle on inputs moved by SENS_ULPS ulp, drawn as arbiter() draws them (an fp32 evaluation is the exact result for
     inputs perturbed by a few ulp)."""
     case, ref = _case(name)
-    g = np.random.default_rng(1000)
-    pert = dict(case)
-    for k in keys:
-        if k in case:
-            v = np.asarray(case[k])
-            pert[k] = (v * (1.0 + SENS_ULPS * ULP * g.standard_normal(v.shape))).astype(np.float32)
-    res = oracle_run(pert)
+    res = oracle_run(perturbed(case, keys, np.random.default_rng(1000)))
     assert np.array_equal(res["out_radii"], ref["out_radii"])
     compare(_as_out(res), ref, f"{name} (inputs +-{SENS_ULPS:g} ulp)", case, cache=cache_dir(name))
+
+
+# ---- the raw-parameter path (SURVEY.md §8 row f1): its own gradient columns, planted into the oracle's RAW output -----------------
+# Rows whose largest entry is below 1e-4 of the column scales, restricted to those where the planted column carries at least 5 % of the
+# row's largest entry: every factor moves an element by at least 5e-5 of the row scale ... and by less than 1e-4 of its column's scale,
+# so only the per-Gaussian pass (":row") sees it. Before that pass the raw path was judged by util.assert_close alone.
+RAW_ROW_ERRORS = [(k, f) for k in ("g_log_scaling", "g_raw_rotation", "g_opacity_logit") for f in (1.05, 2.0, 0.0)]
+
+
+@pytest.mark.parametrize("key,factor", RAW_ROW_ERRORS, ids=[f"{k}x{f:g}" for k, f in RAW_ROW_ERRORS])
+def test_small_raw_rows_wrong_are_rejected(cache_dir, key, factor):
+    case, ref = _case("raw_aa_learn")
+    P = case["means3D"].shape[0]
+    rel = row_magnitude(ref, P).numpy()
+    own = (np.abs(ref[key]).reshape(P, -1) / quantity_scale(ref[key]).numpy().reshape(1, -1)).max(axis=1)
+    sel = (rel > 0) & (rel < 1e-4) & (own >= 0.05 * rel)
+    assert int(sel.sum()) >= 100
+    out = _as_out(ref)
+    out[key][torch.from_numpy(sel)] *= factor
+    msg = _rejects(out, ref, "raw_aa_learn", case, cache_dir("raw_aa_learn"))
+    assert f"{key}:row" in msg or "gradient support" in msg, msg
+
+
+def _activated_rotation_grad(case):
+    """dL/d(normalised quaternion) of a render case: the oracle on the activated inputs (what the reference's rasterizer sees)."""
+    t = lambda k: torch.from_numpy(np.asarray(case[k], dtype=np.float32))
+    xyz, A = t("means3D"), t("affine")
+    alt = (xyz @ A[:3, 2] + A[3, 2])[:, None]
+    vm = t("viewmatrix").clone()
+    if bool(case["learn_wv_only_lastparam"]):
+        vm[3] += t("last_row")
+    act = dict(means3D=xyz, scales=torch.exp(t("log_scaling")), rotations=torch.nn.functional.normalize(t("raw_rotation")),
+               opacities=torch.sigmoid(t("opacity_logit")),
+               colors=torch.cat([t("f_dc").squeeze(1) * 0.28209479177387814 + 0.5, alt, torch.ones_like(alt)], 1), viewmatrix=vm)
+    act = {k: v.contiguous().numpy() for k, v in act.items()}
+    act.update(bg=case["bg"], dL_dcolor=case["dL_dcolor"], H=case["H"], W=case["W"], antialiasing=case["antialiasing"],
+               scale_modifier=case["scaling_modifier"])
+    return oracle_run(act)["g_rotations"].astype(np.float64)
+
+
+def test_dropped_normalize_projection_is_rejected(cache_dir):
+    """On the edges case's quaternions of norm 3e-4 to 3e3 (rows 9-14, make_golden_render.EDGE_QUAT_NORM): dL/dq / |q| without the
+    projection (dL/dq - q^ (q^ . dL/dq)) / |q| that F.normalize's backward applies."""
+    case, ref = _case("raw_edges")
+    dq = _activated_rotation_grad(case)
+    r = np.asarray(case["raw_rotation"], dtype=np.float64)
+    n = np.linalg.norm(r, axis=1, keepdims=True)
+    rows = np.arange(9, 15)
+    assert np.all(np.abs(np.log10(n[rows, 0])) > 2.9)
+    qh = r / n
+    proj = (dq - qh * (qh * dq).sum(1, keepdims=True)) / n
+    # (the oracle's RAW gradient is the projected one on those rows)
+    assert np.allclose(ref["g_raw_rotation"][rows], proj[rows], rtol=1e-3, atol=1e-3 * np.abs(proj[rows]).max())
+    out = _as_out(ref)
+    out["g_raw_rotation"][torch.from_numpy(rows)] = torch.from_numpy((dq / n)[rows].astype(np.float32))
+    msg = _rejects(out, ref, "raw_edges", case, cache_dir("raw_edges"))
+    assert "g_raw_rotation" in msg, msg

@@ -172,17 +172,21 @@ def run_raw(raw, alt_affine, scene, H, W, antialiasing, fused, dL_dinvdepth=None
     return out
 
 
-def render_unfused(cam, pc, pipe, bg):
+def render_unfused(cam, pc, pipe, bg, scaling_modifier=1.0):
     """The unfused counterpart of `eogs2_amd.render.render` for tests: activations and the [rgb, altitude, 1] features as
     PyTorch ops (what gaussian_model.py:109-137 / renderer.py:88-96 compute), then the drop-in GaussianRasterizer."""
     import math
 
     from eogs2_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
 
-    vm = cam.world_view_transform.clone()
-    vm[3] = vm[3] + cam.last_row
-    rs = GaussianRasterizationSettings(int(cam.image_height), int(cam.image_width), math.tan(0.5), math.tan(0.5), bg, 1.0,
-                                       vm, vm, 0, cam.camera_center, False, pipe.debug, pipe.antialiasing)
+    vm, pm = cam.world_view_transform, cam.full_proj_transform
+    if cam.learn_wv_only_lastparam:  # renderer.py:47-53
+        vm, pm = vm.clone(), pm.clone()
+        vm[3] = vm[3] + cam.last_row
+        pm[3] = pm[3] + cam.last_row
+    rs = GaussianRasterizationSettings(int(cam.image_height), int(cam.image_width), math.tan(0.5 * cam.FoVx),
+                                       math.tan(0.5 * cam.FoVy), bg, scaling_modifier, vm, pm, 0, cam.camera_center, False,
+                                       pipe.debug, pipe.antialiasing)
     vsp = torch.zeros_like(pc._xyz, requires_grad=True)
     alt = cam.ECEF_to_UVA(pc._xyz)[:, 2:3]
     feats = torch.cat([pc._features_dc.squeeze(1) * SH_C0 + 0.5, alt, torch.ones_like(alt)], dim=1)
@@ -190,3 +194,98 @@ def render_unfused(cam, pc, pipe, bg):
                                            scales=pc.get_scaling, rotations=pc.get_rotation)
     return {"render": img, "viewspace_points": vsp, "radii": radii, "visibility_filter": torch.nonzero(radii > 0)}
 
+
+
+# ---- the reference's render() on raw parameters: tests/golden/render/*.npz (tests/golden/make_golden_render.py) ----
+RENDER_DIR = os.path.join(GOLDEN_DIR, "render")
+RENDER = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(RENDER_DIR, "*.npz")))
+# fixture output -> the name tests/parity_cases.py compare() knows it by
+RENDER_OUT = {"render": "out_color", "radii": "out_radii", "g_viewspace_points": "g_means2D", "g_xyz": "g_means3D"}
+
+
+def load_render(name):
+    """(case, expected) of a render fixture: the case in compare()'s terms (means3D = xyz, dL_dcolor = the upstream gradient
+    of "render", entry = "render": parity_cases.oracle_run re-runs it through `eogs2_amd.render.render`), the reference's
+    outputs under compare()'s names (plus _visibility_filter and, when the camera learns its last row, _g_last_row)."""
+    z = np.load(os.path.join(RENDER_DIR, name + ".npz"))
+    fx = {k: z[k] for k in z.files}
+    inputs = ("H", "W", "antialiasing", "learn_wv_only_lastparam", "scaling_modifier", "FoVx", "FoVy", "f_dc", "opacity_logit",
+              "log_scaling", "raw_rotation", "viewmatrix", "affine", "last_row", "bg")
+    case = {k: fx[k] for k in inputs}
+    case.update(means3D=fx["xyz"], dL_dcolor=fx["dL_drender"], entry="render")
+    expected = {RENDER_OUT.get(k, k): v for k, v in fx.items() if k not in inputs and k not in ("xyz", "dL_drender")}
+    for k in ("visibility_filter", "g_last_row"):  # (not per-Gaussian or image outputs: the tests check them beside compare())
+        if k in expected:
+            expected["_" + k] = expected.pop(k)
+    return case, expected
+
+
+class RawModel:
+    """The attributes of the reference's GaussianModel that render() reads, over raw-parameter leaves."""
+    active_sh_degree = 0
+
+    def __init__(self, xyz, f_dc, opacity_logit, log_scaling, raw_rotation):
+        leaf = lambda v: v.detach().clone().requires_grad_(True)
+        self._xyz, self._features_dc, self._opacity = leaf(xyz), leaf(f_dc), leaf(opacity_logit)
+        self._scaling, self._rotation = leaf(log_scaling), leaf(raw_rotation)
+
+    get_xyz = property(lambda s: s._xyz)
+    get_opacity = property(lambda s: torch.sigmoid(s._opacity))
+    get_scaling = property(lambda s: torch.exp(s._scaling))
+    get_rotation = property(lambda s: torch.nn.functional.normalize(s._rotation))
+
+
+def run_render_case(case, device, fused=True):
+    """A render case (load_render) through `eogs2_amd.render.render` (fused=False: render_unfused) and backward of
+    sum(render * dL_dcolor): outputs and gradients under compare()'s names. The world-to-view matrix is a leaf, so g_viewmatrix
+    is the whole camera gradient; _g_last_row is `last_row`'s when the camera learns it."""
+    import types
+
+    from eogs2_amd.render import render
+
+    t = lambda k: torch.from_numpy(np.array(case[k], dtype=np.float32, copy=True)).to(device)
+    learn = bool(case["learn_wv_only_lastparam"])
+    wvt = t("viewmatrix").requires_grad_(True)
+    cam = types.SimpleNamespace(FoVx=float(case["FoVx"]), FoVy=float(case["FoVy"]), world_view_transform=wvt,
+                                full_proj_transform=wvt.detach(), learn_wv_only_lastparam=learn,
+                                last_row=t("last_row").requires_grad_(learn), image_height=int(case["H"]),
+                                image_width=int(case["W"]), camera_center=torch.zeros(3, device=device), affine=t("affine"),
+                                image_name="fixture")
+    cam.ECEF_to_UVA = lambda xyz: xyz @ cam.affine[:3, :3] + cam.affine[3, :3]
+    pc = RawModel(t("means3D"), t("f_dc"), t("opacity_logit"), t("log_scaling"), t("raw_rotation"))
+    pipe = types.SimpleNamespace(debug=False, antialiasing=bool(case["antialiasing"]), compute_cov3D_python=False,
+                                 require_radii=True)
+    mod = float(case["scaling_modifier"])
+    out = render(cam, pc, pipe, t("bg"), mod) if fused else render_unfused(cam, pc, pipe, t("bg"), mod)
+    (out["render"] * t("dL_dcolor")).sum().backward()
+    res = dict(out_color=out["render"].detach(), out_radii=out["radii"], _visibility_filter=out["visibility_filter"],
+               g_means2D=out["viewspace_points"].grad, g_means3D=pc._xyz.grad, g_f_dc=pc._features_dc.grad,
+               g_opacity_logit=pc._opacity.grad, g_log_scaling=pc._scaling.grad, g_raw_rotation=pc._rotation.grad,
+               g_viewmatrix=wvt.grad)
+    if learn:
+        res["_g_last_row"] = cam.last_row.grad
+    return res
+
+
+def raw_case(scene, raw, alt_affine, H, W, antialiasing, dL_dinvdepth=None):
+    """The inputs of a `run_raw` call as a case for compare() (entry = "rasterize_raw": parity_cases.oracle_run re-runs it
+    through run_raw_case)."""
+    n = lambda v: v.detach().cpu().numpy()
+    case = dict(means3D=n(raw["xyz"]), f_dc=n(raw["f_dc"]), opacity_logit=n(raw["opacity_logit"]),
+                log_scaling=n(raw["log_scaling"]), raw_rotation=n(raw["raw_rotation"]), alt_affine=n(alt_affine),
+                viewmatrix=n(scene["viewmatrix"]), bg=n(scene["bg"]), dL_dcolor=n(scene["dL_dcolor"]), H=H, W=W,
+                antialiasing=bool(antialiasing), entry="rasterize_raw")
+    if dL_dinvdepth is not None:
+        case["dL_dinvdepth"] = n(dL_dinvdepth)
+    return case
+
+
+def run_raw_case(case, device, fused=True):
+    """run_raw on a raw_case: outputs and gradients under compare()'s names (g_xyz is g_means3D)."""
+    t = lambda k: torch.from_numpy(np.array(case[k], dtype=np.float32, copy=True)).to(device)
+    raw = {k: t("means3D" if k == "xyz" else k) for k in ("xyz", "f_dc", "opacity_logit", "log_scaling", "raw_rotation")}
+    scene = {k: t(k) for k in ("viewmatrix", "bg", "dL_dcolor")}
+    out = run_raw(raw, t("alt_affine"), scene, int(case["H"]), int(case["W"]), bool(case["antialiasing"]), fused,
+                  dL_dinvdepth=t("dL_dinvdepth") if "dL_dinvdepth" in case else None)
+    out["g_means3D"] = out.pop("g_xyz")
+    return out
