@@ -11,4 +11,6 @@ from .rasterizer import (  # noqa: F401
     NUM_CHANNELS,
 )
 
+from . import dsm_eval  # noqa: F401,E402  (DSM registration and MAE: eval/dsmr.py, eval/eval_dsm.py)
+
 __version__ = "0.1.0"

@@ -123,13 +123,24 @@ SIGNATURES = {
     "eogs_tsdf_prior_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
     "eogs_tsdf_prior": (_i, [_i, _i, _i, _p, _p, _p, _z, _p]),
     "eogs_tsdf_surface": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
+    # include/eogs_tsdf.h: DSM evaluation
+    "eogs_tsdf_dsm_downsample": (_i, [_i, _i, _p, _i, _p, _p]),
+    "eogs_tsdf_dsm_ncc_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+    "eogs_tsdf_dsm_ncc": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _z, _p]),
+    "eogs_tsdf_dsm_shift_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_z), C.POINTER(_i)]),
+    "eogs_tsdf_dsm_shift": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
+    "eogs_tsdf_dsm_apply_shift": (_i, [_i, _i, _p, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
+    "eogs_tsdf_dsm_mae_bytes": (_i, [C.POINTER(_z)]),
+    "eogs_tsdf_dsm_mae": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
 }
 # symbols only the HIP library exports (the CPU oracle of the loss is oracle/loss_oracle.py, not a C-ABI twin)
 HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
             "eogs_compact_plan", "eogs_compact_apply", "eogs_resample_forward", "eogs_resample_bytes", "eogs_resample_backward", "eogs_knn_bytes",
             "eogs_knn_mean_dist2", "eogs_shade_bytes", "eogs_shade_forward", "eogs_shade_backward", "eogs_mloss_forward",
             "eogs_mloss_backward", "eogs_tshadow_forward", "eogs_tshadow_backward", "eogs_tsdf_integrate", "eogs_tsdf_normals",
-            "eogs_tsdf_prior_bytes", "eogs_tsdf_prior", "eogs_tsdf_surface")
+            "eogs_tsdf_prior_bytes", "eogs_tsdf_prior", "eogs_tsdf_surface", "eogs_tsdf_dsm_downsample", "eogs_tsdf_dsm_ncc_bytes",
+            "eogs_tsdf_dsm_ncc", "eogs_tsdf_dsm_shift_bytes", "eogs_tsdf_dsm_shift", "eogs_tsdf_dsm_apply_shift",
+            "eogs_tsdf_dsm_mae_bytes", "eogs_tsdf_dsm_mae")
 
 
 class PackTensor(C.Structure):

@@ -64,12 +64,14 @@ int check_launch(hipStream_t s, bool debug, const char* what) {
 // ---- optional per-kernel-group timing with hipEvents on the launch stream ----
 enum { PS_PREPROCESS, PS_DEPTH_SORT, PS_BINNING, PS_RENDER_FWD, PS_RENDER_BWD, PS_GAUSS_BWD, PS_LOSS_FWD, PS_LOSS_BWD, PS_ADAM,
        PS_COMPACT, PS_RESAMPLE_FWD, PS_RESAMPLE_BWD, PS_KNN, PS_SHADE_FWD, PS_SHADE_BWD, PS_MLOSS_FWD, PS_MLOSS_BWD, PS_TSDF,
-       PS_TSDF_NORMALS, PS_TSDF_PRIOR, PS_TSDF_SURFACE, PS_COUNT };
+       PS_TSDF_NORMALS, PS_TSDF_PRIOR, PS_TSDF_SURFACE, PS_DSM_DOWNSAMPLE, PS_DSM_PIVOTS, PS_DSM_MOMENTS, PS_DSM_FINALIZE,
+       PS_DSM_APPLY, PS_DSM_MAE, PS_COUNT };
 static_assert(PS_COUNT <= 32, "eogs_rast_profile_select takes a 32-bit slot mask");
 const char* const kSlotNames[PS_COUNT] = {"preprocess_fwd", "depth_sort", "binning", "render_fwd", "render_bwd", "gaussian_bwd",
                                           "loss_fwd", "loss_bwd", "adam", "compact", "resample_fwd", "resample_bwd", "knn",
                                           "shade_fwd", "shade_bwd", "mloss_fwd", "mloss_bwd", "tsdf",
-                                          "tsdf_normals", "tsdf_prior", "tsdf_surface"};
+                                          "tsdf_normals", "tsdf_prior", "tsdf_surface", "dsm_downsample", "dsm_pivots",
+                                          "dsm_moments", "dsm_finalize", "dsm_apply_shift", "dsm_mae"};
 struct Pending { int slot; hipEvent_t a, b; };
 // process-wide (autograd runs backward on its own thread), guarded by g_prof_mu
 std::mutex g_prof_mu;
@@ -958,6 +960,162 @@ int eogs_tsdf_surface(int nx, int ny, int nz, const float* tsdf_vol, const float
   hipStream_t s = (hipStream_t)stream;
   { ProfScope ps(PS_TSDF_SURFACE, s); launch_tsdf_surface(nx, ny, nz, tsdf_vol, az, index, height, s); }
   LAUNCH_TRY(s, false, "tsdf_surface");
+  return EOGS_OK;
+}
+
+}  // extern "C"
+
+// ---- include/eogs_tsdf.h: DSM evaluation (dsm_eval.hip) ----
+namespace {
+
+int dsm_check_pair(const char* what, int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int irange) {
+  if (Hu <= 0 || Wu <= 0 || Hv <= 0 || Wv <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", what);
+  if (Hv < Hu || Wv < Wu) return fail(EOGS_ERR_INVALID_ARG, "%s: the image to register is smaller than the reference image", what);
+  if ((uint64_t)Hv * Wv > ((uint64_t)1 << 31)) return fail(EOGS_ERR_OVERFLOW, "%s: image too large", what);
+  if (irange < 0 || irange > EOGS_TSDF_DSM_MAX_IRANGE) return fail(EOGS_ERR_INVALID_ARG, "%s: irange outside 0 .. 8", what);
+  if (!u || !v) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", what);
+  return EOGS_OK;
+}
+
+// one level: pivots, the moments of every shift, their sum, the NCC table and its winner
+void dsm_search(int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int f64, int irange, const int32_t* centre,
+                int centre_scale, double* table, eogs_tsdf_dsm_result* result, const DsmNccWS& w, hipStream_t s) {
+  { ProfScope ps(PS_DSM_PIVOTS, s); launch_dsm_pivots((int64_t)Hu * Wu, u, (int64_t)Hv * Wv, v, f64, w.pivots, s); }
+  { ProfScope ps(PS_DSM_MOMENTS, s); launch_dsm_moments(Hu, Wu, u, Wv, v, f64, irange, centre, centre_scale, w, s); }
+  { ProfScope ps(PS_DSM_FINALIZE, s); launch_dsm_finalize(irange, centre, centre_scale, w, table, result, s); }
+}
+
+struct DsmShiftWS {
+  int levels;
+  int hu[DSM_MAX_LEVELS], wu[DSM_MAX_LEVELS], hv[DSM_MAX_LEVELS], wv[DSM_MAX_LEVELS];
+  double *pu[DSM_MAX_LEVELS], *pv[DSM_MAX_LEVELS];  // float64 pyramid levels 1 .. levels-1 ([0] is the caller's image)
+  char* ncc;
+  size_t bytes;
+};
+DsmShiftWS dsm_shift_layout(char* base, int Hu, int Wu, int Hv, int Wv, int irange) {
+  DsmShiftWS w;
+  w.levels = 1;
+  w.hu[0] = Hu; w.wu[0] = Wu; w.hv[0] = Hv; w.wv[0] = Wv;
+  w.pu[0] = w.pv[0] = nullptr;
+  size_t off = 0;
+  while ((Hu < Wu ? Hu : Wu) > 100 && w.levels < DSM_MAX_LEVELS) {  // dsmr.py:168
+    Hu = (Hu + 1) / 2; Wu = (Wu + 1) / 2; Hv = (Hv + 1) / 2; Wv = (Wv + 1) / 2;
+    const int k = w.levels++;
+    w.hu[k] = Hu; w.wu[k] = Wu; w.hv[k] = Hv; w.wv[k] = Wv;
+    off = ws_carve(base, off, w.pu[k], (size_t)Hu * Wu);
+    off = ws_carve(base, off, w.pv[k], (size_t)Hv * Wv);
+  }
+  off = ws_align(off);
+  w.ncc = base ? base + off : nullptr;
+  w.bytes = off + dsm_ncc_layout(nullptr, w.hu[0], w.wu[0], irange).bytes + 256;
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eogs_tsdf_dsm_downsample(int H, int W, const void* in, int f64, double* out, void* stream) {
+  g_err[0] = 0;
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "dsm_downsample: bad sizes");
+  if ((uint64_t)H * W > ((uint64_t)1 << 31)) return fail(EOGS_ERR_OVERFLOW, "dsm_downsample: image too large");
+  if (!in || !out) return fail(EOGS_ERR_INVALID_ARG, "dsm_downsample: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_DSM_DOWNSAMPLE, s); launch_dsm_downsample(H, W, in, f64, out, s); }
+  LAUNCH_TRY(s, false, "dsm_downsample");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_ncc_bytes(int Hu, int Wu, int irange, size_t* bytes) {
+  g_err[0] = 0;
+  if (Hu <= 0 || Wu <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_ncc_bytes: bad argument");
+  if (irange < 0 || irange > EOGS_TSDF_DSM_MAX_IRANGE) return fail(EOGS_ERR_INVALID_ARG, "dsm_ncc_bytes: irange outside 0 .. 8");
+  *bytes = dsm_ncc_layout(nullptr, Hu, Wu, irange).bytes;
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_ncc(int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int f64, int irange, const int32_t* centre,
+                      int centre_scale, double* table, eogs_tsdf_dsm_result* result, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  const int rc = dsm_check_pair("dsm_ncc", Hu, Wu, u, Hv, Wv, v, irange);
+  if (rc != EOGS_OK) return rc;
+  if (!result || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_ncc: NULL argument");
+  if (ws_bytes < dsm_ncc_layout(nullptr, Hu, Wu, irange).bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_ncc: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  dsm_search(Hu, Wu, u, Hv, Wv, v, f64, irange, centre, centre_scale, table, result, dsm_ncc_layout(ws_base(ws), Hu, Wu, irange), s);
+  LAUNCH_TRY(s, false, "dsm_ncc");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_shift_bytes(int Hu, int Wu, int Hv, int Wv, int irange, size_t* bytes, int* levels) {
+  g_err[0] = 0;
+  if (Hu <= 0 || Wu <= 0 || Hv < Hu || Wv < Wu || !bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_shift_bytes: bad argument");
+  if (irange < 0 || irange > EOGS_TSDF_DSM_MAX_IRANGE) return fail(EOGS_ERR_INVALID_ARG, "dsm_shift_bytes: irange outside 0 .. 8");
+  const DsmShiftWS w = dsm_shift_layout(nullptr, Hu, Wu, Hv, Wv, irange);
+  *bytes = w.bytes;
+  if (levels) *levels = w.levels;
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_shift(int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int f64, int irange, double* tables,
+                        eogs_tsdf_dsm_result* results, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  const int rc = dsm_check_pair("dsm_shift", Hu, Wu, u, Hv, Wv, v, irange);
+  if (rc != EOGS_OK) return rc;
+  if (!results || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_shift: NULL argument");
+  const DsmShiftWS w = dsm_shift_layout(ws_base(ws), Hu, Wu, Hv, Wv, irange);
+  if (ws_bytes < w.bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_shift: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int n = 2 * irange + 1;
+  {
+    ProfScope ps(PS_DSM_DOWNSAMPLE, s);
+    for (int k = 1; k < w.levels; k++) {
+      const int src64 = k == 1 ? f64 : 1;
+      launch_dsm_downsample(w.hu[k - 1], w.wu[k - 1], k == 1 ? u : (const void*)w.pu[k - 1], src64, w.pu[k], s);
+      launch_dsm_downsample(w.hv[k - 1], w.wv[k - 1], k == 1 ? v : (const void*)w.pv[k - 1], src64, w.pv[k], s);
+    }
+  }
+  for (int k = w.levels - 1; k >= 0; k--) {
+    // recursive_ncc halves (0, 0) on its way down (dx // 2, dsmr.py:171-172): the coarsest level searches around (0, 0)
+    const int32_t* centre = k == w.levels - 1 ? nullptr : &results[k + 1].dx;
+    dsm_search(w.hu[k], w.wu[k], k == 0 ? u : (const void*)w.pu[k], w.hv[k], w.wv[k], k == 0 ? v : (const void*)w.pv[k],
+               k == 0 ? f64 : 1, irange, centre, 2, tables ? tables + (size_t)k * n * n : nullptr, results + k,
+               dsm_ncc_layout(w.ncc, w.hu[k], w.wu[k], irange), s);
+  }
+  LAUNCH_TRY(s, false, "dsm_shift");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_apply_shift(int H, int W, const void* in, int f64, int dx, int dy, double a, double b, double c, double d,
+                              void* out, void* stream) {
+  g_err[0] = 0;
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "dsm_apply_shift: bad sizes");
+  if ((uint64_t)H * W > ((uint64_t)1 << 31)) return fail(EOGS_ERR_OVERFLOW, "dsm_apply_shift: image too large");
+  if (!in || !out || in == out) return fail(EOGS_ERR_INVALID_ARG, "dsm_apply_shift: NULL or aliased argument");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_DSM_APPLY, s); launch_dsm_apply_shift(H, W, in, f64, dx, dy, a, b, c, d, out, s); }
+  LAUNCH_TRY(s, false, "dsm_apply_shift");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_mae_bytes(size_t* bytes) {
+  g_err[0] = 0;
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_mae_bytes: NULL argument");
+  *bytes = dsm_mae_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_mae(int Hp, int Wp, void* pred, int Hg, int Wg, const void* gt, int f64, int clip_finite, void* diff, double* out,
+                      void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (Hp <= 0 || Wp <= 0 || Hg <= 0 || Wg <= 0) return fail(EOGS_ERR_INVALID_ARG, "dsm_mae: bad sizes");
+  if ((uint64_t)Hp * Wp > ((uint64_t)1 << 31) || (uint64_t)Hg * Wg > ((uint64_t)1 << 31))
+    return fail(EOGS_ERR_OVERFLOW, "dsm_mae: image too large");
+  if (!pred || !gt || !diff || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_mae: NULL argument");
+  if (ws_bytes < dsm_mae_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "dsm_mae: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_DSM_MAE, s); launch_dsm_mae(Hp, Wp, pred, Hg, Wg, gt, f64, clip_finite, diff, out, ws, s); }
+  LAUNCH_TRY(s, false, "dsm_mae");
   return EOGS_OK;
 }
 

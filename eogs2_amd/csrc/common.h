@@ -648,6 +648,30 @@ size_t tsdf_prior_ws_bytes(int nx, int ny, int nz);
 void launch_tsdf_prior(int nx, int ny, int nz, float* tsdf, float* wvol, void* ws, hipStream_t s);
 void launch_tsdf_surface(int nx, int ny, int nz, const float* tsdf, const float* az, int64_t* index, float* height, hipStream_t s);
 
+// ---- DSM evaluation (dsm_eval.hip, include/eogs_tsdf.h eogs_tsdf_dsm_*) ----
+#define DSM_TILE_W 64      // pixels of the reference image per tile of the NCC search
+#define DSM_TILE_H 16
+#define DSM_MOMENTS 6      // count, sum u', sum v', sum u'^2, sum v'^2, sum u'v' per shift
+#define DSM_MAX_GRID 1024  // workgroups of the search and of the reductions (4 per CU): a function of the shape alone
+#define DSM_MAX_LEVELS 32
+struct DsmNccWS {
+  double *pivots, *moments, *partials;  // [2], [n*n][6], [n*n][6][P]
+  int tiles_x, num_tiles, grid, P;
+  size_t bytes;
+};
+DsmNccWS dsm_ncc_layout(char* base, int Hu, int Wu, int irange);
+void launch_dsm_downsample(int H, int W, const void* in, int f64, double* out, hipStream_t s);
+void launch_dsm_pivots(int64_t nu, const void* u, int64_t nv, const void* v, int f64, double* pivots, hipStream_t s);
+void launch_dsm_moments(int Hu, int Wu, const void* u, int Wv, const void* v, int f64, int irange, const int* centre,
+                        int centre_scale, const DsmNccWS& ws, hipStream_t s);
+void launch_dsm_finalize(int irange, const int* centre, int centre_scale, const DsmNccWS& ws, double* table,
+                         eogs_tsdf_dsm_result* result, hipStream_t s);
+void launch_dsm_apply_shift(int H, int W, const void* in, int f64, int dx, int dy, double a, double b, double c, double d, void* out,
+                            hipStream_t s);
+size_t dsm_mae_ws_bytes();
+void launch_dsm_mae(int Hp, int Wp, void* pred, int Hg, int Wg, const void* gt, int f64, int finite_only, void* diff, double* out,
+                    void* ws, hipStream_t s);
+
 // ---- 3-nearest-neighbour statistic (knn.hip, include/eogs_knn.h) ----
 struct KnnWS {
   uint32_t *keyA, *keyB, *valA, *valB, *hist, *dtotal;  // Morton sort ping-pong + radix histograms

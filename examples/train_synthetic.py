@@ -30,7 +30,8 @@ from eogs2_amd.render import render  # noqa: E402
 from eogs2_amd.graph import Branches  # noqa: E402
 from eogs2_amd.resample import render_resample_virtual_camera, resample  # noqa: E402
 from eogs2_amd.shade import randomcam_l, render_pipeline, suncamera_l, translucentshadows_l  # noqa: E402
-from eogs2_amd.synthetic import make_camera, make_scene  # noqa: E402
+from eogs2_amd.dsm_eval import dsm_mae  # noqa: E402
+from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
 C0 = 0.28209479177387814
@@ -108,6 +109,14 @@ def main(argv=None):
                     help="pipe.require_radii: every render also returns radii and `visibility_filter` = nonzero(radii > 0), which waits "
                          "for the device (renderer.py:128-130). The reference's shipped configuration has it OFF "
                          "(gs_config/train.yaml:39: require_radii = not only_prune, only_prune: True): off by default here too")
+    ap.add_argument("--dsm-mae-every", type=int, default=0, metavar="N",
+                    help="every N iterations score the altitude channel of the view's render as a DSM against the altitude render of "
+                         "the unperturbed scene (the one that provides the target image): the reference's NCC registration, shift "
+                         "and MAE (eogs2_amd.dsm_eval.dsm_mae; eval/dsmr.py, eval/eval_dsm.py:56-69), printed as `iteration dx dy mae` "
+                         "and kept in main.last_dsm_mae (beside main.last_ms_per_iter: the returned tuple stays (first loss, last loss, "
+                         "Gaussians), which callers compare between runs). Unit: the altitude channel is xyz @ affine[:3, 2] + affine[3, 2] "
+                         f"(eogs2_amd/render.py), which for the synthetic Nadir camera is synthetic.ALT_SCALE ({ALT_SCALE:g}) x the scene's "
+                         "normalised z, alpha-composited over bg[3]; divide the MAE by ALT_SCALE for normalised z. 0 = off")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     P, H, W = a.gaussians, a.size, a.size
@@ -175,7 +184,10 @@ def main(argv=None):
     target_model = Gaussians(sc["means3D"], sc["colors"][:, :3], sc["opacities"].squeeze(1).clamp(1e-4, 1 - 1e-4),
                              sc["scales"], sc["rotations"])
     with torch.no_grad():
-        gt = view(target_model, colour_camera(0.0))[5]["final"].clone()
+        target_view = view(target_model, colour_camera(0.0))
+        gt = target_view[5]["final"].clone()
+        gt_altitude = target_view[0]["render"][3].clone() if a.dsm_mae_every else None
+        del target_view
     cc_cam = colour_camera(0.15)
     camera_optimizer = torch.optim.Adam([*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction], lr=2e-3)
 
@@ -199,8 +211,11 @@ def main(argv=None):
             L_new_alt, L_new_rgb = randomcam_l(new[0], img, new[1], new[2])
             loss = loss + 1e-4 * L_new_alt + 1e-3 * L_new_rgb
         loss.backward()
+        if a.dsm_mae_every:
+            kept["altitude"] = out["render"][3].detach()  # (under --graph: the recorded step's output tensor, refilled by a replay)
         return loss.detach(), out.get("radii")
 
+    kept, dsm_scores = {}, []  # --dsm-mae-every: the view's altitude of the last step; (iteration, dx, dy, mae)
     first = last = None
     step, stale = None, False  # the recorded graph of fwd_bwd; stale: recorded for parameter tensors that a prune replaced
     torch.cuda.synchronize()
@@ -240,6 +255,11 @@ def main(argv=None):
                 elif not bool(keep.all()):
                     model.prune(keep)
                     stale = True  # new parameter tensors, new shapes: record again
+        if a.dsm_mae_every and it % a.dsm_mae_every == 0:
+            mae, _, _, (sdx, sdy, _, _) = dsm_mae(kept["altitude"], gt_altitude)
+            dsm_scores.append((it, sdx, sdy, mae))
+            if not a.quiet:
+                print(f"iter {it:4d}  DSM registration dx {sdx} dy {sdy}  MAE {mae:.5f} (altitude units = {ALT_SCALE:g} x normalised z)")
         if it == 1 or it % 25 == 0 or it == a.iters:
             v = float(loss)
             first = v if first is None else first
@@ -251,6 +271,7 @@ def main(argv=None):
     t1 = time.perf_counter()
     dt = t1 - t0
     main.last_ms_per_iter = (t1 - t_steady) / timed * 1e3  # steady state: the last half of the run
+    main.last_dsm_mae = dsm_scores
     if not a.quiet:
         print(f"{a.iters} iterations in {dt:.2f} s ({dt / a.iters * 1e3:.2f} ms/iter over all, {main.last_ms_per_iter:.2f} ms/iter over the "
               f"last {timed}; {3 if a.random_camera else 2} renders + resample + render pipeline + losses + Adam each)")
