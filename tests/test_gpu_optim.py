@@ -315,3 +315,327 @@ def test_sum_into_equals_the_sequence_of_adds(dev):
     with pytest.raises(RuntimeError):
         sum_into_([base[0]], [[base[3]]])  # sizes differ
     sum_into_([], [])  # nothing to do
+
+
+# ---- the reference's own lifecycle (tests/golden/optim/*.npz, from its GaussianModel) ----
+import numpy as np  # noqa: E402
+
+import optim_cases as oc  # noqa: E402
+
+
+@pytest.mark.parametrize("name", sorted(oc.CASES))
+def test_lifecycle_matches_the_reference_fixture(dev, name):
+    """Every stage of the fixture on the device with FusedAdam, prune_optimizer, densify_and_clone, densify_and_split and
+    reset_opacity, fed the hashed gradients, the stored masks and the recorded normal draw (optim_cases.replay).
+
+    Structural stages run on the fixture's pre-stage state. What they only move (kept and cloned rows, both moments, the zero
+    moments of new rows, step, the id column, the statistics, the repeated rows of a split) equals the reference bit for bit;
+    a split's new positions and log-scales and the reset's logits go through exp / log / sigmoid / a 3x3 product and are held to
+    the fixture's float64 arrays within max(4 x the reference's own fp32-to-float64 distance for the array, 4 ulp). Adam
+    stretches are held to the float64 arrays within max(2e-6 of the tensor's scale, 4 x that distance) per tensor. Every
+    mask recomputed from the device-side state equals the stored one on every row."""
+    from eogs2_amd import optim
+
+    log = []
+    try:
+        oc.replay(oc.Fixture(name), dev, optim.FusedAdam, optim, exact=False, log=log)
+    finally:
+        print("\n".join(log))
+
+
+# ---- one step from a given state, every element against float64 ----
+def _checked_step(opt, factor=oc.FACTOR_KERNEL):
+    """One `opt.step()`; every element of every parameter and moment against torch's formula in float64 from the state the
+    device held before the step, within `factor` x optim_cases.adam_step_bound. A parameter without a gradient keeps its bits
+    and its step."""
+    pre = []
+    for g in opt.param_groups:
+        for p in g["params"]:
+            st = opt.state.get(p) or {}
+            z = torch.zeros(p.shape)
+            pre.append((g, p, p.detach().cpu().clone(), None if p.grad is None else p.grad.detach().cpu().clone(),
+                        st["exp_avg"].cpu().clone() if st else z, st["exp_avg_sq"].cpu().clone() if st else z.clone(),
+                        int(st["step"]) if st else 0))
+    opt.step()
+    worst = 0.0
+    for g, p, p0, g0, m0, v0, t0 in pre:
+        st = opt.state.get(p) or {}
+        if g0 is None:
+            assert torch.equal(p.detach().cpu(), p0) and (int(st["step"]) if st else 0) == t0
+            if st:
+                assert torch.equal(st["exp_avg"].cpu(), m0) and torch.equal(st["exp_avg_sq"].cpu(), v0)
+            continue
+        assert int(st["step"]) == t0 + 1
+        args = (p0, g0, m0, v0, float(g["lr"]), g["betas"], g["eps"], t0 + 1)
+        want, bound = oc.adam_step_f64(*args), oc.adam_step_bound(*args)
+        for what, got, w, b in (("exp_avg", st["exp_avg"], want[1], bound[0]), ("exp_avg_sq", st["exp_avg_sq"], want[2], bound[1]),
+                                ("param", p.detach(), want[0], bound[2])):
+            if not w.numel():
+                continue
+            r = (got.cpu().double() - w).abs() / b
+            worst = max(worst, float(r.max()))
+            assert float(r.max()) <= factor, (g.get("name"), what, int(r.argmax()), float(r.max()))
+        if float(g["lr"]) == 0.0:
+            assert torch.equal(p.detach().cpu(), p0)
+    return worst
+
+
+@pytest.mark.parametrize("eps", oc.ADAM_GRID_EPS)
+@pytest.mark.parametrize("step", oc.ADAM_GRID_STEPS)
+def test_fused_adam_one_step_elementwise(dev, step, eps):
+    """The grid of optim_cases: step 1..30000 (bias corrections), |g| from 1e-20 (g^2 subnormal) to 1e15, a third of the
+    gradients zero, moments from zero to 1e3 x the gradient scale, both eps. Bound: optim_cases.adam_step_bound, derived
+    from the roundings of the formula, x FACTOR_KERNEL = 2 (the kernel's constants are rounded to fp32 before the launch)."""
+    from eogs2_amd.optim import FusedAdam
+
+    worst = [0.0, 0.0, 0.0]
+    for gscale in oc.ADAM_GRID_GSCALE:
+        r = oc.adam_check_one_step(FusedAdam, dev, step, gscale, eps, oc.FACTOR_KERNEL)
+        worst = [max(a, b) for a, b in zip(worst, r)]
+    print(f"step {step} eps {eps:g}: worst error / bound m {worst[0]:.3f} v {worst[1]:.3f} p {worst[2]:.3f}")
+
+
+def test_fused_adam_squared_gradient_overflow(dev):
+    """|g| = 1e20: g^2 overflows fp32. Like torch.optim.Adam in fp32 on the device the reference trains on (its kernels
+    square the gradient before they scale it by 1 - beta2): v = +inf, the update 0, the parameter's bits unchanged, on both
+    sides. (torch's CPU kernel scales first, (1 - beta2) g g = 1e37, and does not overflow here; it is not the comparison.)"""
+    from eogs2_amd.optim import FusedAdam
+
+    p, g, m, v = oc.adam_grid_state(1.0, n=1029, seed=3)
+    g = torch.where(torch.arange(1029) % 2 == 0, 1e20, -1e20).float()
+    out = []
+    for cls in (torch.optim.Adam, FusedAdam):
+        par = torch.nn.Parameter(p.clone().to(dev))
+        opt = cls([{"params": [par], "lr": 1e-2}], lr=0.0, eps=1e-15)
+        opt.state[par] = {"step": torch.tensor(9.0), "exp_avg": m.clone().to(dev), "exp_avg_sq": v.clone().to(dev)}
+        par.grad = g.clone().to(dev)
+        opt.step()
+        assert int(opt.state[par]["step"]) == 10
+        out.append((par.detach().cpu(), opt.state[par]["exp_avg"].cpu(), opt.state[par]["exp_avg_sq"].cpu()))
+    (pr, mr, vr), (po, mo, vo) = out
+    assert torch.equal(pr, p) and torch.equal(po, p)
+    assert bool(torch.isposinf(vr).all()) and bool(torch.isposinf(vo).all())
+    assert bool(((mo.double() - mr.double()).abs() <= 4 * oc.U * mr.double().abs()).all())
+
+
+def _plain(sizes, d, seed=0, **group_kw):
+    g = torch.Generator().manual_seed(seed)
+    return [dict({"params": [torch.nn.Parameter(torch.randn(n, generator=g).to(d))], "lr": 1e-2 * (1 + i % 3), "name": f"t{i}"},
+                 **{k: v[i % len(v)] for k, v in group_kw.items()}) for i, n in enumerate(sizes)]
+
+
+def _rand_grads(opt, gen, scale=1.0, skip=()):
+    for i, gr in enumerate(opt.param_groups):
+        p = gr["params"][0]
+        p.grad = None if i in skip else (torch.randn(p.shape, generator=gen) * scale + 0.01).to(p.device)
+
+
+@pytest.mark.parametrize("numel", [1, 3, 4, 5, 1023, 1024, 1025, 4097])
+def test_fused_adam_vector_path_tail_and_workgroup_edge(dev, numel):
+    from eogs2_amd.optim import FusedAdam
+
+    opt = FusedAdam(_plain([numel], dev, seed=numel), lr=0.0, eps=1e-15)
+    gen = torch.Generator().manual_seed(numel + 1)
+    for it in range(4):
+        _rand_grads(opt, gen, 10.0 ** (it - 2))
+        _checked_step(opt)
+
+
+@pytest.mark.parametrize("off_p,off_g,off_m,off_v", [(1, 0, 0, 0), (0, 2, 0, 0), (0, 0, 3, 0), (0, 0, 0, 1), (1, 2, 3, 1), (3, 3, 3, 3)])
+def test_fused_adam_unaligned_views_touch_nothing_else(dev, off_p, off_g, off_m, off_v):
+    """Parameter, gradient or moments that start one, two or three floats into a larger buffer (the scalar path): right
+    values, and the guard values either side of every buffer stay as they were."""
+    from eogs2_amd.optim import FusedAdam
+
+    n, pad, guard = 1030, 8, 12345.0
+    gen = torch.Generator().manual_seed(off_p * 64 + off_g * 16 + off_m * 4 + off_v)
+    bufs = {}
+    for k, off in (("p", off_p), ("g", off_g), ("m", off_m), ("v", off_v)):
+        b = torch.full((n + 2 * pad,), guard)
+        x = torch.randn(n, generator=gen)
+        b[pad + off:pad + off + n] = x.abs() if k == "v" else x
+        bufs[k] = (b.to(dev), off)
+    view = lambda k: bufs[k][0][pad + bufs[k][1]:pad + bufs[k][1] + n]
+    par = torch.nn.Parameter(view("p"))
+    assert par.data_ptr() == view("p").data_ptr()
+    opt = FusedAdam([{"params": [par], "lr": 1e-2, "name": "x"}], lr=0.0, eps=1e-15)
+    opt.state[par] = {"step": torch.tensor(3.0), "exp_avg": view("m"), "exp_avg_sq": view("v")}
+    for _ in range(2):
+        view("g").copy_(torch.randn(n, generator=gen).to(dev) + 0.01)
+        par.grad = view("g")
+        _checked_step(opt)
+    for k, (b, off) in bufs.items():
+        outside = torch.cat((b[:pad + off], b[pad + off + n:]))
+        assert bool((outside == guard).all()), k
+    assert opt.state[par]["exp_avg"].data_ptr() == view("m").data_ptr()
+
+
+@pytest.mark.parametrize("n_groups", [17, 33])
+def test_fused_adam_more_tensors_than_one_launch(dev, n_groups):
+    """More single-tensor groups than EOGS_ADAM_MAX_TENSORS = 16 in one step(), mixed sizes, empty tensors in the middle."""
+    from eogs2_amd.optim import FusedAdam
+
+    sizes = [(5, 0, 1024, 3, 4097, 0, 1, 70_001, 256, 1025, 2)[i % 11] for i in range(n_groups)]
+    opt = FusedAdam(_plain(sizes, dev, seed=n_groups), lr=0.0, eps=1e-15)
+    gen = torch.Generator().manual_seed(5)
+    for _ in range(3):
+        _rand_grads(opt, gen)
+        _checked_step(opt)
+    assert all(int(opt.state[g["params"][0]]["step"]) == 3 for g in opt.param_groups)
+
+
+def test_fused_adam_groups_with_their_own_betas_eps_and_steps(dev):
+    """Two betas and two eps in one optimizer; a parameter without a gradient stays untouched with its step not advanced,
+    so groups sit at different steps; a learning rate changed between steps; a group with lr 0 (bits unchanged, moments
+    advance); a non-contiguous gradient."""
+    from eogs2_amd.optim import FusedAdam
+
+    groups = _plain([1000, 1000, 777, 777, 4099, 64], dev, seed=8, betas=[(0.9, 0.999), (0.8, 0.99)], eps=[1e-15, 1e-15, 1e-8])
+    groups[5]["lr"] = 0.0
+    opt = FusedAdam(groups, lr=0.0)
+    gen = torch.Generator().manual_seed(9)
+    for it in range(5):
+        _rand_grads(opt, gen, skip=(2,) if it in (1, 2) else (4,) if it == 3 else ())
+        wide = torch.randn(1000, 2, generator=gen).to(dev)
+        opt.param_groups[1]["params"][0].grad = wide[:, 0]
+        assert not wide[:, 0].is_contiguous()
+        if it == 2:
+            opt.param_groups[0]["lr"] = 3e-5
+        m_before = opt.state[opt.param_groups[5]["params"][0]]["exp_avg"].clone() if it else None
+        _checked_step(opt)
+        if it:
+            assert not torch.equal(m_before, opt.state[opt.param_groups[5]["params"][0]]["exp_avg"])
+    assert [int(opt.state[g["params"][0]]["step"]) for g in opt.param_groups] == [5, 5, 3, 5, 4, 5]
+
+
+@pytest.mark.parametrize("kw", [{"amsgrad": True}, {"weight_decay": 0.1}, {"maximize": True}])
+def test_fused_adam_refuses_what_it_does_not_implement(dev, kw):
+    from eogs2_amd.optim import FusedAdam
+
+    opt = FusedAdam(_plain([8], dev), lr=0.0)
+    opt.param_groups[0].update(kw)
+    opt.param_groups[0]["params"][0].grad = torch.ones(8, device=dev)
+    with pytest.raises(NotImplementedError):
+        opt.step()
+
+
+def test_fused_adam_headline_size(dev):
+    """The six groups at P = 1,048,576, three steps: thousands of workgroups per tensor through the first_block table."""
+    from eogs2_amd.optim import FusedAdam
+
+    opt = FusedAdam(_groups(1_048_576, dev, seed=2), lr=0.0, eps=1e-15)
+    gen = torch.Generator().manual_seed(3)
+    for _ in range(3):
+        _rand_grads(opt, gen, 1e-3)
+        _checked_step(opt)
+
+
+# ---- compaction ----
+def _keep_pattern(N, pattern):
+    k = torch.zeros(N, dtype=torch.bool)
+    if pattern == "all":
+        k[:] = True
+    elif pattern == "first":
+        k[0] = True
+    elif pattern == "last":
+        k[-1] = True
+    elif pattern == "255_256":
+        k[255:257] = True
+    elif pattern == "alternating":
+        k[::2] = True
+    elif pattern == "gap":  # one whole workgroup (rows 256..511) empty between full ones
+        k[:] = True
+        k[256:512] = False
+    else:
+        assert pattern == "none"
+    return k
+
+
+@pytest.mark.parametrize("pattern", ["all", "none", "first", "last", "255_256", "alternating", "gap"])
+@pytest.mark.parametrize("N", [65_535, 65_536, 65_537, 2_097_153])
+def test_compact_rows_scan_rounds_and_patterns(dev, N, pattern):
+    """255, 256, 257 and 8193 workgroups: the single-workgroup scan's 256-entry rounds and its carry."""
+    from eogs2_amd.optim import compact_rows
+
+    mask = _keep_pattern(N, pattern).to(dev)
+    tensors = [torch.arange(N, dtype=torch.int32, device=dev), torch.arange(3 * N, dtype=torch.float32, device=dev).reshape(N, 3),
+               torch.arange(N, dtype=torch.float32, device=dev).reshape(N, 1, 1) * 0.5]
+    for o, t in zip(compact_rows(mask, tensors), tensors):
+        assert o.shape == t[mask].shape and torch.equal(o, t[mask])
+
+
+def test_compact_rows_uint8_mask_wide_rows_and_many_tensors(dev):
+    from eogs2_amd.optim import compact_rows
+
+    N = 70_001
+    g = torch.Generator().manual_seed(21)
+    m8 = torch.randint(0, 256, (N,), generator=g, dtype=torch.uint8)
+    m8[torch.rand(N, generator=g) < 0.5] = 0
+    assert int((m8 > 1).sum()) > 1000
+    m8, keep = m8.to(dev), (m8 != 0).to(dev)
+    wide = torch.randn(N, 64, generator=g).to(dev)  # the widest legal row
+    (o,) = compact_rows(m8, [wide])
+    assert torch.equal(o, wide[keep])
+    with pytest.raises(RuntimeError):
+        compact_rows(m8, [torch.zeros(N, 65, device=dev)])
+    for count in (24, 25, 49):  # EOGS_COMPACT_MAX_TENSORS = 24 per launch; empty rows inside the first batch
+        tensors = []
+        for i in range(count):
+            if i in (3, 11, 23):
+                tensors.append(torch.zeros(N, 0, 3, device=dev))
+            else:
+                tensors.append((torch.randn(N, 1 + i % 5, generator=g) + i).to(dev))
+        outs = compact_rows(m8, tensors)
+        assert len(outs) == count
+        for i, (o, t) in enumerate(zip(outs, tensors)):
+            assert o.shape == t[keep].shape and torch.equal(o, t[keep]), (count, i)
+
+
+def test_compact_c_abi_writes_only_the_kept_rows(dev):
+    """eogs_compact_plan / eogs_compact_apply straight through the C-ABI with outputs inside larger buffers: a sentinel row
+    before and after each output stays untouched."""
+    import ctypes
+
+    from eogs2_amd import _lib
+
+    abi = _lib.get()
+    N, guard = 66_000, -777.0
+    g = torch.Generator().manual_seed(31)
+    keep = (torch.rand(N, generator=g) < 0.37).to(dev).to(torch.uint8)
+    srcs = [torch.randn(N, w, generator=g).to(dev) for w in (3, 1, 9, 64)]
+    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    nbytes = ctypes.c_size_t()
+    abi.check(abi.compact_bytes(N, ctypes.byref(nbytes)))
+    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    n_keep = ctypes.c_int64()
+    abi.check(abi.compact_plan(N, ctypes.c_void_p(keep.data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.byref(n_keep), stream))
+    K = n_keep.value
+    assert K == int(keep.sum())
+    bufs = [torch.full((K + 2, s.shape[1]), guard, device=dev) for s in srcs]
+    S = (ctypes.c_void_p * 4)(*[s.data_ptr() for s in srcs])
+    D = (ctypes.c_void_p * 4)(*[b[1:].data_ptr() for b in bufs])
+    RB = (ctypes.c_int * 4)(*[s.shape[1] * 4 for s in srcs])
+    abi.check(abi.compact_apply(N, ctypes.c_void_p(keep.data_ptr()), 4, ctypes.cast(S, ctypes.c_void_p), ctypes.cast(D, ctypes.c_void_p),
+                                ctypes.cast(RB, ctypes.c_void_p), ctypes.c_void_p(ws.data_ptr()), ws.numel(), stream))
+    torch.cuda.synchronize(dev)
+    for b, s in zip(bufs, srcs):
+        assert torch.equal(b[1:K + 1], s[keep.bool()])
+        assert bool((b[0] == guard).all()) and bool((b[K + 1] == guard).all())
+
+
+def test_sum_into_more_tensors_and_sources_than_one_launch(dev):
+    """11 destinations (EOGS_SUM_MAX_TENSORS = 8) and 6 sources (EOGS_SUM_MAX_SOURCES = 4) in one call: the sequence of adds."""
+    from eogs2_amd.optim import sum_into_
+
+    g = torch.Generator().manual_seed(41)
+    shapes = [(1000, 3), (5,), (0, 3), (777, 4), (1025,), (1,), (300, 1, 3), (4097,), (64,), (2, 2), (1023,)]
+    base = [torch.randn(s, generator=g).to(dev) for s in shapes]
+    srcs = [[(torch.randn(s, generator=g) * 10.0 ** (j - 2)).to(dev) for s in shapes] for j in range(6)]
+    want = [b.clone() for b in base]
+    for s in srcs:
+        for w, x in zip(want, s):
+            w.add_(x)
+    got = [b.clone() for b in base]
+    sum_into_(got, srcs)
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
