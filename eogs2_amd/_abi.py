@@ -106,6 +106,12 @@ SIGNATURES = {
     "eogs_resample_forward": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _p]),
     "eogs_resample_bytes": (_i, [_i, _i, C.POINTER(_z)]),
     "eogs_resample_backward": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
+    # include/eogs_resample.h: flow-matching warp
+    "eogs_resample_flow_forward": (_i, [_i, _i, _i, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "eogs_resample_flow_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+    "eogs_resample_flow_backward": (_i, [_i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _z, _p]),
+    "eogs_resample_flow_stats_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+    "eogs_resample_flow_stats": (_i, [_i, _i, _p, _i64, _i64, _i64, _p, _p, _z, _p]),
     # include/eogs_knn.h
     "eogs_knn_bytes": (_i, [_i, C.POINTER(_z)]),
     "eogs_knn_mean_dist2": (_i, [_i, _p, _p, _p, _z, _p]),
@@ -140,7 +146,8 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_mloss_backward", "eogs_tshadow_forward", "eogs_tshadow_backward", "eogs_tsdf_integrate", "eogs_tsdf_normals",
             "eogs_tsdf_prior_bytes", "eogs_tsdf_prior", "eogs_tsdf_surface", "eogs_tsdf_dsm_downsample", "eogs_tsdf_dsm_ncc_bytes",
             "eogs_tsdf_dsm_ncc", "eogs_tsdf_dsm_shift_bytes", "eogs_tsdf_dsm_shift", "eogs_tsdf_dsm_apply_shift",
-            "eogs_tsdf_dsm_mae_bytes", "eogs_tsdf_dsm_mae")
+            "eogs_tsdf_dsm_mae_bytes", "eogs_tsdf_dsm_mae", "eogs_resample_flow_forward", "eogs_resample_flow_bytes",
+            "eogs_resample_flow_backward", "eogs_resample_flow_stats_bytes", "eogs_resample_flow_stats")
 
 
 class PackTensor(C.Structure):

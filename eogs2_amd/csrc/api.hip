@@ -65,13 +65,14 @@ int check_launch(hipStream_t s, bool debug, const char* what) {
 enum { PS_PREPROCESS, PS_DEPTH_SORT, PS_BINNING, PS_RENDER_FWD, PS_RENDER_BWD, PS_GAUSS_BWD, PS_LOSS_FWD, PS_LOSS_BWD, PS_ADAM,
        PS_COMPACT, PS_RESAMPLE_FWD, PS_RESAMPLE_BWD, PS_KNN, PS_SHADE_FWD, PS_SHADE_BWD, PS_MLOSS_FWD, PS_MLOSS_BWD, PS_TSDF,
        PS_TSDF_NORMALS, PS_TSDF_PRIOR, PS_TSDF_SURFACE, PS_DSM_DOWNSAMPLE, PS_DSM_PIVOTS, PS_DSM_MOMENTS, PS_DSM_FINALIZE,
-       PS_DSM_APPLY, PS_DSM_MAE, PS_COUNT };
+       PS_DSM_APPLY, PS_DSM_MAE, PS_FLOW_FWD, PS_FLOW_BWD, PS_FLOW_STATS, PS_COUNT };
 static_assert(PS_COUNT <= 32, "eogs_rast_profile_select takes a 32-bit slot mask");
 const char* const kSlotNames[PS_COUNT] = {"preprocess_fwd", "depth_sort", "binning", "render_fwd", "render_bwd", "gaussian_bwd",
                                           "loss_fwd", "loss_bwd", "adam", "compact", "resample_fwd", "resample_bwd", "knn",
                                           "shade_fwd", "shade_bwd", "mloss_fwd", "mloss_bwd", "tsdf",
                                           "tsdf_normals", "tsdf_prior", "tsdf_surface", "dsm_downsample", "dsm_pivots",
-                                          "dsm_moments", "dsm_finalize", "dsm_apply_shift", "dsm_mae"};
+                                          "dsm_moments", "dsm_finalize", "dsm_apply_shift", "dsm_mae", "flow_fwd", "flow_bwd",
+                                          "flow_stats"};
 struct Pending { int slot; hipEvent_t a, b; };
 // process-wide (autograd runs backward on its own thread), guarded by g_prof_mu
 std::mutex g_prof_mu;
@@ -791,6 +792,67 @@ int eogs_resample_backward(int C, int Hv, int Wv, int H, int W, int n_out, const
   hipStream_t s = (hipStream_t)stream;
   { ProfScope ps(PS_RESAMPLE_BWD, s); launch_resample_bwd(C, Hv, Wv, H, W, n_out, virtual_render, uva, cam2virt, fill_channel, dL_dsample, dL_duv, dL_dvirtual, dL_duva, ws, s); }
   LAUNCH_TRY(s, false, "resample_bwd");
+  return EOGS_OK;
+}
+
+// ---- include/eogs_resample.h: flow-matching warp ----
+static int flow_check(const char* who, int C, int H, int W) {
+  if (C < 1 || H < 2 || W < 2 || (int64_t)H * W > 0x7FFFFFFF) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (C >= 1, H >= 2, W >= 2)", who);
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_forward(int C, int H, int W, const float* img, const float* flow, int64_t plane_stride,
+                               int64_t row_stride, int64_t col_stride, const float* gate, float* out, void* stream) {
+  g_err[0] = 0;
+  const int rc = flow_check("resample_flow_forward", C, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!img || !flow || !out) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_forward: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_FLOW_FWD, s); launch_flow_fwd(C, H, W, img, flow, plane_stride, row_stride, col_stride, gate, out, s); }
+  LAUNCH_TRY(s, false, "flow_fwd");
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_bytes(int H, int W, size_t* bytes) {
+  g_err[0] = 0;
+  if (H < 2 || W < 2 || (int64_t)H * W > 0x7FFFFFFF || !bytes) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_bytes: bad argument");
+  *bytes = flow_bwd_ws_bytes(H, W);
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_backward(int C, int H, int W, const float* flow, int64_t plane_stride, int64_t row_stride,
+                                int64_t col_stride, const float* gate, const float* dL_dout, float* dL_dimg, void* ws,
+                                size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  const int rc = flow_check("resample_flow_backward", C, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!flow || !dL_dout || !dL_dimg) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_backward: NULL argument");
+  const bool field = row_stride != 0 || col_stride != 0;
+  if (field && (!ws || ws_bytes < flow_bwd_ws_bytes(H, W)))
+    return fail(EOGS_ERR_WORKSPACE, "resample_flow_backward: workspace too small (a flow field needs eogs_resample_flow_bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_FLOW_BWD, s); launch_flow_bwd(C, H, W, flow, plane_stride, row_stride, col_stride, gate, dL_dout, dL_dimg, ws, s); }
+  LAUNCH_TRY(s, false, "flow_bwd");
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_stats_bytes(int H, int W, size_t* bytes) {
+  g_err[0] = 0;
+  if (H < 2 || W < 2 || (int64_t)H * W > 0x7FFFFFFF || !bytes) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_stats_bytes: bad argument");
+  *bytes = flow_stats_ws_bytes(H, W);
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_stats(int H, int W, const float* flow, int64_t plane_stride, int64_t row_stride, int64_t col_stride,
+                             float* stats, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  const int rc = flow_check("resample_flow_stats", 1, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!flow || !stats || !ws) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_stats: NULL argument");
+  if (ws_bytes < flow_stats_ws_bytes(H, W)) return fail(EOGS_ERR_WORKSPACE, "resample_flow_stats: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_FLOW_STATS, s); launch_flow_stats(H, W, flow, plane_stride, row_stride, col_stride, stats, ws, s); }
+  LAUNCH_TRY(s, false, "flow_stats");
   return EOGS_OK;
 }
 

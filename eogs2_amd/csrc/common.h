@@ -624,6 +624,15 @@ void launch_resample_bwd(int C, int Hv, int Wv, int H, int W, int n_out, const f
                          const float* M, int fill_channel, const float* gs, const float* guv, float* gvr, float* guva,
                          void* ws, hipStream_t s);
 
+// ---- flow-matching warp (flow.hip, include/eogs_resample.h eogs_resample_flow_*) ----
+size_t flow_stats_ws_bytes(int H, int W);
+void launch_flow_stats(int H, int W, const float* flow, int64_t sc, int64_t sy, int64_t sx, float* stats, void* ws, hipStream_t s);
+void launch_flow_fwd(int C, int H, int W, const float* img, const float* flow, int64_t sc, int64_t sy, int64_t sx,
+                     const float* gate, float* out, hipStream_t s);
+size_t flow_bwd_ws_bytes(int H, int W);
+void launch_flow_bwd(int C, int H, int W, const float* flow, int64_t sc, int64_t sy, int64_t sx, const float* gate,
+                     const float* g, float* gimg, void* ws, hipStream_t s);
+
 // ---- image chain after the raw render (shade.hip, include/eogs_shade.h) ----
 size_t shade_ws_bytes();
 void launch_shade_fwd(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow, float* cc,

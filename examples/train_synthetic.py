@@ -11,7 +11,8 @@ render pipeline — learnable colour correction, shadow map from the altitude di
 (`eogs2_amd.shade.suncamera_l`, `translucentshadows_l`), `FusedAdam` step on the Gaussians and Adam on the camera
 parameters (§8 f3), transparent-Gaussian prune by stream compaction (`prune_optimizer`, §8 f3). The target is the shaded
 render of the unperturbed scene under an identity colour correction, so the loss must fall. Initial scales come from
-`simple_knn._C.distCUDA2` (§8 f4).
+`simple_knn._C.distCUDA2` (§8 f4). `--flow-matching` adds the reference's flow-matching step between the render pipeline and
+the photometric loss (`eogs2_amd.flow`), against a target displaced by a sub-pixel registration error.
 """
 import argparse
 import math
@@ -31,10 +32,12 @@ from eogs2_amd.graph import Branches  # noqa: E402
 from eogs2_amd.resample import render_resample_virtual_camera, resample  # noqa: E402
 from eogs2_amd.shade import randomcam_l, render_pipeline, suncamera_l, translucentshadows_l  # noqa: E402
 from eogs2_amd.dsm_eval import dsm_mae  # noqa: E402
+from eogs2_amd.flow import apply_flow, perform_flow_matching, performOpticalmatching  # noqa: E402
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
 C0 = 0.28209479177387814
+FLOW_SHIFT = (0.6, -0.35)  # --flow-matching: the target's displacement in pixels (horizontal, vertical)
 
 
 class Camera:
@@ -117,6 +120,13 @@ def main(argv=None):
                          "Gaussians), which callers compare between runs). Unit: the altitude channel is xyz @ affine[:3, 2] + affine[3, 2] "
                          f"(eogs2_amd/render.py), which for the synthetic Nadir camera is synthetic.ALT_SCALE ({ALT_SCALE:g}) x the scene's "
                          "normalised z, alpha-composited over bg[3]; divide the MAE by ALT_SCALE for normalised z. 0 = off")
+    ap.add_argument("--flow-matching", action="store_true",
+                    help="the flow-matching step of the reference's flagship configuration (train_pan.py:347-357, "
+                         "optimization/flowmatching/raft_small.yaml): the target image is displaced by a fixed sub-pixel amount — a "
+                         f"registration error of {FLOW_SHIFT} px — and every iteration warps the shaded image by the predicted flow before "
+                         "the photometric loss (eogs2_amd.flow.perform_flow_matching, on_device=True, perform_cst_displacement=True: the "
+                         "max_value_flow decision stays on the device, so --graph records it). The flow network is a stand-in that "
+                         "answers that displacement as a field: RAFT, which the reference loads from torchvision, is the caller's")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     P, H, W = a.gaussians, a.size, a.size
@@ -188,6 +198,16 @@ def main(argv=None):
         gt = target_view[5]["final"].clone()
         gt_altitude = target_view[0]["render"][3].clone() if a.dsm_mae_every else None
         del target_view
+    warper = None
+    if a.flow_matching:
+        shift = torch.tensor(FLOW_SHIFT, device=dev).view(1, 2, 1, 1).expand(1, 2, H, W)
+        with torch.no_grad():
+            gt = apply_flow(gt, shift).clone()  # gt(x) <- gt(x + shift): what a flow of `shift` applied to the render undoes
+        hp, wp = -(-H // 8) * 8, -(-W // 8) * 8  # the size the network is called with (mode "upscale")
+        field = torch.tensor(FLOW_SHIFT, device=dev).view(1, 2, 1, 1).repeat(1, 1, hp, wp)
+        warper = performOpticalmatching(True, mode="upscale", device=dev, model_name="small", criteria="max_value_flow",
+                                        model=lambda gt_n, img_n, num_flow_updates=12: [field])
+        flow_opt = types.SimpleNamespace(flowmatching=types.SimpleNamespace(max_value_flow=3.0))
     cc_cam = colour_camera(0.15)
     camera_optimizer = torch.optim.Adam([*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction], lr=2e-3)
 
@@ -202,7 +222,10 @@ def main(argv=None):
         model.optimizer.zero_grad(set_to_none=True)
         camera_optimizer.zero_grad(set_to_none=True)
         out, img, sun_rgb, sun_uv, sun_altitude_diff, shaded, new = view(model, cc_cam)
-        loss, _ = photometric_loss(shaded["final"], gt, 0.2)
+        final = shaded["final"]
+        if warper is not None:  # train_pan.py:347-357
+            _, _, final = perform_flow_matching(flow_opt, warper, final, gt, on_device=True)
+        loss, _ = photometric_loss(final, gt, 0.2)
         loss = loss + 1e-3 * translucentshadows_l(shaded["shadowmap"])
         if sun_rgb is not None:
             L_sun_alt, L_sun_rgb = suncamera_l(img, sun_rgb, sun_altitude_diff, sun_uv)

@@ -50,6 +50,35 @@ int eogs_resample_backward(int C, int Hv, int Wv, int H, int W, int n_out, const
                            const float* dL_dsample, const float* dL_duv,
                            float* dL_dvirtual, float* dL_duva, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- flow-matching warp (flowmatching/flow_matching.py:225-269 of the reference) ----
+ * The reference warps an image by a predicted optical flow as grid + flow, two normalisations, a permute and
+ * grid_sample(bilinear, padding_mode="border", align_corners=True), with autograd's atomic scatter as backward. Here:
+ *   img, out     f32[C,H,W] planar; H >= 2 and W >= 2 (the reference divides by W - 1)
+ *   flow         f32, two planes (0: horizontal, 1: vertical, in pixels): element (k, y, x) lies at
+ *                flow[k * plane_stride + y * row_stride + x * col_stride]. row_stride == col_stride == 0 names ONE
+ *                displacement for the whole image (flow[0], flow[plane_stride]), read on the device
+ *   gate         NULL, or one float on the device: where it is 0 the forward copies img and the backward copies dL_dout
+ *                (the reference's host-side `if abs(flow).mean() < max_value_flow`, without the host)
+ *   out[c][y][x] = bilinear sample of img[c] at (x + flow_x, y + flow_y) clamped to [0, W - 1] x [0, H - 1]
+ * The flow receives no gradient (the reference detaches the grid). */
+int eogs_resample_flow_forward(int C, int H, int W, const float* img, const float* flow, int64_t plane_stride,
+                               int64_t row_stride, int64_t col_stride, const float* gate, float* out, void* stream);
+
+/* Workspace of the backward for a flow FIELD (a constant displacement needs none: ws may be NULL). */
+int eogs_resample_flow_bytes(int H, int W, size_t* bytes);
+
+/* dL_dimg f32[C,H,W]: fully overwritten, no memset, no floating-point atomics, bitwise reproducible run to run. A field is
+ * gathered through the buckets of eogs_resample_backward; a constant displacement through a closed-form gather. */
+int eogs_resample_flow_backward(int C, int H, int W, const float* flow, int64_t plane_stride, int64_t row_stride,
+                                int64_t col_stride, const float* gate, const float* dL_dout, float* dL_dimg, void* ws,
+                                size_t ws_bytes, void* stream);
+
+/* stats f32[5] = {mean x, mean y, mean |flow| over both planes, std x, std y} (std unbiased, as torch.std): one pass, sums in
+ * double in a fixed order, bitwise reproducible (flow_matching.py:67-69,255-269,302; flow_matching_toaffine.py:13-14). */
+int eogs_resample_flow_stats_bytes(int H, int W, size_t* bytes);
+int eogs_resample_flow_stats(int H, int W, const float* flow, int64_t plane_stride, int64_t row_stride, int64_t col_stride,
+                             float* stats, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
