@@ -28,6 +28,10 @@ LOSS_L1 = 1
 LOSS_SSIM = 2
 MLOSS_SUN = 0
 MLOSS_RANDOM = 1
+REG_OPACITY = 1  # include/eogs_reg.h EOGS_REG_*: the `want` bits, in the order of terms[] and weights[]
+REG_OPACITY_RADII = 2
+REG_ERANK = 4
+REG_RETIRED_BELOW = -5.0e29
 
 _p = C.c_void_p
 _i = C.c_int
@@ -139,6 +143,16 @@ SIGNATURES = {
     "eogs_tsdf_dsm_mae_bytes": (_i, [C.POINTER(_z)]),
     "eogs_tsdf_dsm_mae": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
 }
+# include/eogs_reg.h, bound like the entries above. A table of its own: tests/test_abi.py pins SIGNATURES to the symbols
+# of the seven headers it names.
+REG_SIGNATURES = {
+    "eogs_reg_gauss_bytes": (_i, [_i64, C.POINTER(_z)]),
+    "eogs_reg_gauss_forward": (_i, [_i64, _u, _p, _p, _p, _f, _p, _p, _p, _z, _p]),
+    "eogs_reg_gauss_backward": (_i, [_i64, _u, _p, _p, _p, _f] + [_p] * 6 + [_p]),
+    "eogs_reg_image_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+    "eogs_reg_image_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "eogs_reg_image_backward": (_i, [_i, _i] + [_p] * 7 + [_p]),
+}
 # symbols only the HIP library exports (the CPU oracle of the loss is oracle/loss_oracle.py, not a C-ABI twin)
 HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
             "eogs_compact_plan", "eogs_compact_apply", "eogs_resample_forward", "eogs_resample_bytes", "eogs_resample_backward", "eogs_knn_bytes",
@@ -147,7 +161,9 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_tsdf_prior_bytes", "eogs_tsdf_prior", "eogs_tsdf_surface", "eogs_tsdf_dsm_downsample", "eogs_tsdf_dsm_ncc_bytes",
             "eogs_tsdf_dsm_ncc", "eogs_tsdf_dsm_shift_bytes", "eogs_tsdf_dsm_shift", "eogs_tsdf_dsm_apply_shift",
             "eogs_tsdf_dsm_mae_bytes", "eogs_tsdf_dsm_mae", "eogs_resample_flow_forward", "eogs_resample_flow_bytes",
-            "eogs_resample_flow_backward", "eogs_resample_flow_stats_bytes", "eogs_resample_flow_stats")
+            "eogs_resample_flow_backward", "eogs_resample_flow_stats_bytes", "eogs_resample_flow_stats", "eogs_reg_gauss_bytes",
+            "eogs_reg_gauss_forward", "eogs_reg_gauss_backward", "eogs_reg_image_bytes", "eogs_reg_image_forward",
+            "eogs_reg_image_backward")
 
 
 class PackTensor(C.Structure):
@@ -182,7 +198,7 @@ class RastABI:
         self.cdll = C.CDLL(self.path)
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -200,7 +216,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -65,14 +65,17 @@ int check_launch(hipStream_t s, bool debug, const char* what) {
 enum { PS_PREPROCESS, PS_DEPTH_SORT, PS_BINNING, PS_RENDER_FWD, PS_RENDER_BWD, PS_GAUSS_BWD, PS_LOSS_FWD, PS_LOSS_BWD, PS_ADAM,
        PS_COMPACT, PS_RESAMPLE_FWD, PS_RESAMPLE_BWD, PS_KNN, PS_SHADE_FWD, PS_SHADE_BWD, PS_MLOSS_FWD, PS_MLOSS_BWD, PS_TSDF,
        PS_TSDF_NORMALS, PS_TSDF_PRIOR, PS_TSDF_SURFACE, PS_DSM_DOWNSAMPLE, PS_DSM_PIVOTS, PS_DSM_MOMENTS, PS_DSM_FINALIZE,
-       PS_DSM_APPLY, PS_DSM_MAE, PS_FLOW_FWD, PS_FLOW_BWD, PS_FLOW_STATS, PS_COUNT };
+       PS_DSM_APPLY, PS_DSM_MAE, PS_FLOW_FWD, PS_FLOW_BWD, PS_FLOW_STATS, PS_REG_FWD, PS_REG_BWD, PS_COUNT };
 static_assert(PS_COUNT <= 32, "eogs_rast_profile_select takes a 32-bit slot mask");
 const char* const kSlotNames[PS_COUNT] = {"preprocess_fwd", "depth_sort", "binning", "render_fwd", "render_bwd", "gaussian_bwd",
                                           "loss_fwd", "loss_bwd", "adam", "compact", "resample_fwd", "resample_bwd", "knn",
                                           "shade_fwd", "shade_bwd", "mloss_fwd", "mloss_bwd", "tsdf",
                                           "tsdf_normals", "tsdf_prior", "tsdf_surface", "dsm_downsample", "dsm_pivots",
                                           "dsm_moments", "dsm_finalize", "dsm_apply_shift", "dsm_mae", "flow_fwd", "flow_bwd",
-                                          "flow_stats"};
+                                          "flow_stats",
+                                          // the Gaussian-space and the render-space groups of eogs_reg.h share one slot
+                                          // each way: these two fill the 32-bit mask
+                                          "reg_fwd", "reg_bwd"};
 struct Pending { int slot; hipEvent_t a, b; };
 // process-wide (autograd runs backward on its own thread), guarded by g_prof_mu
 std::mutex g_prof_mu;
@@ -960,6 +963,90 @@ int eogs_tshadow_backward(int64_t n, const float* a, const float* upstream, floa
   hipStream_t s = (hipStream_t)stream;
   launch_tshadow_bwd(n, a, upstream, g_a, s);
   LAUNCH_TRY(s, false, "tshadow_bwd");
+  return EOGS_OK;
+}
+
+// ---- include/eogs_reg.h ----
+int eogs_reg_gauss_bytes(int64_t P, size_t* bytes) {
+  g_err[0] = 0;
+  if (P <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_bytes: bad argument");
+  *bytes = reg_ws_bytes();
+  return EOGS_OK;
+}
+
+static int reg_gauss_check(const char* who, int64_t P, unsigned want, const float* opacity, const float* log_scales,
+                           const int32_t* radii, float n_init, const float* weights) {
+  if (P <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad size", who);
+  if (want == 0u || (want & ~(EOGS_REG_OPACITY | EOGS_REG_OPACITY_RADII | EOGS_REG_ERANK)))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: `want` selects at least one of the three terms and nothing else", who);
+  if (!opacity || !weights) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  if ((want & EOGS_REG_ERANK) && !log_scales) return fail(EOGS_ERR_INVALID_ARG, "%s: the erank term needs log_scales (NULL argument)", who);
+  if ((want & EOGS_REG_OPACITY_RADII) && !radii) return fail(EOGS_ERR_INVALID_ARG, "%s: the visible-opacity term needs radii (NULL argument)", who);
+  if ((want & (EOGS_REG_OPACITY | EOGS_REG_OPACITY_RADII)) && !(n_init > 0.f))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: n_init must be positive", who);
+  return EOGS_OK;
+}
+
+int eogs_reg_gauss_forward(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
+                           float n_init, const float* weights, float* out, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  const int rc = reg_gauss_check("reg_gauss_forward", P, want, opacity, log_scales, radii, n_init, weights);
+  if (rc != EOGS_OK) return rc;
+  if (!out || !ws) return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_forward: NULL argument");
+  if (ws_bytes < reg_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "reg_gauss_forward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_REG_FWD, s); launch_reg_gauss_fwd(P, want, opacity, log_scales, radii, n_init, weights, out, ws, s); }
+  LAUNCH_TRY(s, false, "reg_gauss_fwd");
+  return EOGS_OK;
+}
+
+int eogs_reg_gauss_backward(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
+                            float n_init, const float* weights, const float* out, const float* g_total,
+                            const float* g_terms, float* g_opacity, float* g_scaling, void* stream) {
+  g_err[0] = 0;
+  const int rc = reg_gauss_check("reg_gauss_backward", P, want, opacity, log_scales, radii, n_init, weights);
+  if (rc != EOGS_OK) return rc;
+  if (!out || !g_opacity) return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_backward: NULL argument");
+  if (((want & EOGS_REG_ERANK) != 0u) != (g_scaling != nullptr))
+    return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_backward: g_scaling goes with the erank term");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_REG_BWD, s);
+    launch_reg_gauss_bwd(P, want, opacity, log_scales, radii, n_init, weights, out, g_total, g_terms, g_opacity, g_scaling, s); }
+  LAUNCH_TRY(s, false, "reg_gauss_bwd");
+  return EOGS_OK;
+}
+
+int eogs_reg_image_bytes(int H, int W, size_t* bytes) {
+  g_err[0] = 0;
+  if (H < 2 || W < 2 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "reg_image_bytes: bad argument");
+  *bytes = reg_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_reg_image_forward(int H, int W, const float* altitude, const float* accumulated_opacity, const float* weights,
+                           float* out, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (H < 2 || W < 2) return fail(EOGS_ERR_INVALID_ARG, "reg_image_forward: bad sizes (H and W must be at least 2)");
+  if ((!altitude && !accumulated_opacity) || !weights || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "reg_image_forward: NULL argument");
+  if (ws_bytes < reg_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "reg_image_forward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_REG_FWD, s); launch_reg_image_fwd(H, W, altitude, accumulated_opacity, weights, out, ws, s); }
+  LAUNCH_TRY(s, false, "reg_image_fwd");
+  return EOGS_OK;
+}
+
+int eogs_reg_image_backward(int H, int W, const float* altitude, const float* accumulated_opacity, const float* weights,
+                            const float* g_total, const float* g_terms, float* g_altitude, float* g_accumulated_opacity,
+                            void* stream) {
+  g_err[0] = 0;
+  if (H < 2 || W < 2) return fail(EOGS_ERR_INVALID_ARG, "reg_image_backward: bad sizes (H and W must be at least 2)");
+  if ((!altitude && !accumulated_opacity) || !weights) return fail(EOGS_ERR_INVALID_ARG, "reg_image_backward: NULL argument");
+  if ((altitude != nullptr) != (g_altitude != nullptr) || (accumulated_opacity != nullptr) != (g_accumulated_opacity != nullptr))
+    return fail(EOGS_ERR_INVALID_ARG, "reg_image_backward: a gradient plane goes with its input, NULL with NULL");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_REG_BWD, s);
+    launch_reg_image_bwd(H, W, altitude, accumulated_opacity, weights, g_total, g_terms, g_altitude, g_accumulated_opacity, s); }
+  LAUNCH_TRY(s, false, "reg_image_bwd");
   return EOGS_OK;
 }
 

@@ -11,6 +11,7 @@
 #include "eogs_resample.h"
 #include "eogs_knn.h"
 #include "eogs_shade.h"
+#include "eogs_reg.h"
 #include "eogs_tsdf.h"
 
 #define NCH EOGS_RAST_CHANNELS  // 5 feature channels
@@ -646,6 +647,18 @@ void launch_mloss_bwd(int H, int W, int mode, const float* alt_diff, const float
                       const float* out, const float* upstream, float* g_alt, float* g_a, float* g_b, hipStream_t s);
 void launch_tshadow_fwd(int64_t n, const float* a, float* out, void* ws, hipStream_t s);
 void launch_tshadow_bwd(int64_t n, const float* a, const float* upstream, float* g_a, hipStream_t s);
+
+// ---- regularisers over the model and over render planes (reg.hip, include/eogs_reg.h) ----
+size_t reg_ws_bytes();
+void launch_reg_gauss_fwd(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
+                          float n_init, const float* weights, float* out, void* ws, hipStream_t s);
+void launch_reg_gauss_bwd(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
+                          float n_init, const float* weights, const float* out, const float* g_total, const float* g_terms,
+                          float* g_opacity, float* g_scaling, hipStream_t s);
+void launch_reg_image_fwd(int H, int W, const float* alt, const float* acc, const float* weights, float* out, void* ws,
+                          hipStream_t s);
+void launch_reg_image_bwd(int H, int W, const float* alt, const float* acc, const float* weights, const float* g_total,
+                          const float* g_terms, float* g_alt, float* g_acc, hipStream_t s);
 
 // ---- TSDF integration (tsdf.hip, include/eogs_tsdf.h) ----
 void launch_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,

@@ -12,7 +12,9 @@ render pipeline — learnable colour correction, shadow map from the altitude di
 parameters (§8 f3), transparent-Gaussian prune by stream compaction (`prune_optimizer`, §8 f3). The target is the shaded
 render of the unperturbed scene under an identity colour correction, so the loss must fall. Initial scales come from
 `simple_knn._C.distCUDA2` (§8 f4). `--flow-matching` adds the reference's flow-matching step between the render pipeline and
-the photometric loss (`eogs2_amd.flow`), against a target displaced by a sub-pixel registration error.
+the photometric loss (`eogs2_amd.flow`), against a target displaced by a sub-pixel registration error. `--opacity-loss W` and
+`--erank-loss W` add the reference's OpacityLoss (W = 0.1 in its shipped configuration) and erankLoss over the raw parameters
+(`eogs2_amd.regularizers`).
 """
 import argparse
 import math
@@ -33,6 +35,7 @@ from eogs2_amd.resample import render_resample_virtual_camera, resample  # noqa:
 from eogs2_amd.shade import randomcam_l, render_pipeline, suncamera_l, translucentshadows_l  # noqa: E402
 from eogs2_amd.dsm_eval import dsm_mae  # noqa: E402
 from eogs2_amd.flow import apply_flow, perform_flow_matching, performOpticalmatching  # noqa: E402
+from eogs2_amd.regularizers import gaussian_regularizers  # noqa: E402
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
@@ -127,6 +130,12 @@ def main(argv=None):
                          "the photometric loss (eogs2_amd.flow.perform_flow_matching, on_device=True, perform_cst_displacement=True: the "
                          "max_value_flow decision stays on the device, so --graph records it). The flow network is a stand-in that "
                          "answers that displacement as a field: RAFT, which the reference loads from torchvision, is the caller's")
+    ap.add_argument("--opacity-loss", type=float, default=0.0, metavar="W",
+                    help="adds W x OpacityLoss (loss/opacity.py:14-17: the sum of the opacities over the initial number of Gaussians) "
+                         "through eogs2_amd.regularizers.gaussian_regularizers; the reference's shipped configuration runs it on "
+                         "every iteration with W = 0.1 (gs_config/train.yaml:118,141). 0 = absent")
+    ap.add_argument("--erank-loss", type=float, default=0.0, metavar="W",
+                    help="adds W x erankLoss (loss/main_loss.py:26-34) in the same launch group as --opacity-loss. 0 = absent")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     P, H, W = a.gaussians, a.size, a.size
@@ -217,6 +226,11 @@ def main(argv=None):
     dist2 = torch.clamp_min(distCUDA2(sc["means3D"]), 1e-7)  # gaussian_model.py:179-182
     model = Gaussians(sc["means3D"] + 2e-4 * noise(P, 3), (sc["colors"][:, :3] + 0.2 * noise(P, 3)).clamp(0.02, 0.98),
                       torch.full((P,), 0.3, device=dev), torch.sqrt(dist2)[:, None].repeat(1, 3), sc["rotations"])
+    # the regularisers over the raw parameters: weights in a device tensor the kernels read (a schedule would write into it
+    # between replays of a recorded graph), terms chosen once; init_number_of_gaussians is the constant P of the start
+    reg_want = tuple(n for n, w in (("opacity", a.opacity_loss), ("erank", a.erank_loss)) if w)
+    reg_weights = torch.tensor([a.opacity_loss, 0.0, a.erank_loss], device=dev) if reg_want else None
+
     def fwd_bwd():
         """Everything between two optimizer steps; reads the model's and the camera's parameter tensors in place."""
         model.optimizer.zero_grad(set_to_none=True)
@@ -233,6 +247,8 @@ def main(argv=None):
         if new is not None:
             L_new_alt, L_new_rgb = randomcam_l(new[0], img, new[1], new[2])
             loss = loss + 1e-4 * L_new_alt + 1e-3 * L_new_rgb
+        if reg_want:  # train_pan.py:450-465: w_L_opacity * L_opacity (+ w_L_erank * L_erank), summed in the kernel
+            loss = loss + gaussian_regularizers(model._opacity, model._scaling, n_init=P, weights=reg_weights, want=reg_want)[0]
         loss.backward()
         if a.dsm_mae_every:
             kept["altitude"] = out["render"][3].detach()  # (under --graph: the recorded step's output tensor, refilled by a replay)
