@@ -15,7 +15,7 @@ constexpr int OT = 16;  // output tile edge (256 pixels = one workgroup)
 // ---- tile kernel, second form (round 4): bucketed gather, no float atomics ----
 // The first form spends its time in ds_add_f32: four taps x n_out channels per output pixel, ~2 LDS cycles per lane each
 // (profiles/r04 resample probes: 72-107 us per backward at 1024^2). Here a pixel that lands in the tile costs two INTEGER LDS
-// atomics: the workgroup takes its candidate output tiles four at a time (1024 pixels),
+// atomics: the workgroup takes its candidate output tiles CHT at a time (four, or eight with one channel),
 //   count : every pixel whose north-west tap cell (x0, y0) lies in [vx0-1, vx0+VTX) x [vy0-1, vy0+VTY) — the cells whose taps can
 //           reach the tile — adds one to the counter of that cell's BUCKET;
 //   scan  : exclusive prefix of the (VTX+1) x (VTY+1) counters;
@@ -64,7 +64,7 @@ void resample_bwd_gather_kernel(int C, int Hv, int Wv, int H, int W, int n_out, 
     for (int ch = 0; ch < NACC; ch++) acc[c][ch] = 0.f;
   for (int e = t; e <= NB; e += BLK) s_cnt[e] = 0u;
 
-  for (int scanned = 0; scanned < nt; scanned += RB) {  // candidate output tiles: RB boxes per round (one round at 1024^2)
+  for (int scanned = 0; scanned < nt; scanned += RB) {  // candidate output tiles: RB boxes per round (1024^2: one round, or four)
     {
       constexpr int RBN = RB / BLK, NW = BLK / 64;
       static_assert(RBN * NW <= 64, "the per-wave candidate counts are scanned by one wave");

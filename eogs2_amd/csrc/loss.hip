@@ -249,7 +249,7 @@ __global__ __launch_bounds__(LTHREADS) void loss_bwd_kernel(int H, int W, const 
       }
     }
     __syncthreads();
-    // (eight adjacent columns per thread, as in the forward)
+    // (HG adjacent columns per thread, as in the forward)
     if (t < LH * (LT / HG)) {
       const int r = t / (LT / HG), c0 = (t % (LT / HG)) * HG;
 #pragma unroll

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import flow_cases as FC
+import resample_cases as RC
 from util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -30,20 +31,7 @@ def run(F, img, flow, upstream, gate=None):
     return out.detach(), x.grad
 
 
-def reference_ops(img, flow, upstream):
-    """flow_matching.py:225-253 as the reference runs it (fp32 torch ops and autograd), on the tensors' device."""
-    x = img.clone().requires_grad_(True)
-    C, H, W = x.shape
-    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
-    grid = torch.stack((xx, yy), dim=0).float().to(x.device).unsqueeze(0)
-    flow_grid = grid + flow
-    flow_grid[:, 0] = 2.0 * flow_grid[:, 0] / (W - 1) - 1.0
-    flow_grid[:, 1] = 2.0 * flow_grid[:, 1] / (H - 1) - 1.0
-    flow_grid = flow_grid.permute(0, 2, 3, 1)
-    out = torch.nn.functional.grid_sample(x.unsqueeze(0), flow_grid.detach(), mode="bilinear", padding_mode="border",
-                                          align_corners=True).squeeze(0)
-    out.backward(upstream)
-    return out.detach(), x.grad
+reference_ops = RC.reference_flow_ops  # flow_matching.py:225-253 as the reference runs it (fp32 torch ops and autograd)
 
 
 def flows_for(H, W, g, dev):
@@ -290,3 +278,57 @@ def test_example_flow_matching(dev):
     assert eager[1] < eager[0], eager  # trains
     graph = train_synthetic.main(args + ["--graph"])
     assert graph == eager, (eager, graph)  # bit for bit
+
+
+# ---- the edge cases of the bucketed gather with FlowSrc (tests/resample_cases.py; checked on the CPU by
+# tests/test_resample_cases.py) ----
+@pytest.mark.parametrize("name", RC.FLOW)
+def test_flow_case_against_the_float64_statement(dev, name):
+    """Full buckets, the 64x32-tile instantiations (one, three and five planes), two scan rounds, strided fields: flows are
+    multiples of 1/8, so cell and weight are exact in fp32 and no element is left out."""
+    from eogs2_amd import flow as F
+
+    c = RC.flow_case(name)
+    img, up, flow = c["img"].to(dev), c["up"].to(dev), c["flow"].to(dev)
+    first = run(F, img, flow, up)
+    err = RC.compare_flow(first, RC.oracle_flow(name), RC.TOL, name)
+    print(f"{name}: out {err['out']:.2e} g_img {err['g_img']:.2e}")
+    if name == "flow_strided":
+        for layout, view in RC.strided_views(flow).items():
+            again = run(F, img, view, up)
+            assert torch.equal(again[0], first[0]) and torch.equal(again[1], first[1]), layout
+
+
+def test_field_backward_overwrites_every_element_of_its_output(dev):
+    """eogs_resample_flow_backward straight through the C-ABI into a buffer full of NaN, five planes at 64x32 tiles (a four-plane
+    and a one-plane pass): every element written, cells no tap reaches with exact zeros, the bits of the autograd path."""
+    from eogs2_amd import _lib
+    from eogs2_amd import flow as F
+
+    c = RC.flow_case("flow_big5")
+    C, H, W = c["img"].shape
+    up, flow = c["up"].to(dev), c["flow"].to(dev)
+    g_img = torch.full((C, H, W), float("nan"), device=dev)
+    nbytes = F._bytes(_lib.get().resample_flow_bytes, H, W)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    F._call("eogs_resample_flow_backward", up.device, C, H, W, flow.data_ptr(), *flow.stride()[1:], None, up.data_ptr(), g_img.data_ptr(),
+            ws.data_ptr(), nbytes)
+    torch.cuda.synchronize()
+    assert not torch.isnan(g_img).any()
+    reached = torch.from_numpy(RC.reached_cells(*RC.flow_tap_cells(c["flow"]), H, W, dilate=1))
+    assert not g_img.cpu()[:, ~reached].any()
+    assert g_img.abs().amax(dim=(1, 2)).min() > 0
+    RC.compare_flow((RC.oracle_flow("flow_big5")[0], g_img), RC.oracle_flow("flow_big5"), RC.TOL, "flow_big5 through the C-ABI")
+    assert torch.equal(run(F, c["img"].to(dev), flow, up)[1], g_img)
+
+
+def test_full_bucket_backward_is_reproducible_bit_for_bit(dev):
+    from eogs2_amd import flow as F
+
+    c = RC.flow_case("flow_converge")
+    img, up, flow = c["img"].to(dev), c["up"].to(dev), c["flow"].to(dev)
+    first = run(F, img, flow, up)
+    assert float(first[1].abs().max()) > 0
+    for _ in range(5):
+        again = run(F, img, flow, up)
+        assert torch.equal(again[0], first[0]) and torch.equal(again[1], first[1])

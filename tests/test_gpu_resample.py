@@ -4,6 +4,7 @@ the same statements run in fp32 by PyTorch on the GPU (what the reference execut
 import pytest
 import torch
 
+import resample_cases as RC
 from util import assert_close
 
 pytestmark = pytest.mark.gpu
@@ -61,12 +62,7 @@ def test_resample_matches_reference_ops_on_gpu_full_size(dev):
     """1024^2 true camera, 2048^2 sun camera: the reference's fp32 op sequence on the same GPU."""
     from eogs2_amd.resample import resample
 
-    def ref_ops(vr, M, uva):
-        uv = torch.einsum("...ij,...j->...i", M, uva)[..., :2]
-        s = torch.nn.functional.grid_sample(vr.unsqueeze(0), uv.unsqueeze(0), align_corners=True).squeeze(0)
-        rgb, a = s[:3], s[3]
-        a[(uv.abs() > 1).any(-1)] = -100
-        return torch.cat([rgb, a[None]], 0), uv
+    ref_ops = RC.reference_resample_ops  # the reference's statements in fp32
 
     c = _case(1024, 1024, 2, seed=7, shift=0.05)
     got = _run(resample, *c, dev)
@@ -193,3 +189,112 @@ def test_backward_is_reproducible_bit_for_bit(dev):
         assert float(grads[0][0].abs().max()) > 0
         for gv, ga in grads[1:]:
             assert torch.equal(gv, grads[0][0]) and torch.equal(ga, grads[0][1])
+
+
+# ---- the edge cases of the bucketed gather (tests/resample_cases.py; the cases themselves are checked on the CPU by
+# tests/test_resample_cases.py) ----
+def _hip(vr, M, uva, n_out, fill_channel):
+    from eogs2_amd.resample import resample
+
+    return resample(vr, M, uva, n_out=n_out, fill_channel=fill_channel)
+
+
+@pytest.mark.parametrize("name", RC.RESAMPLE)
+def test_resample_case_matches_oracle(dev, name):
+    """Forward and backward of every case against the float64 oracle under the rule of the case module: 1e-4 of each quantity's
+    maximum, no element left out of the lattice cases, elsewhere only dL/duva of pixels on a cell border. (The name matches the
+    filter of the first-form test below, whose child runs these cases through the LDS-atomic tile kernel.)"""
+    c = RC.resample_case(name)
+    got, ref = RC.run_resample(_hip, c, dev), RC.oracle_resample(name)
+    f = c["fill_channel"]
+    if f >= 0:
+        assert torch.equal(got["sample"][f] == -100, ref["sample"][f] == -100), "the out-of-view fill covers different pixels"
+    err = RC.compare_resample(got, ref, c, RC.TOL, name)
+    print(f"{name}: " + " ".join(f"{k} {e:.2e}" for k, e in err.items()))
+    assert not got["g_virtual"][c["n_out"]:].any()  # trailing channels receive zeros
+    if name == "all_out":
+        assert not got["g_virtual"].any() and (got["sample"][3] == -100).all() and not got["sample"][:3].any()
+
+
+def _abi_backward(dev, c, g_vr, g_uva):
+    """eogs_resample_backward straight through the C-ABI into the caller's buffers."""
+    import ctypes
+
+    from eogs2_amd import _lib
+    from eogs2_amd.rasterizer import _Ctx, _ptr
+
+    abi = _lib.get()
+    (C, Hv, Wv), (H, W) = c["vr"].shape, c["alt"].shape
+    vr, M = c["vr"].to(dev), c["M"].to(dev)
+    uva = torch.stack((c["U"], c["V"], c["alt"]), dim=-1).to(dev)
+    gs, guv = c["w_s"].to(dev), c["w_uv"].to(dev)
+    with _Ctx(abi, dev) as cx:
+        n = ctypes.c_size_t()
+        abi.check(abi.resample_bytes(H, W, ctypes.byref(n)))
+        ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+        abi.check(abi.resample_backward(C, Hv, Wv, H, W, c["n_out"], _ptr(vr), _ptr(uva), _ptr(M), c["fill_channel"], _ptr(gs), _ptr(guv),
+                                        _ptr(g_vr), _ptr(g_uva), _ptr(ws), ws.numel(), cx.stream))
+    torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("name", ["all_out", "big4", "one_past", RC.channel_name("minify8", 6, 5, -1), RC.channel_name("partly_out", 6, 5, -1)])
+def test_backward_overwrites_every_element_of_its_outputs(dev, name):
+    """dL_dvirtual and dL_duva handed over full of NaN: every element is written, channels >= n_out and every cell no tap
+    reaches (from the float64 coordinates, grown by one cell) with exact zeros — also where no output tile is a candidate."""
+    c = RC.resample_case(name)
+    (C, Hv, Wv), (H, W) = c["vr"].shape, c["alt"].shape
+    g_vr = torch.full((C, Hv, Wv), float("nan"), device=dev)
+    g_uva = torch.full((H, W, 3), float("nan"), device=dev)
+    _abi_backward(dev, c, g_vr, g_uva)
+    g_vr, g_uva = g_vr.cpu(), g_uva.cpu()
+    assert not torch.isnan(g_vr).any() and not torch.isnan(g_uva).any()
+    assert not g_vr[c["n_out"]:].any()
+    reached = torch.from_numpy(RC.reached_cells(*RC.tap_cells(c), Hv, Wv, dilate=1))
+    assert not g_vr[:, ~reached].any()
+    assert (name == "all_out") == (not reached.any())
+    if name == "all_out":
+        assert not g_vr.any()
+    else:
+        assert g_vr[:c["n_out"]].abs().amax(dim=(1, 2)).min() > 0
+    ref = RC.oracle_resample(name)
+    RC.compare_resample(dict(ref, g_virtual=g_vr, g_uva=g_uva), ref, c, RC.TOL, name)
+
+
+@pytest.mark.parametrize("name", ["collapse_exact", "minify8", "rounds4"])
+def test_case_backward_is_reproducible_bit_for_bit(dev, name):
+    """Six backward passes give the same bits: a full bucket ranked by pixel id, tens of pixels per cell, two scan rounds."""
+    c = RC.resample_case(name)
+    runs = [RC.run_resample(_hip, c, dev) for _ in range(6)]
+    assert float(runs[0]["g_virtual"].abs().max()) > 0
+    for r in runs[1:]:
+        assert torch.equal(r["g_virtual"], runs[0]["g_virtual"]) and torch.equal(r["g_uva"], runs[0]["g_uva"])
+
+
+def test_cases_in_sequence_on_one_stream_equal_each_alone(dev):
+    """The 64x32 and 32x32 tile kernels, two scan rounds and a launch without candidates queued back to back on one stream with
+    no synchronisation in between (inputs uploaded beforehand): bit for bit what each case gives alone. The workspace is per
+    call, the kernel form is chosen by static state."""
+    names = ("big4", "one_tile", "rounds4", "all_out")
+
+    def upload(c):
+        uva = torch.stack((c["U"], c["V"], c["alt"]), dim=-1)
+        return {k: t.to(dev) for k, t in dict(vr=c["vr"], uva=uva, M=c["M"], w_s=c["w_s"], w_uv=c["w_uv"]).items()}
+
+    def go(c, d):
+        vr, uva = d["vr"].clone().requires_grad_(True), d["uva"].clone().requires_grad_(True)
+        s, uv = _hip(vr, d["M"], uva, c["n_out"], c["fill_channel"])
+        ((s * d["w_s"]).sum() + (uv * d["w_uv"]).sum()).backward()
+        return s.detach(), uv.detach(), vr.grad, uva.grad
+
+    cases = [RC.resample_case(n) for n in names]
+    on_dev = [upload(c) for c in cases]
+    alone = []
+    for c, d in zip(cases, on_dev):
+        torch.cuda.synchronize()
+        alone.append([t.cpu() for t in go(c, d)])
+    torch.cuda.synchronize()
+    queued = [go(c, d) for c, d in zip(cases, on_dev)]  # nothing waits for the device in here
+    torch.cuda.synchronize()
+    for n, a, q in zip(names, alone, queued):
+        for what, x, y in zip(("sample", "uv", "g_virtual", "g_uva"), a, q):
+            assert torch.equal(x, y.cpu()), f"{n}: {what} differs in sequence"
