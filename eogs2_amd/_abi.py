@@ -32,6 +32,16 @@ REG_OPACITY = 1  # include/eogs_reg.h EOGS_REG_*: the `want` bits, in the order 
 REG_OPACITY_RADII = 2
 REG_ERANK = 4
 REG_RETIRED_BELOW = -5.0e29
+PAN_ONE_CHANNEL = 0  # include/eogs_pan.h EOGS_PAN_*: the map kinds
+PAN_AVERAGE = 1
+PAN_FIXED = 2
+PAN_BASE = 3
+PAN_BASE_SIGMOID = 4
+PAN_TRANSLATE = 5
+PAN_TRANSLATE_FROZEN = 6
+PAN_ORDER_CC_FIRST = 0  # EOGS_PAN_ORDER_*
+PAN_ORDER_MAP_FIRST = 1
+PAN_NPARAMS = 20
 
 _p = C.c_void_p
 _i = C.c_int
@@ -153,6 +163,12 @@ REG_SIGNATURES = {
     "eogs_reg_image_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _z, _p]),
     "eogs_reg_image_backward": (_i, [_i, _i] + [_p] * 7 + [_p]),
 }
+# include/eogs_pan.h, a table of its own for the same reason
+PAN_SIGNATURES = {
+    "eogs_pan_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+    "eogs_pan_forward": (_i, [_i, _i, _i, _i] + [_p] * 8 + [_p]),
+    "eogs_pan_backward": (_i, [_i, _i, _i, _i] + [_p] * 11 + [_p, _z, _p]),
+}
 # symbols only the HIP library exports (the CPU oracle of the loss is oracle/loss_oracle.py, not a C-ABI twin)
 HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
             "eogs_compact_plan", "eogs_compact_apply", "eogs_resample_forward", "eogs_resample_bytes", "eogs_resample_backward", "eogs_knn_bytes",
@@ -163,7 +179,7 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_tsdf_dsm_mae_bytes", "eogs_tsdf_dsm_mae", "eogs_resample_flow_forward", "eogs_resample_flow_bytes",
             "eogs_resample_flow_backward", "eogs_resample_flow_stats_bytes", "eogs_resample_flow_stats", "eogs_reg_gauss_bytes",
             "eogs_reg_gauss_forward", "eogs_reg_gauss_backward", "eogs_reg_image_bytes", "eogs_reg_image_forward",
-            "eogs_reg_image_backward")
+            "eogs_reg_image_backward", "eogs_pan_bytes", "eogs_pan_forward", "eogs_pan_backward")
 
 
 class PackTensor(C.Structure):
@@ -198,7 +214,7 @@ class RastABI:
         self.cdll = C.CDLL(self.path)
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
-        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -216,7 +232,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -1050,6 +1050,57 @@ int eogs_reg_image_backward(int H, int W, const float* altitude, const float* ac
   return EOGS_OK;
 }
 
+// ---- include/eogs_pan.h ----
+int eogs_pan_bytes(int H, int W, size_t* bytes) {
+  g_err[0] = 0;
+  if (H <= 0 || W <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "pan_bytes: bad argument");
+  *bytes = pan_ws_bytes();
+  return EOGS_OK;
+}
+
+static int pan_check(const char* who, int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M,
+                     const float* inshadow, const float* map_params) {
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", who);
+  if (order != EOGS_PAN_ORDER_CC_FIRST && order != EOGS_PAN_ORDER_MAP_FIRST) return fail(EOGS_ERR_INVALID_ARG, "%s: unknown order", who);
+  if (kind < EOGS_PAN_ONE_CHANNEL || kind > EOGS_PAN_TRANSLATE_FROZEN) return fail(EOGS_ERR_INVALID_ARG, "%s: unknown map kind", who);
+  if (!raw || !M) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  if (alt_diff && !inshadow) return fail(EOGS_ERR_INVALID_ARG, "%s: alt_diff needs inshadow (NULL argument)", who);
+  if (pan_map_params(kind) > 0 && !map_params) return fail(EOGS_ERR_INVALID_ARG, "%s: this map kind needs map_params (NULL argument)", who);
+  return EOGS_OK;
+}
+
+int eogs_pan_forward(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M,
+                     const float* inshadow, const float* map_params, float* cc, float* shaded, float* shadow,
+                     void* stream) {
+  g_err[0] = 0;
+  const int rc = pan_check("pan_forward", H, W, order, kind, raw, alt_diff, M, inshadow, map_params);
+  if (rc != EOGS_OK) return rc;
+  if (!shaded || (order == EOGS_PAN_ORDER_MAP_FIRST && !cc)) return fail(EOGS_ERR_INVALID_ARG, "pan_forward: NULL argument");
+  if ((alt_diff != nullptr) != (shadow != nullptr)) return fail(EOGS_ERR_INVALID_ARG, "pan_forward: alt_diff and shadow go together");
+  hipStream_t s = (hipStream_t)stream;
+  launch_pan_fwd(H, W, order, kind, raw, alt_diff, M, inshadow, map_params, cc, shaded, shadow, s);
+  LAUNCH_TRY(s, false, "pan_fwd");
+  return EOGS_OK;
+}
+
+int eogs_pan_backward(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M,
+                      const float* inshadow, const float* map_params, const float* g_shaded, const float* g_cc,
+                      const float* g_shadow, float* g_raw, float* g_alt_diff, float* g_params, void* ws, size_t ws_bytes,
+                      void* stream) {
+  g_err[0] = 0;
+  const int rc = pan_check("pan_backward", H, W, order, kind, raw, alt_diff, M, inshadow, map_params);
+  if (rc != EOGS_OK) return rc;
+  if (!g_raw || !g_params || !ws) return fail(EOGS_ERR_INVALID_ARG, "pan_backward: NULL argument");
+  if ((alt_diff != nullptr) != (g_alt_diff != nullptr) || (!alt_diff && g_shadow))
+    return fail(EOGS_ERR_INVALID_ARG, "pan_backward: alt_diff, g_shadow and g_alt_diff go together");
+  if (ws_bytes < pan_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "pan_backward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  launch_pan_bwd(H, W, order, kind, raw, alt_diff, M, inshadow, map_params, g_shaded, g_cc, g_shadow, g_raw, g_alt_diff, g_params,
+                 ws, s);
+  LAUNCH_TRY(s, false, "pan_bwd");
+  return EOGS_OK;
+}
+
 // ---- include/eogs_tsdf.h ----
 int eogs_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,
                         float model_scale, float trunc_margin, int H, int W, const float* altitude, const float* weight,

@@ -12,6 +12,7 @@
 #include "eogs_knn.h"
 #include "eogs_shade.h"
 #include "eogs_reg.h"
+#include "eogs_pan.h"
 #include "eogs_tsdf.h"
 
 #define NCH EOGS_RAST_CHANNELS  // 5 feature channels
@@ -659,6 +660,15 @@ void launch_reg_image_fwd(int H, int W, const float* alt, const float* acc, cons
                           hipStream_t s);
 void launch_reg_image_bwd(int H, int W, const float* alt, const float* acc, const float* weights, const float* g_total,
                           const float* g_terms, float* g_alt, float* g_acc, hipStream_t s);
+
+// ---- panchromatic camera pipeline (pan.hip, include/eogs_pan.h) ----
+size_t pan_ws_bytes();
+int pan_map_params(int kind);  // floats of map_params the kind reads
+void launch_pan_fwd(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
+                    const float* map_params, float* cc, float* shaded, float* shadow, hipStream_t s);
+void launch_pan_bwd(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
+                    const float* map_params, const float* g_shaded, const float* g_cc, const float* g_shadow, float* g_raw,
+                    float* g_alt, float* g_params, void* ws, hipStream_t s);
 
 // ---- TSDF integration (tsdf.hip, include/eogs_tsdf.h) ----
 void launch_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,

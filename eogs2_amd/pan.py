@@ -1,0 +1,294 @@
+"""Panchromatic camera: colour correction, shadow and the MSI->PAN map over the C-ABI of include/eogs_pan.h.
+
+Same names, arguments and return values as the reference (paths under src/gaussiansplatting/):
+
+* `render_pipeline(cam, raw_render, sun_altitude_diff=None)` — `PANAffineCamera.render_pipeline`
+  (scene/cameras/PAN_affine_cameras.py:73-176), both orders: colour correction and shadow first and the map last
+  (`_render_pipeline`, :83-146), or the map first, then a 1->1 colour correction and a scalar in-shadow tint
+  (`weird_pan_setup`, `_render_pipeline_weird`, :148-176). Returns the same dict (`shadowmap`, `shaded`, `cc`, `final`).
+  `cam` is duck-typed: `use_cc`/`color_correction`, `use_exposure`/`exposure`, `use_shadow`,
+  `inshadow_color_correction`, `msi_to_pan`, `weird_pan_setup`.
+* `pan_map_of(module)` — a `PanMap` for one of the modules `load_msi_to_pan` builds
+  (scene/msi_to_pan/transf_msi_to_pan.py:189-222), recognised by class name and attributes.
+* `pan_shade(raw, alt_diff, M, inshadow, pan_map, order)` — the fused call itself: `(cc, shaded, shadow)`.
+
+One forward and one backward kernel (plus a tiny fixed-order reduction) where the reference runs 15-25 elementwise
+PyTorch kernels and autograd replays them; parameter gradients are reproducible bit for bit. Gradients reach the
+camera's and the map's own Parameters. PyTorch is plumbing; there is no CPU or eager fallback.
+"""
+import ctypes
+
+import torch
+
+from . import _lib, shade as _shade
+from ._abi import (PAN_AVERAGE, PAN_BASE, PAN_BASE_SIGMOID, PAN_FIXED, PAN_NPARAMS, PAN_ONE_CHANNEL, PAN_ORDER_CC_FIRST,
+                   PAN_ORDER_MAP_FIRST, PAN_TRANSLATE, PAN_TRANSLATE_FROZEN)
+from .rasterizer import _Ctx, _ptr
+
+ORDER_CC_FIRST = "cc_first"  # PANAffineCamera._render_pipeline
+ORDER_MAP_FIRST = "map_first"  # PANAffineCamera._render_pipeline_weird (weird_pan_setup)
+_ORDERS = {ORDER_CC_FIRST: PAN_ORDER_CC_FIRST, ORDER_MAP_FIRST: PAN_ORDER_MAP_FIRST, "A": PAN_ORDER_CC_FIRST,
+           "B": PAN_ORDER_MAP_FIRST, False: PAN_ORDER_CC_FIRST, True: PAN_ORDER_MAP_FIRST}
+
+KINDS = ("identity", "only_one_channel", "average", "fixed", "learnable_fixed", "base", "fixedandtranslate")
+# the constants of base_msi_to_pan (transf_msi_to_pan.py:11-14)
+FIXED_PARAMS = (0.438469, 1.1331377, -0.6794343, 1.0, 0.0016913427)
+
+
+class PanMap:
+    """One MSI->PAN map (names as in `load_msi_to_pan`) and the tensors it reads.
+
+    identity / only_one_channel / average: no tensors.
+    fixed, learnable_fixed: `params` f32[5], result `p3 (p0 x0 + p1 x1 + p2 x2 + p4)`; a gradient comes back when
+        `params` requires grad (`unfreeze_msi_to_pan`).
+    base: `weight` (3 values) and `bias` (1) of the Conv2d(3,1,1); sigmoid unless `remove_sigm`.
+    fixedandtranslate: `fixed_weights` (3), `fixed_bias` (1) evaluated without gradient, plus `weight`, `bias` of the
+        learnable Conv2d(3,1,1) when `learn_conv2d`; without it the results do not require grad.
+    """
+
+    def __init__(self, kind, params=None, weight=None, bias=None, fixed_weights=None, fixed_bias=None, remove_sigm=False,
+                 learn_conv2d=False):
+        if kind not in KINDS:
+            raise ValueError(f"Unknown MSI to PAN conversion type: {kind}. Available options are {', '.join(KINDS)}.")
+        self.kind = kind
+        self.remove_sigm = bool(remove_sigm)
+        self.learn_conv2d = bool(learn_conv2d)
+        self.params, self.weight, self.bias = params, weight, bias
+        self.fixed_weights, self.fixed_bias = fixed_weights, fixed_bias
+        if kind in ("fixed", "learnable_fixed"):
+            if self.params is None:
+                self.params = torch.tensor(FIXED_PARAMS)
+            self._numel("params", self.params, 5)
+        elif kind == "base":
+            self._numel("weight", weight, 3)
+            self._numel("bias", bias, 1)
+        elif kind == "fixedandtranslate":
+            if self.fixed_weights is None:
+                self.fixed_weights, self.fixed_bias = torch.tensor(FIXED_PARAMS[:3]), torch.tensor(FIXED_PARAMS[4:])
+            self._numel("fixed_weights", self.fixed_weights, 3)
+            self._numel("fixed_bias", self.fixed_bias, 1)
+            if self.learn_conv2d:
+                self._numel("weight", weight, 3)
+                self._numel("bias", bias, 1)
+
+    def _numel(self, name, t, n):
+        if not torch.is_tensor(t) or t.numel() != n:
+            raise RuntimeError(f"PanMap({self.kind!r}): `{name}` must be a tensor of {n} values")
+
+    @property
+    def planes(self):
+        return 3 if self.kind == "identity" else 1
+
+    @property
+    def differentiable(self):
+        """False when no gradient passes the map (fixedandtranslate without learn_conv2d)."""
+        return not (self.kind == "fixedandtranslate" and not self.learn_conv2d)
+
+    def to(self, device):
+        """Moves the tensors this object created itself (defaults); tensors of the caller's modules stay where they are."""
+        for name in ("params", "weight", "bias", "fixed_weights", "fixed_bias"):
+            t = getattr(self, name)
+            if torch.is_tensor(t) and not isinstance(t, torch.nn.Parameter) and not t.requires_grad:
+                setattr(self, name, t.to(device))
+        return self
+
+    def packed(self, dev):
+        """(kind of eogs_pan.h, map_params tensor or None). The tensor is built with differentiable torch ops from
+        the module's own tensors, so autograd hands the kernel's gradient back to them."""
+        def flat(t, what):
+            if t.device != dev:
+                raise RuntimeError(f"PanMap({self.kind!r}): `{what}` on {t.device}, expected {dev}")
+            return t.reshape(-1).to(torch.float32)
+
+        k = self.kind
+        if k == "only_one_channel":
+            return PAN_ONE_CHANNEL, None
+        if k == "average":
+            return PAN_AVERAGE, None
+        if k in ("fixed", "learnable_fixed"):
+            return PAN_FIXED, flat(self.params, "params")
+        if k == "base":
+            return (PAN_BASE if self.remove_sigm else PAN_BASE_SIGMOID), torch.cat([flat(self.weight, "weight"), flat(self.bias, "bias")])
+        if k == "fixedandtranslate":
+            fixed = [flat(self.fixed_weights, "fixed_weights").detach(), flat(self.fixed_bias, "fixed_bias").detach()]
+            if self.learn_conv2d:
+                return PAN_TRANSLATE, torch.cat(fixed + [flat(self.weight, "weight"), flat(self.bias, "bias")])
+            return PAN_TRANSLATE_FROZEN, torch.cat(fixed)
+        raise RuntimeError("the identity map has no kernel of its own: it is the affine camera's pipeline")
+
+    def __call__(self, image):
+        """The map alone on a (3, H, W) image: (1, H, W), or the image itself for `identity`."""
+        if self.kind == "identity":
+            return image
+        M = torch.eye(3, 4, device=image.device)
+        return pan_shade(image, None, M, None, self, ORDER_CC_FIRST)[1]
+
+
+def pan_map_of(module):
+    """A `PanMap` for a duck-typed `cam.msi_to_pan`: the reference's classes by name and the attributes they carry."""
+    if isinstance(module, PanMap):
+        return module
+    name = type(module).__name__
+    if name == "msi_to_pan_identity":
+        return PanMap("identity")
+    if name == "only_one_channel":
+        if getattr(module, "num_channel", 0) != 0:
+            raise NotImplementedError("only_one_channel: only channel 0 (what load_msi_to_pan builds)")
+        return PanMap("only_one_channel")
+    if name == "average_msitopan":
+        return PanMap("average")
+    if name == "base_msi_to_pan":
+        return PanMap("fixed", params=module.pan_params)
+    if name == "learnable_base_msi_to_pan":
+        return PanMap("learnable_fixed", params=module.pan_params)
+    if name in ("MSI_TO_PAN", "msi_to_pan_fixedandtranslate"):
+        lin = module.linear
+        if not hasattr(lin, "weight"):
+            raise NotImplementedError(f"{name}: use_avgpool (a pooled MSI->PAN map) stays the caller's")
+        ks = tuple(lin.weight.shape[2:])
+        if ks != (1, 1):
+            raise NotImplementedError(f"{name}: kernel_size {ks} != 1 (a real convolution) stays the caller's")
+        if tuple(lin.weight.shape[:2]) != (1, 3):
+            raise NotImplementedError(f"{name}: only 3 MSI channels to 1 PAN channel, got {tuple(lin.weight.shape[:2])}")
+        if name == "MSI_TO_PAN":
+            return PanMap("base", weight=lin.weight, bias=lin.bias, remove_sigm=module.remove_sigm)
+        return PanMap("fixedandtranslate", weight=lin.weight, bias=lin.bias, fixed_weights=module.fixed_weights,
+                      fixed_bias=module.fixed_bias, learn_conv2d=module.learn_conv2d)
+    raise RuntimeError(f"pan_map_of: unknown MSI->PAN module {name}")
+
+
+def _f32c(t, dev, what):
+    if t.device != dev:
+        raise RuntimeError(f"pan_shade: {what} on {t.device}, expected {dev}")
+    return t.detach().to(torch.float32).contiguous()
+
+
+class _PanShade(torch.autograd.Function):
+    """(cc, shaded, shadow) = pan(raw[3,H,W], alt_diff[H,W] | None, M, inshadow, map_params | None; order, kind)"""
+
+    @staticmethod
+    def forward(ctx, raw, alt_diff, M, inshadow, mp, order, kind, differentiable):
+        abi = _lib.get()
+        _, H, W = raw.shape
+        dev = raw.device
+        a_first = order == PAN_ORDER_CC_FIRST
+        x = _f32c(raw, dev, "raw_render")
+        m = _f32c(M, dev, "the colour correction").reshape(-1)
+        d = _f32c(alt_diff, dev, "sun_altitude_diff") if alt_diff is not None else None
+        ins = _f32c(inshadow, dev, "inshadow_color_correction").reshape(-1) if alt_diff is not None else None
+        p = _f32c(mp, dev, "the map's parameters") if mp is not None else None
+        with _Ctx(abi, dev) as cx:
+            cc = torch.empty((3 if a_first else 1, H, W), dtype=torch.float32, device=dev)
+            shaded = torch.empty((1, H, W), dtype=torch.float32, device=dev)
+            shadow = torch.empty((H, W), dtype=torch.float32, device=dev) if d is not None else None
+            abi.check(abi.pan_forward(H, W, order, kind, _ptr(x), _ptr(d), _ptr(m), _ptr(ins), _ptr(p), _ptr(cc), _ptr(shaded),
+                                      _ptr(shadow), cx.stream))
+        ctx.cfg = (H, W, order, kind, d is not None, M.shape, inshadow.shape if inshadow is not None else None)
+        ctx.save_for_backward(x, d, m, ins, p)
+        ctx.set_materialize_grads(False)
+        # what the reference's graph leaves without grad: a map no gradient passes (torch.no_grad, transf_msi_to_pan.py:
+        # 167-177) makes `shaded` a constant where `shaded` is the map's own result
+        if not differentiable and (a_first or d is None):
+            ctx.mark_non_differentiable(shaded)
+        return cc, shaded, shadow
+
+    @staticmethod
+    def backward(ctx, g_cc, g_shaded, g_shadow):
+        if g_cc is None and g_shaded is None and g_shadow is None:
+            return (None,) * 8
+        abi = _lib.get()
+        H, W, order, kind, has_shadow, m_shape, ins_shape = ctx.cfg
+        x, d, m, ins, p = ctx.saved_tensors
+        dev = x.device
+        with _Ctx(abi, dev) as cx:
+            gs = _f32c(g_shaded, dev, "the gradient of shaded") if g_shaded is not None else None
+            gc = _f32c(g_cc, dev, "the gradient of cc") if g_cc is not None else None
+            gsh = _f32c(g_shadow, dev, "the gradient of shadowmap") if (g_shadow is not None and has_shadow) else None
+            g_raw = torch.empty((3, H, W), dtype=torch.float32, device=dev)
+            g_alt = torch.empty((H, W), dtype=torch.float32, device=dev) if has_shadow else None
+            g_par = torch.empty((PAN_NPARAMS,), dtype=torch.float32, device=dev)
+            n = ctypes.c_size_t()
+            abi.check(abi.pan_bytes(H, W, ctypes.byref(n)))
+            ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+            abi.check(abi.pan_backward(H, W, order, kind, _ptr(x), _ptr(d), _ptr(m), _ptr(ins), _ptr(p), _ptr(gs), _ptr(gc),
+                                       _ptr(gsh), _ptr(g_raw), _ptr(g_alt), _ptr(g_par), _ptr(ws), ws.numel(), cx.stream))
+        g_M = g_par[:m.numel()].reshape(m_shape)
+        g_ins = g_par[12:12 + ins.numel()].reshape(ins_shape) if has_shadow else None
+        g_mp = None
+        if p is not None and ctx.needs_input_grad[4]:
+            g_mp = g_par[15:20] if kind == PAN_FIXED else g_par[15:19]
+            if kind == PAN_TRANSLATE:  # {fw[3], fb} are constants, the gradient belongs to {w[3], b}
+                g_mp = torch.cat([torch.zeros_like(g_mp), g_mp])
+        return g_raw, g_alt, g_M, g_ins, g_mp, None, None, None
+
+
+def pan_shade(raw, alt_diff, M, inshadow, pan_map, order=ORDER_CC_FIRST):
+    """The fused pipeline: `(cc, shaded, shadow)`.
+
+    order `"cc_first"` (or "A", `weird_pan_setup=False`): `M` (3, 4), `inshadow` 3 values;
+        cc = M[:, :3] @ raw + M[:, 3]; shaded = map(shadow cc + (1 - shadow) inshadow cc); cc has 3 planes.
+    order `"map_first"` (or "B", `weird_pan_setup=True`): `M` 2 values {w, b}, `inshadow` 1 value;
+        p0 = map(raw); cc = w p0 + b; shaded = shadow cc + (1 - shadow) inshadow cc, and **p0 when `alt_diff` is None**
+        (as the reference: PAN_affine_cameras.py:165-167); cc has 1 plane.
+    shadow = exp(0.4 min(alt_diff, 0)), or None without `alt_diff`. `shaded` is (1, H, W).
+    The `identity` map in order A is `eogs2_amd.shade.shade` itself (3 planes); in order B it raises, as the reference's
+    1->1 convolution does on 3 planes.
+    """
+    if order not in _ORDERS:
+        raise ValueError(f"pan_shade: unknown order {order!r}")
+    order = _ORDERS[order]
+    pan_map = pan_map_of(pan_map)
+    if pan_map.kind == "identity" and order != PAN_ORDER_CC_FIRST:
+        raise RuntimeError("pan_shade: the identity map leaves 3 planes, the 1->1 colour correction of the map-first "
+                           "order takes one (the reference fails in its Conv2d(1,1,1) here)")
+    if not torch.is_tensor(raw) or raw.ndim != 3 or raw.shape[0] != 3:
+        raise RuntimeError(f"pan_shade: raw_render must be (3, H, W), got {tuple(getattr(raw, 'shape', ()))}")
+    _, H, W = raw.shape
+    if H == 0 or W == 0:
+        raise RuntimeError("pan_shade: empty image")
+    if alt_diff is not None and tuple(alt_diff.shape) != (H, W):
+        raise RuntimeError(f"pan_shade: sun_altitude_diff must be ({H}, {W}), got {tuple(alt_diff.shape)}")
+    a_first = order == PAN_ORDER_CC_FIRST
+    if M.numel() != (12 if a_first else 2):
+        raise RuntimeError(f"pan_shade: the colour correction has {12 if a_first else 2} values in this order, got {M.numel()}")
+    if alt_diff is not None and (inshadow is None or inshadow.numel() != (3 if a_first else 1)):
+        raise RuntimeError(f"pan_shade: inshadow must have {3 if a_first else 1} value(s) in this order")
+    if raw.device.type != "cuda":
+        raise RuntimeError(f"pan_shade: raw_render on {raw.device}: the pipeline runs on the GPU, there is no CPU fallback")
+    if pan_map.kind == "identity":
+        return _shade.shade(raw, alt_diff, M.reshape(3, 4), inshadow.reshape(3) if alt_diff is not None else None)
+    kind, mp = pan_map.packed(raw.device)
+    return _PanShade.apply(raw, alt_diff, M, inshadow if alt_diff is not None else None, mp, order, kind,
+                           pan_map.differentiable)
+
+
+def render_pipeline(cam, raw_render, sun_altitude_diff=None):
+    """PANAffineCamera.render_pipeline (PAN_affine_cameras.py:73-176) for a duck-typed camera."""
+    dev = raw_render.device
+    pan_map = pan_map_of(cam.msi_to_pan)
+    use_shadow = bool(getattr(cam, "use_shadow", False)) and sun_altitude_diff is not None
+    alt = sun_altitude_diff if use_shadow else None
+    if getattr(cam, "weird_pan_setup", False):
+        conv = cam.color_correction  # always applied in this order (:156-157)
+        if pan_map.kind == "identity":
+            raise RuntimeError("render_pipeline: the identity map leaves 3 planes, the 1->1 colour correction of "
+                               "weird_pan_setup takes one (the reference fails in its Conv2d(1,1,1) here)")
+        if conv.weight.numel() != 1:
+            raise RuntimeError("render_pipeline: weird_pan_setup needs the camera's Conv2d(1,1,1) colour correction")
+        M = torch.cat([conv.weight.reshape(-1), conv.bias.reshape(-1)])
+        ins = cam.inshadow_color_correction.reshape(-1) if use_shadow else None
+        cc, shaded, shadow = pan_shade(raw_render, alt, M, ins, pan_map, ORDER_MAP_FIRST)
+    else:
+        if getattr(cam, "use_cc", False):
+            conv = cam.color_correction
+            M = torch.cat([conv.weight.reshape(3, 3), conv.bias.reshape(3, 1)], dim=1)
+        elif getattr(cam, "use_exposure", False):
+            M = cam.exposure[0]
+        else:
+            M = torch.eye(3, 4, device=dev)
+        ins = cam.inshadow_color_correction.reshape(3) if use_shadow else None
+        cc, shaded, shadow = pan_shade(raw_render, alt, M, ins, pan_map, ORDER_CC_FIRST)
+    return {"shadowmap": shadow, "shaded": shaded, "cc": cc, "final": shaded}
+
+
+__all__ = ["PanMap", "pan_map_of", "pan_shade", "render_pipeline", "ORDER_CC_FIRST", "ORDER_MAP_FIRST"]

@@ -14,7 +14,9 @@ render of the unperturbed scene under an identity colour correction, so the loss
 `simple_knn._C.distCUDA2` (§8 f4). `--flow-matching` adds the reference's flow-matching step between the render pipeline and
 the photometric loss (`eogs2_amd.flow`), against a target displaced by a sub-pixel registration error. `--opacity-loss W` and
 `--erank-loss W` add the reference's OpacityLoss (W = 0.1 in its shipped configuration) and erankLoss over the raw parameters
-(`eogs2_amd.regularizers`).
+(`eogs2_amd.regularizers`). `--pan-map NAME` makes the camera a panchromatic one: its render pipeline ends in the MSI->PAN map NAME
+(`eogs2_amd.pan.render_pipeline`, the reference's `PANAffineCamera`), the target goes through the same map and the photometric
+loss runs on the one PAN plane; `--pan-first` is the reference's `weird_pan_setup` (map first, then a 1->1 colour correction).
 """
 import argparse
 import math
@@ -36,6 +38,7 @@ from eogs2_amd.shade import randomcam_l, render_pipeline, suncamera_l, transluce
 from eogs2_amd.dsm_eval import dsm_mae  # noqa: E402
 from eogs2_amd.flow import apply_flow, perform_flow_matching, performOpticalmatching  # noqa: E402
 from eogs2_amd.regularizers import gaussian_regularizers  # noqa: E402
+from eogs2_amd.pan import FIXED_PARAMS, KINDS as PAN_KINDS, PanMap, render_pipeline as pan_render_pipeline  # noqa: E402
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
@@ -136,7 +139,20 @@ def main(argv=None):
                          "every iteration with W = 0.1 (gs_config/train.yaml:118,141). 0 = absent")
     ap.add_argument("--erank-loss", type=float, default=0.0, metavar="W",
                     help="adds W x erankLoss (loss/main_loss.py:26-34) in the same launch group as --opacity-loss. 0 = absent")
+    ap.add_argument("--pan-map", choices=[k for k in PAN_KINDS if k != "identity"], default=None, metavar="NAME",
+                    help="a panchromatic camera (scene/cameras/PAN_affine_cameras.py): the render pipeline ends in the MSI->PAN map "
+                         "NAME of the reference's load_msi_to_pan (only_one_channel, average, fixed, learnable_fixed, base, "
+                         "fixedandtranslate) through eogs2_amd.pan.render_pipeline; the target image goes through the same map with its "
+                         "default parameters and the photometric loss runs on one plane. The learnable maps start perturbed and are "
+                         "unfrozen: their parameters join the camera's optimizer")
+    ap.add_argument("--pan-first", action="store_true",
+                    help="with --pan-map: the reference's weird_pan_setup (PAN_affine_cameras.py:148-176): the map first, then a "
+                         "Conv2d(1,1,1) colour correction and a scalar in-shadow tint")
     a = ap.parse_args(argv)
+    if a.pan_first and not a.pan_map:
+        ap.error("--pan-first needs --pan-map")
+    if a.pan_map and a.flow_matching:
+        ap.error("--flow-matching runs on the three-plane pipeline here: not with --pan-map")
     dev = torch.device("cuda:0")
     P, H, W = a.gaussians, a.size, a.size
     sc = make_scene(P, H, W, seed=0, opacity="trained", device=dev)
@@ -171,7 +187,7 @@ def main(argv=None):
                 smp, sun_uv = resample(sun_img, cam2sun, uva)
                 sun_rgb, sun_alt = smp[:3], smp[3]
             sun_altitude_diff = altitude - sun_alt
-            shaded = render_pipeline(cc_cam, img, sun_altitude_diff)
+            shaded = pipeline(cc_cam, img, sun_altitude_diff)
             new = None
             if a.random_camera:
                 smp, new_uv = resample(rnd_img, cam2rnd, uva)
@@ -183,14 +199,47 @@ def main(argv=None):
         sun_rgb, sun_alt, sun_uv = render_resample_virtual_camera(sun, cam2sun, uva, m, pipe, bg,
                                                                   altitude_only=a.sun_altitude_only)
         sun_altitude_diff = altitude - sun_alt
-        shaded = render_pipeline(cc_cam, img, sun_altitude_diff)
+        shaded = pipeline(cc_cam, img, sun_altitude_diff)
         new = None
         if a.random_camera:  # train_pan.py:375-391 / loss/main_loss.py:123-164
             new_rgb, new_alt, new_uv = render_resample_virtual_camera(rnd, cam2rnd, uva, m, pipe, bg)
             new = (altitude - new_alt, new_rgb, new_uv)
         return out, img, sun_rgb, sun_uv, sun_altitude_diff, shaded, new
 
+    pipeline = pan_render_pipeline if a.pan_map else render_pipeline
+
+    def pan_map(perturb):
+        """The MSI->PAN map of --pan-map with the reference's initial values (transf_msi_to_pan.py:11-14,116-117); the
+        trainee's (perturb > 0) learnable tensors are Parameters that start off those values."""
+        dflt = torch.tensor(FIXED_PARAMS, device=dev)
+        param = lambda t, rel: torch.nn.Parameter(t + rel * perturb * torch.randn(t.shape, generator=gcam).to(dev)) if perturb else t  # noqa: E731
+        if a.pan_map == "fixed":
+            return PanMap("fixed", params=dflt)
+        if a.pan_map == "learnable_fixed":
+            return PanMap("learnable_fixed", params=param(dflt.clone(), 0.5))
+        if a.pan_map == "base":
+            return PanMap("base", weight=param(dflt[:3].clone(), 0.5), bias=param(dflt[4:].clone(), 0.5))
+        if a.pan_map == "fixedandtranslate":
+            return PanMap("fixedandtranslate", weight=param(torch.zeros(3, device=dev), 0.5), bias=param(torch.zeros(1, device=dev), 0.5),
+                          fixed_weights=dflt[:3].clone(), fixed_bias=dflt[4:].clone(), learn_conv2d=True)
+        return PanMap(a.pan_map)
+
+    def pan_camera(perturb):
+        c = types.SimpleNamespace(use_cc=True, use_exposure=False, use_shadow=True, weird_pan_setup=a.pan_first)
+        n = 1 if a.pan_first else 3  # PAN_affine_cameras.py:46-60: the map-first order overrides the (3,3) conv with a (1,1) one
+        c.color_correction = torch.nn.Conv2d(n, n, 1, bias=True).to(dev)
+        with torch.no_grad():
+            c.color_correction.weight.copy_((torch.eye(n) + perturb * torch.randn(n, n, generator=gcam)).reshape(n, n, 1, 1))
+            c.color_correction.bias.zero_()
+        c.inshadow_color_correction = torch.nn.Parameter(torch.full((n, 1, 1), 0.05, device=dev))
+        c.msi_to_pan = pan_map(perturb)
+        m = c.msi_to_pan
+        c.map_parameters = [t for t in (m.params, m.weight, m.bias) if isinstance(t, torch.nn.Parameter)]
+        return c
+
     def colour_camera(perturb):
+        if a.pan_map:
+            return pan_camera(perturb)
         c = types.SimpleNamespace(use_cc=True, use_exposure=False, use_shadow=True)
         c.color_correction = torch.nn.Conv2d(3, 3, 1, bias=True).to(dev)  # affine_cameras.py:219-231
         with torch.no_grad():
@@ -218,7 +267,8 @@ def main(argv=None):
                                         model=lambda gt_n, img_n, num_flow_updates=12: [field])
         flow_opt = types.SimpleNamespace(flowmatching=types.SimpleNamespace(max_value_flow=3.0))
     cc_cam = colour_camera(0.15)
-    camera_optimizer = torch.optim.Adam([*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction], lr=2e-3)
+    camera_optimizer = torch.optim.Adam([*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction,
+                                         *getattr(cc_cam, "map_parameters", ())], lr=2e-3)
 
     # the trainee: perturbed colours / opacities / positions, scales re-initialised from the 3-NN statistic
     g = torch.Generator().manual_seed(1)
