@@ -169,6 +169,17 @@ PAN_SIGNATURES = {
     "eogs_pan_forward": (_i, [_i, _i, _i, _i] + [_p] * 8 + [_p]),
     "eogs_pan_backward": (_i, [_i, _i, _i, _i] + [_p] * 11 + [_p, _z, _p]),
 }
+# include/eogs_density.h, a table of its own for the same reason
+DENSITY_SIGNATURES = {
+    "eogs_density_stats_update": (_i, [_i64, _p, _p, _i, _p, _p, _p, _p]),
+    "eogs_density_bytes": (_i, [_i64, C.POINTER(_z)]),
+    "eogs_density_decide": (_i, [_i64, _p, _p, _p, _p, _f, _f, _f, _i, _f, _f, _p, _p, _z, C.POINTER(_i64), _p]),
+    "eogs_density_split_rows": (_i, [_i64, _p, _p, _p, _i, _p, _z, _p]),
+    "eogs_density_build": (_i, [_i64, _i, _p, C.POINTER(_i64), _i, _p, _p, _p, _f, _p, _z, _p]),
+}
+DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP = 1, 2, 4, 8  # EOGS_DENSITY_*: the flag byte
+DENSITY_COPY, DENSITY_ZERO, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2, 3  # the tensor kinds of eogs_density_build
+DENSITY_MAX_N = 8
 # symbols only the HIP library exports (the CPU oracle of the loss is oracle/loss_oracle.py, not a C-ABI twin)
 HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
             "eogs_compact_plan", "eogs_compact_apply", "eogs_resample_forward", "eogs_resample_bytes", "eogs_resample_backward", "eogs_knn_bytes",
@@ -179,7 +190,8 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_tsdf_dsm_mae_bytes", "eogs_tsdf_dsm_mae", "eogs_resample_flow_forward", "eogs_resample_flow_bytes",
             "eogs_resample_flow_backward", "eogs_resample_flow_stats_bytes", "eogs_resample_flow_stats", "eogs_reg_gauss_bytes",
             "eogs_reg_gauss_forward", "eogs_reg_gauss_backward", "eogs_reg_image_bytes", "eogs_reg_image_forward",
-            "eogs_reg_image_backward", "eogs_pan_bytes", "eogs_pan_forward", "eogs_pan_backward")
+            "eogs_reg_image_backward", "eogs_pan_bytes", "eogs_pan_forward", "eogs_pan_backward", "eogs_density_stats_update",
+            "eogs_density_bytes", "eogs_density_decide", "eogs_density_split_rows", "eogs_density_build")
 
 
 class PackTensor(C.Structure):
@@ -192,6 +204,12 @@ class SumTensor(C.Structure):
     """eogs_sum_tensor (include/eogs_optim.h)"""
 
     _fields_ = [("dst", _p), ("src", _p * 4), ("numel", _i64)]
+
+
+class DensityTensor(C.Structure):
+    """eogs_density_tensor (include/eogs_density.h)"""
+
+    _fields_ = [("src", _p), ("dst", _p), ("row_bytes", _i), ("kind", _i)]
 
 
 class AdamTensor(C.Structure):
@@ -214,7 +232,7 @@ class RastABI:
         self.cdll = C.CDLL(self.path)
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
-        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -232,7 +250,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -1101,6 +1101,107 @@ int eogs_pan_backward(int H, int W, int order, int kind, const float* raw, const
   return EOGS_OK;
 }
 
+// ---- include/eogs_density.h ----
+int eogs_density_stats_update(int64_t P, const float* viewspace_grad, const void* radii, int radii_is_float,
+                              float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream) {
+  g_err[0] = 0;
+  if (P < 0 || P > EOGS_DENSITY_MAX_ROWS) return fail(EOGS_ERR_INVALID_ARG, "density_stats_update: bad row count");
+  if (P > 0 && (!viewspace_grad || !radii || !xyz_gradient_accum || !denom || !max_radii2D))
+    return fail(EOGS_ERR_INVALID_ARG, "density_stats_update: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  launch_density_stats(P, viewspace_grad, radii, radii_is_float, xyz_gradient_accum, denom, max_radii2D, s);
+  LAUNCH_TRY(s, false, "density_stats_update");
+  return EOGS_OK;
+}
+
+int eogs_density_bytes(int64_t P, size_t* bytes) {
+  g_err[0] = 0;
+  if (P < 0 || P > EOGS_DENSITY_MAX_ROWS || !bytes) return fail(EOGS_ERR_INVALID_ARG, "density_bytes: bad argument");
+  *bytes = density_layout(nullptr, P).bytes;
+  return EOGS_OK;
+}
+
+static int density_check(const char* who, int64_t P, const void* flags, const void* ws, size_t ws_bytes, DensityWS* w) {
+  if (P < 0 || P > EOGS_DENSITY_MAX_ROWS) return fail(EOGS_ERR_INVALID_ARG, "%s: bad row count", who);
+  if ((P > 0 && !flags) || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  char* base = ws_base(const_cast<void*>(ws));
+  *w = density_layout(base, P);
+  if ((size_t)(base - (const char*)ws) + w->bytes - 256 > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  return EOGS_OK;
+}
+
+int eogs_density_decide(int64_t P, const float* xyz_gradient_accum, const float* denom, const float* opacity,
+                        const float* scaling, float grad_threshold, float dense_threshold, float min_opacity, int use_screen,
+                        float big_threshold, float split_div, uint8_t* flags, void* ws, size_t ws_bytes, int64_t* counts,
+                        void* stream) {
+  g_err[0] = 0;
+  DensityWS w;
+  const int rc = density_check("density_decide", P, flags, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (!counts) return fail(EOGS_ERR_INVALID_ARG, "density_decide: NULL counts");
+  if (P > 0 && (!xyz_gradient_accum || !denom || !opacity || !scaling)) return fail(EOGS_ERR_INVALID_ARG, "density_decide: NULL argument");
+  if (!(split_div > 0.f)) return fail(EOGS_ERR_INVALID_ARG, "density_decide: split_div must be positive");
+  hipStream_t s = (hipStream_t)stream;
+  launch_density_decide(w, P, xyz_gradient_accum, denom, opacity, scaling, grad_threshold, dense_threshold, min_opacity, use_screen,
+                        big_threshold, split_div, flags, s);
+  LAUNCH_TRY(s, false, "density_decide");
+  uint32_t total[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(total, w.cnt + 4 * (size_t)w.nblk, sizeof total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < 4; k++) counts[k] = (int64_t)total[k];
+  return EOGS_OK;
+}
+
+int eogs_density_split_rows(int64_t P, const uint8_t* flags, const void* src, void* dst, int row_bytes, const void* ws,
+                            size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  DensityWS w;
+  const int rc = density_check("density_split_rows", P, flags, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (row_bytes < 0 || row_bytes > 256 || (row_bytes & 3))
+    return fail(EOGS_ERR_INVALID_ARG, "density_split_rows: row sizes must be multiples of 4 up to 256 bytes");
+  if (row_bytes > 0 && P > 0 && (!src || !dst)) return fail(EOGS_ERR_INVALID_ARG, "density_split_rows: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  launch_density_split_rows(w, P, flags, src, dst, row_bytes, s);
+  LAUNCH_TRY(s, false, "density_split_rows");
+  return EOGS_OK;
+}
+
+int eogs_density_build(int64_t P, int N, const uint8_t* flags, const int64_t* counts, int n_tensors,
+                       const eogs_density_tensor* tensors, const float* rotation, const float* samples, float split_div,
+                       const void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  DensityWS w;
+  const int rc = density_check("density_build", P, flags, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (N < 1 || N > EOGS_DENSITY_MAX_N) return fail(EOGS_ERR_INVALID_ARG, "density_build: N out of range");
+  if (!counts) return fail(EOGS_ERR_INVALID_ARG, "density_build: NULL counts");
+  for (int k = 0; k < 4; k++)
+    if (counts[k] < 0 || counts[k] > P) return fail(EOGS_ERR_INVALID_ARG, "density_build: counts are not those of density_decide on these rows");
+  if (counts[EOGS_DENSITY_N_KEPT_SPLIT] > counts[EOGS_DENSITY_N_SPLIT] || counts[EOGS_DENSITY_N_KEPT] + counts[EOGS_DENSITY_N_SPLIT] > P)
+    return fail(EOGS_ERR_INVALID_ARG, "density_build: counts are not those of density_decide on these rows");
+  if (n_tensors < 0 || (n_tensors > 0 && !tensors)) return fail(EOGS_ERR_INVALID_ARG, "density_build: bad tensor list");
+  if (!(split_div > 0.f)) return fail(EOGS_ERR_INVALID_ARG, "density_build: split_div must be positive");
+  const int64_t n_out = counts[0] + counts[1] + (int64_t)N * counts[3];
+  bool computed = false;
+  for (int t = 0; t < n_tensors; t++) {
+    const eogs_density_tensor& T = tensors[t];
+    if (T.row_bytes < 0 || T.row_bytes > 256 || (T.row_bytes & 3))
+      return fail(EOGS_ERR_INVALID_ARG, "density_build: row sizes must be multiples of 4 up to 256 bytes");
+    if (T.kind < EOGS_DENSITY_COPY || T.kind > EOGS_DENSITY_SCALING) return fail(EOGS_ERR_INVALID_ARG, "density_build: unknown tensor kind");
+    if ((T.kind == EOGS_DENSITY_XYZ || T.kind == EOGS_DENSITY_SCALING) && T.row_bytes != 12)
+      return fail(EOGS_ERR_INVALID_ARG, "density_build: xyz and scaling rows hold three floats");
+    if (T.row_bytes > 0 && ((P > 0 && !T.src) || (n_out > 0 && !T.dst))) return fail(EOGS_ERR_INVALID_ARG, "density_build: NULL tensor pointer");
+    computed = computed || T.kind == EOGS_DENSITY_XYZ;
+  }
+  if (computed && counts[EOGS_DENSITY_N_KEPT_SPLIT] > 0 && (!rotation || !samples))
+    return fail(EOGS_ERR_INVALID_ARG, "density_build: split rows need rotation and samples (NULL argument)");
+  hipStream_t s = (hipStream_t)stream;
+  launch_density_build(w, P, N, flags, counts, n_tensors, tensors, rotation, samples, split_div, s);
+  LAUNCH_TRY(s, false, "density_build");
+  return EOGS_OK;
+}
+
 // ---- include/eogs_tsdf.h ----
 int eogs_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,
                         float model_scale, float trunc_margin, int H, int W, const float* altitude, const float* weight,

@@ -13,6 +13,7 @@
 #include "eogs_shade.h"
 #include "eogs_reg.h"
 #include "eogs_pan.h"
+#include "eogs_density.h"
 #include "eogs_tsdf.h"
 
 #define NCH EOGS_RAST_CHANNELS  // 5 feature channels
@@ -617,6 +618,24 @@ void launch_pack_columns(int64_t rows, int n, const eogs_pack_tensor* tensors, f
 void launch_compact_plan(const CompactWS& w, int64_t n_rows, const uint8_t* keep, hipStream_t s);
 void launch_compact_apply(const CompactWS& w, int64_t n_rows, const uint8_t* keep, int n_tensors, const void* const* src,
                           void* const* dst, const int* row_bytes, hipStream_t s);
+
+// ---- adaptive density control (density.hip, include/eogs_density.h) ----
+struct DensityWS {
+  uint32_t* cnt;  // [nblk + 1][4] rows of the four kinds per 256-row workgroup -> exclusive prefixes, totals at [nblk]
+  uint32_t nblk;
+  size_t bytes;
+};
+DensityWS density_layout(char* base, int64_t P);
+void launch_density_stats(int64_t P, const float* vg, const void* radii, int radii_is_float, float* accum, float* denom,
+                          float* maxr, hipStream_t s);
+void launch_density_decide(const DensityWS& w, int64_t P, const float* accum, const float* denom, const float* opacity,
+                           const float* scaling, float thr_grad, float thr_dense, float min_opacity, int use_screen, float thr_big,
+                           float split_div, uint8_t* flags, hipStream_t s);
+void launch_density_split_rows(const DensityWS& w, int64_t P, const uint8_t* flags, const void* src, void* dst, int row_bytes,
+                               hipStream_t s);
+void launch_density_build(const DensityWS& w, int64_t P, int N, const uint8_t* flags, const int64_t* counts, int n_tensors,
+                          const eogs_density_tensor* tensors, const float* rotation, const float* samples, float split_div,
+                          hipStream_t s);
 
 // ---- virtual-camera resample (resample.hip, include/eogs_resample.h) ----
 void launch_resample_fwd(int C, int Hv, int Wv, int H, int W, int n_out, const float* vr, const float* uva,

@@ -75,8 +75,11 @@ def render(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0, separate_
         # renderer.py:128-130 returns the INDICES (`nonzero`, which waits for the device to learn how many there are). While
         # a HIP graph is being recorded nothing may wait: the boolean mask is returned instead — `t[visibility_filter]`
         # reads and writes the same elements either way (train_pan.py:679-686).
+        # `pipe.visibility_as_mask` (not in the reference's pipe; absent = False) asks for the mask in eager mode too: callers
+        # that hand `radii` to eogs2_amd.density need neither the indices nor the wait.
         capturing = radii.is_cuda and torch.cuda.is_current_stream_capturing()
-        out["visibility_filter"] = (radii > 0) if capturing else torch.nonzero(radii > 0)
+        as_mask = capturing or getattr(pipe, "visibility_as_mask", False)
+        out["visibility_filter"] = (radii > 0) if as_mask else torch.nonzero(radii > 0)
     return out
 
 

@@ -17,6 +17,8 @@ the photometric loss (`eogs2_amd.flow`), against a target displaced by a sub-pix
 (`eogs2_amd.regularizers`). `--pan-map NAME` makes the camera a panchromatic one: its render pipeline ends in the MSI->PAN map NAME
 (`eogs2_amd.pan.render_pipeline`, the reference's `PANAffineCamera`), the target goes through the same map and the photometric
 loss runs on the one PAN plane; `--pan-first` is the reference's `weird_pan_setup` (map first, then a 1->1 colour correction).
+`--densify-every K` is the reference's `only_prune: False` (train_pan.py:679-711): the densification statistics every iteration
+(`eogs2_amd.density.DensityStats.update`, one launch, no wait) and `densify_and_prune` plus the transparent prune every K iterations.
 """
 import argparse
 import math
@@ -30,6 +32,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from eogs2_amd.losses import photometric_loss  # noqa: E402
+from eogs2_amd.density import DensityStats, densify_and_prune  # noqa: E402
 from eogs2_amd.optim import FusedAdam, alive_rows, prune_optimizer, retire_rows  # noqa: E402
 from eogs2_amd.render import render  # noqa: E402
 from eogs2_amd.graph import Branches  # noqa: E402
@@ -77,13 +80,32 @@ class Gaussians:
                                    ("scaling", "scaling", lrs["scaling"]), ("rotation", "rotation", lrs["rotation"]))]
         self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)  # gaussian_model.py:262 with the fused step
         self.max_radii2D = torch.zeros(P, device=xyz.device)
+        self.stats = None  # --densify-every: DensityStats (xyz_gradient_accum, denom and the max_radii2D above)
 
     get_xyz = property(lambda s: s._xyz)
 
-    def prune(self, keep):  # gaussian_model.py:488-505
-        t, (self.max_radii2D,) = prune_optimizer(self.optimizer, keep, extra=(self.max_radii2D,))
+    def _adopt(self, t):
         self._xyz, self._features_dc, self._features_rest = t["xyz"], t["f_dc"], t["f_rest"]
         self._opacity, self._scaling, self._rotation = t["opacity"], t["scaling"], t["rotation"]
+
+    def track_density(self):
+        self.stats = DensityStats(self._xyz.shape[0], self._xyz.device)
+        self.max_radii2D = self.stats.max_radii2D
+
+    def prune(self, keep):  # gaussian_model.py:488-505
+        if self.stats is not None:
+            t, extra = prune_optimizer(self.optimizer, keep, extra=self.stats.tensors())
+            self.stats = DensityStats.of(extra)
+            self.max_radii2D = self.stats.max_radii2D
+        else:
+            t, (self.max_radii2D,) = prune_optimizer(self.optimizer, keep, extra=(self.max_radii2D,))
+        self._adopt(t)
+
+    def densify_and_prune(self, **kw):  # gaussian_model.py:685-717, one pass (eogs2_amd.density)
+        t, self.stats, info = densify_and_prune(self.optimizer, self.stats, **kw)
+        self.max_radii2D = self.stats.max_radii2D
+        self._adopt(t)
+        return info
 
 
 def main(argv=None):
@@ -145,6 +167,17 @@ def main(argv=None):
                          "fixedandtranslate) through eogs2_amd.pan.render_pipeline; the target image goes through the same map with its "
                          "default parameters and the photometric loss runs on one plane. The learnable maps start perturbed and are "
                          "unfrozen: their parameters join the camera's optimizer")
+    ap.add_argument("--densify-every", type=int, default=0, metavar="K",
+                    help="adaptive density control, the reference's `only_prune: False` (train_pan.py:679-711): every iteration "
+                         "the densification statistics (eogs2_amd.density.DensityStats.update: one launch on the render's radii and "
+                         "the screen-space gradient, no nonzero and no wait), every K iterations densify_and_prune in one pass "
+                         "(eogs2_amd.density.densify_and_prune) followed by the transparent prune; implies radii; with --graph the "
+                         "step is recorded again after each. 0 = off")
+    ap.add_argument("--densify-grad-threshold", type=float, default=None, metavar="T",
+                    help="with --densify-every: densify_grad_threshold (mean screen-space gradient norm at or above which a "
+                         "Gaussian is cloned or split). The reference's value is tuned to its scenes; by default this example takes "
+                         "the 0.95 quantile of the statistic over the rows seen so far at the first densification (one readback "
+                         "there) and keeps it: about a twentieth of the Gaussians are densified each time")
     ap.add_argument("--pan-first", action="store_true",
                     help="with --pan-map: the reference's weird_pan_setup (PAN_affine_cameras.py:148-176): the map first, then a "
                          "Conv2d(1,1,1) colour correction and a scalar in-shadow tint")
@@ -163,7 +196,8 @@ def main(argv=None):
     rnd = Camera(make_camera(H, W, seed=9, device=dev), H, W)
     cam2rnd = torch.eye(3, device=dev)
     cam2rnd[:2, 2] = (rnd.affine[2, :2] - cam.affine[2, :2]) / 350.0
-    pipe = types.SimpleNamespace(debug=False, antialiasing=False, compute_cov3D_python=False, require_radii=a.require_radii)
+    pipe = types.SimpleNamespace(debug=False, antialiasing=False, compute_cov3D_python=False, require_radii=a.require_radii or bool(a.densify_every),
+                                 visibility_as_mask=bool(a.densify_every))  # (the statistics kernel reads radii: no index list, no wait)
     bg = sc["bg"]
     U, V = torch.meshgrid(torch.linspace(-1, 1, W, device=dev), torch.linspace(-1, 1, H, device=dev), indexing="xy")
 
@@ -278,6 +312,11 @@ def main(argv=None):
                       torch.full((P,), 0.3, device=dev), torch.sqrt(dist2)[:, None].repeat(1, 3), sc["rotations"])
     # the regularisers over the raw parameters: weights in a device tensor the kernels read (a schedule would write into it
     # between replays of a recorded graph), terms chosen once; init_number_of_gaussians is the constant P of the start
+    extent, grad_threshold = 0.0, a.densify_grad_threshold
+    if a.densify_every:
+        model.track_density()
+        torch.manual_seed(0)  # densify_and_prune draws the split samples from the device's default generator: the same run twice
+        extent = 0.5 * float((sc["means3D"].max(dim=0).values - sc["means3D"].min(dim=0).values).max())  # cameras_extent's role
     reg_want = tuple(n for n, w in (("opacity", a.opacity_loss), ("erank", a.erank_loss)) if w)
     reg_weights = torch.tensor([a.opacity_loss, 0.0, a.erank_loss], device=dev) if reg_want else None
 
@@ -302,7 +341,7 @@ def main(argv=None):
         loss.backward()
         if a.dsm_mae_every:
             kept["altitude"] = out["render"][3].detach()  # (under --graph: the recorded step's output tensor, refilled by a replay)
-        return loss.detach(), out.get("radii")
+        return loss.detach(), out.get("radii"), out["viewspace_points"].grad
 
     kept, dsm_scores = {}, []  # --dsm-mae-every: the view's altitude of the last step; (iteration, dx, dy, mae)
     first = last = None
@@ -323,13 +362,26 @@ def main(argv=None):
             elif stale:
                 step.record_again()  # new parameter tensors, new shapes (fwd_bwd reads them from `model`); same memory pool
             stale = False
-            loss, radii = step()
+            loss, radii, vs_grad = step()
         else:
-            loss, radii = fwd_bwd()
+            loss, radii, vs_grad = fwd_bwd()
         model.optimizer.step()
         camera_optimizer.step()
         with torch.no_grad():
-            if radii is not None:  # train_pan.py:681-686 (densification statistics: only with require_radii)
+            if model.stats is not None:  # train_pan.py:679-690 in one launch, outside the recorded step: once per iteration
+                model.stats.update(vs_grad, radii)
+                if it % a.densify_every == 0:  # train_pan.py:692-711
+                    if grad_threshold is None:
+                        seen = model.stats.denom > 0
+                        mean_norm = (model.stats.xyz_gradient_accum[seen] / model.stats.denom[seen]).double()
+                        grad_threshold = float(torch.quantile(mean_norm, 0.95)) if mean_norm.numel() else math.inf
+                    model.densify_and_prune(grad_threshold=grad_threshold, min_opacity=0.005, screen_size_threshold=extent,
+                                            max_screen_size=None, scene_extent=extent, radii=radii)
+                    keep = model._opacity.reshape(-1) >= math.log(0.005 / 0.995)
+                    if not bool(keep.all()):
+                        model.prune(keep)
+                    stale = True  # new parameter tensors, new shapes: record again
+            elif radii is not None:  # train_pan.py:681-686 (densification statistics: only with require_radii)
                 model.max_radii2D = torch.maximum(model.max_radii2D, radii.float())
             if it % a.prune_every == 0 and not a.no_prune:  # train_pan.py:673-678
                 keep = model._opacity.squeeze() >= math.log(0.005 / 0.995)
@@ -361,6 +413,9 @@ def main(argv=None):
     dt = t1 - t0
     main.last_ms_per_iter = (t1 - t_steady) / timed * 1e3  # steady state: the last half of the run
     main.last_dsm_mae = dsm_scores
+    main.last_params = None
+    if a.densify_every:  # what callers compare between runs, beside the returned tuple
+        main.last_params = {g["name"]: g["params"][0].detach().cpu() for g in model.optimizer.param_groups}
     if not a.quiet:
         print(f"{a.iters} iterations in {dt:.2f} s ({dt / a.iters * 1e3:.2f} ms/iter over all, {main.last_ms_per_iter:.2f} ms/iter over the "
               f"last {timed}; {3 if a.random_camera else 2} renders + resample + render pipeline + losses + Adam each)")
