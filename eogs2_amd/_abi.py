@@ -177,6 +177,13 @@ DENSITY_SIGNATURES = {
     "eogs_density_split_rows": (_i, [_i64, _p, _p, _p, _i, _p, _z, _p]),
     "eogs_density_build": (_i, [_i64, _i, _p, C.POINTER(_i64), _i, _p, _p, _p, _f, _p, _z, _p]),
 }
+# include/eogs_step.h, a table of its own for the same reason
+STEP_SIGNATURES = {
+    "eogs_step_gate": (_i, [_i, _p, _i, _p, _p]),
+    "eogs_step_adam_bytes": (_i, [_i, C.POINTER(_z)]),
+    "eogs_step_adam": (_i, [_i, _p, C.c_double, C.c_double, C.c_double, _p, _p, _z, _p]),
+}
+STEP_MAX_FORWARDS = STEP_MAX_TENSORS = 16  # EOGS_STEP_MAX_*
 DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP = 1, 2, 4, 8  # EOGS_DENSITY_*: the flag byte
 DENSITY_COPY, DENSITY_ZERO, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2, 3  # the tensor kinds of eogs_density_build
 DENSITY_MAX_N = 8
@@ -191,7 +198,8 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_resample_flow_backward", "eogs_resample_flow_stats_bytes", "eogs_resample_flow_stats", "eogs_reg_gauss_bytes",
             "eogs_reg_gauss_forward", "eogs_reg_gauss_backward", "eogs_reg_image_bytes", "eogs_reg_image_forward",
             "eogs_reg_image_backward", "eogs_pan_bytes", "eogs_pan_forward", "eogs_pan_backward", "eogs_density_stats_update",
-            "eogs_density_bytes", "eogs_density_decide", "eogs_density_split_rows", "eogs_density_build")
+            "eogs_density_bytes", "eogs_density_decide", "eogs_density_split_rows", "eogs_density_build", "eogs_step_gate",
+            "eogs_step_adam_bytes", "eogs_step_adam")
 
 
 class PackTensor(C.Structure):
@@ -218,6 +226,25 @@ class AdamTensor(C.Structure):
     _fields_ = [("param", _p), ("grad", _p), ("exp_avg", _p), ("exp_avg_sq", _p), ("numel", _i64), ("lr", _f)]
 
 
+class StepForward(C.Structure):
+    """eogs_step_forward (include/eogs_step.h)"""
+
+    _fields_ = [("geom", _p), ("geom_bytes", _z), ("P", _i), ("capacity", _i64)]
+
+
+class StepAdamTensor(C.Structure):
+    """eogs_step_adam_tensor (include/eogs_step.h)"""
+
+    _fields_ = [("param", _p), ("grad", _p), ("exp_avg", _p), ("exp_avg_sq", _p), ("numel", _i64), ("lr", _p), ("step", _p),
+                ("retire_below", _f)]
+
+
+class StepAdamScalars(C.Structure):
+    """eogs_step_adam_scalars (include/eogs_step.h): one row of the prologue's table"""
+
+    _fields_ = [("lr", _f), ("inv_bc1", _f), ("sqrt_bc2", _f), ("skip", _f)]
+
+
 class RastError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -232,7 +259,8 @@ class RastABI:
         self.cdll = C.CDLL(self.path)
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
-        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items()):
+        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
+                                  *STEP_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -250,7 +278,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

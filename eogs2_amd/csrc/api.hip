@@ -404,7 +404,7 @@ int eogs_rast_capacity_token(int P, int64_t num_rendered, double slack, int have
                       nr_shallow(num_rendered), alt);
   // A capacity token carries the list granularity and the 8-item build of the EARLIER forward: speed only, every choice computes
   // the same values (ABI 3-7 also carried a choice of backward formulation that did matter for parity; gone with ABI 8).
-  if (fits) *fits = exact >= 0 && nr_slots(exact) <= slots && nr_entries(exact) <= ents;
+  if (fits) *fits = exact >= 0 && capacity_fits(nr_slots(exact), nr_entries(exact), slots, ents);
   return EOGS_OK;
 }
 
@@ -670,6 +670,56 @@ int eogs_adam_step(int n, const eogs_adam_tensor* tensors, double beta1, double 
   { ProfScope ps(PS_ADAM, s); rc = launch_adam(n, tensors, beta1, beta2, eps, step, s); }
   if (rc) return fail(EOGS_ERR_OVERFLOW, "adam_step: too many elements for one launch");
   LAUNCH_TRY(s, false, "adam");
+  return EOGS_OK;
+}
+
+// ---- include/eogs_step.h ----
+int eogs_step_gate(int n, const eogs_step_forward* fw, int accumulate, uint32_t* gate, void* stream) {
+  g_err[0] = 0;
+  if (n < 0 || n > EOGS_STEP_MAX_FORWARDS || (n > 0 && !fw) || !gate)
+    return fail(EOGS_ERR_INVALID_ARG, "step_gate: bad argument (at most 16 forwards, a gate)");
+  const uint32_t* misc[EOGS_STEP_MAX_FORWARDS];
+  uint32_t cap_slots[EOGS_STEP_MAX_FORWARDS], cap_entries[EOGS_STEP_MAX_FORWARDS];
+  for (int i = 0; i < n; i++) {
+    if (fw[i].P <= 0 || !fw[i].geom || fw[i].capacity < 0) return fail(EOGS_ERR_INVALID_ARG, "step_gate: bad forward descriptor");
+    char* base = ws_base(const_cast<void*>(fw[i].geom));
+    const GeomWS g = geom_layout(base, fw[i].P);
+    if ((size_t)(base - (const char*)fw[i].geom) + g.bytes - 256 > fw[i].geom_bytes)
+      return fail(EOGS_ERR_WORKSPACE, "step_gate: geom workspace too small");
+    misc[i] = g.misc;
+    cap_slots[i] = nr_slots(fw[i].capacity);
+    cap_entries[i] = nr_entries(fw[i].capacity);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  launch_step_gate(n, misc, cap_slots, cap_entries, accumulate, gate, s);
+  LAUNCH_TRY(s, false, "step_gate");
+  return EOGS_OK;
+}
+
+int eogs_step_adam_bytes(int n, size_t* bytes) {
+  if (n < 0 || n > EOGS_STEP_MAX_TENSORS || !bytes) return fail(EOGS_ERR_INVALID_ARG, "step_adam_bytes: bad argument (at most 16 tensors)");
+  *bytes = (size_t)n * sizeof(eogs_step_adam_scalars);
+  return EOGS_OK;
+}
+
+int eogs_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, double beta2, double eps, const uint32_t* gate,
+                   void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  if (n < 0 || n > EOGS_STEP_MAX_TENSORS) return fail(EOGS_ERR_INVALID_ARG, "step_adam: bad argument (at most 16 tensors)");
+  if (n == 0) return EOGS_OK;
+  if (!tensors) return fail(EOGS_ERR_INVALID_ARG, "step_adam: NULL tensors");
+  for (int i = 0; i < n; i++) {
+    const eogs_step_adam_tensor& t = tensors[i];
+    if (t.numel < 0 || !t.lr || !t.step || (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)))
+      return fail(EOGS_ERR_INVALID_ARG, "step_adam: NULL tensor member");
+  }
+  if (!ws || ws_bytes < (size_t)n * sizeof(eogs_step_adam_scalars)) return fail(EOGS_ERR_WORKSPACE, "step_adam: workspace too small");
+  if ((uintptr_t)ws & 15u) return fail(EOGS_ERR_INVALID_ARG, "step_adam: workspace not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  { ProfScope ps(PS_ADAM, s); rc = launch_step_adam(n, tensors, beta1, beta2, eps, gate, (eogs_step_adam_scalars*)ws, s); }
+  if (rc) return fail(EOGS_ERR_OVERFLOW, "step_adam: too many elements for one launch");
+  LAUNCH_TRY(s, false, "step_adam");
   return EOGS_OK;
 }
 

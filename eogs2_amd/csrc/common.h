@@ -14,6 +14,7 @@
 #include "eogs_reg.h"
 #include "eogs_pan.h"
 #include "eogs_density.h"
+#include "eogs_step.h"
 #include "eogs_tsdf.h"
 
 #define NCH EOGS_RAST_CHANNELS  // 5 feature channels
@@ -444,6 +445,11 @@ static inline int ceil_log2_u32(uint32_t n) {  // smallest b with (1<<b) >= n
 // backward walks back to front since ABI 8, and the hint lived in a per-process table beside the token).
 static inline uint32_t nr_slots(int64_t R) { return (uint32_t)((uint64_t)R & 0x7FFFFFFFull); }
 static inline uint32_t nr_entries(int64_t R) { return (uint32_t)(((uint64_t)R >> 32) & 0x07FFFFFFull); }
+// THE rule "a forward fits a capacity": its record slots and its list entries are both at most the capacity token's. One
+// statement for the host (eogs_rast_capacity_token's *fits) and the device (step_gate_kernel, optim.hip).
+__host__ __device__ inline bool capacity_fits(uint64_t slots, uint64_t entries, uint64_t cap_slots, uint64_t cap_entries) {
+  return slots <= cap_slots && entries <= cap_entries;
+}
 static inline int nr_alt(int64_t R) { return (int)(((uint64_t)R >> 59) & 1ull); }  // altitude-only forward (EOGS_FLAG_ALT_ONLY)
 static inline int nr_shallow(int64_t R) { return (int)(((uint64_t)R >> 60) & 1ull); }
 static inline int nr_sorted(int64_t R) { return (int)(((uint64_t)R >> 61) & 1ull); }
@@ -613,6 +619,11 @@ struct CompactWS {
 CompactWS compact_layout(char* base, int64_t n_rows);
 int launch_adam(int n, const eogs_adam_tensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s);
 int launch_sum_into(int n, const eogs_sum_tensor* tensors, int nsrc, hipStream_t s);
+// (include/eogs_step.h) `misc`: each forward's count words (geom_layout().misc)
+void launch_step_gate(int n, const uint32_t* const* misc, const uint32_t* cap_slots, const uint32_t* cap_entries, int accumulate,
+                      uint32_t* gate, hipStream_t s);
+int launch_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, double beta2, double eps, const uint32_t* gate,
+                     eogs_step_adam_scalars* ws, hipStream_t s);
 void launch_pack_columns(int64_t rows, int n, const eogs_pack_tensor* tensors, float* packed, int packed_cols, int unpack,
                          hipStream_t s);
 void launch_compact_plan(const CompactWS& w, int64_t n_rows, const uint8_t* keep, hipStream_t s);

@@ -3,6 +3,8 @@
 // boolean-mask gathers of _prune_optimizer / prune_points (gaussian_model.py:466-505).
 // Both are pure HBM streams: Adam reads 16 and writes 12 bytes per element in one launch for all groups; compaction
 // reads each kept row once and writes it once, all tensors in one launch, positions from one ballot/prefix scan.
+// include/eogs_step.h: the same Adam stream with t and lr read from device scalars (a one-workgroup prologue forms the bias
+// corrections), and the single-wave gate over the forwards' count words: the optimizer step inside a recorded graph.
 #include "common.h"
 
 namespace {
@@ -16,29 +18,27 @@ struct AdamTable {
   int n;
 };
 
-__global__ __launch_bounds__(BLK) void adam_kernel(AdamTable tab, float w1, float beta2, float w2, float eps, float inv_bc1,
-                                                   float sqrt_bc2) {
-  // which tensor does this workgroup belong to (n <= 16: linear search on kernel arguments, wave-uniform)
-  int ti = 0;
-  while (ti + 1 < tab.n && blockIdx.x >= tab.first_block[ti + 1]) ti++;
-  const eogs_adam_tensor T = tab.t[ti];
-  const int64_t i0 = ((int64_t)(blockIdx.x - tab.first_block[ti]) * BLK + threadIdx.x) * ADAM_VEC;
-  if (i0 >= T.numel) return;
-  const float step_size = T.lr * inv_bc1;
+// The elements of one thread, shared by adam_kernel and step_adam_kernel: one body, so equal fp32 scalars give equal bits.
+// RETIRE: after the update an element < retire_below is stored as EOGS_STEP_RETIRED_LOGIT (include/eogs_step.h).
+template <bool RETIRE>
+__device__ __forceinline__ void adam_elements(float* __restrict__ param, const float* __restrict__ grad, float* __restrict__ exp_avg,
+                                              float* __restrict__ exp_avg_sq, int64_t numel, int64_t i0, float lr, float w1,
+                                              float beta2, float w2, float eps, float inv_bc1, float sqrt_bc2, float retire_below) {
+  const float step_size = lr * inv_bc1;
   float p[ADAM_VEC], g[ADAM_VEC], m[ADAM_VEC], v[ADAM_VEC];
-  const bool full = i0 + ADAM_VEC <= T.numel && ((((uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.exp_avg |
-                                                   (uintptr_t)T.exp_avg_sq) & 15u) == 0);
+  const bool full = i0 + ADAM_VEC <= numel && ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg |
+                                                 (uintptr_t)exp_avg_sq) & 15u) == 0);
   if (full) {
-    const float4 a = *reinterpret_cast<const float4*>(T.param + i0), b = *reinterpret_cast<const float4*>(T.grad + i0);
-    const float4 c = *reinterpret_cast<const float4*>(T.exp_avg + i0), d = *reinterpret_cast<const float4*>(T.exp_avg_sq + i0);
+    const float4 a = *reinterpret_cast<const float4*>(param + i0), b = *reinterpret_cast<const float4*>(grad + i0);
+    const float4 c = *reinterpret_cast<const float4*>(exp_avg + i0), d = *reinterpret_cast<const float4*>(exp_avg_sq + i0);
     p[0] = a.x; p[1] = a.y; p[2] = a.z; p[3] = a.w; g[0] = b.x; g[1] = b.y; g[2] = b.z; g[3] = b.w;
     m[0] = c.x; m[1] = c.y; m[2] = c.z; m[3] = c.w; v[0] = d.x; v[1] = d.y; v[2] = d.z; v[3] = d.w;
   } else {
 #pragma unroll
     for (int k = 0; k < ADAM_VEC; k++) {
-      const bool in = i0 + k < T.numel;
-      p[k] = in ? T.param[i0 + k] : 0.f; g[k] = in ? T.grad[i0 + k] : 0.f;
-      m[k] = in ? T.exp_avg[i0 + k] : 0.f; v[k] = in ? T.exp_avg_sq[i0 + k] : 0.f;
+      const bool in = i0 + k < numel;
+      p[k] = in ? param[i0 + k] : 0.f; g[k] = in ? grad[i0 + k] : 0.f;
+      m[k] = in ? exp_avg[i0 + k] : 0.f; v[k] = in ? exp_avg_sq[i0 + k] : 0.f;
     }
   }
 #pragma unroll
@@ -49,17 +49,110 @@ __global__ __launch_bounds__(BLK) void adam_kernel(AdamTable tab, float w1, floa
     v[k] = v[k] * beta2 + w2 * (g[k] * g[k]);
     const float denom = sqrtf(v[k]) / sqrt_bc2 + eps;
     p[k] = p[k] - step_size * (m[k] / denom);
+    if (RETIRE && p[k] < retire_below) p[k] = EOGS_STEP_RETIRED_LOGIT;
   }
   if (full) {
-    *reinterpret_cast<float4*>(T.param + i0) = make_float4(p[0], p[1], p[2], p[3]);
-    *reinterpret_cast<float4*>(T.exp_avg + i0) = make_float4(m[0], m[1], m[2], m[3]);
-    *reinterpret_cast<float4*>(T.exp_avg_sq + i0) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(param + i0) = make_float4(p[0], p[1], p[2], p[3]);
+    *reinterpret_cast<float4*>(exp_avg + i0) = make_float4(m[0], m[1], m[2], m[3]);
+    *reinterpret_cast<float4*>(exp_avg_sq + i0) = make_float4(v[0], v[1], v[2], v[3]);
   } else {
 #pragma unroll
     for (int k = 0; k < ADAM_VEC; k++)
-      if (i0 + k < T.numel) {
-        T.param[i0 + k] = p[k]; T.exp_avg[i0 + k] = m[k]; T.exp_avg_sq[i0 + k] = v[k];
+      if (i0 + k < numel) {
+        param[i0 + k] = p[k]; exp_avg[i0 + k] = m[k]; exp_avg_sq[i0 + k] = v[k];
       }
+  }
+}
+
+__global__ __launch_bounds__(BLK) void adam_kernel(AdamTable tab, float w1, float beta2, float w2, float eps, float inv_bc1,
+                                                   float sqrt_bc2) {
+  // which tensor does this workgroup belong to (n <= 16: linear search on kernel arguments, wave-uniform)
+  int ti = 0;
+  while (ti + 1 < tab.n && blockIdx.x >= tab.first_block[ti + 1]) ti++;
+  const eogs_adam_tensor T = tab.t[ti];
+  const int64_t i0 = ((int64_t)(blockIdx.x - tab.first_block[ti]) * BLK + threadIdx.x) * ADAM_VEC;
+  if (i0 >= T.numel) return;
+  adam_elements<false>(T.param, T.grad, T.exp_avg, T.exp_avg_sq, T.numel, i0, T.lr, w1, beta2, w2, eps, inv_bc1, sqrt_bc2, 0.f);
+}
+
+// ---- the step inside a recorded graph (include/eogs_step.h): t and lr are device scalars ----
+struct StepPrologueTable {
+  const float* lr[EOGS_STEP_MAX_TENSORS];
+  float* step[EOGS_STEP_MAX_TENSORS];
+  int n;
+};
+
+// One workgroup of one wave, lane i = descriptor i. The only launch that writes the step counts, and nothing else reads them
+// while it runs: the many workgroups of the element kernel read the table this one leaves in `ws`.
+__global__ __launch_bounds__(64) void step_adam_prologue_kernel(StepPrologueTable tab, double beta1, double beta2,
+                                                                const uint32_t* __restrict__ gate,
+                                                                eogs_step_adam_scalars* __restrict__ ws) {
+  const int i = threadIdx.x;
+  if (i >= tab.n) return;
+  eogs_step_adam_scalars sc;
+  sc.lr = *tab.lr[i];
+  if (!gate || gate[0] != 0u) {
+    float* step = tab.step[i];
+    const float t = *step + 1.0f;
+    *step = t;
+    // bias corrections in double, the expressions of launch_adam
+    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
+    sc.inv_bc1 = (float)(1.0 / bc1);
+    sc.sqrt_bc2 = (float)sqrt(bc2);
+    sc.skip = 0.f;
+  } else {
+    sc.inv_bc1 = 0.f;
+    sc.sqrt_bc2 = 1.f;
+    sc.skip = 1.f;
+  }
+  ws[i] = sc;
+}
+
+struct StepAdamTable {
+  eogs_step_adam_tensor t[EOGS_STEP_MAX_TENSORS];
+  uint32_t first_block[EOGS_STEP_MAX_TENSORS + 1];  // workgroup range of each tensor
+  uint8_t slot[EOGS_STEP_MAX_TENSORS];              // which entry of ws is this tensor's (empty tensors have one too)
+  int n;
+};
+
+__global__ __launch_bounds__(BLK) void step_adam_kernel(StepAdamTable tab, const eogs_step_adam_scalars* __restrict__ ws, float w1,
+                                                        float beta2, float w2, float eps) {
+  int ti = 0;
+  while (ti + 1 < tab.n && blockIdx.x >= tab.first_block[ti + 1]) ti++;
+  const eogs_step_adam_scalars sc = ws[tab.slot[ti]];  // (wave-uniform: written by the prologue launch before this one)
+  if (sc.skip != 0.f) return;                          // gate closed: no load, no store
+  const eogs_step_adam_tensor T = tab.t[ti];
+  const int64_t i0 = ((int64_t)(blockIdx.x - tab.first_block[ti]) * BLK + threadIdx.x) * ADAM_VEC;
+  if (i0 >= T.numel) return;
+  adam_elements<true>(T.param, T.grad, T.exp_avg, T.exp_avg_sq, T.numel, i0, sc.lr, w1, beta2, w2, eps, sc.inv_bc1, sc.sqrt_bc2,
+                      T.retire_below);
+}
+
+struct GateTable {
+  const uint32_t* misc[EOGS_STEP_MAX_FORWARDS];
+  uint32_t cap_slots[EOGS_STEP_MAX_FORWARDS], cap_entries[EOGS_STEP_MAX_FORWARDS];
+  int n;
+};
+
+// One wave, lane i = forward i: reads the count words its forward_prepare wrote, one lane stores the two result words.
+__global__ __launch_bounds__(64) void step_gate_kernel(GateTable tab, int accumulate, uint32_t* __restrict__ gate) {
+  const int i = threadIdx.x;
+  bool bad = false;
+  if (i < tab.n) {
+    const uint32_t* m = tab.misc[i];
+    const uint64_t slots = (uint64_t)m[MISC_TOTAL_LO] | ((uint64_t)m[MISC_TOTAL_HI] << 32);
+    const uint64_t entries = (uint64_t)m[MISC_MACRO_LO] | ((uint64_t)m[MISC_MACRO_HI] << 32);
+    bad = !capacity_fits(slots, entries, tab.cap_slots[i], tab.cap_entries[i]) || (m[MISC_ERR] & 1u) != 0u;
+  }
+  const unsigned long long b = __ballot(bad);
+  if (threadIdx.x == 0) {
+    uint32_t open = b == 0ull ? 1u : 0u, mask = (uint32_t)b;
+    if (accumulate) {
+      open &= gate[0] != 0u ? 1u : 0u;
+      mask |= gate[1];
+    }
+    gate[0] = open;
+    gate[1] = mask;
   }
 }
 
@@ -244,6 +337,44 @@ int launch_adam(int n, const eogs_adam_tensor* tensors, double beta1, double bet
   const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
   hipLaunchKernelGGL(adam_kernel, dim3((uint32_t)blocks), dim3(BLK), 0, s, tab, (float)(1.0 - beta1), (float)beta2,
                      (float)(1.0 - beta2), (float)eps, (float)(1.0 / bc1), (float)sqrt(bc2));
+  return 0;
+}
+
+void launch_step_gate(int n, const uint32_t* const* misc, const uint32_t* cap_slots, const uint32_t* cap_entries, int accumulate,
+                      uint32_t* gate, hipStream_t s) {
+  GateTable tab;
+  tab.n = n;
+  for (int i = 0; i < EOGS_STEP_MAX_FORWARDS; i++) {
+    tab.misc[i] = i < n ? misc[i] : nullptr;
+    tab.cap_slots[i] = i < n ? cap_slots[i] : 0u;
+    tab.cap_entries[i] = i < n ? cap_entries[i] : 0u;
+  }
+  hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(64), 0, s, tab, accumulate, gate);
+}
+
+int launch_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, double beta2, double eps, const uint32_t* gate,
+                     eogs_step_adam_scalars* ws, hipStream_t s) {
+  StepPrologueTable pro;
+  StepAdamTable tab;
+  pro.n = n;
+  tab.n = 0;
+  uint64_t blocks = 0;
+  for (int i = 0; i < EOGS_STEP_MAX_TENSORS; i++) {
+    pro.lr[i] = i < n ? tensors[i].lr : nullptr;
+    pro.step[i] = i < n ? tensors[i].step : nullptr;
+    if (i >= n || tensors[i].numel <= 0) continue;
+    tab.t[tab.n] = tensors[i];
+    tab.slot[tab.n] = (uint8_t)i;
+    tab.first_block[tab.n] = (uint32_t)blocks;
+    blocks += (uint64_t)((tensors[i].numel + ADAM_CHUNK - 1) / ADAM_CHUNK);
+    tab.n++;
+  }
+  tab.first_block[tab.n] = (uint32_t)blocks;
+  if (blocks > 0x7FFFFFFFull) return -1;
+  hipLaunchKernelGGL(step_adam_prologue_kernel, dim3(1), dim3(64), 0, s, pro, beta1, beta2, gate, ws);
+  if (tab.n == 0) return 0;
+  hipLaunchKernelGGL(step_adam_kernel, dim3((uint32_t)blocks), dim3(BLK), 0, s, tab, (const eogs_step_adam_scalars*)ws,
+                     (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps);
   return 0;
 }
 

@@ -15,6 +15,18 @@ with larger workspaces when that happened.
         color, loss, *grads = step()                              # replay (+ check)
         optimizer.step()
 
+The optimizer can be part of the recording: `eogs2_amd.optim.FusedAdam(capturable=True)` keeps its step counts and learning
+rates on the device, and `eogs2_amd.rasterizer.captured_gate()` gives the device's own verdict on the replay's forwards:
+
+    def fwd_bwd_step():
+        ... renders, losses, loss.backward() ...
+        optimizer.step(gate=rasterizer.captured_gate())           # (None in the eager warm-up runs: nothing to gate)
+    step = GraphedStep(fwd_bwd_step)                              # idempotent=True holds, see GraphedStep
+
+A replay that outgrew its list workspaces drew the background and computed gradients of that; with the gate closed the
+optimizer launches of that replay change no parameter, no moment and no counter, so the step can be recorded with larger
+workspaces and replayed as if the failed replay had not happened.
+
 What a recorded forward freezes besides its capacities is the list granularity (per-tile lists or 32-px block lists,
 DESIGN.md §2.3) of the last eager forward of that shape: an eager loop re-decides it per forward, so near the switch the two
 loops take different — equally valid, individually oracle-tested — kernel variants and their gradients differ at the
@@ -148,9 +160,11 @@ class GraphedStep:
     def __init__(self, fn, warmup=2, idempotent=True):
         """fn() -> anything (tensors it returns are the graph's output buffers, rewritten by every replay).
         warmup: eager runs before the capture (at least 1: their counts size the captured workspaces).
-        idempotent: fn may simply be run again when a replay did not fit (true for forward + backward; false as soon as fn
-        updates its own inputs, e.g. an optimizer step inside — then __call__ raises CapacityExceeded instead and the
-        caller decides)."""
+        idempotent: fn may simply be run again when a replay did not fit. True for forward + backward, and for a step whose
+        in-graph updates are ALL gated by `rasterizer.captured_gate()` (FusedAdam(capturable=True).step(gate=...)): an
+        outgrown replay then changes no parameter, moment or counter, so the step is recorded again and replayed. False as
+        soon as fn updates its own inputs ungated — then __call__ raises CapacityExceeded instead and the caller decides.
+        The eager warm-up runs (here and in record_again) are not replays: they really run fn, optimizer included."""
         if warmup < 1:
             raise ValueError("GraphedStep needs at least one eager run before the capture")
         self.fn, self.idempotent = fn, idempotent

@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from ._abi import AdamTensor, SumTensor
+from ._abi import AdamTensor, StepAdamTensor, SumTensor
 from .rasterizer import _Ctx, _ptr
 
 MAX_TENSORS = 16  # EOGS_ADAM_MAX_TENSORS
@@ -58,15 +58,126 @@ def sum_into_(dsts, sources):
 
 
 class FusedAdam(torch.optim.Adam):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(params, lr=lr, betas=betas, eps=eps)
+    """`torch.optim.Adam` with `step()` replaced by the library's multi-tensor launch.
+
+    capturable=False (the default): the step number and the learning rates are host values of each launch
+    (eogs_adam_step, include/eogs_optim.h).
+
+    capturable=True: `state[p]["step"]` is a device fp32 scalar, as torch's own capturable Adam keeps it, every group's
+    learning rate is mirrored in a device fp32 scalar `group["lr_tensor"]`, and `step()` queues kernels alone (eogs_step_adam,
+    include/eogs_step.h: a one-workgroup prologue forms the bias corrections on the device, the element kernel is the one of
+    the host path): a `torch.cuda.graph` capture or `eogs2_amd.graph.GraphedStep` records it, and every replay advances the
+    counters. Run one step eagerly before a capture (a GraphedStep's warm-up does): it creates the state and the scalars.
+    * `group["lr"]` is uploaded at `step()` when it changed since the last upload; inside a capture a changed value raises,
+      because the recorded launch reads the tensor. Between replays write the tensor: `group["lr_tensor"].fill_(x)`.
+    * `step(gate=g)`, `g` a device uint32[2] tensor (`eogs2_amd.rasterizer.captured_gate()`): with `g[0] == 0` the step
+      changes nothing — no parameter, no moment, no counter.
+    * `optimizer.retire_below = {"opacity": -6.0}` (group name -> threshold): after the update the elements of that group's
+      tensor below the threshold are stored as RETIRED_LOGIT, i.e. `retire_rows(optimizer, p >= threshold)` right after
+      `step()`, in the same launch.
+    Not captured: the addresses of parameters, gradients, moments, counters and `lr_tensor` are part of the recording; after
+    anything that replaces them (prune, densification, `load_state_dict`) record again."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False):
+        if capturable:
+            super().__init__(params, lr=lr, betas=betas, eps=eps, capturable=True)
+        else:
+            super().__init__(params, lr=lr, betas=betas, eps=eps)
+        self.retire_below = {}
+        self._ws = {}       # (device, betas, eps, first tensor of the chunk) -> the prologue's table of that launch pair
+        self._ws_row = {}   # parameter -> (table, row) of the last step
+
+    def step_scalars(self, p):
+        """The prologue's row {lr, 1 / bc1, sqrt(bc2), skip} of parameter `p` in the last capturable step: a device fp32[4]
+        view into the launch's table (include/eogs_step.h eogs_step_adam_scalars)."""
+        ws, row = self._ws_row[p]
+        return ws[row]
+
+    def _lr_tensor(self, group, dev, capturing):
+        lr = float(group["lr"])
+        t = group.get("lr_tensor")
+        if t is not None and t.device == dev and group.get("lr_uploaded") == lr:
+            return t
+        if capturing:
+            raise RuntimeError("FusedAdam: group['lr'] changed (or was never uploaded) inside a graph capture: the recorded step "
+                               "reads group['lr_tensor']; run one step eagerly first, then write the tensor between replays")
+        if t is None or t.device != dev:
+            t = group["lr_tensor"] = torch.empty((), dtype=torch.float32, device=dev)
+        t.fill_(lr)
+        group["lr_uploaded"] = lr
+        return t
 
     @torch.no_grad()
-    def step(self, closure=None):
+    def _step_capturable(self, gate):
+        abi = _lib.get()
+        retire = dict(getattr(self, "retire_below", None) or {})
+        unknown = set(retire) - {g.get("name") for g in self.param_groups}
+        if unknown:
+            raise ValueError(f"FusedAdam.retire_below names no parameter group: {sorted(unknown)}")
+        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        batches = {}
+        for group in self.param_groups:
+            if group.get("amsgrad") or group.get("weight_decay") or group.get("maximize"):
+                raise NotImplementedError("FusedAdam mirrors the reference's configuration: plain Adam")
+            if not group.get("capturable"):
+                raise RuntimeError("FusedAdam(capturable=True): every parameter group must be capturable")
+            below = float(retire.get(group.get("name"), float("-inf")))
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse or p.dtype != torch.float32:
+                    raise RuntimeError("FusedAdam: dense fp32 parameters only")
+                state = self.state[p]
+                if len(state) == 0:  # lazy init, like torch.optim.Adam(capturable=True)
+                    if capturing:
+                        raise RuntimeError("FusedAdam: the optimizer state must exist before a graph capture (its zeros would be "
+                                           "recorded with the step): run one step eagerly first")
+                    state["step"] = torch.zeros((), dtype=torch.float32, device=p.device)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if not (p.is_contiguous() and state["exp_avg"].is_contiguous() and state["exp_avg_sq"].is_contiguous()):
+                    raise RuntimeError("FusedAdam: parameters and moments must be contiguous")
+                st = state["step"]
+                if st.device != p.device or st.dtype != torch.float32 or st.numel() != 1:
+                    if capturing:
+                        raise RuntimeError("FusedAdam: state['step'] must be a device fp32 scalar before a graph capture")
+                    st = state["step"] = st.to(device=p.device, dtype=torch.float32).reshape(())  # (a checkpoint's CPU step: once)
+                g = p.grad.contiguous()
+                lr_t = self._lr_tensor(group, p.device, capturing)
+                batches.setdefault((p.device, tuple(group["betas"]), group["eps"]), []).append((p, g, state, lr_t, below))
+        self._ws_row = {}
+        for (dev, (b1, b2), eps), items in batches.items():
+            if gate is not None:
+                if not (isinstance(gate, torch.Tensor) and gate.device == dev and gate.numel() == 2 and gate.is_contiguous()
+                        and gate.dtype in (torch.uint32, torch.int32)):
+                    raise RuntimeError("FusedAdam.step: gate must be a contiguous uint32[2] tensor on the parameters' device")
+            with _Ctx(abi, dev) as cx:
+                for i0 in range(0, len(items), MAX_TENSORS):
+                    chunk = items[i0:i0 + MAX_TENSORS]
+                    key = (dev, (b1, b2), eps, i0)
+                    ws = self._ws.get(key)
+                    if ws is None:  # kept for the optimizer's life: a recorded graph points into it
+                        ws = self._ws[key] = torch.empty((MAX_TENSORS, 4), dtype=torch.float32, device=dev)
+                    arr = (StepAdamTensor * len(chunk))()
+                    for row, (a, (p, g, st, lr_t, below)) in enumerate(zip(arr, chunk)):
+                        a.param, a.grad = p.data_ptr(), g.data_ptr()
+                        a.exp_avg, a.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+                        a.numel, a.lr, a.step, a.retire_below = p.numel(), lr_t.data_ptr(), st["step"].data_ptr(), below
+                        self._ws_row[p] = (ws, row)
+                    abi.check(abi.step_adam(len(chunk), ctypes.cast(arr, ctypes.c_void_p), b1, b2, eps, _ptr(gate), _ptr(ws),
+                                            ws.numel() * 4, cx.stream))
+
+    @torch.no_grad()
+    def step(self, closure=None, *, gate=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.defaults.get("capturable"):
+            self._step_capturable(gate)
+            return loss
+        if gate is not None or getattr(self, "retire_below", None):
+            raise RuntimeError("FusedAdam: gate= and retire_below need capturable=True (they act inside the launch)")
         abi = _lib.get()
         # tensors are batched per (device, betas, eps, step): the reference has one such class
         batches = {}

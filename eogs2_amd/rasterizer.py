@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._abi import (FLAG_ALT_ONLY, FLAG_ANTIALIASING, FLAG_DEBUG, FLAG_DEFER_COUNTS, FLAG_NO_READBACK, FLAG_RAW_PARAMS, MIRROR_BYTES,
-                   RastError)
+                   STEP_MAX_FORWARDS, RastError, StepForward)
 
 NUM_CHANNELS = 5  # DGR/cuda_rasterizer/config.h:15
 
@@ -200,6 +200,7 @@ class record_captured:
             n = (mirror.data_ptr() + mirror.numel() - p0) // MIRROR_BYTES
             self.slots = [ctypes.c_void_p(p0 + i * MIRROR_BYTES) for i in range(max(0, n))]
         self.forwards = []
+        self.gate = {}  # device -> the uint32[2] tensor of captured_gate()
 
     def take_slot(self):
         return self.slots.pop(0) if self.slots else None
@@ -212,6 +213,37 @@ class record_captured:
     def __exit__(self, *a):
         global _recording
         _recording = self.prev
+
+
+def captured_gate():
+    """Inside a graph capture under `record_captured` (eogs2_amd.graph.GraphedStep): queues eogs_step_gate
+    (include/eogs_step.h) on the current stream over the forwards recorded so far in the scope and returns its device
+    uint32[2] tensor — [0] = 1 when every one of them had room for its lists in this replay and raised no error, [1] = which
+    did not. What follows in the graph and must not act on a replay that drew the background — `FusedAdam(capturable=True)
+    .step(gate=...)` — takes it. The tensor is allocated once per scope, from the capture's pool; a later call in the same
+    scope rewrites it over the forwards recorded by then. With `eogs2_amd.graph.Branches`, call it after the join.
+    Outside a capture: None — eager forwards are exact, there is nothing to gate."""
+    if not (torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()):
+        return None
+    rec = _recording
+    if rec is None:
+        raise RuntimeError("captured_gate: this capture runs outside a record_captured scope, so its forwards are unknown "
+                           "(eogs2_amd.graph.GraphedStep opens one)")
+    dev = rec.forwards[0].key[0] if rec.forwards else torch.device("cuda", torch.cuda.current_device())
+    if any(f.key[0] != dev for f in rec.forwards):
+        raise RuntimeError("captured_gate: the recorded forwards live on more than one device")
+    abi = _lib.get()
+    gate = rec.gate.get(dev)
+    if gate is None:
+        gate = rec.gate[dev] = torch.empty((2,), dtype=torch.int32, device=dev).view(torch.uint32)
+    with _Ctx(abi, dev) as cx:
+        for i0 in range(0, max(1, len(rec.forwards)), STEP_MAX_FORWARDS):
+            chunk = rec.forwards[i0:i0 + STEP_MAX_FORWARDS]
+            arr = (StepForward * max(1, len(chunk)))()
+            for a, f in zip(arr, chunk):
+                a.geom, a.geom_bytes, a.P, a.capacity = f.geom.data_ptr(), f.geom.numel(), f.key[1], f.capacity
+            abi.check(abi.step_gate(len(chunk), ctypes.cast(arr, ctypes.c_void_p), int(i0 > 0), _ptr(gate), cx.stream))
+    return gate
 
 
 def last_exact_token(device):
@@ -699,4 +731,5 @@ __all__ = [
     "BackwardPlan",
     "set_backward_plan",
     "chunk_ranges",
+    "captured_gate",
 ]

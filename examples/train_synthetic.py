@@ -34,6 +34,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from eogs2_amd.losses import photometric_loss  # noqa: E402
 from eogs2_amd.density import DensityStats, densify_and_prune  # noqa: E402
 from eogs2_amd.optim import FusedAdam, alive_rows, prune_optimizer, retire_rows  # noqa: E402
+from eogs2_amd.rasterizer import captured_gate  # noqa: E402
 from eogs2_amd.render import render  # noqa: E402
 from eogs2_amd.graph import Branches  # noqa: E402
 from eogs2_amd.resample import render_resample_virtual_camera, resample  # noqa: E402
@@ -65,7 +66,7 @@ class Gaussians:
 
     active_sh_degree = 0
 
-    def __init__(self, xyz, rgb, opacity, scales, rotations):
+    def __init__(self, xyz, rgb, opacity, scales, rotations, capturable=False):
         P = xyz.shape[0]
         self._xyz = torch.nn.Parameter(xyz.clone())
         self._features_dc = torch.nn.Parameter(((rgb - 0.5) / C0).reshape(P, 1, 3).contiguous())
@@ -78,7 +79,8 @@ class Gaussians:
                   for k, n, lr in (("xyz", "xyz", lrs["xyz"]), ("f_dc", "features_dc", lrs["f_dc"]),
                                    ("f_rest", "features_rest", lrs["f_rest"]), ("opacity", "opacity", lrs["opacity"]),
                                    ("scaling", "scaling", lrs["scaling"]), ("rotation", "rotation", lrs["rotation"]))]
-        self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15)  # gaussian_model.py:262 with the fused step
+        # gaussian_model.py:262 with the fused step; capturable: step counts and learning rates on the device (--optimizer-in-graph)
+        self.optimizer = FusedAdam(groups, lr=0.0, eps=1e-15, capturable=True) if capturable else FusedAdam(groups, lr=0.0, eps=1e-15)
         self.max_radii2D = torch.zeros(P, device=xyz.device)
         self.stats = None  # --densify-every: DensityStats (xyz_gradient_accum, denom and the max_radii2D above)
 
@@ -116,7 +118,13 @@ def main(argv=None):
     ap.add_argument("--quiet", action="store_true")
     ap.add_argument("--graph", action="store_true",
                     help="record renders + losses + backward once into a HIP graph and replay it (eogs2_amd.graph.GraphedStep); "
-                         "the optimizers stay outside, the graph is recorded again after every prune")
+                         "the optimizers stay outside unless --optimizer-in-graph, the graph is recorded again after every prune")
+    ap.add_argument("--optimizer-in-graph", action="store_true",
+                    help="both optimizers become FusedAdam(capturable=True): step counts and learning rates live on the device. "
+                         "With --graph they are stepped INSIDE the recorded step, behind eogs2_amd.rasterizer.captured_gate() (a replay "
+                         "that outgrew its list workspaces updates nothing and is recorded again); with --defer-prune K the "
+                         "per-iteration retire of transparent Gaussians moves into the Adam launch (FusedAdam.retire_below) and the "
+                         "compaction stays at its interval. Without --graph the same optimizers run eagerly")
     ap.add_argument("--sun-altitude-only", action="store_true",
                     help="the sun camera renders and resamples its altitude channel alone — what the reference's shipped "
                          "configuration consumes of it (iterstart_L_sun_resample is never reached, gs_config/train.yaml:123); "
@@ -301,15 +309,25 @@ def main(argv=None):
                                         model=lambda gt_n, img_n, num_flow_updates=12: [field])
         flow_opt = types.SimpleNamespace(flowmatching=types.SimpleNamespace(max_value_flow=3.0))
     cc_cam = colour_camera(0.15)
-    camera_optimizer = torch.optim.Adam([*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction,
-                                         *getattr(cc_cam, "map_parameters", ())], lr=2e-3)
+    camera_parameters = [*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction, *getattr(cc_cam, "map_parameters", ())]
+    if a.optimizer_in_graph:  # one prologue + one element launch for the handful of 3-12 element tensors
+        camera_optimizer = FusedAdam(camera_parameters, lr=2e-3, capturable=True)
+    else:
+        camera_optimizer = torch.optim.Adam(camera_parameters, lr=2e-3)
 
     # the trainee: perturbed colours / opacities / positions, scales re-initialised from the 3-NN statistic
     g = torch.Generator().manual_seed(1)
     noise = lambda *s: torch.randn(*s, generator=g).to(dev)
     dist2 = torch.clamp_min(distCUDA2(sc["means3D"]), 1e-7)  # gaussian_model.py:179-182
     model = Gaussians(sc["means3D"] + 2e-4 * noise(P, 3), (sc["colors"][:, :3] + 0.2 * noise(P, 3)).clamp(0.02, 0.98),
-                      torch.full((P,), 0.3, device=dev), torch.sqrt(dist2)[:, None].repeat(1, 3), sc["rotations"])
+                      torch.full((P,), 0.3, device=dev), torch.sqrt(dist2)[:, None].repeat(1, 3), sc["rotations"],
+                      capturable=a.optimizer_in_graph)
+    min_logit = math.log(0.005 / 0.995)  # the transparent prune's threshold on the raw logit
+    retire_in_step = bool(a.optimizer_in_graph and a.defer_prune and not a.no_prune)
+    if retire_in_step:  # train_pan.py:673-678 in its deferred form, every iteration, inside the Adam launch
+        model.optimizer.retire_below = {"opacity": min_logit}
+    steps_inside = bool(a.optimizer_in_graph and a.graph)
+    eager_run = {"on": False}  # --optimizer-in-graph --graph: the one iteration that runs fwd_bwd eagerly (the first)
     # the regularisers over the raw parameters: weights in a device tensor the kernels read (a schedule would write into it
     # between replays of a recorded graph), terms chosen once; init_number_of_gaussians is the constant P of the start
     extent, grad_threshold = 0.0, a.densify_grad_threshold
@@ -339,6 +357,12 @@ def main(argv=None):
         if reg_want:  # train_pan.py:450-465: w_L_opacity * L_opacity (+ w_L_erank * L_erank), summed in the kernel
             loss = loss + gaussian_regularizers(model._opacity, model._scaling, n_init=P, weights=reg_weights, want=reg_want)[0]
         loss.backward()
+        # --optimizer-in-graph --graph: both optimizers inside the recorded step, gated by the device's own verdict on this
+        # replay's forwards. (The eager warm-up runs of the recording skip them: a warm-up is not an iteration.)
+        if steps_inside and (eager_run["on"] or torch.cuda.is_current_stream_capturing()):
+            gate = captured_gate()  # None in the eager run
+            model.optimizer.step(gate=gate)
+            camera_optimizer.step(gate=gate)
         if a.dsm_mae_every:
             kept["altitude"] = out["render"][3].detach()  # (under --graph: the recorded step's output tensor, refilled by a replay)
         return loss.detach(), out.get("radii"), out["viewspace_points"].grad
@@ -350,11 +374,19 @@ def main(argv=None):
     t0 = time.perf_counter()
     t_steady = None  # (the clock of the last `timed` iterations: without the first ones, which allocate and record)
     timed = max(1, a.iters // 2)
+    stamps = []  # host clock (before, after) the iteration's fwd_bwd or replay: what tools/step_probe.py reads
     for it in range(1, a.iters + 1):
         if it == a.iters - timed + 1:
             torch.cuda.synchronize()
             t_steady = time.perf_counter()
-        if a.graph:
+        t_in = time.perf_counter()
+        if steps_inside and it == 1:
+            # the first iteration runs eagerly: it creates the optimizers' state and uploads the learning rates, which a
+            # recording reads from device tensors that must exist before it
+            eager_run["on"] = True
+            loss, radii, vs_grad = fwd_bwd()
+            eager_run["on"] = False
+        elif a.graph:
             if step is None:
                 from eogs2_amd.graph import GraphedStep
 
@@ -365,8 +397,10 @@ def main(argv=None):
             loss, radii, vs_grad = step()
         else:
             loss, radii, vs_grad = fwd_bwd()
-        model.optimizer.step()
-        camera_optimizer.step()
+        stamps.append((t_in, time.perf_counter()))
+        if not steps_inside:
+            model.optimizer.step()
+            camera_optimizer.step()
         with torch.no_grad():
             if model.stats is not None:  # train_pan.py:679-690 in one launch, outside the recorded step: once per iteration
                 model.stats.update(vs_grad, radii)
@@ -384,10 +418,11 @@ def main(argv=None):
             elif radii is not None:  # train_pan.py:681-686 (densification statistics: only with require_radii)
                 model.max_radii2D = torch.maximum(model.max_radii2D, radii.float())
             if it % a.prune_every == 0 and not a.no_prune:  # train_pan.py:673-678
-                keep = model._opacity.squeeze() >= math.log(0.005 / 0.995)
+                keep = model._opacity.squeeze() >= min_logit
                 last_point = it + a.prune_every > a.iters
                 if a.defer_prune and not last_point and (it // a.prune_every) % a.defer_prune:
-                    retire_rows(model.optimizer, keep)
+                    if not retire_in_step:  # (else every step has already retired them)
+                        retire_rows(model.optimizer, keep)
                 elif a.defer_prune:
                     alive = alive_rows(model.optimizer) & keep
                     if not bool(alive.all()):
@@ -413,6 +448,7 @@ def main(argv=None):
     dt = t1 - t0
     main.last_ms_per_iter = (t1 - t_steady) / timed * 1e3  # steady state: the last half of the run
     main.last_dsm_mae = dsm_scores
+    main.last_stamps, main.last_step = stamps, step  # (step: the GraphedStep of --graph, else None)
     main.last_params = None
     if a.densify_every:  # what callers compare between runs, beside the returned tuple
         main.last_params = {g["name"]: g["params"][0].detach().cpu() for g in model.optimizer.param_groups}
