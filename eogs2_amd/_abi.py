@@ -183,6 +183,21 @@ STEP_SIGNATURES = {
     "eogs_step_adam_bytes": (_i, [_i, C.POINTER(_z)]),
     "eogs_step_adam": (_i, [_i, _p, C.c_double, C.c_double, C.c_double, _p, _p, _z, _p]),
 }
+# include/eogs_monitor.h, a table of its own for the same reason
+MONITOR_SIGNATURES = {
+    "eogs_monitor_state_bytes": (_i, [C.POINTER(_z)]),
+    "eogs_monitor_reset": (_i, [_p, _z, _i, _p]),
+    "eogs_monitor_observe_bytes": (_i, [_i, _i, _i, _i, C.POINTER(_z)]),
+    "eogs_monitor_observe": (_i, [_i, _i, _i, _p, _p, _p, C.c_double, _i, _i, _p, _p, _p, _z, _p]),
+    "eogs_monitor_model_bytes": (_i, [_i64, C.POINTER(_z)]),
+    "eogs_monitor_observe_model": (_i, [_i64, _p, _p, _p, _p, _z, _p]),
+    "eogs_monitor_end_iteration": (_i, [_p, _p, _p, _p]),
+    "eogs_monitor_close_interval": (_i, [_i, _i, _i64, _p, _p, _p]),
+}
+MONITOR_RING = 16  # EOGS_MONITOR_RING
+MONITOR_METRICS = ("photometric", "L1", "pan_psnr", "pan_ssim", "msi_psnr", "msi_ssim")  # EOGS_MONITOR_<NAME>: the index
+MONITOR_KINDS = ("pan", "msi")  # EOGS_MONITOR_KIND_*
+MONITOR_OPERATORS = ("min", "max")  # EOGS_MONITOR_MIN, _MAX
 STEP_MAX_FORWARDS = STEP_MAX_TENSORS = 16  # EOGS_STEP_MAX_*
 DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP = 1, 2, 4, 8  # EOGS_DENSITY_*: the flag byte
 DENSITY_COPY, DENSITY_ZERO, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2, 3  # the tensor kinds of eogs_density_build
@@ -199,7 +214,9 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_reg_gauss_forward", "eogs_reg_gauss_backward", "eogs_reg_image_bytes", "eogs_reg_image_forward",
             "eogs_reg_image_backward", "eogs_pan_bytes", "eogs_pan_forward", "eogs_pan_backward", "eogs_density_stats_update",
             "eogs_density_bytes", "eogs_density_decide", "eogs_density_split_rows", "eogs_density_build", "eogs_step_gate",
-            "eogs_step_adam_bytes", "eogs_step_adam")
+            "eogs_step_adam_bytes", "eogs_step_adam", "eogs_monitor_state_bytes", "eogs_monitor_reset", "eogs_monitor_observe_bytes",
+            "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
+            "eogs_monitor_close_interval")
 
 
 class PackTensor(C.Structure):
@@ -245,6 +262,23 @@ class StepAdamScalars(C.Structure):
     _fields_ = [("lr", _f), ("inv_bc1", _f), ("sqrt_bc2", _f), ("skip", _f)]
 
 
+class MonitorRecord(C.Structure):
+    """eogs_monitor_record (include/eogs_monitor.h)"""
+
+    _fields_ = [("interval", _i64), ("iteration", _i64), ("means", C.c_double * 6), ("ema_loss", C.c_double),
+                ("ema_photometric", C.c_double), ("mean_opacity", C.c_double), ("rows", _i64), ("best", C.c_double),
+                ("counter", _i64), ("early_stop", _i64), ("reserved", _i64)]
+
+
+class MonitorState(C.Structure):
+    """eogs_monitor_state (include/eogs_monitor.h)"""
+
+    _fields_ = [("sums", C.c_double * 6), ("n_photo", _i64), ("n_pan", _i64), ("n_msi", _i64), ("ema_loss", C.c_double),
+                ("ema_photometric", C.c_double), ("iteration", _i64), ("best", C.c_double), ("counter", _i64), ("early_stop", _i64),
+                ("intervals", _i64), ("last", _f * 4), ("mean_opacity", _f), ("reserved0", _f), ("rows", _i64), ("reserved1", _i64),
+                ("latest", MonitorRecord), ("ring", MonitorRecord * MONITOR_RING)]
+
+
 class RastError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -260,7 +294,7 @@ class RastABI:
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
-                                  *STEP_SIGNATURES.items()):
+                                  *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -278,7 +312,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -1470,4 +1470,124 @@ int eogs_tsdf_dsm_mae(int Hp, int Wp, void* pred, int Hg, int Wg, const void* gt
   return EOGS_OK;
 }
 
+// ---- include/eogs_monitor.h ----
+int eogs_monitor_state_bytes(size_t* bytes) {
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "monitor_state_bytes: NULL argument");
+  *bytes = sizeof(eogs_monitor_state);
+  return EOGS_OK;
+}
+
+static int monitor_state_check(const char* who, const void* state) {
+  if (!state) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL state", who);
+  if ((uintptr_t)state & 15u) return fail(EOGS_ERR_INVALID_ARG, "%s: state not 16-byte aligned", who);
+  return EOGS_OK;
+}
+
+int eogs_monitor_reset(void* state, size_t state_bytes, int op, void* stream) {
+  g_err[0] = 0;
+  const int rc = monitor_state_check("monitor_reset", state);
+  if (rc != EOGS_OK) return rc;
+  if (state_bytes < sizeof(eogs_monitor_state)) return fail(EOGS_ERR_WORKSPACE, "monitor_reset: state buffer too small");
+  if (op != EOGS_MONITOR_MIN && op != EOGS_MONITOR_MAX) return fail(EOGS_ERR_INVALID_ARG, "monitor_reset: operator is min or max");
+  hipStream_t s = (hipStream_t)stream;
+  launch_monitor_reset(state, op, s);
+  LAUNCH_TRY(s, false, "monitor_reset");
+  return EOGS_OK;
+}
+
+static int monitor_image_check(const char* who, int planes, int H, int W) {
+  if (planes <= 0 || H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", who);
+  if (planes > 65535 || (H + 31) / 32 > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: too many planes / rows for one launch", who);
+  return EOGS_OK;
+}
+
+int eogs_monitor_observe_bytes(int planes, int H, int W, int standalone, size_t* bytes) {
+  const int rc = monitor_image_check("monitor_observe_bytes", planes, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe_bytes: NULL argument");
+  size_t n = 256 + monitor_sq_bytes(planes, H, W);
+  if (standalone) n += 256 + loss_layout(nullptr, planes, H, W, EOGS_LOSS_L1 | EOGS_LOSS_SSIM).bytes;
+  *bytes = n;
+  return EOGS_OK;
+}
+
+int eogs_monitor_observe(int planes, int H, int W, const float* image, const float* gt, const float* loss_out,
+                         double lambda_dssim, int kind, int photometric_on, const uint32_t* gate, void* state, void* ws,
+                         size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  int rc = monitor_image_check("monitor_observe", planes, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (kind != EOGS_MONITOR_KIND_PAN && kind != EOGS_MONITOR_KIND_MSI)
+    return fail(EOGS_ERR_INVALID_ARG, "monitor_observe: kind is pan or msi");
+  if (!image || !gt || !ws) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe: NULL argument");
+  if (!(lambda_dssim == lambda_dssim)) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe: lambda_dssim is NaN");
+  rc = monitor_state_check("monitor_observe", state);
+  if (rc != EOGS_OK) return rc;
+  char* base = ws_base(ws);
+  const size_t sq = monitor_sq_bytes(planes, H, W);
+  size_t need = (size_t)(base - (char*)ws) + sq;
+  LossWS w;
+  const unsigned mode = EOGS_LOSS_L1 | EOGS_LOSS_SSIM;
+  if (!loss_out) {
+    w = loss_layout(base + sq + 256, planes, H, W, mode);
+    need += 256 + w.bytes - 256;
+  }
+  if (need > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "monitor_observe: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const float lam = (float)lambda_dssim, oml = (float)(1.0 - lambda_dssim);  // torch rounds the Python scalars once each
+  if (!loss_out) {
+    float* out = reinterpret_cast<float*>(base + sq);
+    { ProfScope ps(PS_LOSS_FWD, s); launch_loss_fwd(w, planes, H, W, image, gt, mode, oml, -lam, lam, out, nullptr, s); }
+    loss_out = out;
+  }
+  launch_monitor_observe(planes, H, W, image, gt, loss_out, oml, lam, kind, photometric_on != 0, gate, state,
+                         reinterpret_cast<double*>(base), s);
+  LAUNCH_TRY(s, false, "monitor_observe");
+  return EOGS_OK;
+}
+
+int eogs_monitor_model_bytes(int64_t P, size_t* bytes) {
+  if (P <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "monitor_model_bytes: bad argument");
+  *bytes = monitor_model_ws_bytes(P);
+  return EOGS_OK;
+}
+
+int eogs_monitor_observe_model(int64_t P, const float* opacity, const uint32_t* gate, void* state, void* ws, size_t ws_bytes,
+                               void* stream) {
+  g_err[0] = 0;
+  if (P <= 0) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe_model: bad size");
+  if (!opacity || !ws) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe_model: NULL argument");
+  const int rc = monitor_state_check("monitor_observe_model", state);
+  if (rc != EOGS_OK) return rc;
+  if (ws_bytes < monitor_model_ws_bytes(P)) return fail(EOGS_ERR_WORKSPACE, "monitor_observe_model: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  launch_monitor_model(P, opacity, gate, state, ws, s);
+  LAUNCH_TRY(s, false, "monitor_observe_model");
+  return EOGS_OK;
+}
+
+int eogs_monitor_end_iteration(const float* loss, const uint32_t* gate, void* state, void* stream) {
+  g_err[0] = 0;
+  if (!loss) return fail(EOGS_ERR_INVALID_ARG, "monitor_end_iteration: NULL loss");
+  const int rc = monitor_state_check("monitor_end_iteration", state);
+  if (rc != EOGS_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  launch_monitor_end_iteration(loss, gate, state, s);
+  LAUNCH_TRY(s, false, "monitor_end_iteration");
+  return EOGS_OK;
+}
+
+int eogs_monitor_close_interval(int metric, int op, int64_t patience, const uint32_t* gate, void* state, void* stream) {
+  g_err[0] = 0;
+  if (metric < 0 || metric >= EOGS_MONITOR_METRICS) return fail(EOGS_ERR_INVALID_ARG, "monitor_close_interval: unknown metric");
+  if (op != EOGS_MONITOR_MIN && op != EOGS_MONITOR_MAX)
+    return fail(EOGS_ERR_INVALID_ARG, "monitor_close_interval: operator is min or max");
+  const int rc = monitor_state_check("monitor_close_interval", state);
+  if (rc != EOGS_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  launch_monitor_close(metric, op, patience, gate, state, s);
+  LAUNCH_TRY(s, false, "monitor_close_interval");
+  return EOGS_OK;
+}
+
 }  // extern "C"

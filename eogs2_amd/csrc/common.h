@@ -15,6 +15,7 @@
 #include "eogs_pan.h"
 #include "eogs_density.h"
 #include "eogs_step.h"
+#include "eogs_monitor.h"
 #include "eogs_tsdf.h"
 
 #define NCH EOGS_RAST_CHANNELS  // 5 feature channels
@@ -690,6 +691,17 @@ void launch_reg_image_fwd(int H, int W, const float* alt, const float* acc, cons
                           hipStream_t s);
 void launch_reg_image_bwd(int H, int W, const float* alt, const float* acc, const float* weights, const float* g_total,
                           const float* g_terms, float* g_alt, float* g_acc, hipStream_t s);
+
+// ---- training monitor (monitor.hip, include/eogs_monitor.h) ----
+size_t monitor_sq_bytes(int planes, int H, int W);  // the per-plane partials of observe, a multiple of 256
+size_t monitor_model_ws_bytes(int64_t P);
+void launch_monitor_reset(void* state, int op, hipStream_t s);
+void launch_monitor_observe(int planes, int H, int W, const float* img, const float* gt, const float* loss_out,
+                            float one_minus_lambda, float lambda, int kind, int photometric_on, const uint32_t* gate, void* state,
+                            double* partial, hipStream_t s);
+void launch_monitor_model(int64_t P, const float* opacity, const uint32_t* gate, void* state, void* ws, hipStream_t s);
+void launch_monitor_end_iteration(const float* loss, const uint32_t* gate, void* state, hipStream_t s);
+void launch_monitor_close(int metric, int op, int64_t patience, const uint32_t* gate, void* state, hipStream_t s);
 
 // ---- panchromatic camera pipeline (pan.hip, include/eogs_pan.h) ----
 size_t pan_ws_bytes();

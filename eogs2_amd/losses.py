@@ -98,10 +98,14 @@ def ssim(img1, img2, window_size=11, size_average=True):
     return psum[:, 1].view(N, C).sum(1) / float(C * H * W)
 
 
-def photometric_loss(image, gt_image, lambda_dssim):
-    """(loss, Ll1) with loss = (1 - lambda) * L1 + lambda * (1 - SSIM), one fused forward + one fused backward."""
+def photometric_loss(image, gt_image, lambda_dssim, return_out=False):
+    """(loss, Ll1) with loss = (1 - lambda) * L1 + lambda * (1 - SSIM), one fused forward + one fused backward.
+    `return_out=True` appends the kernel's detached out[3] = {loss, L1 mean, SSIM mean}: what
+    `eogs2_amd.monitor.TrainingMonitor.observe(loss_out=...)` reads on the device instead of evaluating SSIM again."""
     lam = float(lambda_dssim)
     out, _ = _Photometric.apply(image, gt_image, LOSS_L1 | LOSS_SSIM, 1.0 - lam, -lam, lam, False)
+    if return_out:
+        return out[0], out[1].detach(), out.detach()
     return out[0], out[1].detach()
 
 

@@ -19,6 +19,8 @@ the photometric loss (`eogs2_amd.flow`), against a target displaced by a sub-pix
 loss runs on the one PAN plane; `--pan-first` is the reference's `weird_pan_setup` (map first, then a 1->1 colour correction).
 `--densify-every K` is the reference's `only_prune: False` (train_pan.py:679-711): the densification statistics every iteration
 (`eogs2_amd.density.DensityStats.update`, one launch, no wait) and `densify_and_prune` plus the transparent prune every K iterations.
+`--monitor` keeps the reference's training metrics and early stopper on the device (`eogs2_amd.monitor.TrainingMonitor`;
+train_pan.py:423-429,471-495,512-597): every iteration feeds it without a wait, every 10 iterations one record is fetched and printed.
 """
 import argparse
 import math
@@ -42,11 +44,13 @@ from eogs2_amd.shade import randomcam_l, render_pipeline, suncamera_l, transluce
 from eogs2_amd.dsm_eval import dsm_mae  # noqa: E402
 from eogs2_amd.flow import apply_flow, perform_flow_matching, performOpticalmatching  # noqa: E402
 from eogs2_amd.regularizers import gaussian_regularizers  # noqa: E402
+from eogs2_amd.monitor import MONITOR_METRICS, TrainingMonitor  # noqa: E402
 from eogs2_amd.pan import FIXED_PARAMS, KINDS as PAN_KINDS, PanMap, render_pipeline as pan_render_pipeline  # noqa: E402
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
 C0 = 0.28209479177387814
+MONITOR_INTERVAL = 10  # --monitor: iterations per record (the reference's tb_log_interval)
 FLOW_SHIFT = (0.6, -0.35)  # --flow-matching: the target's displacement in pixels (horizontal, vertical)
 
 
@@ -189,7 +193,20 @@ def main(argv=None):
     ap.add_argument("--pan-first", action="store_true",
                     help="with --pan-map: the reference's weird_pan_setup (PAN_affine_cameras.py:148-176): the map first, then a "
                          "Conv2d(1,1,1) colour correction and a scalar in-shadow tint")
+    ap.add_argument("--monitor", action="store_true",
+                    help="the reference's training metrics on the device (eogs2_amd.monitor.TrainingMonitor): per iteration the "
+                         "photometric loss's own L1 and SSIM, the PSNR, the mean opacity and the two moving averages go into a device "
+                         "buffer without a wait (inside the recorded step with --graph, behind the same gate as the optimizers); every "
+                         f"{MONITOR_INTERVAL} iterations (tb_log_interval) the interval is closed and ONE record is fetched and printed. Off by default")
+    ap.add_argument("--early-stop-patience", type=int, default=None, metavar="N",
+                    help="with --monitor: the reference's early stopper (utils/callback_utils.py) with patience N intervals; the run "
+                         "ends at the interval whose record carries the flag. Default: no early stopping (use_early_stopping: False)")
+    ap.add_argument("--early-stop-metric", choices=MONITOR_METRICS, default="photometric", metavar="NAME",
+                    help=f"with --monitor: the stopper's metric_name, one of {', '.join(MONITOR_METRICS)} (photometric: "
+                         "optimization/early_stopping/l_photom.yaml); PSNR and SSIM are watched with operator max, the losses with min")
     a = ap.parse_args(argv)
+    if a.early_stop_patience is not None and not a.monitor:
+        ap.error("--early-stop-patience needs --monitor")
     if a.pan_first and not a.pan_map:
         ap.error("--pan-first needs --pan-map")
     if a.pan_map and a.flow_matching:
@@ -337,6 +354,17 @@ def main(argv=None):
         extent = 0.5 * float((sc["means3D"].max(dim=0).values - sc["means3D"].min(dim=0).values).max())  # cameras_extent's role
     reg_want = tuple(n for n, w in (("opacity", a.opacity_loss), ("erank", a.erank_loss)) if w)
     reg_weights = torch.tensor([a.opacity_loss, 0.0, a.erank_loss], device=dev) if reg_want else None
+    mon = None
+    if a.monitor:
+        mon = TrainingMonitor(dev, metric_name=a.early_stop_metric, patience=a.early_stop_patience,
+                              operator="max" if a.early_stop_metric.endswith(("psnr", "ssim")) else "min")
+        mon.reset()  # the state exists (and is reset) before any recording: a recorded reset would run on every replay
+
+    def feed_monitor(final, photo_out, loss, gate):
+        """train_pan.py:423-429,471-495 without their .item() waits and without the second SSIM: four launch groups, no wait."""
+        mon.observe(final, gt, "pan" if a.pan_map else "msi", loss_out=photo_out, lambda_dssim=0.2, gate=gate)
+        mon.observe_model(model._opacity, gate=gate)  # (train_pan.py:331: the opacities the iteration rendered with)
+        mon.end_iteration(loss, gate=gate)
 
     def fwd_bwd():
         """Everything between two optimizer steps; reads the model's and the camera's parameter tensors in place."""
@@ -346,7 +374,10 @@ def main(argv=None):
         final = shaded["final"]
         if warper is not None:  # train_pan.py:347-357
             _, _, final = perform_flow_matching(flow_opt, warper, final, gt, on_device=True)
-        loss, _ = photometric_loss(final, gt, 0.2)
+        if mon is None:
+            loss, _ = photometric_loss(final, gt, 0.2)
+        else:  # the same launches; out[3] = {loss, L1, SSIM} stays on the device for the monitor
+            loss, _, photo_out = photometric_loss(final, gt, 0.2, return_out=True)
         loss = loss + 1e-3 * translucentshadows_l(shaded["shadowmap"])
         if sun_rgb is not None:
             L_sun_alt, L_sun_rgb = suncamera_l(img, sun_rgb, sun_altitude_diff, sun_uv)
@@ -357,6 +388,12 @@ def main(argv=None):
         if reg_want:  # train_pan.py:450-465: w_L_opacity * L_opacity (+ w_L_erank * L_erank), summed in the kernel
             loss = loss + gaussian_regularizers(model._opacity, model._scaling, n_init=P, weights=reg_weights, want=reg_want)[0]
         loss.backward()
+        # --monitor: like the optimizers, inside the recorded step only with --optimizer-in-graph --graph (gated as they are:
+        # an outgrown replay is not counted), else after it, from the tensors kept here (under --graph: refilled by a replay)
+        if mon is not None:
+            kept["monitor"] = (final.detach(), photo_out, loss.detach())
+            if steps_inside and (eager_run["on"] or torch.cuda.is_current_stream_capturing()):
+                feed_monitor(*kept["monitor"], captured_gate())
         # --optimizer-in-graph --graph: both optimizers inside the recorded step, gated by the device's own verdict on this
         # replay's forwards. (The eager warm-up runs of the recording skip them: a warm-up is not an iteration.)
         if steps_inside and (eager_run["on"] or torch.cuda.is_current_stream_capturing()):
@@ -369,11 +406,14 @@ def main(argv=None):
 
     kept, dsm_scores = {}, []  # --dsm-mae-every: the view's altitude of the last step; (iteration, dx, dy, mae)
     first = last = None
+    stopped_at = 0  # --monitor --early-stop-patience: the iteration whose record carried the flag
+    main.last_monitor_record = None
     step, stale = None, False  # the recorded graph of fwd_bwd; stale: recorded for parameter tensors that a prune replaced
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     t_steady = None  # (the clock of the last `timed` iterations: without the first ones, which allocate and record)
     timed = max(1, a.iters // 2)
+    a_iters_asked = a.iters
     stamps = []  # host clock (before, after) the iteration's fwd_bwd or replay: what tools/step_probe.py reads
     for it in range(1, a.iters + 1):
         if it == a.iters - timed + 1:
@@ -399,6 +439,8 @@ def main(argv=None):
             loss, radii, vs_grad = fwd_bwd()
         stamps.append((t_in, time.perf_counter()))
         if not steps_inside:
+            if mon is not None:
+                feed_monitor(*kept["monitor"], None)
             model.optimizer.step()
             camera_optimizer.step()
         with torch.no_grad():
@@ -436,16 +478,34 @@ def main(argv=None):
             dsm_scores.append((it, sdx, sdy, mae))
             if not a.quiet:
                 print(f"iter {it:4d}  DSM registration dx {sdx} dy {sdy}  MAE {mae:.5f} (altitude units = {ALT_SCALE:g} x normalised z)")
-        if it == 1 or it % 25 == 0 or it == a.iters:
+        if mon is not None and it % MONITOR_INTERVAL == 0:  # train_pan.py:512-597: means, early stopper, reset; ONE wait
+            mon.close_interval()
+            rec = mon.fetch()
+            main.last_monitor_record = rec
+            if not a.quiet:
+                print(f"iter {it:4d}  monitor " + "  ".join(f"{k} {v:.5g}" if isinstance(v, float) else f"{k} {v}" for k, v in rec.items()))
+            if rec["early_stop"]:
+                if not a.quiet:
+                    print(f"iter {it:4d}  early stop: {a.early_stop_metric} has not improved on {rec['best']:.5g} for {rec['counter']} intervals")
+                stopped_at = it
+        if it == 1 or it % 25 == 0 or it == a.iters or stopped_at:
             v = float(loss)
             first = v if first is None else first
             last = v
             if not a.quiet:
                 print(f"iter {it:4d}  loss {v:.5f}  gaussians {model._xyz.shape[0]}  device memory in use "
                       f"{(lambda f, t: (t - f) / 2**20)(*torch.cuda.mem_get_info()):.0f} MiB")
+        if stopped_at:  # train_pan.py:574-578: opt.iterations = iteration
+            break
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     dt = t1 - t0
+    if stopped_at:  # an early stop: the clocks of the iterations that ran
+        a.iters = stopped_at
+        if t_steady is None:
+            t_steady, timed = t0, stopped_at
+        else:
+            timed = stopped_at - (a_iters_asked - timed)
     main.last_ms_per_iter = (t1 - t_steady) / timed * 1e3  # steady state: the last half of the run
     main.last_dsm_mae = dsm_scores
     main.last_stamps, main.last_step = stamps, step  # (step: the GraphedStep of --graph, else None)
