@@ -194,6 +194,17 @@ MONITOR_SIGNATURES = {
     "eogs_monitor_end_iteration": (_i, [_p, _p, _p, _p]),
     "eogs_monitor_close_interval": (_i, [_i, _i, _i64, _p, _p, _p]),
 }
+# include/eogs_dsm.h, a table of its own for the same reason
+DSM_SIGNATURES = {
+    "eogs_dsm_bounds_bytes": (_i, [C.POINTER(_z)]),
+    "eogs_dsm_bounds": (_i, [_p, _p, _p, _z, _p]),
+    "eogs_dsm_raster_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+    "eogs_dsm_raster": (_i, [_p, C.c_double, C.c_double, C.c_double, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+}
+DSM_Z_QUANTUM = 2.0 ** -20  # EOGS_DSM_Z_QUANTUM
+DSM_Z_MAX = 32768.0  # EOGS_DSM_Z_MAX
+DSM_MAX_RADIUS = 4  # EOGS_DSM_MAX_RADIUS
+DSM_SRC_CLOUD, DSM_SRC_VIEW, DSM_SRC_GRID = 0, 1, 2  # EOGS_DSM_SRC_*
 MONITOR_RING = 16  # EOGS_MONITOR_RING
 MONITOR_METRICS = ("photometric", "L1", "pan_psnr", "pan_ssim", "msi_psnr", "msi_ssim")  # EOGS_MONITOR_<NAME>: the index
 MONITOR_KINDS = ("pan", "msi")  # EOGS_MONITOR_KIND_*
@@ -216,7 +227,7 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_density_bytes", "eogs_density_decide", "eogs_density_split_rows", "eogs_density_build", "eogs_step_gate",
             "eogs_step_adam_bytes", "eogs_step_adam", "eogs_monitor_state_bytes", "eogs_monitor_reset", "eogs_monitor_observe_bytes",
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
-            "eogs_monitor_close_interval")
+            "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster")
 
 
 class PackTensor(C.Structure):
@@ -279,6 +290,20 @@ class MonitorState(C.Structure):
                 ("latest", MonitorRecord), ("ring", MonitorRecord * MONITOR_RING)]
 
 
+class DsmSource(C.Structure):
+    """eogs_dsm_source (include/eogs_dsm.h)"""
+
+    _fields_ = [("kind", _i), ("H", _i), ("W", _i), ("N", _i64), ("cloud", _p), ("altitude", _p), ("u_axis", _p), ("v_axis", _p),
+                ("affine", _p), ("scale", C.c_double), ("shift", C.c_double * 3)]
+
+
+class DsmBounds(C.Structure):
+    """eogs_dsm_bounds_result (include/eogs_dsm.h)"""
+
+    _fields_ = [("xmin", C.c_double), ("xmax", C.c_double), ("ymin", C.c_double), ("ymax", C.c_double), ("nonfinite", _i64),
+                ("count", _i64)]
+
+
 class RastError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -294,7 +319,7 @@ class RastABI:
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
-                                  *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items()):
+                                  *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -312,7 +337,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -1590,4 +1590,80 @@ int eogs_monitor_close_interval(int metric, int op, int64_t patience, const uint
   return EOGS_OK;
 }
 
+// ---- include/eogs_dsm.h ----
+static int dsm_source_check(const char* who, const eogs_dsm_source* src) {
+  if (!src) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL source", who);
+  if (src->kind == EOGS_DSM_SRC_CLOUD) {
+    if (src->N < 0) return fail(EOGS_ERR_INVALID_ARG, "%s: negative point count", who);
+    if (src->N > 0 && !src->cloud) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL cloud", who);
+    if ((uintptr_t)src->cloud & 7u) return fail(EOGS_ERR_INVALID_ARG, "%s: cloud not 8-byte aligned", who);
+    return EOGS_OK;
+  }
+  if (src->kind != EOGS_DSM_SRC_VIEW && src->kind != EOGS_DSM_SRC_GRID) return fail(EOGS_ERR_INVALID_ARG, "%s: unknown source kind", who);
+  if (src->H <= 0 || src->W <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad image size", who);
+  if (!src->altitude || !src->u_axis || !src->v_axis) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL image or axis", who);
+  if (src->kind == EOGS_DSM_SRC_VIEW) {
+    if (!src->affine) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL affine", who);
+    if (!(src->scale == src->scale)) return fail(EOGS_ERR_INVALID_ARG, "%s: scale is NaN", who);
+  }
+  return EOGS_OK;
+}
+
+int eogs_dsm_bounds_bytes(size_t* bytes) {
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_bounds_bytes: NULL argument");
+  *bytes = 256 + dsm_bounds_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_dsm_bounds(const eogs_dsm_source* src, eogs_dsm_bounds_result* result, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  const int rc = dsm_source_check("dsm_bounds", src);
+  if (rc != EOGS_OK) return rc;
+  if (!result || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_bounds: NULL argument");
+  if ((uintptr_t)result & 7u) return fail(EOGS_ERR_INVALID_ARG, "dsm_bounds: result not 8-byte aligned");
+  char* base = ws_base(ws);
+  if ((size_t)(base - (char*)ws) + dsm_bounds_ws_bytes() > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_bounds: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  launch_dsm_bounds(*src, result, base, s);
+  LAUNCH_TRY(s, false, "dsm_bounds");
+  return EOGS_OK;
+}
+
+static int dsm_grid_check(const char* who, int xsize, int ysize, int radius) {
+  if (radius < 0 || radius > EOGS_DSM_MAX_RADIUS) return fail(EOGS_ERR_INVALID_ARG, "%s: radius out of range", who);
+  if (xsize <= 0 || ysize <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: xsize and ysize must be positive", who);
+  if (((int64_t)xsize + 2 * radius) * ((int64_t)ysize + 2 * radius) >= ((int64_t)1 << 31))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: raster too large", who);
+  return EOGS_OK;
+}
+
+int eogs_dsm_raster_bytes(int xsize, int ysize, int radius, size_t* bytes) {
+  const int rc = dsm_grid_check("dsm_raster_bytes", xsize, ysize, radius);
+  if (rc != EOGS_OK) return rc;
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster_bytes: NULL argument");
+  *bytes = 256 + dsm_raster_layout(nullptr, xsize, ysize, radius).bytes;
+  return EOGS_OK;
+}
+
+int eogs_dsm_raster(const eogs_dsm_source* src, double xoff, double yoff, double res, int xsize, int ysize, int radius,
+                    float* out, int32_t* count, int64_t* skipped, void* ws, size_t ws_bytes, void* stream) {
+  g_err[0] = 0;
+  int rc = dsm_source_check("dsm_raster", src);
+  if (rc != EOGS_OK) return rc;
+  rc = dsm_grid_check("dsm_raster", xsize, ysize, radius);
+  if (rc != EOGS_OK) return rc;
+  const double big = 1.7976931348623157e308;
+  if (!(res > 0. && res <= big)) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: resolution must be positive and finite");
+  if (!(xoff >= -big && xoff <= big && yoff >= -big && yoff <= big)) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: xoff, yoff must be finite");
+  if (!out || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: NULL argument");
+  if ((uintptr_t)skipped & 7u) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: skipped not 8-byte aligned");
+  char* base = ws_base(ws);
+  const DsmRasterWS w = dsm_raster_layout(base, xsize, ysize, radius);
+  if ((size_t)(base - (char*)ws) + w.bytes > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_raster: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  launch_dsm_raster(*src, xoff, yoff, res, xsize, ysize, radius, w, out, count, skipped, s);
+  LAUNCH_TRY(s, false, "dsm_raster");
+  return EOGS_OK;
+}
+
 }  // extern "C"

@@ -17,6 +17,7 @@
 #include "eogs_step.h"
 #include "eogs_monitor.h"
 #include "eogs_tsdf.h"
+#include "eogs_dsm.h"
 
 #define NCH EOGS_RAST_CHANNELS  // 5 feature channels
 #define TILE EOGS_RAST_TILE     // 16x16 pixel tiles: the reference's binning granularity (tile rect, radii)
@@ -745,6 +746,20 @@ void launch_dsm_apply_shift(int H, int W, const void* in, int f64, int dx, int d
 size_t dsm_mae_ws_bytes();
 void launch_dsm_mae(int Hp, int Wp, void* pred, int Hg, int Wg, const void* gt, int f64, int finite_only, void* diff, double* out,
                     void* ws, hipStream_t s);
+
+// ---- DSM raster (dsm_raster.hip, include/eogs_dsm.h) ----
+struct DsmRasterWS {
+  long long* sums;              // [ph][pw] fixed-point sums of the home cells, the grid padded by `radius`
+  uint32_t* counts;             // [ph][pw] points per home cell; the top bit marks a poisoned cell
+  unsigned long long* skipped;  // points left out for a non-finite x or y
+  int pw, ph;
+  size_t bytes;                 // a multiple of 256: the clear pass zeroes all of it
+};
+DsmRasterWS dsm_raster_layout(char* base, int xsize, int ysize, int radius);
+size_t dsm_bounds_ws_bytes();
+void launch_dsm_bounds(const eogs_dsm_source& src, eogs_dsm_bounds_result* result, void* ws, hipStream_t s);
+void launch_dsm_raster(const eogs_dsm_source& src, double xoff, double yoff, double res, int xsize, int ysize, int radius,
+                       const DsmRasterWS& w, float* out, int32_t* count, int64_t* skipped, hipStream_t s);
 
 // ---- 3-nearest-neighbour statistic (knn.hip, include/eogs_knn.h) ----
 struct KnnWS {

@@ -1,0 +1,259 @@
+"""The DSM raster on the GPU over include/eogs_dsm.h: the step between the render (or the TSDF fusion) and the score of the
+finished DSM (`eogs2_amd.dsm_eval`). The reference takes it with the third-party `plyflatten` in utils/dsm_utils.py:7-51
+(train_pan.py:738-797, render_pan.py:402) and tsdf.py:530-600. Names follow it so that a user can swap imports:
+
+  cloud_bounds(cloud)                                       xmin, xmax, ymin, ymax of a float64 [N, 3] cloud (one read-back)
+  raster_geometry(xmin, xmax, ymin, ymax, resolution)       dsm_utils.py:20-25 -> (xoff, yoff, xsize, ysize), host float64
+  plyflatten(cloud, xoff, yoff, resolution, xsize, ysize,   plyflatten's name and signature; float32 [ysize, xsize, 1]
+             radius=1, sigma=inf, return_count=False)
+  dsm_from_view(altitude_render, affine, scene_params,      compute_dsm_from_view without its scene_name lookup
+                resolution, radius=1, geometry=None)        -> (profile, dsm); no cloud is materialised
+  TSDFVolume.extract_dsm(scene_params, resolution)          eogs2_amd.tsdf: tsdf.py:530-600 without the file write
+
+GPU tensors only; CPU tensors raise (no CPU fallback). The raster's arithmetic is stated in include/eogs_dsm.h and DESIGN.md
+§8: the home cell is floor((x - xoff) / res), floor((yoff - y) / res) in IEEE double, a point contributes float32(z) to the
+(2 radius + 1)^2 cells around it that lie inside the raster, a cell holds the mean of its contributions or NaN. Where
+plyflatten keeps a running float32 mean in point order, this returns the mean itself, within Z_QUANTUM / 2 + ulp32 of the
+float64 mean, with the same bits on every run and for every order of the points. A non-finite z, or |z| > Z_MAX, makes the
+cells of its footprint NaN. A non-finite x or y raises in `cloud_bounds` / `dsm_from_view` / `extract_dsm` (the reference's
+`int(nan)` raises too) and is skipped and counted in `plyflatten` (`skipped_out`).
+
+`plyflatten` and `dsm_from_view` with a given geometry wait for nothing and can be captured in a `torch.cuda.graph` after
+one warm-up call on the capture stream (workspaces are allocated per (device, stream, raster shape) on first use and kept;
+`clear_workspaces()` drops them). With `geometry=None` there is one wait, for the bounds, as in the reference.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._abi import DSM_MAX_RADIUS, DSM_SRC_CLOUD, DSM_SRC_GRID, DSM_SRC_VIEW, DSM_Z_MAX, DSM_Z_QUANTUM, DsmBounds, DsmSource
+from .rasterizer import _Ctx, _ptr
+
+Z_QUANTUM = DSM_Z_QUANTUM  # include/eogs_dsm.h EOGS_DSM_Z_QUANTUM
+Z_MAX = DSM_Z_MAX  # EOGS_DSM_Z_MAX
+MAX_RADIUS = DSM_MAX_RADIUS  # EOGS_DSM_MAX_RADIUS
+_ws_cache = {}
+_axes_cache = {}
+
+
+def _on_device(t, what):
+    if not torch.is_tensor(t):
+        raise TypeError(f"dsm_raster {what}: expected a tensor, not {type(t).__name__}")
+    if t.device.type != "cuda":
+        raise RuntimeError(f"dsm_raster {what}: tensors live on '{t.device.type}'; the DSM raster runs on the GPU only, there is "
+                           "no CPU fallback")
+
+
+def _workspace(key, dev, make):
+    """One set of buffers per (device, stream, call shape), reused by later calls."""
+    key = (dev, torch.cuda.current_stream(dev).cuda_stream) + key
+    if key not in _ws_cache:
+        _ws_cache[key] = make()
+    return _ws_cache[key]
+
+
+def clear_workspaces():
+    """Drops every cached workspace (not while a captured graph that uses them is alive)."""
+    _ws_cache.clear()
+    _axes_cache.clear()
+
+
+def _bytes(dev, n):
+    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=dev)
+
+
+def _cloud_source(cloud, what):
+    _on_device(cloud, what)
+    if cloud.dtype != torch.float64 or cloud.ndim != 2 or cloud.shape[1] != 3:
+        raise TypeError(f"dsm_raster {what}: the cloud is a float64 [N, 3] tensor, not {cloud.dtype} {tuple(cloud.shape)}")
+    cloud = cloud.detach().contiguous()
+    src = DsmSource(kind=DSM_SRC_CLOUD, N=cloud.shape[0], cloud=cloud.data_ptr() if cloud.shape[0] else None)
+    return src, (cloud,)
+
+
+def _shift3(scene_params):
+    c = np.asarray(scene_params[0].detach().cpu() if torch.is_tensor(scene_params[0]) else scene_params[0], dtype=np.float64).reshape(-1)
+    if c.shape != (3,):
+        raise ValueError("dsm_raster: scene_params[0] is the scene's centre, three numbers")
+    return (ctypes.c_double * 3)(*c.tolist())
+
+
+def view_axes(H, W, dev):
+    """(u [W], v [H]) = torch.linspace(-1, 1, .) in float32 on the device, as scene/cameras/affine_cameras.py:139-143 builds
+    its UV grid; cached per size and device."""
+    key = (dev, H, W)
+    if key not in _axes_cache:
+        _axes_cache[key] = (torch.linspace(-1, 1, W, device=dev), torch.linspace(-1, 1, H, device=dev))
+    return _axes_cache[key]
+
+
+def _axis(t, n, dev, what):
+    t = t.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if t.numel() != n:
+        raise ValueError(f"dsm_raster {what}: an axis has {t.numel()} entries, the image needs {n}")
+    return t
+
+
+def _view_source(altitude, affine, scene_params, uv_axes, what):
+    _on_device(altitude, what)
+    alt = altitude.detach()
+    if alt.dtype != torch.float32:
+        raise TypeError(f"dsm_raster {what}: the altitude image is float32, not {alt.dtype}")
+    H, W = alt.shape[-2:] if alt.ndim >= 2 else (0, 0)
+    if alt.ndim < 2 or alt.numel() != H * W or H * W == 0:
+        raise TypeError(f"dsm_raster {what}: the altitude image is a non-empty single-channel [H, W], not {tuple(alt.shape)}")
+    alt = alt.contiguous()
+    dev = alt.device
+    f = lambda t: t.detach().to(device=dev, dtype=torch.float32)  # noqa: E731
+    if hasattr(affine, "Ainv") and hasattr(affine, "affine"):  # a camera of the reference: affine_cameras.py:151-159
+        Ainv, b = f(affine.Ainv), f(affine.affine)[3, :3]
+    elif torch.is_tensor(affine) and tuple(affine.shape) == (4, 4):
+        Ainv, b = torch.inverse(f(affine)[:3, :3].T), f(affine)[3, :3]  # :159
+    else:
+        Ainv, b = (f(t) for t in affine)  # (Ainv [3, 3], b [3])
+    aff = torch.cat([Ainv.reshape(-1), b.reshape(-1)]).contiguous()
+    if aff.numel() != 12:
+        raise ValueError(f"dsm_raster {what}: affine is a camera, its 4 x 4 matrix or (Ainv [3, 3], b [3])")
+    u, v = view_axes(H, W, dev) if uv_axes is None else (_axis(uv_axes[0], W, dev, what), _axis(uv_axes[1], H, dev, what))
+    src = DsmSource(kind=DSM_SRC_VIEW, H=H, W=W, altitude=alt.data_ptr(), u_axis=u.data_ptr(), v_axis=v.data_ptr(),
+                    affine=aff.data_ptr(), scale=float(scene_params[1]), shift=_shift3(scene_params))
+    return src, (alt, u, v, aff)
+
+
+def _grid_source(height, axis0, axis1, scene_params, what="extract_dsm"):
+    """The surface of a TSDF volume (tsdf.py:538-556): point (i, j) = (axis0[i], axis1[j], height[i][j]) + scene_params[0]."""
+    _on_device(height, what)
+    h = height.detach().to(dtype=torch.float32).contiguous()
+    nx, ny = h.shape
+    a0, a1 = _axis(axis0, nx, h.device, what), _axis(axis1, ny, h.device, what)
+    src = DsmSource(kind=DSM_SRC_GRID, H=nx, W=ny, altitude=h.data_ptr(), u_axis=a1.data_ptr(), v_axis=a0.data_ptr(), scale=1.0,
+                    shift=_shift3(scene_params))
+    return src, (h, a0, a1)
+
+
+def _bounds(src, dev, what):
+    abi = _lib.get()
+
+    def make():
+        nb = ctypes.c_size_t()
+        abi.check(abi.dsm_bounds_bytes(ctypes.byref(nb)))
+        return _bytes(dev, nb.value), _bytes(dev, ctypes.sizeof(DsmBounds))
+
+    ws, res = _workspace(("bounds",), dev, make)
+    with _Ctx(abi, dev) as cx:
+        abi.check(abi.dsm_bounds(ctypes.byref(src), _ptr(res), _ptr(ws), ws.numel(), cx.stream))
+    r = DsmBounds.from_buffer_copy(res.cpu().numpy().tobytes())  # the one read-back
+    if r.count == 0:
+        raise ValueError(f"dsm_raster {what}: the cloud is empty, it has no bounds")
+    if r.nonfinite:
+        raise ValueError(f"dsm_raster {what}: {r.nonfinite} of {r.count} points have a non-finite x or y")
+    return np.float64(r.xmin), np.float64(r.xmax), np.float64(r.ymin), np.float64(r.ymax)
+
+
+def cloud_bounds(cloud):
+    """(xmin, xmax, ymin, ymax) of a float64 [N, 3] cloud as numpy float64: `cloud[:, 0].min()`, ... of dsm_utils.py:18-19,
+    exact in any order. One pass on the device, one read-back. ValueError for an empty cloud or a non-finite x or y."""
+    src, keep = _cloud_source(cloud, "cloud_bounds")
+    return _bounds(src, cloud.device, "cloud_bounds")
+
+
+def raster_geometry(xmin, xmax, ymin, ymax, resolution):
+    """dsm_utils.py:20-25 (tsdf.py:564-569), the reference's own four lines in numpy float64: (xoff, yoff, xsize, ysize)."""
+    xmin, xmax, ymin, ymax = (np.float64(v) for v in (xmin, xmax, ymin, ymax))
+    xoff = np.floor(xmin / resolution) * resolution
+    xsize = int(1 + np.floor((xmax - xoff) / resolution))
+    yoff = np.ceil(ymax / resolution) * resolution
+    ysize = int(1 - np.floor((ymin - yoff) / resolution))
+    return xoff, yoff, xsize, ysize
+
+
+def _check_grid(xoff, yoff, resolution, xsize, ysize, radius, what):
+    if isinstance(radius, bool) or int(radius) != radius or not 0 <= int(radius) <= MAX_RADIUS:
+        raise ValueError(f"dsm_raster {what}: radius must be an integer 0 .. {MAX_RADIUS}")
+    if int(xsize) != xsize or int(ysize) != ysize or xsize <= 0 or ysize <= 0:
+        raise ValueError(f"dsm_raster {what}: xsize and ysize must be positive integers, not {xsize}, {ysize}")
+    if not (math.isfinite(float(resolution)) and float(resolution) > 0):
+        raise ValueError(f"dsm_raster {what}: resolution must be positive and finite")
+    if not (math.isfinite(float(xoff)) and math.isfinite(float(yoff))):
+        raise ValueError(f"dsm_raster {what}: xoff and yoff must be finite")
+
+
+def _raster(src, dev, xoff, yoff, resolution, xsize, ysize, radius, return_count, skipped_out):
+    abi = _lib.get()
+    xsize, ysize, radius = int(xsize), int(ysize), int(radius)
+
+    def make():
+        nb = ctypes.c_size_t()
+        abi.check(abi.dsm_raster_bytes(xsize, ysize, radius, ctypes.byref(nb)))
+        return (_bytes(dev, nb.value),)
+
+    (ws,) = _workspace(("raster", xsize, ysize, radius), dev, make)
+    out = torch.empty((ysize, xsize, 1), dtype=torch.float32, device=dev)
+    count = torch.empty((ysize, xsize), dtype=torch.int32, device=dev) if return_count else None
+    if skipped_out is not None:
+        _on_device(skipped_out, "plyflatten")
+        if skipped_out.dtype != torch.int64 or skipped_out.numel() != 1 or skipped_out.device != dev:
+            raise TypeError("dsm_raster plyflatten: skipped_out is one int64 on the cloud's device")
+    with _Ctx(abi, dev) as cx:
+        abi.check(abi.dsm_raster(ctypes.byref(src), float(xoff), float(yoff), float(resolution), xsize, ysize, radius, _ptr(out),
+                                 _ptr(count), _ptr(skipped_out), _ptr(ws), ws.numel(), cx.stream))
+    return (out, count) if return_count else out
+
+
+def plyflatten(cloud, xoff, yoff, resolution, xsize, ysize, radius=1, sigma=float("inf"), return_count=False, skipped_out=None):
+    """plyflatten's name and signature over a float64 [N, 3] cloud on the GPU (N = 0 gives an all-NaN raster): float32
+    [ysize, xsize, 1], the mean of float32(z) over the points whose (2 radius + 1)^2 footprint covers the cell, NaN where
+    there is none. `return_count=True` returns (raster, int32 [ysize, xsize] contributions per cell, -1 under a poisoned
+    footprint). `skipped_out`, one int64 on the device, receives the number of points skipped for a non-finite x or y.
+    Only sigma = inf (every weight 1) exists: the reference passes nothing else. No host wait."""
+    if not math.isinf(float(sigma)) or float(sigma) < 0:
+        raise NotImplementedError("dsm_raster plyflatten: only sigma = inf (unit weights) is implemented, the reference's setting")
+    _check_grid(xoff, yoff, resolution, xsize, ysize, radius, "plyflatten")
+    src, keep = _cloud_source(cloud, "plyflatten")
+    return _raster(src, cloud.device, xoff, yoff, resolution, xsize, ysize, radius, return_count, skipped_out)
+
+
+def make_profile(dsm, xoff, yoff, resolution):
+    """The reference's profile (dsm_utils.py:42-50) as a plain dict; the CRS, the driver and the GeoTIFF write stay the
+    caller's. `transform` holds the six coefficients of affine.Affine(res, 0, xoff, 0, -res, yoff)."""
+    res = float(resolution)
+    return {"dtype": "float32", "height": int(dsm.shape[0]), "width": int(dsm.shape[1]), "count": 1, "nodata": float("nan"),
+            "transform": (res, 0.0, float(xoff), 0.0, -res, float(yoff))}
+
+
+def _from_source(src, dev, resolution, radius, geometry, return_count, what):
+    if geometry is None:
+        xoff, yoff, xsize, ysize = raster_geometry(*_bounds(src, dev, what), resolution)
+    else:
+        xoff, yoff, xsize, ysize = geometry
+    _check_grid(xoff, yoff, resolution, xsize, ysize, radius, what)
+    res = _raster(src, dev, xoff, yoff, resolution, xsize, ysize, radius, return_count, None)
+    dsm = res[0] if return_count else res
+    profile = make_profile(dsm, xoff, yoff, resolution)
+    return (profile, dsm, res[1]) if return_count else (profile, dsm)
+
+
+def dsm_from_view(altitude_render, affine, scene_params, resolution, radius=1, geometry=None, uv_axes=None, return_count=False):
+    """compute_dsm_from_view (dsm_utils.py:7-51) for one rendered altitude image, float32 [H, W] (or [1, H, W]), without
+    materialising the cloud: pixel (r, c) is the point Ainv ((u[c], v[r], altitude[r][c]) - b) * scene_params[1] +
+    scene_params[0], in double. `affine` is a camera with the reference's `.affine` / `.Ainv`, its 4 x 4 matrix (the
+    inverse is then taken as affine_cameras.py:159 takes it) or (Ainv [3, 3], b [3]). `uv_axes=(u [W], v [H])` hands over
+    the camera's own UV grid; the default is torch.linspace(-1, 1, .) on the image's device, as the camera builds it.
+    Returns (profile, dsm [ysize, xsize, 1]). geometry=None: the grid comes from the bounds (one host wait, ValueError for a
+    non-finite x or y); geometry=(xoff, yoff, xsize, ysize): no wait at all."""
+    src, keep = _view_source(altitude_render, affine, scene_params, uv_axes, "dsm_from_view")
+    return _from_source(src, altitude_render.device, resolution, radius, geometry, return_count, "dsm_from_view")
+
+
+def dsm_from_surface(height, axis0, axis1, scene_params, resolution, radius=1, geometry=None, return_count=False):
+    """The second half of the reference's TSDFVolume.extract_dsm (tsdf.py:538-600) for a surface height f32 [nx, ny] over
+    the volume's first two axes: x, y and height go to the kernel as fp32 and scene_params[0] is added in double there."""
+    src, keep = _grid_source(height, axis0, axis1, scene_params)
+    return _from_source(src, height.device, resolution, radius, geometry, return_count, "extract_dsm")
+
+
+__all__ = ["MAX_RADIUS", "Z_MAX", "Z_QUANTUM", "clear_workspaces", "cloud_bounds", "dsm_from_surface", "dsm_from_view",
+           "make_profile", "plyflatten", "raster_geometry", "view_axes"]

@@ -12,6 +12,7 @@ The stages around integrate are HIP as well:
   TSDFVolume.apply_prior()           tsdf.py:602-638, in place (two kernels, no voxel-sized index tensors)
   TSDFVolume.surface()               tsdf.py:530-536: the top-most voxel with t < 0 per column and its height
   TSDFVolume.surface_cloud(sp)       tsdf.py:538-556: the float64 point cloud the reference hands to plyflatten
+  TSDFVolume.extract_dsm(sp, res)    tsdf.py:530-600 without the file write: the surface rasterised on the device
 No CPU / eager fallback: CPU tensors raise.
 """
 import ctypes
@@ -20,7 +21,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, dsm_raster
 from .rasterizer import _Ctx, _ptr
 
 
@@ -66,6 +67,13 @@ class TSDFVolume:
         xy = torch.stack(torch.meshgrid([self.axes[0], self.axes[1]], indexing="ij"), dim=-1)
         cloud = torch.cat([xy, height.unsqueeze(-1)], dim=-1).detach().cpu().reshape(-1, 3).numpy()
         return cloud + scene_params[0]
+
+    def extract_dsm(self, scene_params, resolution):
+        """tsdf.py:530-600 without the file write: (profile, dsm float32 [ysize, xsize, 1]) on the device. x, y and the
+        height go to the raster kernel as fp32, `+ scene_params[0]` happens there in double; the grid comes from the
+        bounds of those points (the one host wait). The profile is dsm_raster.make_profile's plain dict."""
+        _, height = self.surface()
+        return dsm_raster.dsm_from_surface(height, self.axes[0], self.axes[1], scene_params, resolution)
 
 
 class RangeImage:

@@ -21,6 +21,8 @@ loss runs on the one PAN plane; `--pan-first` is the reference's `weird_pan_setu
 (`eogs2_amd.density.DensityStats.update`, one launch, no wait) and `densify_and_prune` plus the transparent prune every K iterations.
 `--monitor` keeps the reference's training metrics and early stopper on the device (`eogs2_amd.monitor.TrainingMonitor`;
 train_pan.py:423-429,471-495,512-597): every iteration feeds it without a wait, every 10 iterations one record is fetched and printed.
+`--dsm-mae-every N` scores the view's altitude against the unperturbed scene's (`eogs2_amd.dsm_eval.dsm_mae`); with `--dsm-resolution R`
+both are first flattened into DSMs on the device (`eogs2_amd.dsm_raster.dsm_from_view`): render -> DSM -> registered MAE.
 """
 import argparse
 import math
@@ -42,6 +44,7 @@ from eogs2_amd.graph import Branches  # noqa: E402
 from eogs2_amd.resample import render_resample_virtual_camera, resample  # noqa: E402
 from eogs2_amd.shade import randomcam_l, render_pipeline, suncamera_l, translucentshadows_l  # noqa: E402
 from eogs2_amd.dsm_eval import dsm_mae  # noqa: E402
+from eogs2_amd.dsm_raster import dsm_from_view  # noqa: E402
 from eogs2_amd.flow import apply_flow, perform_flow_matching, performOpticalmatching  # noqa: E402
 from eogs2_amd.regularizers import gaussian_regularizers  # noqa: E402
 from eogs2_amd.monitor import MONITOR_METRICS, TrainingMonitor  # noqa: E402
@@ -160,6 +163,13 @@ def main(argv=None):
                          "Gaussians), which callers compare between runs). Unit: the altitude channel is xyz @ affine[:3, 2] + affine[3, 2] "
                          f"(eogs2_amd/render.py), which for the synthetic Nadir camera is synthetic.ALT_SCALE ({ALT_SCALE:g}) x the scene's "
                          "normalised z, alpha-composited over bg[3]; divide the MAE by ALT_SCALE for normalised z. 0 = off")
+    ap.add_argument("--dsm-resolution", type=float, default=0.0, metavar="R",
+                    help="with --dsm-mae-every: score DSMs instead of altitude images. The altitude of the view's render and the "
+                         "altitude of the unperturbed scene are each flattened into a DSM of cell size R on the device "
+                         "(eogs2_amd.dsm_raster.dsm_from_view; utils/dsm_utils.py:7-51), both on the grid of the unperturbed scene's, "
+                         f"and dsm_mae scores those over their filled cells. The scene's normalised coordinates times ALT_SCALE ({ALT_SCALE:g}) "
+                         f"stand in for UTM metres, so R is in altitude units and the {ALT_SCALE:g}-unit-wide scene at --size 160 has about "
+                         "one pixel per cell at R = 5. 0 = off: the altitude image is scored as it is")
     ap.add_argument("--flow-matching", action="store_true",
                     help="the flow-matching step of the reference's flagship configuration (train_pan.py:347-357, "
                          "optimization/flowmatching/raft_small.yaml): the target image is displaced by a fixed sub-pixel amount — a "
@@ -207,6 +217,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.early_stop_patience is not None and not a.monitor:
         ap.error("--early-stop-patience needs --monitor")
+    if a.dsm_resolution and not a.dsm_mae_every:
+        ap.error("--dsm-resolution needs --dsm-mae-every")
     if a.pan_first and not a.pan_map:
         ap.error("--pan-first needs --pan-map")
     if a.pan_map and a.flow_matching:
@@ -315,6 +327,12 @@ def main(argv=None):
         gt = target_view[5]["final"].clone()
         gt_altitude = target_view[0]["render"][3].clone() if a.dsm_mae_every else None
         del target_view
+    dsm_cam = dsm_scene = dsm_geometry = gt_dsm = None
+    if a.dsm_mae_every and a.dsm_resolution:  # scene_params: a UTM-sized centre, normalised coordinates x ALT_SCALE as metres
+        dsm_scene = [(5e5, 4.3e6, 0.0), ALT_SCALE]
+        dsm_cam = types.SimpleNamespace(affine=cam.affine, Ainv=torch.inverse(cam.affine[:3, :3].T))  # affine_cameras.py:159
+        profile, gt_dsm = dsm_from_view(gt_altitude, dsm_cam, dsm_scene, a.dsm_resolution)  # the one wait: the target's bounds
+        dsm_geometry = (profile["transform"][2], profile["transform"][5], profile["width"], profile["height"])
     warper = None
     if a.flow_matching:
         shift = torch.tensor(FLOW_SHIFT, device=dev).view(1, 2, 1, 1).expand(1, 2, H, W)
@@ -474,7 +492,11 @@ def main(argv=None):
                     model.prune(keep)
                     stale = True  # new parameter tensors, new shapes: record again
         if a.dsm_mae_every and it % a.dsm_mae_every == 0:
-            mae, _, _, (sdx, sdy, _, _) = dsm_mae(kept["altitude"], gt_altitude)
+            if dsm_geometry is not None:  # render -> DSM -> registered MAE, all on the device
+                _, pred_dsm = dsm_from_view(kept["altitude"], dsm_cam, dsm_scene, a.dsm_resolution, geometry=dsm_geometry)
+                mae, _, _, (sdx, sdy, _, _) = dsm_mae(pred_dsm[:, :, 0], gt_dsm[:, :, 0], clip="finite")  # empty cells are NaN
+            else:
+                mae, _, _, (sdx, sdy, _, _) = dsm_mae(kept["altitude"], gt_altitude)
             dsm_scores.append((it, sdx, sdy, mae))
             if not a.quiet:
                 print(f"iter {it:4d}  DSM registration dx {sdx} dy {sdy}  MAE {mae:.5f} (altitude units = {ALT_SCALE:g} x normalised z)")
