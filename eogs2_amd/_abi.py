@@ -107,6 +107,8 @@ SIGNATURES = {
     "eogs_rast_selftest": (_i, [_p, C.POINTER(_u), _p]),
     # include/eogs_loss.h
     "eogs_loss_bytes": (_i, [_i, _i, _i, _u, C.POINTER(_z)]),
+    "eogs_loss_tile_shape": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "eogs_loss_window": (_i, [C.POINTER(C.c_float)]),
     "eogs_loss_forward": (_i, [_i, _i, _i, _p, _p, _u, _f, _f, _f, _p, _p, _p, _z, _p]),
     "eogs_loss_backward": (_i, [_i, _i, _i, _p, _p, _u, _f, _f, _p, _p, _p, _z, _p, _p]),
     # include/eogs_optim.h
@@ -214,7 +216,7 @@ DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP = 1, 2, 4, 
 DENSITY_COPY, DENSITY_ZERO, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2, 3  # the tensor kinds of eogs_density_build
 DENSITY_MAX_N = 8
 # symbols only the HIP library exports (the CPU oracle of the loss is oracle/loss_oracle.py, not a C-ABI twin)
-HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
+HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_tile_shape", "eogs_loss_window", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
             "eogs_compact_plan", "eogs_compact_apply", "eogs_resample_forward", "eogs_resample_bytes", "eogs_resample_backward", "eogs_knn_bytes",
             "eogs_knn_mean_dist2", "eogs_shade_bytes", "eogs_shade_forward", "eogs_shade_backward", "eogs_mloss_forward",
             "eogs_mloss_backward", "eogs_tshadow_forward", "eogs_tshadow_backward", "eogs_tsdf_integrate", "eogs_tsdf_normals",

@@ -616,12 +616,33 @@ int eogs_loss_bytes(int planes, int H, int W, unsigned mode, size_t* bytes) {
   return EOGS_OK;
 }
 
+int eogs_loss_tile_shape(int* tile_h, int* tile_w) {
+  if (!tile_h || !tile_w) return fail(EOGS_ERR_INVALID_ARG, "loss_tile_shape: NULL argument");
+  loss_tile_shape(tile_h, tile_w);
+  return EOGS_OK;
+}
+
+int eogs_loss_window(float* taps) {
+  if (!taps) return fail(EOGS_ERR_INVALID_ARG, "loss_window: NULL argument");
+  const LossWindow win = loss_window();
+  for (int i = 0; i < LOSS_WIN; i++) taps[i] = win.w[i];
+  return EOGS_OK;
+}
+
+// launch_loss_fwd / launch_loss_bwd put the rows of tiles in gridDim.y and the planes in gridDim.z: 65535 each. The tile height
+// is loss.hip's own (the monitor's standalone path launches the same forward and asks the same question).
+static bool loss_grid_fits(int planes, int H) {
+  int tile_h, tile_w;
+  loss_tile_shape(&tile_h, &tile_w);
+  return planes <= 65535 && (H - 1) / tile_h + 1 <= 65535;
+}
+
 static int loss_check(const char* who, int planes, int H, int W, const void* img, const void* gt, unsigned mode,
                       const void* ws, size_t ws_bytes, LossWS* out) {
   if (planes <= 0 || H <= 0 || W <= 0 || !(mode & (EOGS_LOSS_L1 | EOGS_LOSS_SSIM)) ||
       (mode & ~(EOGS_LOSS_L1 | EOGS_LOSS_SSIM)))
     return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes or mode", who);
-  if (planes > 65535 || (H + 31) / 32 > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: too many planes / rows for one launch", who);
+  if (!loss_grid_fits(planes, H)) return fail(EOGS_ERR_INVALID_ARG, "%s: too many planes / rows for one launch", who);
   if (!img || !gt || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
   char* base = ws_base(const_cast<void*>(ws));
   *out = loss_layout(base, planes, H, W, mode);
@@ -1497,7 +1518,7 @@ int eogs_monitor_reset(void* state, size_t state_bytes, int op, void* stream) {
 
 static int monitor_image_check(const char* who, int planes, int H, int W) {
   if (planes <= 0 || H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", who);
-  if (planes > 65535 || (H + 31) / 32 > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: too many planes / rows for one launch", who);
+  if (!loss_grid_fits(planes, H)) return fail(EOGS_ERR_INVALID_ARG, "%s: too many planes / rows for one launch", who);
   return EOGS_OK;
 }
 

@@ -594,16 +594,19 @@ void launch_selftest(uint32_t* out, hipStream_t s);
 // ---- photometric loss (loss.hip, include/eogs_loss.h) ----
 #define LOSS_WIN EOGS_LOSS_WINDOW
 struct LossWindow {
-  float w[LOSS_WIN];
+  float w[LOSS_WIN];  // the 1-D taps, applied along rows, then columns
+  float ws, c1, c0;   // of the reference's 2-D fp32 window: its sum Ws, 1 - Ws, Ws (1 - Ws) (loss.hip: moments about a pivot)
 };
 struct LossWS {
-  float* partial;    // [planes][tiles][2] per-workgroup {sum|x-y|, sum SSIM}
+  float* partial;    // [planes][tiles][2] per-workgroup {sum|x-y|, sum (SSIM - 1)}
   float* plane_tmp;  // [planes][2]
   float* maps;       // [3][planes][H][W] dSSIM/d{mu1, E[x^2], E[xy]} (EOGS_LOSS_SSIM only)
   size_t map_stride;
   int tiles;
   size_t bytes;
 };
+void loss_tile_shape(int* tile_h, int* tile_w);
+LossWindow loss_window();
 LossWS loss_layout(char* base, int planes, int H, int W, unsigned mode);
 void launch_loss_fwd(const LossWS& w, int planes, int H, int W, const float* img, const float* gt, unsigned mode,
                      float w_l1, float w_ssim, float bias, float* out, float* plane_sums, hipStream_t s);

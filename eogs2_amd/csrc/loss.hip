@@ -2,7 +2,7 @@
 // (SURVEY.md §8 row f2). Reference semantics: src/gaussiansplatting/utils/loss_utils.py:18-19 (l1_loss), :26-42 (window),
 // :45-85 (ssim/_ssim: five depthwise conv2d with zero padding 5, C1 = 0.01^2, C2 = 0.03^2), image_utils.py:27-28 (lphotom).
 //
-// One workgroup = one 32x32 output tile of one plane. The 42x42 input patch (zero outside the image, like conv2d's
+// One workgroup = one LTY x LT = 16x32 output tile of one plane. The 26x42 input patch (zero outside the image, like conv2d's
 // padding) is staged in LDS once; the separable window runs as a horizontal pass LDS->LDS and a vertical pass
 // LDS->registers, so each input pixel is fetched from HBM/L2 once per tile instead of 121 times. Forward keeps the three
 // partial-derivative maps dS/dmu1, dS/dE[x^2], dS/dE[xy]; backward is the same separable window applied to those maps
@@ -79,15 +79,32 @@ __global__ __launch_bounds__(LTHREADS) void loss_fwd_kernel(int H, int W, const 
   }
   __syncthreads();
 
+  // The moments are formed about a pivot p, one per tile: u = x - p, v = y - p (the padding's zeros too: they are values of
+  // the image the window sees). Where an image is flat to 1e-2 — where sigma^2 = E[x^2] - mu^2 would cancel seven digits against
+  // C2 = 9e-4 — the sums of u, u^2, uv are of the size of the variances themselves, and their rounding (and the 6e-8 by which a
+  // product of two taps differs from the reference's fp32 2-D window entry) no longer shows. Any finite p is exact algebra;
+  // what matters is that it represents the tile. It is the median of five ground-truth pixels — the corners and the centre of
+  // the tile's part inside the image — so no single pixel (a glint on water at a tile's origin) decides it; fminf / fmaxf pass
+  // over a NaN sample, and a pivot that is still not finite would spread over the tile, so it is replaced by 0.
+  float piv = 0.f;
   if (WITH_SSIM) {
-    // horizontal pass: 42 rows x 32 columns x 5 moments. A thread takes EIGHT adjacent columns of one row: their windows
-    // overlap, so it reads 18 + 18 staged values once instead of 8 x (11 + 11) (round 4: the kernel was bound by its LDS
-    // reads — 86 k dwords per tile, 28 k now; every output's own sum keeps its order, k ascending)
+    const int hh = min(LTY, H - y0), ww = min(LT, W - x0);
+    const float a = s_y[HALO][HALO], b = s_y[HALO][HALO + ww - 1], c = s_y[HALO + hh - 1][HALO];
+    const float d = s_y[HALO + hh - 1][HALO + ww - 1], e = s_y[HALO + hh / 2][HALO + ww / 2];
+    const float f = fmaxf(fminf(a, b), fminf(c, d)), g = fminf(fmaxf(a, b), fmaxf(c, d));
+    const float m = fmaxf(fminf(f, g), fminf(fmaxf(f, g), e));  // median of {e, f, g} = median of the five
+    piv = (m - m == 0.f) ? m : 0.f;
+  }
+
+  if (WITH_SSIM) {
+    // horizontal pass: LH rows x 32 columns x 5 moments. A thread takes HG = 4 adjacent columns of one row: their windows
+    // overlap, so it reads 14 + 14 staged values once instead of 4 x (11 + 11) (round 4: the kernel was bound by its LDS
+    // reads; every output's own sum keeps its order, k ascending)
     if (t < LH * (LT / HG)) {
       const int r = t / (LT / HG), c0 = (t % (LT / HG)) * HG;
       float xa[HG + LOSS_WIN - 1], ya[HG + LOSS_WIN - 1];
 #pragma unroll
-      for (int k = 0; k < HG + LOSS_WIN - 1; k++) { xa[k] = s_x[r][c0 + k]; ya[k] = s_y[r][c0 + k]; }
+      for (int k = 0; k < HG + LOSS_WIN - 1; k++) { xa[k] = s_x[r][c0 + k] - piv; ya[k] = s_y[r][c0 + k] - piv; }
 #pragma unroll
       for (int o = 0; o < HG; o++) {
         float m1 = 0.f, m2 = 0.f, e11 = 0.f, e22 = 0.f, e12 = 0.f;
@@ -130,17 +147,29 @@ __global__ __launch_bounds__(LTHREADS) void loss_fwd_kernel(int H, int W, const 
     const float a = s_x[r + HALO][tx + HALO], b = s_y[r + HALO][tx + HALO];
     if (WITH_L1 && inside) l1 += fabsf(a - b);
     if (WITH_SSIM) {
-      const float mu1 = vs[0][j], mu2 = vs[1][j], e11 = vs[2][j], e22 = vs[3][j], e12 = vs[4][j];
+      // No contraction from here to the maps, and S by a division as the reference forms it: where the render equals the
+      // ground truth, numerator and denominator are then the same operations on the same values, S is 1 and the loss 0 to
+      // the bit, as in the reference (a fused 2 mu1 mu2 + C1 beside an unfused mu1^2 + mu2^2 + C1 would differ by an ulp).
+#pragma clang fp contract(off)
+      const float U = vs[0][j], V = vs[1][j], Uu = vs[2][j], Vv = vs[3][j], Uv = vs[4][j];
+      // Back to the reference's quantities. Its window sums to Ws = 1 - 6.9e-8, not to 1, so its variances are not
+      // shift-invariant: with x = p + u,
+      //   mu1 = Ws p + U,   E[x^2] - mu1^2 = (Uu - U^2) + (1 - Ws) 2 p U + Ws (1 - Ws) p^2     (and alike for y, xy)
+      // The last two terms are 1e-8 and kept: float64 of the reference's arithmetic has them (win.ws, .c1, .c0: LossWindow),
+      // and against C2 they show — without them the mean SSIM of a 0.95-flat image with 1 % noise is 15.8 x its bound off.
+      const float mu1 = piv * win.ws + U, mu2 = piv * win.ws + V;
+      const float pp = win.c0 * piv * piv, p1 = win.c1 * piv;
       // _ssim (loss_utils.py:58-80)
       const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
       const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-      const float s11 = e11 - mu1_sq, s22 = e22 - mu2_sq, s12 = e12 - mu12;
+      const float s11 = (Uu - U * U) + (p1 * (2.f * U) + pp), s22 = (Vv - V * V) + (p1 * (2.f * V) + pp);
+      const float s12 = (Uv - U * V) + (p1 * (U + V) + pp);
       const float A1 = 2.f * mu12 + C1, A2 = 2.f * s12 + C2;
       const float B1 = mu1_sq + mu2_sq + C1, B2 = s11 + s22 + C2;
       const float inv = 1.f / (B1 * B2);
-      const float S = A1 * A2 * inv;
+      const float S = (A1 * A2) / (B1 * B2);
       if (inside) {
-        ss += S;
+        ss += S - 1.f;  // sum of S - 1 (exact per pixel for S in [1/2, 2]): near SSIM = 1 the sums keep their digits for 1 - SSIM
         // derivatives with respect to the three window sums that depend on x: mu1, E[x^2], E[xy]
         const float d11 = -S / B2;         // dS/dsigma1_sq
         const float d12 = 2.f * A1 * inv;  // dS/dsigma12
@@ -180,23 +209,28 @@ __global__ __launch_bounds__(LTHREADS) void loss_plane_reduce_kernel(const float
   }
 }
 
-__global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restrict__ plane_tmp, int planes, float inv_n,
-                                                           float w_l1, float w_ssim, float bias,
+// plane_tmp[.][1] holds the plane's sum of S - 1 (0 without EOGS_LOSS_SSIM): `hw`, the pixels of a plane, turns it back into
+// the sum of S. The means and out[0] are formed in double and rounded once each: with bias = -w_ssim (lphotom's
+// lambda (1 - SSIM)) and SSIM near 1, out[0] cancels from 0.2 down to the loss, and an SSIM mean rounded to fp32 on the way
+// (half an ulp of 1: 3e-8) would leave the loss of a nearly converged view with five digits.
+__global__ __launch_bounds__(64) void loss_finalize_kernel(const float* __restrict__ plane_tmp, int planes, double hw,
+                                                           bool with_ssim, float w_l1, float w_ssim, float bias,
                                                            float* __restrict__ out, float* __restrict__ plane_sums) {
   if (threadIdx.x != 0) return;
-  float a = 0.f, b = 0.f;
+  double a = 0.0, b = 0.0;
   for (int p = 0; p < planes; p++) {
-    a += plane_tmp[2 * p];
-    b += plane_tmp[2 * p + 1];
+    a += (double)plane_tmp[2 * p];
+    b += (double)plane_tmp[2 * p + 1];
     if (plane_sums) {
       plane_sums[2 * p] = plane_tmp[2 * p];
-      plane_sums[2 * p + 1] = plane_tmp[2 * p + 1];
+      plane_sums[2 * p + 1] = with_ssim ? (float)(hw + (double)plane_tmp[2 * p + 1]) : 0.f;
     }
   }
-  const float l1m = a * inv_n, sm = b * inv_n;
-  out[0] = w_l1 * l1m + w_ssim * sm + bias;
-  out[1] = l1m;
-  out[2] = sm;
+  const double n = hw * (double)planes;
+  const double l1m = a / n, sm = with_ssim ? 1.0 + b / n : 0.0;
+  out[0] = (float)((double)w_l1 * l1m + ((double)w_ssim * sm + (double)bias));
+  out[1] = (float)l1m;
+  out[2] = (float)sm;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -308,6 +342,12 @@ __global__ __launch_bounds__(LTHREADS) void loss_bwd_kernel(int H, int W, const 
 
 }  // namespace
 
+// the output tile of one workgroup: what the grids below, the workspace layout and the API's size limits are counted in
+void loss_tile_shape(int* tile_h, int* tile_w) {
+  *tile_h = LTY;
+  *tile_w = LT;
+}
+
 LossWS loss_layout(char* base, int planes, int H, int W, unsigned mode) {
   LossWS w;
   const size_t tiles = (size_t)((W + LT - 1) / LT) * ((H + LTY - 1) / LTY);
@@ -327,15 +367,28 @@ LossWS loss_layout(char* base, int planes, int H, int W, unsigned mode) {
 }
 
 LossWindow loss_window() {
-  // gaussian(11, 1.5) (loss_utils.py:26-33): exp in double, stored as fp32, normalised by the fp32 sum
+  // gaussian(11, 1.5) (loss_utils.py:26-33): exp in double, stored as fp32, normalised by the fp32 sum. That sum is the
+  // reference's `gauss.sum()`, which comes out as the exact sum rounded once (3.75923276); an fp32 running sum lands one
+  // ulp below it (3.75923252) and made every tap 6e-8 too heavy: the window summed to 1 + 8.9e-8 where the reference's
+  // sums to 1 - 6.9e-8, which sigma^2 = E[x^2] - mu^2 turns into 1.6e-7 mu^2 against C2 = 9e-4 (mean SSIM of a bright flat
+  // image with 1 % noise: 1.3e-5 off).
   LossWindow win;
-  float g[LOSS_WIN], sum = 0.f;
+  float g[LOSS_WIN];
+  double acc = 0.0;
   for (int i = 0; i < LOSS_WIN; i++) {
     const double d = (double)(i - LOSS_WIN / 2);
     g[i] = (float)exp(-(d * d) / (2.0 * 1.5 * 1.5));
-    sum += g[i];
+    acc += (double)g[i];
   }
+  const float sum = (float)acc;
   for (int i = 0; i < LOSS_WIN; i++) win.w[i] = g[i] / sum;
+  // the sum of the reference's 2-D window, whose entries are the fp32 products of the taps (loss_utils.py:37-38)
+  double ws = 0.0;
+  for (int i = 0; i < LOSS_WIN; i++)
+    for (int j = 0; j < LOSS_WIN; j++) ws += (double)(float)(win.w[i] * win.w[j]);
+  win.ws = (float)ws;
+  win.c1 = (float)(1.0 - ws);
+  win.c0 = (float)(ws * (1.0 - ws));
   return win;
 }
 
@@ -347,9 +400,8 @@ void launch_loss_fwd(const LossWS& w, int planes, int H, int W, const float* img
   auto* kern = ss ? (l1 ? loss_fwd_kernel<true, true> : loss_fwd_kernel<false, true>) : loss_fwd_kernel<true, false>;
   hipLaunchKernelGGL(kern, grid, dim3(LTHREADS), 0, s, H, W, img, gt, win, w.maps, w.map_stride, w.partial);
   hipLaunchKernelGGL(loss_plane_reduce_kernel, dim3(planes), dim3(LTHREADS), 0, s, w.partial, w.tiles, w.plane_tmp);
-  const float inv_n = (float)(1.0 / ((double)planes * H * W));
-  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, w.plane_tmp, planes, inv_n, w_l1, w_ssim, bias, out,
-                     plane_sums);
+  hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(64), 0, s, w.plane_tmp, planes, (double)H * (double)W, ss, w_l1,
+                     w_ssim, bias, out, plane_sums);
 }
 
 void launch_loss_bwd(const LossWS& w, int planes, int H, int W, const float* img, const float* gt, unsigned mode,

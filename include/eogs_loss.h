@@ -32,6 +32,15 @@ extern "C" {
  * written by forward and re-read by backward). */
 int eogs_loss_bytes(int planes, int H, int W, unsigned mode, size_t* bytes);
 
+/* The output tile of one workgroup, in pixels. eogs_loss_forward / _backward launch ceil(H / tile_h) rows of workgroups in one
+ * grid dimension and `planes` in another, 65535 at most each: larger inputs are EOGS_ERR_INVALID_ARG. The workspace holds one
+ * pair of partial sums per tile. */
+int eogs_loss_tile_shape(int* tile_h, int* tile_w);
+
+/* The EOGS_LOSS_WINDOW taps of the 1-D window the kernels apply along rows, then columns: the reference's gaussian(11, 1.5)
+ * (loss_utils.py:26-33) bit for bit, host memory. */
+int eogs_loss_window(float* taps);
+
 /* Forward. Writes
  *   out        f32[3]          {w_l1*l1_mean + w_ssim*ssim_mean + bias, l1_mean, ssim_mean}  (means over all planes)
  *   plane_sums f32[planes][2]  {sum|x-y|, sum SSIM} per plane (for size_average=False); may be NULL
