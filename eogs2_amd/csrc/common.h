@@ -591,7 +591,8 @@ int gaussian_bwd_wide(int64_t R, int P);
 void launch_gaussian_bwd(const GaussBwdArgs& a, const GeomWS& g, const BinWS& b, int p_begin, int p_end, hipStream_t s);
 void launch_selftest(uint32_t* out, hipStream_t s);
 
-// ---- photometric loss (loss.hip, include/eogs_loss.h) ----
+// ---- the photometric loss's forward (loss.hip). Its entries live in loss.hip; these cross to a second user, monitor.hip:
+// eogs_monitor_observe without a loss_out runs the same forward on the same workspace layout ----
 #define LOSS_WIN EOGS_LOSS_WINDOW
 struct LossWindow {
   float w[LOSS_WIN];  // the 1-D taps, applied along rows, then columns
@@ -605,175 +606,11 @@ struct LossWS {
   int tiles;
   size_t bytes;
 };
-void loss_tile_shape(int* tile_h, int* tile_w);
-LossWindow loss_window();
 LossWS loss_layout(char* base, int planes, int H, int W, unsigned mode);
+bool loss_grid_fits(int planes, int H);  // planes and rows of tiles within one launch's grid
 void launch_loss_fwd(const LossWS& w, int planes, int H, int W, const float* img, const float* gt, unsigned mode,
                      float w_l1, float w_ssim, float bias, float* out, float* plane_sums, hipStream_t s);
-void launch_loss_bwd(const LossWS& w, int planes, int H, int W, const float* img, const float* gt, unsigned mode,
-                     float w_l1, float w_ssim, const float* upstream, const float* plane_grad, float* dimg,
-                     hipStream_t s);
 
-// ---- optimizer / compaction (optim.hip, include/eogs_optim.h) ----
-#define EOGS_COMPACT_MAX_TENSORS 24  // tensors per compaction launch (more are split over launches)
-struct CompactWS {
-  uint32_t* blk;  // [nblk + 1] kept rows per 256-row workgroup -> exclusive prefix, total at [nblk]
-  uint32_t nblk;
-  size_t bytes;
-};
-CompactWS compact_layout(char* base, int64_t n_rows);
-int launch_adam(int n, const eogs_adam_tensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s);
-int launch_sum_into(int n, const eogs_sum_tensor* tensors, int nsrc, hipStream_t s);
-// (include/eogs_step.h) `misc`: each forward's count words (geom_layout().misc)
-void launch_step_gate(int n, const uint32_t* const* misc, const uint32_t* cap_slots, const uint32_t* cap_entries, int accumulate,
-                      uint32_t* gate, hipStream_t s);
-int launch_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, double beta2, double eps, const uint32_t* gate,
-                     eogs_step_adam_scalars* ws, hipStream_t s);
-void launch_pack_columns(int64_t rows, int n, const eogs_pack_tensor* tensors, float* packed, int packed_cols, int unpack,
-                         hipStream_t s);
-void launch_compact_plan(const CompactWS& w, int64_t n_rows, const uint8_t* keep, hipStream_t s);
-void launch_compact_apply(const CompactWS& w, int64_t n_rows, const uint8_t* keep, int n_tensors, const void* const* src,
-                          void* const* dst, const int* row_bytes, hipStream_t s);
-
-// ---- adaptive density control (density.hip, include/eogs_density.h) ----
-struct DensityWS {
-  uint32_t* cnt;  // [nblk + 1][4] rows of the four kinds per 256-row workgroup -> exclusive prefixes, totals at [nblk]
-  uint32_t nblk;
-  size_t bytes;
-};
-DensityWS density_layout(char* base, int64_t P);
-void launch_density_stats(int64_t P, const float* vg, const void* radii, int radii_is_float, float* accum, float* denom,
-                          float* maxr, hipStream_t s);
-void launch_density_decide(const DensityWS& w, int64_t P, const float* accum, const float* denom, const float* opacity,
-                           const float* scaling, float thr_grad, float thr_dense, float min_opacity, int use_screen, float thr_big,
-                           float split_div, uint8_t* flags, hipStream_t s);
-void launch_density_split_rows(const DensityWS& w, int64_t P, const uint8_t* flags, const void* src, void* dst, int row_bytes,
-                               hipStream_t s);
-void launch_density_build(const DensityWS& w, int64_t P, int N, const uint8_t* flags, const int64_t* counts, int n_tensors,
-                          const eogs_density_tensor* tensors, const float* rotation, const float* samples, float split_div,
-                          hipStream_t s);
-
-// ---- virtual-camera resample (resample.hip, include/eogs_resample.h) ----
-void launch_resample_fwd(int C, int Hv, int Wv, int H, int W, int n_out, const float* vr, const float* uva,
-                         const float* M, int fill_channel, float fill_value, float* sample, float* uv, hipStream_t s);
-size_t resample_bwd_ws_bytes(int H, int W);
-void launch_resample_bwd(int C, int Hv, int Wv, int H, int W, int n_out, const float* vr, const float* uva,
-                         const float* M, int fill_channel, const float* gs, const float* guv, float* gvr, float* guva,
-                         void* ws, hipStream_t s);
-
-// ---- flow-matching warp (flow.hip, include/eogs_resample.h eogs_resample_flow_*) ----
-size_t flow_stats_ws_bytes(int H, int W);
-void launch_flow_stats(int H, int W, const float* flow, int64_t sc, int64_t sy, int64_t sx, float* stats, void* ws, hipStream_t s);
-void launch_flow_fwd(int C, int H, int W, const float* img, const float* flow, int64_t sc, int64_t sy, int64_t sx,
-                     const float* gate, float* out, hipStream_t s);
-size_t flow_bwd_ws_bytes(int H, int W);
-void launch_flow_bwd(int C, int H, int W, const float* flow, int64_t sc, int64_t sy, int64_t sx, const float* gate,
-                     const float* g, float* gimg, void* ws, hipStream_t s);
-
-// ---- image chain after the raw render (shade.hip, include/eogs_shade.h) ----
-size_t shade_ws_bytes();
-void launch_shade_fwd(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow, float* cc,
-                      float* shaded, float* shadow, hipStream_t s);
-void launch_shade_bwd(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
-                      const float* g_shaded, const float* g_cc, const float* g_shadow, float* g_raw, float* g_alt,
-                      float* g_params, void* ws, hipStream_t s);
-void launch_mloss_fwd(int H, int W, int mode, const float* alt_diff, const float* a, const float* b, const float* uv, float* out,
-                      void* ws, hipStream_t s);
-void launch_mloss_bwd(int H, int W, int mode, const float* alt_diff, const float* a, const float* b, const float* uv,
-                      const float* out, const float* upstream, float* g_alt, float* g_a, float* g_b, hipStream_t s);
-void launch_tshadow_fwd(int64_t n, const float* a, float* out, void* ws, hipStream_t s);
-void launch_tshadow_bwd(int64_t n, const float* a, const float* upstream, float* g_a, hipStream_t s);
-
-// ---- regularisers over the model and over render planes (reg.hip, include/eogs_reg.h) ----
-size_t reg_ws_bytes();
-void launch_reg_gauss_fwd(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
-                          float n_init, const float* weights, float* out, void* ws, hipStream_t s);
-void launch_reg_gauss_bwd(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
-                          float n_init, const float* weights, const float* out, const float* g_total, const float* g_terms,
-                          float* g_opacity, float* g_scaling, hipStream_t s);
-void launch_reg_image_fwd(int H, int W, const float* alt, const float* acc, const float* weights, float* out, void* ws,
-                          hipStream_t s);
-void launch_reg_image_bwd(int H, int W, const float* alt, const float* acc, const float* weights, const float* g_total,
-                          const float* g_terms, float* g_alt, float* g_acc, hipStream_t s);
-
-// ---- training monitor (monitor.hip, include/eogs_monitor.h) ----
-size_t monitor_sq_bytes(int planes, int H, int W);  // the per-plane partials of observe, a multiple of 256
-size_t monitor_model_ws_bytes(int64_t P);
-void launch_monitor_reset(void* state, int op, hipStream_t s);
-void launch_monitor_observe(int planes, int H, int W, const float* img, const float* gt, const float* loss_out,
-                            float one_minus_lambda, float lambda, int kind, int photometric_on, const uint32_t* gate, void* state,
-                            double* partial, hipStream_t s);
-void launch_monitor_model(int64_t P, const float* opacity, const uint32_t* gate, void* state, void* ws, hipStream_t s);
-void launch_monitor_end_iteration(const float* loss, const uint32_t* gate, void* state, hipStream_t s);
-void launch_monitor_close(int metric, int op, int64_t patience, const uint32_t* gate, void* state, hipStream_t s);
-
-// ---- panchromatic camera pipeline (pan.hip, include/eogs_pan.h) ----
-size_t pan_ws_bytes();
-int pan_map_params(int kind);  // floats of map_params the kind reads
-void launch_pan_fwd(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
-                    const float* map_params, float* cc, float* shaded, float* shadow, hipStream_t s);
-void launch_pan_bwd(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
-                    const float* map_params, const float* g_shaded, const float* g_cc, const float* g_shadow, float* g_raw,
-                    float* g_alt, float* g_params, void* ws, hipStream_t s);
-
-// ---- TSDF integration (tsdf.hip, include/eogs_tsdf.h) ----
-void launch_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,
-                           float scale, float trunc, int H, int W, const float* alt, const float* wgt, float* tsdf,
-                           float* wvol, hipStream_t s);
-void launch_tsdf_normals(int H, int W, const float* alt, const float* affine, const float* view_dir, float* normals, float* angle,
-                         float* weights, hipStream_t s);
-size_t tsdf_prior_ws_bytes(int nx, int ny, int nz);
-void launch_tsdf_prior(int nx, int ny, int nz, float* tsdf, float* wvol, void* ws, hipStream_t s);
-void launch_tsdf_surface(int nx, int ny, int nz, const float* tsdf, const float* az, int64_t* index, float* height, hipStream_t s);
-
-// ---- DSM evaluation (dsm_eval.hip, include/eogs_tsdf.h eogs_tsdf_dsm_*) ----
-#define DSM_TILE_W 64      // pixels of the reference image per tile of the NCC search
-#define DSM_TILE_H 16
-#define DSM_MOMENTS 6      // count, sum u', sum v', sum u'^2, sum v'^2, sum u'v' per shift
-#define DSM_MAX_GRID 1024  // workgroups of the search and of the reductions (4 per CU): a function of the shape alone
-#define DSM_MAX_LEVELS 32
-struct DsmNccWS {
-  double *pivots, *moments, *partials;  // [2], [n*n][6], [n*n][6][P]
-  int tiles_x, num_tiles, grid, P;
-  size_t bytes;
-};
-DsmNccWS dsm_ncc_layout(char* base, int Hu, int Wu, int irange);
-void launch_dsm_downsample(int H, int W, const void* in, int f64, double* out, hipStream_t s);
-void launch_dsm_pivots(int64_t nu, const void* u, int64_t nv, const void* v, int f64, double* pivots, hipStream_t s);
-void launch_dsm_moments(int Hu, int Wu, const void* u, int Wv, const void* v, int f64, int irange, const int* centre,
-                        int centre_scale, const DsmNccWS& ws, hipStream_t s);
-void launch_dsm_finalize(int irange, const int* centre, int centre_scale, const DsmNccWS& ws, double* table,
-                         eogs_tsdf_dsm_result* result, hipStream_t s);
-void launch_dsm_apply_shift(int H, int W, const void* in, int f64, int dx, int dy, double a, double b, double c, double d, void* out,
-                            hipStream_t s);
-size_t dsm_mae_ws_bytes();
-void launch_dsm_mae(int Hp, int Wp, void* pred, int Hg, int Wg, const void* gt, int f64, int finite_only, void* diff, double* out,
-                    void* ws, hipStream_t s);
-
-// ---- DSM raster (dsm_raster.hip, include/eogs_dsm.h) ----
-struct DsmRasterWS {
-  long long* sums;              // [ph][pw] fixed-point sums of the home cells, the grid padded by `radius`
-  uint32_t* counts;             // [ph][pw] points per home cell; the top bit marks a poisoned cell
-  unsigned long long* skipped;  // points left out for a non-finite x or y
-  int pw, ph;
-  size_t bytes;                 // a multiple of 256: the clear pass zeroes all of it
-};
-DsmRasterWS dsm_raster_layout(char* base, int xsize, int ysize, int radius);
-size_t dsm_bounds_ws_bytes();
-void launch_dsm_bounds(const eogs_dsm_source& src, eogs_dsm_bounds_result* result, void* ws, hipStream_t s);
-void launch_dsm_raster(const eogs_dsm_source& src, double xoff, double yoff, double res, int xsize, int ysize, int radius,
-                       const DsmRasterWS& w, float* out, int32_t* count, int64_t* skipped, hipStream_t s);
-
-// ---- 3-nearest-neighbour statistic (knn.hip, include/eogs_knn.h) ----
-struct KnnWS {
-  uint32_t *keyA, *keyB, *valA, *valB, *hist, *dtotal;  // Morton sort ping-pong + radix histograms
-  float4* sorted;                                       // points in Morton order
-  float* boxes;                                         // (nbox + 1) x {lo[3], hi[3]}; the last one is the scene box
-  uint32_t nblk, nbox;
-  size_t bytes;
-};
-KnnWS knn_layout(char* base, int P);
-void launch_knn(const KnnWS& w, int P, const float* pts, float* out, hipStream_t s);
 // `passes` stable 8-bit LSD passes over 32-bit keys with a 32-bit payload, ping-ponging A -> B -> A ... (binning.hip)
 void launch_sort_u32(uint32_t* keyA, uint32_t* valA, uint32_t* keyB, uint32_t* valB, uint32_t n, int passes, uint32_t* hist,
                      uint32_t nblk, uint32_t* dtotal, hipStream_t s);

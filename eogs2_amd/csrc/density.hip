@@ -8,7 +8,7 @@
 //                  clones, kept samples per copy) is one contiguous run in every tensor — the shape of compact_apply_kernel
 // No atomics anywhere: ranks come from ballots, offsets from the scan. The build (-ffp-contract=off) keeps every product
 // and sum of the 3 x 3 rotation rounded on its own, as the reference's elementwise build_rotation does.
-#include "common.h"
+#include "api_util.h"
 
 namespace {
 
@@ -231,15 +231,12 @@ __global__ __launch_bounds__(BLK) void density_split_rows_kernel(int64_t P, cons
 
 }  // namespace
 
-void launch_density_stats(int64_t P, const float* vg, const void* radii, int radii_is_float, float* accum, float* denom,
-                          float* maxr, hipStream_t s) {
-  if (P <= 0) return;
-  const unsigned blocks = (unsigned)((P + BLK - 1) / BLK);
-  if (radii_is_float) hipLaunchKernelGGL(density_stats_kernel<true>, dim3(blocks), dim3(BLK), 0, s, P, vg, radii, accum, denom, maxr);
-  else hipLaunchKernelGGL(density_stats_kernel<false>, dim3(blocks), dim3(BLK), 0, s, P, vg, radii, accum, denom, maxr);
-}
-
-DensityWS density_layout(char* base, int64_t P) {
+struct DensityWS {
+  uint32_t* cnt;  // [nblk + 1][4] rows of the four kinds per 256-row workgroup -> exclusive prefixes, totals at [nblk]
+  uint32_t nblk;
+  size_t bytes;
+};
+static DensityWS density_layout(char* base, int64_t P) {
   DensityWS w;
   w.nblk = (uint32_t)((P + DROWS - 1) / DROWS);
   w.cnt = reinterpret_cast<uint32_t*>(base);
@@ -247,16 +244,7 @@ DensityWS density_layout(char* base, int64_t P) {
   return w;
 }
 
-void launch_density_decide(const DensityWS& w, int64_t P, const float* accum, const float* denom, const float* opacity,
-                           const float* scaling, float thr_grad, float thr_dense, float min_opacity, int use_screen, float thr_big,
-                           float split_div, uint8_t* flags, hipStream_t s) {
-  if (w.nblk)
-    hipLaunchKernelGGL(density_decide_kernel, dim3(w.nblk), dim3(BLK), 0, s, P, accum, denom, opacity, scaling, thr_grad, thr_dense,
-                       min_opacity, use_screen, thr_big, split_div, flags, w.cnt);
-  hipLaunchKernelGGL(density_scan_kernel, dim3(4), dim3(BLK), 0, s, w.cnt, w.nblk);
-}
-
-void launch_density_build(const DensityWS& w, int64_t P, int N, const uint8_t* flags, const int64_t* counts, int n_tensors,
+static void launch_density_build(const DensityWS& w, int64_t P, int N, const uint8_t* flags, const int64_t* counts, int n_tensors,
                           const eogs_density_tensor* tensors, const float* rotation, const float* samples, float split_div,
                           hipStream_t s) {
   if (!w.nblk) return;
@@ -278,9 +266,116 @@ void launch_density_build(const DensityWS& w, int64_t P, int N, const uint8_t* f
   }
 }
 
-void launch_density_split_rows(const DensityWS& w, int64_t P, const uint8_t* flags, const void* src, void* dst, int row_bytes,
-                               hipStream_t s) {
-  if (!w.nblk || row_bytes == 0) return;
-  hipLaunchKernelGGL(density_split_rows_kernel, dim3(w.nblk), dim3(BLK), 0, s, P, flags, w.cnt, static_cast<const uint32_t*>(src),
-                     static_cast<uint32_t*>(dst), (uint32_t)(row_bytes / 4));
+static int density_check(const char* who, int64_t P, const void* flags, const void* ws, size_t ws_bytes, DensityWS* w) {
+  if (P < 0 || P > EOGS_DENSITY_MAX_ROWS) return fail(EOGS_ERR_INVALID_ARG, "%s: bad row count", who);
+  if ((P > 0 && !flags) || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  char* base = ws_base(const_cast<void*>(ws));
+  *w = density_layout(base, P);
+  if ((size_t)(base - (const char*)ws) + w->bytes - 256 > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  return EOGS_OK;
 }
+
+extern "C" {
+
+int eogs_density_stats_update(int64_t P, const float* viewspace_grad, const void* radii, int radii_is_float,
+                              float* xyz_gradient_accum, float* denom, float* max_radii2D, void* stream) {
+  clear_error();
+  if (P < 0 || P > EOGS_DENSITY_MAX_ROWS) return fail(EOGS_ERR_INVALID_ARG, "density_stats_update: bad row count");
+  if (P > 0 && (!viewspace_grad || !radii || !xyz_gradient_accum || !denom || !max_radii2D))
+    return fail(EOGS_ERR_INVALID_ARG, "density_stats_update: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned blocks = (unsigned)((P + BLK - 1) / BLK);
+  if (P > 0 && radii_is_float)
+    hipLaunchKernelGGL(density_stats_kernel<true>, dim3(blocks), dim3(BLK), 0, s, P, viewspace_grad, radii, xyz_gradient_accum, denom,
+                       max_radii2D);
+  else if (P > 0)
+    hipLaunchKernelGGL(density_stats_kernel<false>, dim3(blocks), dim3(BLK), 0, s, P, viewspace_grad, radii, xyz_gradient_accum, denom,
+                       max_radii2D);
+  LAUNCH_TRY(s, false, "density_stats_update");
+  return EOGS_OK;
+}
+
+int eogs_density_bytes(int64_t P, size_t* bytes) {
+  clear_error();
+  if (P < 0 || P > EOGS_DENSITY_MAX_ROWS || !bytes) return fail(EOGS_ERR_INVALID_ARG, "density_bytes: bad argument");
+  *bytes = density_layout(nullptr, P).bytes;
+  return EOGS_OK;
+}
+
+int eogs_density_decide(int64_t P, const float* xyz_gradient_accum, const float* denom, const float* opacity,
+                        const float* scaling, float grad_threshold, float dense_threshold, float min_opacity, int use_screen,
+                        float big_threshold, float split_div, uint8_t* flags, void* ws, size_t ws_bytes, int64_t* counts,
+                        void* stream) {
+  clear_error();
+  DensityWS w;
+  const int rc = density_check("density_decide", P, flags, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (!counts) return fail(EOGS_ERR_INVALID_ARG, "density_decide: NULL counts");
+  if (P > 0 && (!xyz_gradient_accum || !denom || !opacity || !scaling)) return fail(EOGS_ERR_INVALID_ARG, "density_decide: NULL argument");
+  if (!(split_div > 0.f)) return fail(EOGS_ERR_INVALID_ARG, "density_decide: split_div must be positive");
+  hipStream_t s = (hipStream_t)stream;
+  if (w.nblk)
+    hipLaunchKernelGGL(density_decide_kernel, dim3(w.nblk), dim3(BLK), 0, s, P, xyz_gradient_accum, denom, opacity, scaling,
+                       grad_threshold, dense_threshold, min_opacity, use_screen, big_threshold, split_div, flags, w.cnt);
+  hipLaunchKernelGGL(density_scan_kernel, dim3(4), dim3(BLK), 0, s, w.cnt, w.nblk);
+  LAUNCH_TRY(s, false, "density_decide");
+  uint32_t total[4] = {0, 0, 0, 0};
+  HIP_TRY(hipMemcpyAsync(total, w.cnt + 4 * (size_t)w.nblk, sizeof total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  for (int k = 0; k < 4; k++) counts[k] = (int64_t)total[k];
+  return EOGS_OK;
+}
+
+int eogs_density_split_rows(int64_t P, const uint8_t* flags, const void* src, void* dst, int row_bytes, const void* ws,
+                            size_t ws_bytes, void* stream) {
+  clear_error();
+  DensityWS w;
+  const int rc = density_check("density_split_rows", P, flags, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (row_bytes < 0 || row_bytes > 256 || (row_bytes & 3))
+    return fail(EOGS_ERR_INVALID_ARG, "density_split_rows: row sizes must be multiples of 4 up to 256 bytes");
+  if (row_bytes > 0 && P > 0 && (!src || !dst)) return fail(EOGS_ERR_INVALID_ARG, "density_split_rows: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  if (w.nblk && row_bytes != 0)
+    hipLaunchKernelGGL(density_split_rows_kernel, dim3(w.nblk), dim3(BLK), 0, s, P, flags, w.cnt, static_cast<const uint32_t*>(src),
+                       static_cast<uint32_t*>(dst), (uint32_t)(row_bytes / 4));
+  LAUNCH_TRY(s, false, "density_split_rows");
+  return EOGS_OK;
+}
+
+int eogs_density_build(int64_t P, int N, const uint8_t* flags, const int64_t* counts, int n_tensors,
+                       const eogs_density_tensor* tensors, const float* rotation, const float* samples, float split_div,
+                       const void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  DensityWS w;
+  const int rc = density_check("density_build", P, flags, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (N < 1 || N > EOGS_DENSITY_MAX_N) return fail(EOGS_ERR_INVALID_ARG, "density_build: N out of range");
+  if (!counts) return fail(EOGS_ERR_INVALID_ARG, "density_build: NULL counts");
+  for (int k = 0; k < 4; k++)
+    if (counts[k] < 0 || counts[k] > P) return fail(EOGS_ERR_INVALID_ARG, "density_build: counts are not those of density_decide on these rows");
+  if (counts[EOGS_DENSITY_N_KEPT_SPLIT] > counts[EOGS_DENSITY_N_SPLIT] || counts[EOGS_DENSITY_N_KEPT] + counts[EOGS_DENSITY_N_SPLIT] > P)
+    return fail(EOGS_ERR_INVALID_ARG, "density_build: counts are not those of density_decide on these rows");
+  if (n_tensors < 0 || (n_tensors > 0 && !tensors)) return fail(EOGS_ERR_INVALID_ARG, "density_build: bad tensor list");
+  if (!(split_div > 0.f)) return fail(EOGS_ERR_INVALID_ARG, "density_build: split_div must be positive");
+  const int64_t n_out = counts[0] + counts[1] + (int64_t)N * counts[3];
+  bool computed = false;
+  for (int t = 0; t < n_tensors; t++) {
+    const eogs_density_tensor& T = tensors[t];
+    if (T.row_bytes < 0 || T.row_bytes > 256 || (T.row_bytes & 3))
+      return fail(EOGS_ERR_INVALID_ARG, "density_build: row sizes must be multiples of 4 up to 256 bytes");
+    if (T.kind < EOGS_DENSITY_COPY || T.kind > EOGS_DENSITY_SCALING) return fail(EOGS_ERR_INVALID_ARG, "density_build: unknown tensor kind");
+    if ((T.kind == EOGS_DENSITY_XYZ || T.kind == EOGS_DENSITY_SCALING) && T.row_bytes != 12)
+      return fail(EOGS_ERR_INVALID_ARG, "density_build: xyz and scaling rows hold three floats");
+    if (T.row_bytes > 0 && ((P > 0 && !T.src) || (n_out > 0 && !T.dst))) return fail(EOGS_ERR_INVALID_ARG, "density_build: NULL tensor pointer");
+    computed = computed || T.kind == EOGS_DENSITY_XYZ;
+  }
+  if (computed && counts[EOGS_DENSITY_N_KEPT_SPLIT] > 0 && (!rotation || !samples))
+    return fail(EOGS_ERR_INVALID_ARG, "density_build: split rows need rotation and samples (NULL argument)");
+  hipStream_t s = (hipStream_t)stream;
+  launch_density_build(w, P, N, flags, counts, n_tensors, tensors, rotation, samples, split_div, s);
+  LAUNCH_TRY(s, false, "density_build");
+  return EOGS_OK;
+}
+
+}  // extern "C"

@@ -8,7 +8,13 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "common.h"
+#include "api_util.h"
+
+#define DSM_TILE_W 64      // pixels of the reference image per tile of the NCC search
+#define DSM_TILE_H 16
+#define DSM_MOMENTS 6      // count, sum u', sum v', sum u'^2, sum v'^2, sum u'v' per shift
+#define DSM_MAX_GRID 1024  // workgroups of the search and of the reductions (4 per CU): a function of the shape alone
+#define DSM_MAX_LEVELS 32
 
 namespace {
 
@@ -365,14 +371,19 @@ unsigned blocks_for(int64_t n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
-void launch_dsm_downsample(int H, int W, const void* in, int f64, double* out, hipStream_t s) {
+static void launch_dsm_downsample(int H, int W, const void* in, int f64, double* out, hipStream_t s) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const unsigned g = blocks_for((int64_t)Ho * Wo);
   if (f64) hipLaunchKernelGGL(dsm_downsample_kernel<double>, dim3(g), dim3(256), 0, s, H, W, (const double*)in, Ho, Wo, out);
   else hipLaunchKernelGGL(dsm_downsample_kernel<float>, dim3(g), dim3(256), 0, s, H, W, (const float*)in, Ho, Wo, out);
 }
 
-DsmNccWS dsm_ncc_layout(char* base, int Hu, int Wu, int irange) {
+struct DsmNccWS {
+  double *pivots, *moments, *partials;  // [2], [n*n][6], [n*n][6][P]
+  int tiles_x, num_tiles, grid, P;
+  size_t bytes;
+};
+static DsmNccWS dsm_ncc_layout(char* base, int Hu, int Wu, int irange) {
   DsmNccWS ws;
   const int n = 2 * irange + 1;
   ws.tiles_x = (Wu + kTW - 1) / kTW;
@@ -387,33 +398,65 @@ DsmNccWS dsm_ncc_layout(char* base, int Hu, int Wu, int irange) {
   return ws;
 }
 
-void launch_dsm_pivots(int64_t nu, const void* u, int64_t nv, const void* v, int f64, double* pivots, hipStream_t s) {
-  if (f64) hipLaunchKernelGGL(dsm_pivot_kernel<double>, dim3(2), dim3(256), 0, s, nu, (const double*)u, nv, (const double*)v, pivots);
-  else hipLaunchKernelGGL(dsm_pivot_kernel<float>, dim3(2), dim3(256), 0, s, nu, (const float*)u, nv, (const float*)v, pivots);
+static int dsm_check_pair(const char* what, int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int irange) {
+  if (Hu <= 0 || Wu <= 0 || Hv <= 0 || Wv <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", what);
+  if (Hv < Hu || Wv < Wu) return fail(EOGS_ERR_INVALID_ARG, "%s: the image to register is smaller than the reference image", what);
+  if ((uint64_t)Hv * Wv > ((uint64_t)1 << 31)) return fail(EOGS_ERR_OVERFLOW, "%s: image too large", what);
+  if (irange < 0 || irange > EOGS_TSDF_DSM_MAX_IRANGE) return fail(EOGS_ERR_INVALID_ARG, "%s: irange outside 0 .. 8", what);
+  if (!u || !v) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", what);
+  return EOGS_OK;
 }
 
-void launch_dsm_moments(int Hu, int Wu, const void* u, int Wv, const void* v, int f64, int irange, const int* centre,
-                        int centre_scale, const DsmNccWS& ws, hipStream_t s) {
-  if (f64)
-    hipLaunchKernelGGL(dsm_moments_kernel<double>, dim3(ws.grid), dim3(256), 0, s, Hu, Wu, (const double*)u, Wv, (const double*)v, irange,
-                       centre, centre_scale, ws.pivots, ws.tiles_x, ws.num_tiles, ws.partials, ws.P);
-  else
-    hipLaunchKernelGGL(dsm_moments_kernel<float>, dim3(ws.grid), dim3(256), 0, s, Hu, Wu, (const float*)u, Wv, (const float*)v, irange,
-                       centre, centre_scale, ws.pivots, ws.tiles_x, ws.num_tiles, ws.partials, ws.P);
+// one level: pivots, the moments of every shift, their sum, the NCC table and its winner
+static void dsm_search(int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int f64, int irange, const int32_t* centre,
+                       int centre_scale, double* table, eogs_tsdf_dsm_result* result, const DsmNccWS& w, hipStream_t s) {
+  const int64_t nu = (int64_t)Hu * Wu, nv = (int64_t)Hv * Wv;
+  {
+    ProfScope ps(PS_DSM_PIVOTS, s);
+    if (f64) hipLaunchKernelGGL(dsm_pivot_kernel<double>, dim3(2), dim3(256), 0, s, nu, (const double*)u, nv, (const double*)v, w.pivots);
+    else hipLaunchKernelGGL(dsm_pivot_kernel<float>, dim3(2), dim3(256), 0, s, nu, (const float*)u, nv, (const float*)v, w.pivots);
+  }
+  {
+    ProfScope ps(PS_DSM_MOMENTS, s);
+    if (f64)
+      hipLaunchKernelGGL(dsm_moments_kernel<double>, dim3(w.grid), dim3(256), 0, s, Hu, Wu, (const double*)u, Wv, (const double*)v, irange,
+                         centre, centre_scale, w.pivots, w.tiles_x, w.num_tiles, w.partials, w.P);
+    else
+      hipLaunchKernelGGL(dsm_moments_kernel<float>, dim3(w.grid), dim3(256), 0, s, Hu, Wu, (const float*)u, Wv, (const float*)v, irange,
+                         centre, centre_scale, w.pivots, w.tiles_x, w.num_tiles, w.partials, w.P);
+  }
+  {
+    ProfScope ps(PS_DSM_FINALIZE, s);
+    const int n = 2 * irange + 1;
+    hipLaunchKernelGGL(dsm_reduce_kernel, dim3(n * n), dim3(256), 0, s, w.partials, w.P, w.moments);
+    hipLaunchKernelGGL(dsm_argmax_kernel, dim3(1), dim3(256), 0, s, irange, w.moments, w.pivots, centre, centre_scale, table, result);
+  }
 }
 
-void launch_dsm_finalize(int irange, const int* centre, int centre_scale, const DsmNccWS& ws, double* table,
-                         eogs_tsdf_dsm_result* result, hipStream_t s) {
-  const int n = 2 * irange + 1;
-  hipLaunchKernelGGL(dsm_reduce_kernel, dim3(n * n), dim3(256), 0, s, ws.partials, ws.P, ws.moments);
-  hipLaunchKernelGGL(dsm_argmax_kernel, dim3(1), dim3(256), 0, s, irange, ws.moments, ws.pivots, centre, centre_scale, table, result);
-}
-
-void launch_dsm_apply_shift(int H, int W, const void* in, int f64, int dx, int dy, double a, double b, double c, double d, void* out,
-                            hipStream_t s) {
-  const unsigned g = blocks_for((int64_t)H * W);
-  if (f64) hipLaunchKernelGGL(dsm_apply_shift_kernel<double>, dim3(g), dim3(256), 0, s, H, W, (const double*)in, dx, dy, a, b, c, d, (double*)out);
-  else hipLaunchKernelGGL(dsm_apply_shift_kernel<float>, dim3(g), dim3(256), 0, s, H, W, (const float*)in, dx, dy, a, b, c, d, (float*)out);
+struct DsmShiftWS {
+  int levels;
+  int hu[DSM_MAX_LEVELS], wu[DSM_MAX_LEVELS], hv[DSM_MAX_LEVELS], wv[DSM_MAX_LEVELS];
+  double *pu[DSM_MAX_LEVELS], *pv[DSM_MAX_LEVELS];  // float64 pyramid levels 1 .. levels-1 ([0] is the caller's image)
+  char* ncc;
+  size_t bytes;
+};
+static DsmShiftWS dsm_shift_layout(char* base, int Hu, int Wu, int Hv, int Wv, int irange) {
+  DsmShiftWS w;
+  w.levels = 1;
+  w.hu[0] = Hu; w.wu[0] = Wu; w.hv[0] = Hv; w.wv[0] = Wv;
+  w.pu[0] = w.pv[0] = nullptr;
+  size_t off = 0;
+  while ((Hu < Wu ? Hu : Wu) > 100 && w.levels < DSM_MAX_LEVELS) {  // dsmr.py:168
+    Hu = (Hu + 1) / 2; Wu = (Wu + 1) / 2; Hv = (Hv + 1) / 2; Wv = (Wv + 1) / 2;
+    const int k = w.levels++;
+    w.hu[k] = Hu; w.wu[k] = Wu; w.hv[k] = Hv; w.wv[k] = Wv;
+    off = ws_carve(base, off, w.pu[k], (size_t)Hu * Wu);
+    off = ws_carve(base, off, w.pv[k], (size_t)Hv * Wv);
+  }
+  off = ws_align(off);
+  w.ncc = base ? base + off : nullptr;
+  w.bytes = off + dsm_ncc_layout(nullptr, w.hu[0], w.wu[0], irange).bytes + 256;
+  return w;
 }
 
 static unsigned reduce_blocks(int64_t n) {
@@ -421,23 +464,134 @@ static unsigned reduce_blocks(int64_t n) {
   return (unsigned)(b < DSM_MAX_GRID ? b : DSM_MAX_GRID);
 }
 
-size_t dsm_mae_ws_bytes() { return (size_t)DSM_MAX_GRID * 3 * sizeof(double) + 256; }
+static size_t dsm_mae_ws_bytes() { return (size_t)DSM_MAX_GRID * 3 * sizeof(double) + 256; }
 
-void launch_dsm_mae(int Hp, int Wp, void* pred, int Hg, int Wg, const void* gt, int f64, int finite_only, void* diff, double* out,
-                    void* ws, hipStream_t s) {
+extern "C" {
+
+int eogs_tsdf_dsm_downsample(int H, int W, const void* in, int f64, double* out, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "dsm_downsample: bad sizes");
+  if ((uint64_t)H * W > ((uint64_t)1 << 31)) return fail(EOGS_ERR_OVERFLOW, "dsm_downsample: image too large");
+  if (!in || !out) return fail(EOGS_ERR_INVALID_ARG, "dsm_downsample: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_DSM_DOWNSAMPLE, s); launch_dsm_downsample(H, W, in, f64, out, s); }
+  LAUNCH_TRY(s, false, "dsm_downsample");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_ncc_bytes(int Hu, int Wu, int irange, size_t* bytes) {
+  clear_error();
+  if (Hu <= 0 || Wu <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_ncc_bytes: bad argument");
+  if (irange < 0 || irange > EOGS_TSDF_DSM_MAX_IRANGE) return fail(EOGS_ERR_INVALID_ARG, "dsm_ncc_bytes: irange outside 0 .. 8");
+  *bytes = dsm_ncc_layout(nullptr, Hu, Wu, irange).bytes;
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_ncc(int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int f64, int irange, const int32_t* centre,
+                      int centre_scale, double* table, eogs_tsdf_dsm_result* result, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const int rc = dsm_check_pair("dsm_ncc", Hu, Wu, u, Hv, Wv, v, irange);
+  if (rc != EOGS_OK) return rc;
+  if (!result || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_ncc: NULL argument");
+  if (ws_bytes < dsm_ncc_layout(nullptr, Hu, Wu, irange).bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_ncc: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  dsm_search(Hu, Wu, u, Hv, Wv, v, f64, irange, centre, centre_scale, table, result, dsm_ncc_layout(ws_base(ws), Hu, Wu, irange), s);
+  LAUNCH_TRY(s, false, "dsm_ncc");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_shift_bytes(int Hu, int Wu, int Hv, int Wv, int irange, size_t* bytes, int* levels) {
+  clear_error();
+  if (Hu <= 0 || Wu <= 0 || Hv < Hu || Wv < Wu || !bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_shift_bytes: bad argument");
+  if (irange < 0 || irange > EOGS_TSDF_DSM_MAX_IRANGE) return fail(EOGS_ERR_INVALID_ARG, "dsm_shift_bytes: irange outside 0 .. 8");
+  const DsmShiftWS w = dsm_shift_layout(nullptr, Hu, Wu, Hv, Wv, irange);
+  *bytes = w.bytes;
+  if (levels) *levels = w.levels;
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_shift(int Hu, int Wu, const void* u, int Hv, int Wv, const void* v, int f64, int irange, double* tables,
+                        eogs_tsdf_dsm_result* results, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const int rc = dsm_check_pair("dsm_shift", Hu, Wu, u, Hv, Wv, v, irange);
+  if (rc != EOGS_OK) return rc;
+  if (!results || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_shift: NULL argument");
+  const DsmShiftWS w = dsm_shift_layout(ws_base(ws), Hu, Wu, Hv, Wv, irange);
+  if (ws_bytes < w.bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_shift: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int n = 2 * irange + 1;
+  {
+    ProfScope ps(PS_DSM_DOWNSAMPLE, s);
+    for (int k = 1; k < w.levels; k++) {
+      const int src64 = k == 1 ? f64 : 1;
+      launch_dsm_downsample(w.hu[k - 1], w.wu[k - 1], k == 1 ? u : (const void*)w.pu[k - 1], src64, w.pu[k], s);
+      launch_dsm_downsample(w.hv[k - 1], w.wv[k - 1], k == 1 ? v : (const void*)w.pv[k - 1], src64, w.pv[k], s);
+    }
+  }
+  for (int k = w.levels - 1; k >= 0; k--) {
+    // recursive_ncc halves (0, 0) on its way down (dx // 2, dsmr.py:171-172): the coarsest level searches around (0, 0)
+    const int32_t* centre = k == w.levels - 1 ? nullptr : &results[k + 1].dx;
+    dsm_search(w.hu[k], w.wu[k], k == 0 ? u : (const void*)w.pu[k], w.hv[k], w.wv[k], k == 0 ? v : (const void*)w.pv[k],
+               k == 0 ? f64 : 1, irange, centre, 2, tables ? tables + (size_t)k * n * n : nullptr, results + k,
+               dsm_ncc_layout(w.ncc, w.hu[k], w.wu[k], irange), s);
+  }
+  LAUNCH_TRY(s, false, "dsm_shift");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_apply_shift(int H, int W, const void* in, int f64, int dx, int dy, double a, double b, double c, double d,
+                              void* out, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "dsm_apply_shift: bad sizes");
+  if ((uint64_t)H * W > ((uint64_t)1 << 31)) return fail(EOGS_ERR_OVERFLOW, "dsm_apply_shift: image too large");
+  if (!in || !out || in == out) return fail(EOGS_ERR_INVALID_ARG, "dsm_apply_shift: NULL or aliased argument");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned g = blocks_for((int64_t)H * W);
+  {
+    ProfScope ps(PS_DSM_APPLY, s);
+    if (f64) hipLaunchKernelGGL(dsm_apply_shift_kernel<double>, dim3(g), dim3(256), 0, s, H, W, (const double*)in, dx, dy, a, b, c, d, (double*)out);
+    else hipLaunchKernelGGL(dsm_apply_shift_kernel<float>, dim3(g), dim3(256), 0, s, H, W, (const float*)in, dx, dy, a, b, c, d, (float*)out);
+  }
+  LAUNCH_TRY(s, false, "dsm_apply_shift");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_mae_bytes(size_t* bytes) {
+  clear_error();
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_mae_bytes: NULL argument");
+  *bytes = dsm_mae_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_tsdf_dsm_mae(int Hp, int Wp, void* pred, int Hg, int Wg, const void* gt, int f64, int clip_finite, void* diff, double* out,
+                      void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (Hp <= 0 || Wp <= 0 || Hg <= 0 || Wg <= 0) return fail(EOGS_ERR_INVALID_ARG, "dsm_mae: bad sizes");
+  if ((uint64_t)Hp * Wp > ((uint64_t)1 << 31) || (uint64_t)Hg * Wg > ((uint64_t)1 << 31))
+    return fail(EOGS_ERR_OVERFLOW, "dsm_mae: image too large");
+  if (!pred || !gt || !diff || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_mae: NULL argument");
+  if (ws_bytes < dsm_mae_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "dsm_mae: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   double* part = (double*)ws_base(ws);
   const int h = Hp < Hg ? Hp : Hg, w = Wp < Wg ? Wp : Wg;
   const unsigned gb = reduce_blocks((int64_t)Hg * Wg), pb = reduce_blocks((int64_t)Hp * Wp);
-  if (f64) {
-    hipLaunchKernelGGL(dsm_minmax_kernel<double>, dim3(gb), dim3(256), 0, s, (int64_t)Hg * Wg, (const double*)gt, part);
-    hipLaunchKernelGGL(dsm_bounds_kernel<double>, dim3(1), dim3(256), 0, s, (int)gb, part, finite_only, out);
-    hipLaunchKernelGGL(dsm_mae_kernel<double>, dim3(pb), dim3(256), 0, s, Hp, Wp, (double*)pred, Wg, (const double*)gt, h, w, out,
-                       (double*)diff, part);
-  } else {
-    hipLaunchKernelGGL(dsm_minmax_kernel<float>, dim3(gb), dim3(256), 0, s, (int64_t)Hg * Wg, (const float*)gt, part);
-    hipLaunchKernelGGL(dsm_bounds_kernel<float>, dim3(1), dim3(256), 0, s, (int)gb, part, finite_only, out);
-    hipLaunchKernelGGL(dsm_mae_kernel<float>, dim3(pb), dim3(256), 0, s, Hp, Wp, (float*)pred, Wg, (const float*)gt, h, w, out,
-                       (float*)diff, part);
+  {
+    ProfScope ps(PS_DSM_MAE, s);
+    if (f64) {
+      hipLaunchKernelGGL(dsm_minmax_kernel<double>, dim3(gb), dim3(256), 0, s, (int64_t)Hg * Wg, (const double*)gt, part);
+      hipLaunchKernelGGL(dsm_bounds_kernel<double>, dim3(1), dim3(256), 0, s, (int)gb, part, clip_finite, out);
+      hipLaunchKernelGGL(dsm_mae_kernel<double>, dim3(pb), dim3(256), 0, s, Hp, Wp, (double*)pred, Wg, (const double*)gt, h, w, out,
+                         (double*)diff, part);
+    } else {
+      hipLaunchKernelGGL(dsm_minmax_kernel<float>, dim3(gb), dim3(256), 0, s, (int64_t)Hg * Wg, (const float*)gt, part);
+      hipLaunchKernelGGL(dsm_bounds_kernel<float>, dim3(1), dim3(256), 0, s, (int)gb, part, clip_finite, out);
+      hipLaunchKernelGGL(dsm_mae_kernel<float>, dim3(pb), dim3(256), 0, s, Hp, Wp, (float*)pred, Wg, (const float*)gt, h, w, out,
+                         (float*)diff, part);
+    }
+    hipLaunchKernelGGL(dsm_mae_final_kernel, dim3(1), dim3(256), 0, s, (int)pb, part, out);
   }
-  hipLaunchKernelGGL(dsm_mae_final_kernel, dim3(1), dim3(256), 0, s, (int)pb, part, out);
+  LAUNCH_TRY(s, false, "dsm_mae");
+  return EOGS_OK;
 }
+
+}  // extern "C"

@@ -13,7 +13,8 @@
 // (2 radius + 1)^2 neighbourhood of each output cell and divides once, in double.
 #include <math.h>
 
-#include "common.h"
+#include "api_util.h"
+#include "reduce.h"
 
 namespace {
 
@@ -60,29 +61,13 @@ __device__ inline void load_point(const eogs_dsm_source& s, int64_t idx, double&
 
 __device__ inline bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN and +-inf
 
-__device__ inline double wave_min_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ inline double wave_max_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ inline int64_t wave_sum_i64(int64_t v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // The workgroup's result on thread 0. Only finite values enter the minima and maxima, so fmin / fmax never see a NaN.
 __device__ inline DsmPartial wg_reduce(DsmPartial p, DsmPartial* s_red) {
-  p.xmin = wave_min_d(p.xmin);
-  p.xmax = wave_max_d(p.xmax);
-  p.ymin = wave_min_d(p.ymin);
-  p.ymax = wave_max_d(p.ymax);
-  p.nonfinite = wave_sum_i64(p.nonfinite);
+  p.xmin = wave_min(p.xmin);
+  p.xmax = wave_max(p.xmax);
+  p.ymin = wave_min(p.ymin);
+  p.ymax = wave_max(p.ymax);
+  p.nonfinite = wave_sum(p.nonfinite);
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = p;
   __syncthreads();
   if (threadIdx.x == 0)
@@ -215,17 +200,16 @@ inline int blocks_for(int64_t n, int maxblk) {
 
 }  // namespace
 
-size_t dsm_bounds_ws_bytes() { return (size_t)DSM_BOUNDS_MAXBLK * sizeof(DsmPartial); }
+static size_t dsm_bounds_ws_bytes() { return (size_t)DSM_BOUNDS_MAXBLK * sizeof(DsmPartial); }
 
-void launch_dsm_bounds(const eogs_dsm_source& src, eogs_dsm_bounds_result* result, void* ws, hipStream_t s) {
-  const int64_t n = src_points(src);
-  const int nblk = blocks_for(n, DSM_BOUNDS_MAXBLK);
-  DsmPartial* partial = reinterpret_cast<DsmPartial*>(ws);
-  hipLaunchKernelGGL(dsm_bounds_kernel, dim3(nblk), dim3(DT), 0, s, src, n, partial);
-  hipLaunchKernelGGL(dsm_bounds_final_kernel, dim3(1), dim3(DT), 0, s, nblk, n, partial, result);
-}
-
-DsmRasterWS dsm_raster_layout(char* base, int xsize, int ysize, int radius) {
+struct DsmRasterWS {
+  long long* sums;              // [ph][pw] fixed-point sums of the home cells, the grid padded by `radius`
+  uint32_t* counts;             // [ph][pw] points per home cell; the top bit marks a poisoned cell
+  unsigned long long* skipped;  // points left out for a non-finite x or y
+  int pw, ph;
+  size_t bytes;                 // a multiple of 256: the clear pass zeroes all of it
+};
+static DsmRasterWS dsm_raster_layout(char* base, int xsize, int ysize, int radius) {
   DsmRasterWS w;
   w.pw = xsize + 2 * radius;
   w.ph = ysize + 2 * radius;
@@ -238,14 +222,92 @@ DsmRasterWS dsm_raster_layout(char* base, int xsize, int ysize, int radius) {
   return w;
 }
 
-void launch_dsm_raster(const eogs_dsm_source& src, double xoff, double yoff, double res, int xsize, int ysize, int radius,
-                       const DsmRasterWS& w, float* out, int32_t* count, int64_t* skipped, hipStream_t s) {
+static int dsm_source_check(const char* who, const eogs_dsm_source* src) {
+  if (!src) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL source", who);
+  if (src->kind == EOGS_DSM_SRC_CLOUD) {
+    if (src->N < 0) return fail(EOGS_ERR_INVALID_ARG, "%s: negative point count", who);
+    if (src->N > 0 && !src->cloud) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL cloud", who);
+    if ((uintptr_t)src->cloud & 7u) return fail(EOGS_ERR_INVALID_ARG, "%s: cloud not 8-byte aligned", who);
+    return EOGS_OK;
+  }
+  if (src->kind != EOGS_DSM_SRC_VIEW && src->kind != EOGS_DSM_SRC_GRID) return fail(EOGS_ERR_INVALID_ARG, "%s: unknown source kind", who);
+  if (src->H <= 0 || src->W <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad image size", who);
+  if (!src->altitude || !src->u_axis || !src->v_axis) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL image or axis", who);
+  if (src->kind == EOGS_DSM_SRC_VIEW) {
+    if (!src->affine) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL affine", who);
+    if (!(src->scale == src->scale)) return fail(EOGS_ERR_INVALID_ARG, "%s: scale is NaN", who);
+  }
+  return EOGS_OK;
+}
+
+static int dsm_grid_check(const char* who, int xsize, int ysize, int radius) {
+  if (radius < 0 || radius > EOGS_DSM_MAX_RADIUS) return fail(EOGS_ERR_INVALID_ARG, "%s: radius out of range", who);
+  if (xsize <= 0 || ysize <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: xsize and ysize must be positive", who);
+  if (((int64_t)xsize + 2 * radius) * ((int64_t)ysize + 2 * radius) >= ((int64_t)1 << 31))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: raster too large", who);
+  return EOGS_OK;
+}
+
+extern "C" {
+
+int eogs_dsm_bounds_bytes(size_t* bytes) {
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_bounds_bytes: NULL argument");
+  *bytes = 256 + dsm_bounds_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_dsm_bounds(const eogs_dsm_source* src, eogs_dsm_bounds_result* result, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const int rc = dsm_source_check("dsm_bounds", src);
+  if (rc != EOGS_OK) return rc;
+  if (!result || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_bounds: NULL argument");
+  if ((uintptr_t)result & 7u) return fail(EOGS_ERR_INVALID_ARG, "dsm_bounds: result not 8-byte aligned");
+  char* base = ws_base(ws);
+  if ((size_t)(base - (char*)ws) + dsm_bounds_ws_bytes() > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_bounds: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = src_points(*src);
+  const int nblk = blocks_for(n, DSM_BOUNDS_MAXBLK);
+  DsmPartial* partial = reinterpret_cast<DsmPartial*>(base);
+  hipLaunchKernelGGL(dsm_bounds_kernel, dim3(nblk), dim3(DT), 0, s, *src, n, partial);
+  hipLaunchKernelGGL(dsm_bounds_final_kernel, dim3(1), dim3(DT), 0, s, nblk, n, partial, result);
+  LAUNCH_TRY(s, false, "dsm_bounds");
+  return EOGS_OK;
+}
+
+int eogs_dsm_raster_bytes(int xsize, int ysize, int radius, size_t* bytes) {
+  const int rc = dsm_grid_check("dsm_raster_bytes", xsize, ysize, radius);
+  if (rc != EOGS_OK) return rc;
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster_bytes: NULL argument");
+  *bytes = 256 + dsm_raster_layout(nullptr, xsize, ysize, radius).bytes;
+  return EOGS_OK;
+}
+
+int eogs_dsm_raster(const eogs_dsm_source* src, double xoff, double yoff, double res, int xsize, int ysize, int radius,
+                    float* out, int32_t* count, int64_t* skipped, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  int rc = dsm_source_check("dsm_raster", src);
+  if (rc != EOGS_OK) return rc;
+  rc = dsm_grid_check("dsm_raster", xsize, ysize, radius);
+  if (rc != EOGS_OK) return rc;
+  const double big = 1.7976931348623157e308;
+  if (!(res > 0. && res <= big)) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: resolution must be positive and finite");
+  if (!(xoff >= -big && xoff <= big && yoff >= -big && yoff <= big)) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: xoff, yoff must be finite");
+  if (!out || !ws) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: NULL argument");
+  if ((uintptr_t)skipped & 7u) return fail(EOGS_ERR_INVALID_ARG, "dsm_raster: skipped not 8-byte aligned");
+  char* base = ws_base(ws);
+  const DsmRasterWS w = dsm_raster_layout(base, xsize, ysize, radius);
+  if ((size_t)(base - (char*)ws) + w.bytes > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "dsm_raster: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   const size_t n16 = w.bytes / 16;
   hipLaunchKernelGGL(dsm_clear_kernel, dim3(blocks_for((int64_t)n16, 1024)), dim3(DT), 0, s, n16, reinterpret_cast<uint4*>(w.sums));
-  const int64_t n = src_points(src);
+  const int64_t n = src_points(*src);
   if (n > 0)
-    hipLaunchKernelGGL(dsm_scatter_kernel, dim3(blocks_for(n, DSM_SCATTER_MAXBLK)), dim3(DT), 0, s, src, n, xoff, yoff, res, radius,
+    hipLaunchKernelGGL(dsm_scatter_kernel, dim3(blocks_for(n, DSM_SCATTER_MAXBLK)), dim3(DT), 0, s, *src, n, xoff, yoff, res, radius,
                        w.pw, w.ph, reinterpret_cast<unsigned long long*>(w.sums), w.counts, w.skipped);
   hipLaunchKernelGGL(dsm_stencil_kernel, dim3(blocks_for((int64_t)xsize * ysize, 4096)), dim3(DT), 0, s, xsize, ysize, radius, w.pw,
                      w.sums, w.counts, w.skipped, out, count, skipped);
+  LAUNCH_TRY(s, false, "dsm_raster");
+  return EOGS_OK;
 }
+
+}  // extern "C"

@@ -10,8 +10,9 @@
 // A one-element `gate` on the device switches the warp off (forward and backward become copies) without a host read.
 // All kernels are HBM-bound streams with neighbouring lanes on neighbouring addresses.
 #include "bucket_gather.h"
-#include "common.h"
+#include "api_util.h"
 #include "flow_taps.h"
+#include "reduce.h"
 
 namespace {
 
@@ -199,12 +200,6 @@ __global__ __launch_bounds__(BLK) void flow_bwd_cst_kernel(int C, int H, int W, 
 constexpr int ST_MAX_GRID = 256;
 constexpr int ST_N = 5;  // sum x', sum y', sum |x| + |y|, sum x'^2, sum y'^2
 
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(BLK) void flow_stats_partial_kernel(int H, int W, const FlowField fl, double* __restrict__ part) {
   __shared__ double s_red[BLK / 64][ST_N];
   const float2 piv = fl.at(0, 0);
@@ -254,30 +249,15 @@ inline int stats_grid(int H, int W) {
 
 }  // namespace
 
-size_t flow_stats_ws_bytes(int H, int W) { return (size_t)stats_grid(H, W) * ST_N * sizeof(double) + 256; }
-
-void launch_flow_stats(int H, int W, const float* flow, int64_t sc, int64_t sy, int64_t sx, float* stats, void* ws, hipStream_t s) {
-  const FlowField fl{flow, sc, sy, sx};
-  double* part = reinterpret_cast<double*>(ws_base(ws));
-  const int nb = stats_grid(H, W);
-  hipLaunchKernelGGL(flow_stats_partial_kernel, dim3(nb), dim3(BLK), 0, s, H, W, fl, part);
-  hipLaunchKernelGGL(flow_stats_final_kernel, dim3(1), dim3(64), 0, s, H, W, fl, (const double*)part, nb, stats);
-}
-
-void launch_flow_fwd(int C, int H, int W, const float* img, const float* flow, int64_t sc, int64_t sy, int64_t sx,
-                     const float* gate, float* out, hipStream_t s) {
-  const int HW = H * W;
-  hipLaunchKernelGGL(flow_fwd_kernel, dim3((HW + BLK - 1) / BLK), dim3(BLK), 0, s, C, H, W, img, FlowField{flow, sc, sy, sx}, gate,
-                     out);
-}
+static size_t flow_stats_ws_bytes(int H, int W) { return (size_t)stats_grid(H, W) * ST_N * sizeof(double) + 256; }
 
 // the field backward's workspace: one box per 16 x 16 output tile (a constant displacement needs none)
-size_t flow_bwd_ws_bytes(int H, int W) {
+static size_t flow_bwd_ws_bytes(int H, int W) {
   const size_t nt = (size_t)((W + OT - 1) / OT) * ((H + OT - 1) / OT);
   return (nt * sizeof(int4) + 255) / 256 * 256 + 256;
 }
 
-void launch_flow_bwd(int C, int H, int W, const float* flow, int64_t sc, int64_t sy, int64_t sx, const float* gate,
+static void launch_flow_bwd(int C, int H, int W, const float* flow, int64_t sc, int64_t sy, int64_t sx, const float* gate,
                      const float* g, float* gimg, void* ws, hipStream_t s) {
   if (sy == 0 && sx == 0) {
     hipLaunchKernelGGL(flow_bwd_cst_kernel, dim3((W + CTX - 1) / CTX, (H + CTY - 1) / CTY), dim3(BLK), 0, s, C, H, W, flow, sc,
@@ -299,3 +279,79 @@ void launch_flow_bwd(int C, int H, int W, const float* flow, int64_t sc, int64_t
                        g + c0 * HW, (const int4*)bbox, ntx, nty, gimg + c0 * HW);
   }
 }
+
+static int flow_check(const char* who, int C, int H, int W) {
+  if (C < 1 || H < 2 || W < 2 || (int64_t)H * W > 0x7FFFFFFF) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (C >= 1, H >= 2, W >= 2)", who);
+  return EOGS_OK;
+}
+
+extern "C" {
+
+int eogs_resample_flow_forward(int C, int H, int W, const float* img, const float* flow, int64_t plane_stride,
+                               int64_t row_stride, int64_t col_stride, const float* gate, float* out, void* stream) {
+  clear_error();
+  const int rc = flow_check("resample_flow_forward", C, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!img || !flow || !out) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_forward: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int HW = H * W;
+  {
+    ProfScope ps(PS_FLOW_FWD, s);
+    hipLaunchKernelGGL(flow_fwd_kernel, dim3((HW + BLK - 1) / BLK), dim3(BLK), 0, s, C, H, W, img,
+                       FlowField{flow, plane_stride, row_stride, col_stride}, gate, out);
+  }
+  LAUNCH_TRY(s, false, "flow_fwd");
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_bytes(int H, int W, size_t* bytes) {
+  clear_error();
+  if (H < 2 || W < 2 || (int64_t)H * W > 0x7FFFFFFF || !bytes) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_bytes: bad argument");
+  *bytes = flow_bwd_ws_bytes(H, W);
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_backward(int C, int H, int W, const float* flow, int64_t plane_stride, int64_t row_stride,
+                                int64_t col_stride, const float* gate, const float* dL_dout, float* dL_dimg, void* ws,
+                                size_t ws_bytes, void* stream) {
+  clear_error();
+  const int rc = flow_check("resample_flow_backward", C, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!flow || !dL_dout || !dL_dimg) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_backward: NULL argument");
+  const bool field = row_stride != 0 || col_stride != 0;
+  if (field && (!ws || ws_bytes < flow_bwd_ws_bytes(H, W)))
+    return fail(EOGS_ERR_WORKSPACE, "resample_flow_backward: workspace too small (a flow field needs eogs_resample_flow_bytes)");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_FLOW_BWD, s); launch_flow_bwd(C, H, W, flow, plane_stride, row_stride, col_stride, gate, dL_dout, dL_dimg, ws, s); }
+  LAUNCH_TRY(s, false, "flow_bwd");
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_stats_bytes(int H, int W, size_t* bytes) {
+  clear_error();
+  if (H < 2 || W < 2 || (int64_t)H * W > 0x7FFFFFFF || !bytes) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_stats_bytes: bad argument");
+  *bytes = flow_stats_ws_bytes(H, W);
+  return EOGS_OK;
+}
+
+int eogs_resample_flow_stats(int H, int W, const float* flow, int64_t plane_stride, int64_t row_stride, int64_t col_stride,
+                             float* stats, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const int rc = flow_check("resample_flow_stats", 1, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!flow || !stats || !ws) return fail(EOGS_ERR_INVALID_ARG, "resample_flow_stats: NULL argument");
+  if (ws_bytes < flow_stats_ws_bytes(H, W)) return fail(EOGS_ERR_WORKSPACE, "resample_flow_stats: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const FlowField fl{flow, plane_stride, row_stride, col_stride};
+  double* part = reinterpret_cast<double*>(ws_base(ws));
+  const int nb = stats_grid(H, W);
+  {
+    ProfScope ps(PS_FLOW_STATS, s);
+    hipLaunchKernelGGL(flow_stats_partial_kernel, dim3(nb), dim3(BLK), 0, s, H, W, fl, part);
+    hipLaunchKernelGGL(flow_stats_final_kernel, dim3(1), dim3(64), 0, s, H, W, fl, (const double*)part, nb, stats);
+  }
+  LAUNCH_TRY(s, false, "flow_stats");
+  return EOGS_OK;
+}
+
+}  // extern "C"

@@ -5,7 +5,8 @@
 // radix passes (binning.hip), points gathered into Morton order once so every later access is coalesced, boxes of 256
 // sorted points, one lane per point: +-3 Morton neighbours give the rejection radius, then every box nearer than it is
 // scanned. Neighbouring lanes are neighbouring points, so a wave scans nearly the same boxes.
-#include "common.h"
+#include "api_util.h"
+#include "reduce.h"
 
 namespace {
 
@@ -13,17 +14,6 @@ constexpr int KBOX = 256;       // sorted points per box (= one workgroup)
 constexpr float KNN_FAR = 1e37f;  // the reference's FLT_MAX (simple_knn.cu:27)
 
 struct Box { float lo[3], hi[3]; };
-
-__device__ inline float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // per-workgroup min/max of the rows [row0, row0+BLK) (given by index through `order` if non-NULL) -> out[blockIdx]
 __global__ __launch_bounds__(BLK) void knn_box_kernel(int P, const float* __restrict__ pts, const uint32_t* __restrict__ order,
@@ -165,7 +155,14 @@ __global__ __launch_bounds__(BLK) void knn_search_kernel(int P, const float4* __
 
 }  // namespace
 
-KnnWS knn_layout(char* base, int P) {
+struct KnnWS {
+  uint32_t *keyA, *keyB, *valA, *valB, *hist, *dtotal;  // Morton sort ping-pong + radix histograms
+  float4* sorted;                                       // points in Morton order
+  float* boxes;                                         // (nbox + 1) x {lo[3], hi[3]}; the last one is the scene box
+  uint32_t nblk, nbox;
+  size_t bytes;
+};
+static KnnWS knn_layout(char* base, int P) {
   KnnWS w;
   size_t n = (size_t)P, o = 0;
   w.nblk = ceil_div_u32(n, BLK * SORTP_ITEMS);
@@ -182,16 +179,39 @@ KnnWS knn_layout(char* base, int P) {
   return w;
 }
 
-void launch_knn(const KnnWS& w, int P, const float* pts, float* out, hipStream_t s) {
+extern "C" {
+
+int eogs_knn_bytes(int P, size_t* bytes) {
+  if (P < 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "knn_bytes: bad argument");
+  *bytes = knn_layout(nullptr, P).bytes;
+  return EOGS_OK;
+}
+
+int eogs_knn_mean_dist2(int P, const float* points, float* mean_dist2, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (P < 0) return fail(EOGS_ERR_INVALID_ARG, "knn_mean_dist2: bad size");
+  if (P == 0) return EOGS_OK;
+  if (!points || !mean_dist2 || !ws) return fail(EOGS_ERR_INVALID_ARG, "knn_mean_dist2: NULL argument");
+  char* base = ws_base(ws);
+  const KnnWS w = knn_layout(base, P);
+  if ((size_t)(base - (char*)ws) + w.bytes - 256 > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "knn_mean_dist2: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   const uint32_t nb = w.nbox;
   Box* boxes = reinterpret_cast<Box*>(w.boxes);
   Box* scene = boxes + nb;
-  // scene bounding box (unsorted boxes are only a stepping stone for the reduction)
-  hipLaunchKernelGGL(knn_box_kernel, dim3(nb), dim3(BLK), 0, s, P, pts, (const uint32_t*)nullptr, boxes);
-  hipLaunchKernelGGL(knn_scene_kernel, dim3(1), dim3(BLK), 0, s, boxes, (int)nb, scene);
-  hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(BLK), 0, s, P, pts, scene, w.keyA, w.valA);
-  launch_sort_u32(w.keyA, w.valA, w.keyB, w.valB, (uint32_t)P, 4, w.hist, w.nblk, w.dtotal, s);  // 4 passes: back in A
-  hipLaunchKernelGGL(knn_gather_kernel, dim3(nb), dim3(BLK), 0, s, P, pts, w.valA, w.sorted);
-  hipLaunchKernelGGL(knn_box_kernel, dim3(nb), dim3(BLK), 0, s, P, pts, w.valA, boxes);
-  hipLaunchKernelGGL(knn_search_kernel, dim3(nb), dim3(BLK), 0, s, P, w.sorted, w.valA, boxes, (int)nb, out);
+  {
+    ProfScope ps(PS_KNN, s);
+    // scene bounding box (unsorted boxes are only a stepping stone for the reduction)
+    hipLaunchKernelGGL(knn_box_kernel, dim3(nb), dim3(BLK), 0, s, P, points, (const uint32_t*)nullptr, boxes);
+    hipLaunchKernelGGL(knn_scene_kernel, dim3(1), dim3(BLK), 0, s, boxes, (int)nb, scene);
+    hipLaunchKernelGGL(knn_morton_kernel, dim3(nb), dim3(BLK), 0, s, P, points, scene, w.keyA, w.valA);
+    launch_sort_u32(w.keyA, w.valA, w.keyB, w.valB, (uint32_t)P, 4, w.hist, w.nblk, w.dtotal, s);  // 4 passes: back in A
+    hipLaunchKernelGGL(knn_gather_kernel, dim3(nb), dim3(BLK), 0, s, P, points, w.valA, w.sorted);
+    hipLaunchKernelGGL(knn_box_kernel, dim3(nb), dim3(BLK), 0, s, P, points, w.valA, boxes);
+    hipLaunchKernelGGL(knn_search_kernel, dim3(nb), dim3(BLK), 0, s, P, w.sorted, w.valA, boxes, (int)nb, mean_dist2);
+  }
+  LAUNCH_TRY(s, false, "knn");
+  return EOGS_OK;
 }
+
+}  // extern "C"

@@ -10,7 +10,8 @@
 //     dS_sum/dx(p) = W*Dm (p) + 2 x(p) W*D11 (p) + y(p) W*D12 (p)
 // HBM-bound by design: forward reads 8 and writes 12 B/pixel, backward reads 20 and writes 4 B/pixel.
 // Sums are reduced per workgroup, then in a fixed order by one small kernel: bitwise reproducible, no atomics.
-#include "common.h"
+#include "api_util.h"
+#include "reduce.h"
 
 // The library is built with -ffp-contract=off for the rasterizer's sake (its parity is against an fp32 restatement of the
 // reference's arithmetic). The loss has no such twin — its oracle is float64, its tolerance relative — and its window sums are
@@ -31,16 +32,6 @@ constexpr int RPT = LTY / 8;       // adjacent output rows per thread (32 x 8 th
 constexpr int HG = 4;              // adjacent output columns per thread in the horizontal pass
 static_assert(LTY % 8 == 0 && LT % HG == 0 && LH * (LT / HG) <= 256, "tile shape against 256 threads");
 constexpr int LTHREADS = 256;
-
-__device__ inline float block_sum(float v, float* s_red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[w] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 template <bool WITH_L1, bool WITH_SSIM>
@@ -182,8 +173,8 @@ __global__ __launch_bounds__(LTHREADS) void loss_fwd_kernel(int H, int W, const 
     }
   }
   const size_t blk = ((size_t)plane * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-  const float l1s = WITH_L1 ? block_sum(l1, s_red) : 0.f;
-  const float sss = WITH_SSIM ? block_sum(ss, s_red) : 0.f;
+  const float l1s = WITH_L1 ? wg_sum(l1, s_red) : 0.f;
+  const float sss = WITH_SSIM ? wg_sum(ss, s_red) : 0.f;
   if (t == 0) {
     partial[2 * blk] = l1s;
     partial[2 * blk + 1] = sss;
@@ -201,8 +192,8 @@ __global__ __launch_bounds__(LTHREADS) void loss_plane_reduce_kernel(const float
     a += partial[2 * ((size_t)plane * tiles + i)];
     b += partial[2 * ((size_t)plane * tiles + i) + 1];
   }
-  a = block_sum(a, s_red);
-  b = block_sum(b, s_red);
+  a = wg_sum(a, s_red);
+  b = wg_sum(b, s_red);
   if (threadIdx.x == 0) {
     plane_tmp[2 * plane] = a;
     plane_tmp[2 * plane + 1] = b;
@@ -342,12 +333,6 @@ __global__ __launch_bounds__(LTHREADS) void loss_bwd_kernel(int H, int W, const 
 
 }  // namespace
 
-// the output tile of one workgroup: what the grids below, the workspace layout and the API's size limits are counted in
-void loss_tile_shape(int* tile_h, int* tile_w) {
-  *tile_h = LTY;
-  *tile_w = LT;
-}
-
 LossWS loss_layout(char* base, int planes, int H, int W, unsigned mode) {
   LossWS w;
   const size_t tiles = (size_t)((W + LT - 1) / LT) * ((H + LTY - 1) / LTY);
@@ -366,7 +351,7 @@ LossWS loss_layout(char* base, int planes, int H, int W, unsigned mode) {
   return w;
 }
 
-LossWindow loss_window() {
+static LossWindow loss_window() {
   // gaussian(11, 1.5) (loss_utils.py:26-33): exp in double, stored as fp32, normalised by the fp32 sum. That sum is the
   // reference's `gauss.sum()`, which comes out as the exact sum rounded once (3.75923276); an fp32 running sum lands one
   // ulp below it (3.75923252) and made every tap 6e-8 too heavy: the window summed to 1 + 8.9e-8 where the reference's
@@ -404,14 +389,81 @@ void launch_loss_fwd(const LossWS& w, int planes, int H, int W, const float* img
                      w_ssim, bias, out, plane_sums);
 }
 
-void launch_loss_bwd(const LossWS& w, int planes, int H, int W, const float* img, const float* gt, unsigned mode,
-                     float w_l1, float w_ssim, const float* upstream, const float* plane_grad, float* dimg,
-                     hipStream_t s) {
+// launch_loss_fwd / the backward put the rows of tiles in gridDim.y and the planes in gridDim.z: 65535 each (the monitor's
+// standalone path launches the same forward and asks the same question)
+bool loss_grid_fits(int planes, int H) { return planes <= 65535 && (H - 1) / LTY + 1 <= 65535; }
+
+static int loss_check(const char* who, int planes, int H, int W, const void* img, const void* gt, unsigned mode,
+                      const void* ws, size_t ws_bytes, LossWS* out) {
+  if (planes <= 0 || H <= 0 || W <= 0 || !(mode & (EOGS_LOSS_L1 | EOGS_LOSS_SSIM)) ||
+      (mode & ~(EOGS_LOSS_L1 | EOGS_LOSS_SSIM)))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes or mode", who);
+  if (!loss_grid_fits(planes, H)) return fail(EOGS_ERR_INVALID_ARG, "%s: too many planes / rows for one launch", who);
+  if (!img || !gt || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  char* base = ws_base(const_cast<void*>(ws));
+  *out = loss_layout(base, planes, H, W, mode);
+  if ((size_t)(base - (const char*)ws) + out->bytes - 256 > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  return EOGS_OK;
+}
+
+extern "C" {
+
+int eogs_loss_bytes(int planes, int H, int W, unsigned mode, size_t* bytes) {
+  if (planes < 0 || H < 0 || W < 0 || !bytes || !(mode & (EOGS_LOSS_L1 | EOGS_LOSS_SSIM)))
+    return fail(EOGS_ERR_INVALID_ARG, "loss_bytes: bad argument");
+  *bytes = loss_layout(nullptr, planes, H, W, mode).bytes;
+  return EOGS_OK;
+}
+
+// the output tile of one workgroup: what the grids, the workspace layout and the size limits are counted in
+int eogs_loss_tile_shape(int* tile_h, int* tile_w) {
+  if (!tile_h || !tile_w) return fail(EOGS_ERR_INVALID_ARG, "loss_tile_shape: NULL argument");
+  *tile_h = LTY;
+  *tile_w = LT;
+  return EOGS_OK;
+}
+
+int eogs_loss_window(float* taps) {
+  if (!taps) return fail(EOGS_ERR_INVALID_ARG, "loss_window: NULL argument");
+  const LossWindow win = loss_window();
+  for (int i = 0; i < LOSS_WIN; i++) taps[i] = win.w[i];
+  return EOGS_OK;
+}
+
+int eogs_loss_forward(int planes, int H, int W, const float* img, const float* gt, unsigned mode, float w_l1,
+                      float w_ssim, float bias, float* out, float* plane_sums, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  LossWS w;
+  const int rc = loss_check("loss_forward", planes, H, W, img, gt, mode, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (!out) return fail(EOGS_ERR_INVALID_ARG, "loss_forward: NULL out");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_LOSS_FWD, s); launch_loss_fwd(w, planes, H, W, img, gt, mode, w_l1, w_ssim, bias, out, plane_sums, s); }
+  LAUNCH_TRY(s, false, "loss_fwd");
+  return EOGS_OK;
+}
+
+int eogs_loss_backward(int planes, int H, int W, const float* img, const float* gt, unsigned mode, float w_l1,
+                       float w_ssim, const float* upstream, const float* plane_grad, const void* ws, size_t ws_bytes,
+                       float* dL_dimg, void* stream) {
+  clear_error();
+  LossWS w;
+  const int rc = loss_check("loss_backward", planes, H, W, img, gt, mode, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (!dL_dimg) return fail(EOGS_ERR_INVALID_ARG, "loss_backward: NULL dL_dimg");
+  hipStream_t s = (hipStream_t)stream;
   const dim3 grid((W + LT - 1) / LT, (H + LTY - 1) / LTY, planes);
   const LossWindow win = loss_window();
   const float inv_n = (float)(1.0 / ((double)planes * H * W));
   const bool l1 = mode & EOGS_LOSS_L1, ss = mode & EOGS_LOSS_SSIM;
   auto* kern = ss ? (l1 ? loss_bwd_kernel<true, true> : loss_bwd_kernel<false, true>) : loss_bwd_kernel<true, false>;
-  hipLaunchKernelGGL(kern, grid, dim3(LTHREADS), 0, s, H, W, img, gt, win, w.maps, w.map_stride, w_l1, w_ssim, inv_n,
-                     upstream, plane_grad, dimg);
+  {
+    ProfScope ps(PS_LOSS_BWD, s);
+    hipLaunchKernelGGL(kern, grid, dim3(LTHREADS), 0, s, H, W, img, gt, win, w.maps, w.map_stride, w_l1, w_ssim, inv_n,
+                       upstream, plane_grad, dL_dimg);
+  }
+  LAUNCH_TRY(s, false, "loss_bwd");
+  return EOGS_OK;
 }
+
+}  // extern "C"

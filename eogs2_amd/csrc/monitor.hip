@@ -12,28 +12,14 @@
 // Every launch that writes the state starts with the gate: gate[0] == 0 leaves every byte of the state as it was.
 #include <math.h>
 
-#include "common.h"
+#include "api_util.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int MT = 256;        // threads per workgroup
 constexpr int MSQ_MAXBLK = 256;   // workgroups per plane of the squared-difference pass
 constexpr int MMODEL_MAXBLK = 1024;  // workgroups of the model pass
-
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// the workgroup's sum, returned on thread 0: waves in index order
-__device__ inline double wg_sum_d(double v, double* s_red) {
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
-}
 
 __device__ inline bool gate_closed(const uint32_t* gate) { return gate != nullptr && gate[0] == 0u; }
 
@@ -80,7 +66,7 @@ __global__ __launch_bounds__(MT) void monitor_sq_kernel(int64_t n, const float* 
       }
     }
   }
-  const double s = wg_sum_d((double)acc, s_red);
+  const double s = wg_sum((double)acc, s_red);
   if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
 }
 
@@ -97,7 +83,7 @@ __global__ __launch_bounds__(MT) void monitor_observe_kernel(int planes, int nbl
   for (int p = 0; p < planes; p++) {
     double a = 0.;
     for (int b = threadIdx.x; b < nblk; b += MT) a += partial[(size_t)p * nblk + b];
-    const double tot = wg_sum_d(a, s_red);
+    const double tot = wg_sum(a, s_red);
     if (threadIdx.x == 0) {
       const float mse = (float)(tot / (double)n);
       psnr_sum += (double)(20.f * log10f(1.f / sqrtf(mse)));  // mse 0: +inf, as the reference's
@@ -128,8 +114,6 @@ __global__ __launch_bounds__(MT) void monitor_observe_kernel(int planes, int nbl
 }
 
 // ---- the model: mean opacity over the rows that are not retired, and their number ----------------------------------
-__device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }  // reg.hip's
-
 __global__ __launch_bounds__(MT) void monitor_model_kernel(int64_t P, const float* __restrict__ opacity,
                                                            double* __restrict__ partial) {
   __shared__ double s_red[MT / 64];
@@ -154,8 +138,8 @@ __global__ __launch_bounds__(MT) void monitor_model_kernel(int64_t P, const floa
       rows += 1.;
     }
   }
-  const double s = wg_sum_d(sum, s_red);
-  const double r = wg_sum_d(rows, s_red);
+  const double s = wg_sum(sum, s_red);
+  const double r = wg_sum(rows, s_red);
   if (threadIdx.x == 0) {
     partial[2 * (size_t)blockIdx.x] = s;
     partial[2 * (size_t)blockIdx.x + 1] = r;
@@ -172,8 +156,8 @@ __global__ __launch_bounds__(MT) void monitor_model_final_kernel(int nblk, const
     a += partial[2 * (size_t)b];
     r += partial[2 * (size_t)b + 1];
   }
-  const double sum = wg_sum_d(a, s_red);
-  const double rows = wg_sum_d(r, s_red);
+  const double sum = wg_sum(a, s_red);
+  const double rows = wg_sum(r, s_red);
   if (threadIdx.x != 0) return;
   st->mean_opacity = rows > 0. ? (float)(sum / rows) : 0.f;
   st->rows = (int64_t)rows;
@@ -237,38 +221,139 @@ __global__ void monitor_close_kernel(int metric, int op, int64_t patience, const
 
 }  // namespace
 
-size_t monitor_sq_bytes(int planes, int H, int W) {
+static size_t monitor_sq_bytes(int planes, int H, int W) {  // the per-plane partials of observe, a multiple of 256
   return (((size_t)planes * sq_blocks((int64_t)H * W) * sizeof(double)) + 255) & ~(size_t)255;
 }
 
-size_t monitor_model_ws_bytes(int64_t P) { return (size_t)model_blocks(P) * 2 * sizeof(double) + 256; }
+static size_t monitor_model_ws_bytes(int64_t P) { return (size_t)model_blocks(P) * 2 * sizeof(double) + 256; }
 
-void launch_monitor_reset(void* state, int op, hipStream_t s) {
-  hipLaunchKernelGGL(monitor_reset_kernel, dim3(1), dim3(MT), 0, s, (eogs_monitor_state*)state, op);
+static int monitor_state_check(const char* who, const void* state) {
+  if (!state) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL state", who);
+  if ((uintptr_t)state & 15u) return fail(EOGS_ERR_INVALID_ARG, "%s: state not 16-byte aligned", who);
+  return EOGS_OK;
 }
 
-void launch_monitor_observe(int planes, int H, int W, const float* img, const float* gt, const float* loss_out,
-                            float one_minus_lambda, float lambda, int kind, int photometric_on, const uint32_t* gate, void* state,
-                            double* partial, hipStream_t s) {
+static int monitor_image_check(const char* who, int planes, int H, int W) {
+  if (planes <= 0 || H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", who);
+  if (!loss_grid_fits(planes, H)) return fail(EOGS_ERR_INVALID_ARG, "%s: too many planes / rows for one launch", who);
+  return EOGS_OK;
+}
+
+extern "C" {
+
+int eogs_monitor_state_bytes(size_t* bytes) {
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "monitor_state_bytes: NULL argument");
+  *bytes = sizeof(eogs_monitor_state);
+  return EOGS_OK;
+}
+
+int eogs_monitor_reset(void* state, size_t state_bytes, int op, void* stream) {
+  clear_error();
+  const int rc = monitor_state_check("monitor_reset", state);
+  if (rc != EOGS_OK) return rc;
+  if (state_bytes < sizeof(eogs_monitor_state)) return fail(EOGS_ERR_WORKSPACE, "monitor_reset: state buffer too small");
+  if (op != EOGS_MONITOR_MIN && op != EOGS_MONITOR_MAX) return fail(EOGS_ERR_INVALID_ARG, "monitor_reset: operator is min or max");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(monitor_reset_kernel, dim3(1), dim3(MT), 0, s, (eogs_monitor_state*)state, op);
+  LAUNCH_TRY(s, false, "monitor_reset");
+  return EOGS_OK;
+}
+
+int eogs_monitor_observe_bytes(int planes, int H, int W, int standalone, size_t* bytes) {
+  const int rc = monitor_image_check("monitor_observe_bytes", planes, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe_bytes: NULL argument");
+  size_t n = 256 + monitor_sq_bytes(planes, H, W);
+  if (standalone) n += 256 + loss_layout(nullptr, planes, H, W, EOGS_LOSS_L1 | EOGS_LOSS_SSIM).bytes;
+  *bytes = n;
+  return EOGS_OK;
+}
+
+int eogs_monitor_observe(int planes, int H, int W, const float* image, const float* gt, const float* loss_out,
+                         double lambda_dssim, int kind, int photometric_on, const uint32_t* gate, void* state, void* ws,
+                         size_t ws_bytes, void* stream) {
+  clear_error();
+  int rc = monitor_image_check("monitor_observe", planes, H, W);
+  if (rc != EOGS_OK) return rc;
+  if (kind != EOGS_MONITOR_KIND_PAN && kind != EOGS_MONITOR_KIND_MSI)
+    return fail(EOGS_ERR_INVALID_ARG, "monitor_observe: kind is pan or msi");
+  if (!image || !gt || !ws) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe: NULL argument");
+  if (!(lambda_dssim == lambda_dssim)) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe: lambda_dssim is NaN");
+  rc = monitor_state_check("monitor_observe", state);
+  if (rc != EOGS_OK) return rc;
+  char* base = ws_base(ws);
+  const size_t sq = monitor_sq_bytes(planes, H, W);
+  size_t need = (size_t)(base - (char*)ws) + sq;
+  LossWS w;
+  const unsigned mode = EOGS_LOSS_L1 | EOGS_LOSS_SSIM;
+  if (!loss_out) {
+    w = loss_layout(base + sq + 256, planes, H, W, mode);
+    need += 256 + w.bytes - 256;
+  }
+  if (need > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "monitor_observe: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  const float lam = (float)lambda_dssim, oml = (float)(1.0 - lambda_dssim);  // torch rounds the Python scalars once each
+  if (!loss_out) {
+    float* out = reinterpret_cast<float*>(base + sq);
+    { ProfScope ps(PS_LOSS_FWD, s); launch_loss_fwd(w, planes, H, W, image, gt, mode, oml, -lam, lam, out, nullptr, s); }
+    loss_out = out;
+  }
   const int64_t n = (int64_t)H * W;
   const int nb = sq_blocks(n);
-  hipLaunchKernelGGL(monitor_sq_kernel, dim3(nb, planes), dim3(MT), 0, s, n, img, gt, partial);
-  hipLaunchKernelGGL(monitor_observe_kernel, dim3(1), dim3(MT), 0, s, planes, nb, n, (const double*)partial, loss_out,
-                     one_minus_lambda, lambda, kind, photometric_on, gate, (eogs_monitor_state*)state);
+  double* partial = reinterpret_cast<double*>(base);
+  hipLaunchKernelGGL(monitor_sq_kernel, dim3(nb, planes), dim3(MT), 0, s, n, image, gt, partial);
+  hipLaunchKernelGGL(monitor_observe_kernel, dim3(1), dim3(MT), 0, s, planes, nb, n, (const double*)partial, loss_out, oml, lam, kind,
+                     photometric_on != 0, gate, (eogs_monitor_state*)state);
+  LAUNCH_TRY(s, false, "monitor_observe");
+  return EOGS_OK;
 }
 
-void launch_monitor_model(int64_t P, const float* opacity, const uint32_t* gate, void* state, void* ws, hipStream_t s) {
+int eogs_monitor_model_bytes(int64_t P, size_t* bytes) {
+  if (P <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "monitor_model_bytes: bad argument");
+  *bytes = monitor_model_ws_bytes(P);
+  return EOGS_OK;
+}
+
+int eogs_monitor_observe_model(int64_t P, const float* opacity, const uint32_t* gate, void* state, void* ws, size_t ws_bytes,
+                               void* stream) {
+  clear_error();
+  if (P <= 0) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe_model: bad size");
+  if (!opacity || !ws) return fail(EOGS_ERR_INVALID_ARG, "monitor_observe_model: NULL argument");
+  const int rc = monitor_state_check("monitor_observe_model", state);
+  if (rc != EOGS_OK) return rc;
+  if (ws_bytes < monitor_model_ws_bytes(P)) return fail(EOGS_ERR_WORKSPACE, "monitor_observe_model: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
   const int nb = model_blocks(P);
   hipLaunchKernelGGL(monitor_model_kernel, dim3(nb), dim3(MT), 0, s, P, opacity, partial);
   hipLaunchKernelGGL(monitor_model_final_kernel, dim3(1), dim3(MT), 0, s, nb, (const double*)partial, gate,
                      (eogs_monitor_state*)state);
+  LAUNCH_TRY(s, false, "monitor_observe_model");
+  return EOGS_OK;
 }
 
-void launch_monitor_end_iteration(const float* loss, const uint32_t* gate, void* state, hipStream_t s) {
+int eogs_monitor_end_iteration(const float* loss, const uint32_t* gate, void* state, void* stream) {
+  clear_error();
+  if (!loss) return fail(EOGS_ERR_INVALID_ARG, "monitor_end_iteration: NULL loss");
+  const int rc = monitor_state_check("monitor_end_iteration", state);
+  if (rc != EOGS_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(monitor_end_iteration_kernel, dim3(1), dim3(64), 0, s, loss, gate, (eogs_monitor_state*)state);
+  LAUNCH_TRY(s, false, "monitor_end_iteration");
+  return EOGS_OK;
 }
 
-void launch_monitor_close(int metric, int op, int64_t patience, const uint32_t* gate, void* state, hipStream_t s) {
+int eogs_monitor_close_interval(int metric, int op, int64_t patience, const uint32_t* gate, void* state, void* stream) {
+  clear_error();
+  if (metric < 0 || metric >= EOGS_MONITOR_METRICS) return fail(EOGS_ERR_INVALID_ARG, "monitor_close_interval: unknown metric");
+  if (op != EOGS_MONITOR_MIN && op != EOGS_MONITOR_MAX)
+    return fail(EOGS_ERR_INVALID_ARG, "monitor_close_interval: operator is min or max");
+  const int rc = monitor_state_check("monitor_close_interval", state);
+  if (rc != EOGS_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(monitor_close_kernel, dim3(1), dim3(64), 0, s, metric, op, patience, gate, (eogs_monitor_state*)state);
+  LAUNCH_TRY(s, false, "monitor_close_interval");
+  return EOGS_OK;
 }
+
+}  // extern "C"

@@ -5,7 +5,9 @@
 // reads each kept row once and writes it once, all tensors in one launch, positions from one ballot/prefix scan.
 // include/eogs_step.h: the same Adam stream with t and lr read from device scalars (a one-workgroup prologue forms the bias
 // corrections), and the single-wave gate over the forwards' count words: the optimizer step inside a recorded graph.
-#include "common.h"
+#include "api_util.h"
+
+#define EOGS_COMPACT_MAX_TENSORS 24  // tensors per compaction launch (more are split over launches)
 
 namespace {
 
@@ -309,17 +311,8 @@ __global__ __launch_bounds__(BLK) void pack_columns_kernel(PackTable tab, int64_
 
 }  // namespace
 
-void launch_pack_columns(int64_t rows, int n, const eogs_pack_tensor* tensors, float* packed, int packed_cols, int unpack,
-                         hipStream_t s) {
-  PackTable tab;
-  tab.n = n;
-  for (int i = 0; i < n; i++) tab.t[i] = tensors[i];
-  const unsigned blocks = (unsigned)((rows + BLK - 1) / BLK);
-  if (unpack) hipLaunchKernelGGL(pack_columns_kernel<true>, dim3(blocks), dim3(BLK), 0, s, tab, rows, packed, packed_cols);
-  else hipLaunchKernelGGL(pack_columns_kernel<false>, dim3(blocks), dim3(BLK), 0, s, tab, rows, packed, packed_cols);
-}
-
-int launch_adam(int n, const eogs_adam_tensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s) {
+// the three table builders: 0, or -1 when the chunks of all tensors exceed one launch's grid
+static int launch_adam(int n, const eogs_adam_tensor* tensors, double beta1, double beta2, double eps, int64_t step, hipStream_t s) {
   AdamTable tab;
   tab.n = 0;
   uint64_t blocks = 0;
@@ -340,20 +333,8 @@ int launch_adam(int n, const eogs_adam_tensor* tensors, double beta1, double bet
   return 0;
 }
 
-void launch_step_gate(int n, const uint32_t* const* misc, const uint32_t* cap_slots, const uint32_t* cap_entries, int accumulate,
-                      uint32_t* gate, hipStream_t s) {
-  GateTable tab;
-  tab.n = n;
-  for (int i = 0; i < EOGS_STEP_MAX_FORWARDS; i++) {
-    tab.misc[i] = i < n ? misc[i] : nullptr;
-    tab.cap_slots[i] = i < n ? cap_slots[i] : 0u;
-    tab.cap_entries[i] = i < n ? cap_entries[i] : 0u;
-  }
-  hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(64), 0, s, tab, accumulate, gate);
-}
-
-int launch_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, double beta2, double eps, const uint32_t* gate,
-                     eogs_step_adam_scalars* ws, hipStream_t s) {
+static int launch_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, double beta2, double eps,
+                            const uint32_t* gate, eogs_step_adam_scalars* ws, hipStream_t s) {
   StepPrologueTable pro;
   StepAdamTable tab;
   pro.n = n;
@@ -378,7 +359,7 @@ int launch_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, 
   return 0;
 }
 
-int launch_sum_into(int n, const eogs_sum_tensor* tensors, int nsrc, hipStream_t s) {
+static int launch_sum_into(int n, const eogs_sum_tensor* tensors, int nsrc, hipStream_t s) {
   SumTable tab;
   tab.n = 0;
   tab.nsrc = nsrc;
@@ -397,7 +378,12 @@ int launch_sum_into(int n, const eogs_sum_tensor* tensors, int nsrc, hipStream_t
   return 0;
 }
 
-CompactWS compact_layout(char* base, int64_t n_rows) {
+struct CompactWS {
+  uint32_t* blk;  // [nblk + 1] kept rows per 256-row workgroup -> exclusive prefix, total at [nblk]
+  uint32_t nblk;
+  size_t bytes;
+};
+static CompactWS compact_layout(char* base, int64_t n_rows) {
   CompactWS w;
   w.nblk = (uint32_t)((n_rows + COMPACT_ROWS - 1) / COMPACT_ROWS);
   w.blk = reinterpret_cast<uint32_t*>(base);
@@ -405,23 +391,183 @@ CompactWS compact_layout(char* base, int64_t n_rows) {
   return w;
 }
 
-void launch_compact_plan(const CompactWS& w, int64_t n_rows, const uint8_t* keep, hipStream_t s) {
-  if (w.nblk) hipLaunchKernelGGL(compact_count_kernel, dim3(w.nblk), dim3(BLK), 0, s, keep, n_rows, w.blk);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(BLK), 0, s, w.blk, w.nblk);
+static int compact_check(const char* who, int64_t n_rows, const void* keep, const void* ws, size_t ws_bytes, CompactWS* w) {
+  if (n_rows < 0 || n_rows > (int64_t)0x7FFFFFFF * 128) return fail(EOGS_ERR_INVALID_ARG, "%s: bad row count", who);
+  if ((n_rows > 0 && !keep) || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  char* base = ws_base(const_cast<void*>(ws));
+  *w = compact_layout(base, n_rows);
+  if ((size_t)(base - (const char*)ws) + w->bytes - 256 > ws_bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  return EOGS_OK;
 }
 
-void launch_compact_apply(const CompactWS& w, int64_t n_rows, const uint8_t* keep, int n_tensors, const void* const* src,
-                          void* const* dst, const int* row_bytes, hipStream_t s) {
-  for (int t0 = 0; t0 < n_tensors; t0 += EOGS_COMPACT_MAX_TENSORS) {
-    CompactTable tab;
-    tab.n = 0;
-    for (int t = t0; t < n_tensors && tab.n < EOGS_COMPACT_MAX_TENSORS; t++) {
-      if (row_bytes[t] == 0) continue;
-      tab.src[tab.n] = (const char*)src[t];
-      tab.dst[tab.n] = (char*)dst[t];
-      tab.row_words[tab.n] = row_bytes[t] / 4;
-      tab.n++;
-    }
-    if (tab.n && w.nblk) hipLaunchKernelGGL(compact_apply_kernel, dim3(w.nblk), dim3(BLK), 0, s, tab, keep, n_rows, w.blk);
-  }
+extern "C" {
+
+// ---- include/eogs_optim.h ----
+int eogs_adam_step(int n, const eogs_adam_tensor* tensors, double beta1, double beta2, double eps, int64_t step, void* stream) {
+  clear_error();
+  if (n < 0 || n > EOGS_ADAM_MAX_TENSORS || (n > 0 && !tensors) || step < 1)
+    return fail(EOGS_ERR_INVALID_ARG, "adam_step: bad argument (at most 16 tensors, step >= 1)");
+  for (int i = 0; i < n; i++)
+    if (tensors[i].numel < 0 || (tensors[i].numel > 0 && (!tensors[i].param || !tensors[i].grad || !tensors[i].exp_avg ||
+                                                          !tensors[i].exp_avg_sq)))
+      return fail(EOGS_ERR_INVALID_ARG, "adam_step: NULL tensor");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  { ProfScope ps(PS_ADAM, s); rc = launch_adam(n, tensors, beta1, beta2, eps, step, s); }
+  if (rc) return fail(EOGS_ERR_OVERFLOW, "adam_step: too many elements for one launch");
+  LAUNCH_TRY(s, false, "adam");
+  return EOGS_OK;
 }
+
+int eogs_sum_into(int n, const eogs_sum_tensor* tensors, int nsrc, void* stream) {
+  clear_error();
+  if (n < 0 || n > EOGS_SUM_MAX_TENSORS || nsrc < 0 || nsrc > EOGS_SUM_MAX_SOURCES || (n > 0 && !tensors))
+    return fail(EOGS_ERR_INVALID_ARG, "sum_into: bad argument (at most 8 tensors with at most 4 sources each)");
+  for (int i = 0; i < n; i++) {
+    if (tensors[i].numel < 0 || (tensors[i].numel > 0 && !tensors[i].dst)) return fail(EOGS_ERR_INVALID_ARG, "sum_into: NULL tensor");
+    for (int k = 0; k < nsrc; k++)
+      if (tensors[i].numel > 0 && !tensors[i].src[k]) return fail(EOGS_ERR_INVALID_ARG, "sum_into: NULL source");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (launch_sum_into(n, tensors, nsrc, s)) return fail(EOGS_ERR_OVERFLOW, "sum_into: too many elements for one launch");
+  LAUNCH_TRY(s, false, "sum_into");
+  return EOGS_OK;
+}
+
+int eogs_pack_columns(int64_t rows, int n, const eogs_pack_tensor* tensors, float* packed, int packed_cols, int unpack,
+                      void* stream) {
+  clear_error();
+  if (rows < 0 || n < 0 || n > EOGS_PACK_MAX_TENSORS || packed_cols < 0 || packed_cols > 16)
+    return fail(EOGS_ERR_INVALID_ARG, "pack_columns: bad sizes");
+  if (rows == 0 || n == 0) return EOGS_OK;
+  if (!tensors || !packed) return fail(EOGS_ERR_INVALID_ARG, "pack_columns: NULL argument");
+  int total = 0;
+  PackTable tab;
+  tab.n = n;
+  for (int i = 0; i < n; i++) {
+    const eogs_pack_tensor& t = tensors[i];
+    if (!t.data || t.width <= 0 || t.col0 < 0 || t.ncols <= 0 || t.col0 + t.ncols > t.width)
+      return fail(EOGS_ERR_INVALID_ARG, "pack_columns: bad tensor descriptor");
+    total += t.ncols;
+    tab.t[i] = t;
+  }
+  if (total != packed_cols) return fail(EOGS_ERR_INVALID_ARG, "pack_columns: packed_cols is not the sum of the column counts");
+  hipStream_t s = (hipStream_t)stream;
+  const unsigned blocks = (unsigned)((rows + BLK - 1) / BLK);
+  if (unpack) hipLaunchKernelGGL(pack_columns_kernel<true>, dim3(blocks), dim3(BLK), 0, s, tab, rows, packed, packed_cols);
+  else hipLaunchKernelGGL(pack_columns_kernel<false>, dim3(blocks), dim3(BLK), 0, s, tab, rows, packed, packed_cols);
+  LAUNCH_TRY(s, false, "pack_columns");
+  return EOGS_OK;
+}
+
+int eogs_compact_bytes(int64_t n_rows, size_t* bytes) {
+  if (n_rows < 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "compact_bytes: bad argument");
+  *bytes = compact_layout(nullptr, n_rows).bytes;
+  return EOGS_OK;
+}
+
+int eogs_compact_plan(int64_t n_rows, const uint8_t* keep, void* ws, size_t ws_bytes, int64_t* n_keep, void* stream) {
+  clear_error();
+  CompactWS w;
+  const int rc = compact_check("compact_plan", n_rows, keep, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (!n_keep) return fail(EOGS_ERR_INVALID_ARG, "compact_plan: NULL n_keep");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps(PS_COMPACT, s);
+    if (w.nblk) hipLaunchKernelGGL(compact_count_kernel, dim3(w.nblk), dim3(BLK), 0, s, keep, n_rows, w.blk);
+    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(BLK), 0, s, w.blk, w.nblk);
+  }
+  LAUNCH_TRY(s, false, "compact_plan");
+  uint32_t total = 0;
+  HIP_TRY(hipMemcpyAsync(&total, w.blk + w.nblk, sizeof total, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  *n_keep = (int64_t)total;
+  return EOGS_OK;
+}
+
+int eogs_compact_apply(int64_t n_rows, const uint8_t* keep, int n_tensors, const void* const* src, void* const* dst,
+                       const int* row_bytes, const void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  CompactWS w;
+  const int rc = compact_check("compact_apply", n_rows, keep, ws, ws_bytes, &w);
+  if (rc != EOGS_OK) return rc;
+  if (n_tensors < 0 || (n_tensors > 0 && (!src || !dst || !row_bytes))) return fail(EOGS_ERR_INVALID_ARG, "compact_apply: bad tensor list");
+  for (int t = 0; t < n_tensors; t++)
+    if (row_bytes[t] < 0 || row_bytes[t] > 256 || (row_bytes[t] & 3) || (row_bytes[t] > 0 && n_rows > 0 && (!src[t] || !dst[t])))
+      return fail(EOGS_ERR_INVALID_ARG, "compact_apply: row sizes must be multiples of 4 up to 256 bytes, pointers non-NULL");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps(PS_COMPACT, s);
+    for (int t0 = 0; t0 < n_tensors; t0 += EOGS_COMPACT_MAX_TENSORS) {
+      CompactTable tab;
+      tab.n = 0;
+      for (int t = t0; t < n_tensors && tab.n < EOGS_COMPACT_MAX_TENSORS; t++) {
+        if (row_bytes[t] == 0) continue;
+        tab.src[tab.n] = (const char*)src[t];
+        tab.dst[tab.n] = (char*)dst[t];
+        tab.row_words[tab.n] = row_bytes[t] / 4;
+        tab.n++;
+      }
+      if (tab.n && w.nblk) hipLaunchKernelGGL(compact_apply_kernel, dim3(w.nblk), dim3(BLK), 0, s, tab, keep, n_rows, w.blk);
+    }
+  }
+  LAUNCH_TRY(s, false, "compact_apply");
+  return EOGS_OK;
+}
+
+// ---- include/eogs_step.h ----
+int eogs_step_gate(int n, const eogs_step_forward* fw, int accumulate, uint32_t* gate, void* stream) {
+  clear_error();
+  if (n < 0 || n > EOGS_STEP_MAX_FORWARDS || (n > 0 && !fw) || !gate)
+    return fail(EOGS_ERR_INVALID_ARG, "step_gate: bad argument (at most 16 forwards, a gate)");
+  GateTable tab;
+  tab.n = n;
+  for (int i = 0; i < EOGS_STEP_MAX_FORWARDS; i++) {
+    tab.misc[i] = nullptr;
+    tab.cap_slots[i] = tab.cap_entries[i] = 0u;
+  }
+  for (int i = 0; i < n; i++) {
+    if (fw[i].P <= 0 || !fw[i].geom || fw[i].capacity < 0) return fail(EOGS_ERR_INVALID_ARG, "step_gate: bad forward descriptor");
+    char* base = ws_base(const_cast<void*>(fw[i].geom));
+    const GeomWS g = geom_layout(base, fw[i].P);
+    if ((size_t)(base - (const char*)fw[i].geom) + g.bytes - 256 > fw[i].geom_bytes)
+      return fail(EOGS_ERR_WORKSPACE, "step_gate: geom workspace too small");
+    tab.misc[i] = g.misc;  // each forward's count words
+    tab.cap_slots[i] = nr_slots(fw[i].capacity);
+    tab.cap_entries[i] = nr_entries(fw[i].capacity);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(step_gate_kernel, dim3(1), dim3(64), 0, s, tab, accumulate, gate);
+  LAUNCH_TRY(s, false, "step_gate");
+  return EOGS_OK;
+}
+
+int eogs_step_adam_bytes(int n, size_t* bytes) {
+  if (n < 0 || n > EOGS_STEP_MAX_TENSORS || !bytes) return fail(EOGS_ERR_INVALID_ARG, "step_adam_bytes: bad argument (at most 16 tensors)");
+  *bytes = (size_t)n * sizeof(eogs_step_adam_scalars);
+  return EOGS_OK;
+}
+
+int eogs_step_adam(int n, const eogs_step_adam_tensor* tensors, double beta1, double beta2, double eps, const uint32_t* gate,
+                   void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (n < 0 || n > EOGS_STEP_MAX_TENSORS) return fail(EOGS_ERR_INVALID_ARG, "step_adam: bad argument (at most 16 tensors)");
+  if (n == 0) return EOGS_OK;
+  if (!tensors) return fail(EOGS_ERR_INVALID_ARG, "step_adam: NULL tensors");
+  for (int i = 0; i < n; i++) {
+    const eogs_step_adam_tensor& t = tensors[i];
+    if (t.numel < 0 || !t.lr || !t.step || (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq)))
+      return fail(EOGS_ERR_INVALID_ARG, "step_adam: NULL tensor member");
+  }
+  if (!ws || ws_bytes < (size_t)n * sizeof(eogs_step_adam_scalars)) return fail(EOGS_ERR_WORKSPACE, "step_adam: workspace too small");
+  if ((uintptr_t)ws & 15u) return fail(EOGS_ERR_INVALID_ARG, "step_adam: workspace not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  { ProfScope ps(PS_ADAM, s); rc = launch_step_adam(n, tensors, beta1, beta2, eps, gate, (eogs_step_adam_scalars*)ws, s); }
+  if (rc) return fail(EOGS_ERR_OVERFLOW, "step_adam: too many elements for one launch");
+  LAUNCH_TRY(s, false, "step_adam");
+  return EOGS_OK;
+}
+
+}  // extern "C"

@@ -8,7 +8,7 @@
 // parameters: the pixel loop carries no branch on them. Nothing is saved between forward and backward. The parameter
 // sums are reduced per wave (shuffles), per workgroup (LDS, fixed order) and then column by column over the workgroups'
 // partials by a second kernel, again in a fixed order — no atomics, bitwise reproducible.
-#include "common.h"
+#include "api_util.h"
 
 namespace {
 
@@ -353,29 +353,69 @@ void pan_dispatch(int order, int kind, PanArgs& a) {
 
 }  // namespace
 
-size_t pan_ws_bytes() { return (size_t)PMAXBLK * PK * sizeof(float) + 256; }
+static size_t pan_ws_bytes() { return (size_t)PMAXBLK * PK * sizeof(float) + 256; }
 
-int pan_map_params(int kind) { return map_nparams(kind); }
+static int pan_check(const char* who, int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M,
+                     const float* inshadow, const float* map_params) {
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", who);
+  if (order != EOGS_PAN_ORDER_CC_FIRST && order != EOGS_PAN_ORDER_MAP_FIRST) return fail(EOGS_ERR_INVALID_ARG, "%s: unknown order", who);
+  if (kind < EOGS_PAN_ONE_CHANNEL || kind > EOGS_PAN_TRANSLATE_FROZEN) return fail(EOGS_ERR_INVALID_ARG, "%s: unknown map kind", who);
+  if (!raw || !M) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  if (alt_diff && !inshadow) return fail(EOGS_ERR_INVALID_ARG, "%s: alt_diff needs inshadow (NULL argument)", who);
+  if (map_nparams(kind) > 0 && !map_params) return fail(EOGS_ERR_INVALID_ARG, "%s: this map kind needs map_params (NULL argument)", who);
+  return EOGS_OK;
+}
 
-void launch_pan_fwd(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
-                    const float* map_params, float* cc, float* shaded, float* shadow, hipStream_t s) {
+extern "C" {
+
+int eogs_pan_bytes(int H, int W, size_t* bytes) {
+  clear_error();
+  if (H <= 0 || W <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "pan_bytes: bad argument");
+  *bytes = pan_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_pan_forward(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M,
+                     const float* inshadow, const float* map_params, float* cc, float* shaded, float* shadow,
+                     void* stream) {
+  clear_error();
+  const int rc = pan_check("pan_forward", H, W, order, kind, raw, alt_diff, M, inshadow, map_params);
+  if (rc != EOGS_OK) return rc;
+  if (!shaded || (order == EOGS_PAN_ORDER_MAP_FIRST && !cc)) return fail(EOGS_ERR_INVALID_ARG, "pan_forward: NULL argument");
+  if ((alt_diff != nullptr) != (shadow != nullptr)) return fail(EOGS_ERR_INVALID_ARG, "pan_forward: alt_diff and shadow go together");
+  hipStream_t s = (hipStream_t)stream;
   PanArgs a{};
   a.n = (int64_t)H * W;
   a.raw = raw, a.alt_diff = alt_diff, a.M = M, a.ins = inshadow, a.mp = map_params;
   a.cc = cc, a.shaded = shaded, a.shadow = shadow;
   a.bwd = false, a.s = s;
   pan_dispatch(order, kind, a);
+  LAUNCH_TRY(s, false, "pan_fwd");
+  return EOGS_OK;
 }
 
-void launch_pan_bwd(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
-                    const float* map_params, const float* g_shaded, const float* g_cc, const float* g_shadow, float* g_raw,
-                    float* g_alt, float* g_params, void* ws, hipStream_t s) {
+int eogs_pan_backward(int H, int W, int order, int kind, const float* raw, const float* alt_diff, const float* M,
+                      const float* inshadow, const float* map_params, const float* g_shaded, const float* g_cc,
+                      const float* g_shadow, float* g_raw, float* g_alt_diff, float* g_params, void* ws, size_t ws_bytes,
+                      void* stream) {
+  clear_error();
+  const int rc = pan_check("pan_backward", H, W, order, kind, raw, alt_diff, M, inshadow, map_params);
+  if (rc != EOGS_OK) return rc;
+  if (!g_raw || !g_params || !ws) return fail(EOGS_ERR_INVALID_ARG, "pan_backward: NULL argument");
+  if ((alt_diff != nullptr) != (g_alt_diff != nullptr) || (!alt_diff && g_shadow))
+    return fail(EOGS_ERR_INVALID_ARG, "pan_backward: alt_diff, g_shadow and g_alt_diff go together");
+  if (ws_bytes < pan_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "pan_backward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   PanArgs a{};
   a.n = (int64_t)H * W;
   a.raw = raw, a.alt_diff = alt_diff, a.M = M, a.ins = inshadow, a.mp = map_params;
-  a.g_shaded = g_shaded, a.g_cc = g_cc, a.g_shadow = g_shadow, a.g_raw = g_raw, a.g_alt = g_alt;
+  a.g_shaded = g_shaded, a.g_cc = g_cc, a.g_shadow = g_shadow, a.g_raw = g_raw, a.g_alt = g_alt_diff;
   a.partial = reinterpret_cast<float*>(ws_base(ws));
   a.bwd = true, a.s = s;
   pan_dispatch(order, kind, a);
   hipLaunchKernelGGL(pan_reduce_kernel, dim3(PK), dim3(PT), 0, s, (const float*)a.partial, a.nb, g_params);
+  LAUNCH_TRY(s, false, "pan_bwd");
+  return EOGS_OK;
 }
+
+}  // extern "C"

@@ -16,6 +16,7 @@
 // through LDS so that their global loads are contiguous dwords per lane. Records are read in Gaussian-id order
 // (a workgroup's 256 Gaussians own one contiguous region), flags first, then two records per trip.
 #include "common.h"
+#include "reduce.h"
 #include <type_traits>
 
 namespace {
@@ -114,23 +115,6 @@ __device__ inline float raw_activate(float s[3], float q[4], bool* clamped = nul
   return inv;
 }
 
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-// the same sum on the DPP path (six VALU instructions, no LDS round trips; the total read from lane 63: every lane gets it)
-__device__ inline float wave_sum_dpp(float v) {
-#define GB_DPP(x, ctrl, rows) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, rows, 0xF, true))
-  v += GB_DPP(v, 0x121, 0xF);  // row_ror:1
-  v += GB_DPP(v, 0x122, 0xF);  // row_ror:2
-  v += GB_DPP(v, 0x124, 0xF);  // row_ror:4
-  v += GB_DPP(v, 0x128, 0xF);  // row_ror:8: every lane holds its row's sum
-  v += GB_DPP(v, 0x142, 0xA);  // row_bcast15 into rows 1 and 3
-  v += GB_DPP(v, 0x143, 0xC);  // row_bcast31 into rows 2 and 3
-#undef GB_DPP
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 // listed tiles from which a Gaussian's records are summed by its whole wave instead of by its own lane (gaussian_bwd_kernel)
 #ifndef GB_COOP
 #define GB_COOP 64u

@@ -1,0 +1,58 @@
+// reduce.h — the fixed-order wave64 / workgroup reductions and two scalar helpers the side modules share (device only).
+// The library is built without fast-math and with -ffp-contract=off: each of these is ONE expression tree, so every kernel
+// that sums through it rounds in the same order — what the modules' "same bits on every run" (and monitor.hip's "same
+// bits as reg.hip") rest on.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+// butterfly over the 64 lanes (float, double, int64_t): every lane returns the same value
+template <typename T>
+__device__ inline T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// ... its minimum / maximum counterparts (float, double; fmin / fmax pass over a NaN)
+template <typename T>
+__device__ inline T wave_min(T v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+template <typename T>
+__device__ inline T wave_max(T v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// The sum over a workgroup of four waves, returned on every thread: lanes by the butterfly, then waves 0, 1, 2, 3 left to
+// right. `s_red` holds four values; the leading barrier lets a kernel reuse it from one call to the next.
+template <typename T>
+__device__ inline T wg_sum(T v, T* s_red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+
+// the float sum on the DPP path: four rotations inside each row of 16 lanes, the row totals handed on by row_bcast15 /
+// row_bcast31, lane 63 read back — seven VALU instructions and no LDS round trip (__shfl_xor is a ds_bpermute_b32: six
+// dependent ones cost the quad forward 4 % when this sum sat in its chunk loop, profiles/r05_ab_plain_trips.txt)
+__device__ inline float wave_sum_dpp(float v) {
+#define WS_DPP(x, ctrl, rows) __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), ctrl, rows, 0xF, true))
+  v += WS_DPP(v, 0x121, 0xF);  // row_ror:1
+  v += WS_DPP(v, 0x122, 0xF);  // row_ror:2
+  v += WS_DPP(v, 0x124, 0xF);  // row_ror:4
+  v += WS_DPP(v, 0x128, 0xF);  // row_ror:8: every lane holds its row's sum
+  v += WS_DPP(v, 0x142, 0xA);  // row_bcast15 into rows 1 and 3
+  v += WS_DPP(v, 0x143, 0xC);  // row_bcast31 into rows 2 and 3
+#undef WS_DPP
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+__device__ inline float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+// reg.hip's opacity terms and monitor.hip's mean opacity must agree to the bit
+__device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }

@@ -8,7 +8,8 @@
 // per element with plain stores. Sums: float64 per lane, per wave, per workgroup, then one workgroup combines the
 // partials in a fixed order — no atomics, a grid that depends on the shape alone, bitwise reproducible. Weights and
 // upstream gradients are read from device memory, so a recorded graph follows a caller that rewrites them.
-#include "common.h"
+#include "api_util.h"
+#include "reduce.h"
 
 namespace {
 
@@ -21,12 +22,6 @@ inline int reg_blocks(int64_t n) {
   return (int)(b < 1 ? 1 : (b > RMAXBLK ? RMAXBLK : b));
 }
 
-__device__ inline double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // the workgroup's sum of each of K per-lane accumulators, written by its first K lanes to partial[block][k]
 template <int K>
 __device__ inline void wg_partials(double (&a)[K], double* __restrict__ partial) {
@@ -34,7 +29,7 @@ __device__ inline void wg_partials(double (&a)[K], double* __restrict__ partial)
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < K; k++) {
-    a[k] = wave_sum_d(a[k]);
+    a[k] = wave_sum(a[k]);
     if (lane == 0) s_red[wv][k] = a[k];
   }
   __syncthreads();
@@ -50,18 +45,10 @@ __device__ inline void wg_partials(double (&a)[K], double* __restrict__ partial)
 __device__ inline double column_sum(const double* __restrict__ partial, int nblk, int k, double* s_red) {
   double a = 0.;
   for (int b = threadIdx.x; b < nblk; b += RT) a += partial[(size_t)b * RK + k];
-  a = wave_sum_d(a);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+  return wg_sum(a, s_red);
 }
 
-__device__ inline float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
-
 // ---- Gaussian-space terms ------------------------------------------------------------------------------------------
-__device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
-
 // main_loss.py:27-32 for one row; everything backward needs again
 struct ErankRow {
   float s[3], s2[3], S, q[3], lq[3], e, t, m;
@@ -259,34 +246,110 @@ __global__ __launch_bounds__(RT) void reg_image_bwd_kernel(int H, int W, const f
 
 }  // namespace
 
-size_t reg_ws_bytes() { return (size_t)RMAXBLK * RK * sizeof(double) + 256; }
+static size_t reg_ws_bytes() { return (size_t)RMAXBLK * RK * sizeof(double) + 256; }
 
-void launch_reg_gauss_fwd(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
-                          float n_init, const float* weights, float* out, void* ws, hipStream_t s) {
+static int reg_gauss_check(const char* who, int64_t P, unsigned want, const float* opacity, const float* log_scales,
+                           const int32_t* radii, float n_init, const float* weights) {
+  if (P <= 0) return fail(EOGS_ERR_INVALID_ARG, "%s: bad size", who);
+  if (want == 0u || (want & ~(EOGS_REG_OPACITY | EOGS_REG_OPACITY_RADII | EOGS_REG_ERANK)))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: `want` selects at least one of the three terms and nothing else", who);
+  if (!opacity || !weights) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  if ((want & EOGS_REG_ERANK) && !log_scales) return fail(EOGS_ERR_INVALID_ARG, "%s: the erank term needs log_scales (NULL argument)", who);
+  if ((want & EOGS_REG_OPACITY_RADII) && !radii) return fail(EOGS_ERR_INVALID_ARG, "%s: the visible-opacity term needs radii (NULL argument)", who);
+  if ((want & (EOGS_REG_OPACITY | EOGS_REG_OPACITY_RADII)) && !(n_init > 0.f))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: n_init must be positive", who);
+  return EOGS_OK;
+}
+
+extern "C" {
+
+int eogs_reg_gauss_bytes(int64_t P, size_t* bytes) {
+  clear_error();
+  if (P <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_bytes: bad argument");
+  *bytes = reg_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_reg_gauss_forward(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
+                           float n_init, const float* weights, float* out, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const int rc = reg_gauss_check("reg_gauss_forward", P, want, opacity, log_scales, radii, n_init, weights);
+  if (rc != EOGS_OK) return rc;
+  if (!out || !ws) return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_forward: NULL argument");
+  if (ws_bytes < reg_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "reg_gauss_forward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
   const int nb = reg_blocks(P);
-  hipLaunchKernelGGL(reg_gauss_fwd_kernel, dim3(nb), dim3(RT), 0, s, P, want, opacity, log_scales, radii, partial);
-  hipLaunchKernelGGL(reg_gauss_final_kernel, dim3(1), dim3(RT), 0, s, (const double*)partial, nb, want, n_init, weights, out);
+  {
+    ProfScope ps(PS_REG_FWD, s);
+    hipLaunchKernelGGL(reg_gauss_fwd_kernel, dim3(nb), dim3(RT), 0, s, P, want, opacity, log_scales, radii, partial);
+    hipLaunchKernelGGL(reg_gauss_final_kernel, dim3(1), dim3(RT), 0, s, (const double*)partial, nb, want, n_init, weights, out);
+  }
+  LAUNCH_TRY(s, false, "reg_gauss_fwd");
+  return EOGS_OK;
 }
 
-void launch_reg_gauss_bwd(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
-                          float n_init, const float* weights, const float* out, const float* g_total, const float* g_terms,
-                          float* g_opacity, float* g_scaling, hipStream_t s) {
-  hipLaunchKernelGGL(reg_gauss_bwd_kernel, dim3(reg_blocks(P)), dim3(RT), 0, s, P, want, opacity, log_scales, radii, n_init,
-                     weights, out, g_total, g_terms, g_opacity, g_scaling);
+int eogs_reg_gauss_backward(int64_t P, unsigned want, const float* opacity, const float* log_scales, const int32_t* radii,
+                            float n_init, const float* weights, const float* out, const float* g_total,
+                            const float* g_terms, float* g_opacity, float* g_scaling, void* stream) {
+  clear_error();
+  const int rc = reg_gauss_check("reg_gauss_backward", P, want, opacity, log_scales, radii, n_init, weights);
+  if (rc != EOGS_OK) return rc;
+  if (!out || !g_opacity) return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_backward: NULL argument");
+  if (((want & EOGS_REG_ERANK) != 0u) != (g_scaling != nullptr))
+    return fail(EOGS_ERR_INVALID_ARG, "reg_gauss_backward: g_scaling goes with the erank term");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps(PS_REG_BWD, s);
+    hipLaunchKernelGGL(reg_gauss_bwd_kernel, dim3(reg_blocks(P)), dim3(RT), 0, s, P, want, opacity, log_scales, radii, n_init,
+                       weights, out, g_total, g_terms, g_opacity, g_scaling);
+  }
+  LAUNCH_TRY(s, false, "reg_gauss_bwd");
+  return EOGS_OK;
 }
 
-void launch_reg_image_fwd(int H, int W, const float* alt, const float* acc, const float* weights, float* out, void* ws,
-                          hipStream_t s) {
+int eogs_reg_image_bytes(int H, int W, size_t* bytes) {
+  clear_error();
+  if (H < 2 || W < 2 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "reg_image_bytes: bad argument");
+  *bytes = reg_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_reg_image_forward(int H, int W, const float* altitude, const float* accumulated_opacity, const float* weights,
+                           float* out, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (H < 2 || W < 2) return fail(EOGS_ERR_INVALID_ARG, "reg_image_forward: bad sizes (H and W must be at least 2)");
+  if ((!altitude && !accumulated_opacity) || !weights || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "reg_image_forward: NULL argument");
+  if (ws_bytes < reg_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "reg_image_forward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
   const int nb = reg_blocks((int64_t)H * W);
-  hipLaunchKernelGGL(reg_image_fwd_kernel, dim3(nb), dim3(RT), 0, s, H, W, alt, acc, partial);
-  hipLaunchKernelGGL(reg_image_final_kernel, dim3(1), dim3(RT), 0, s, (const double*)partial, nb, H, W, alt != nullptr,
-                     acc != nullptr, weights, out);
+  {
+    ProfScope ps(PS_REG_FWD, s);
+    hipLaunchKernelGGL(reg_image_fwd_kernel, dim3(nb), dim3(RT), 0, s, H, W, altitude, accumulated_opacity, partial);
+    hipLaunchKernelGGL(reg_image_final_kernel, dim3(1), dim3(RT), 0, s, (const double*)partial, nb, H, W, altitude != nullptr,
+                       accumulated_opacity != nullptr, weights, out);
+  }
+  LAUNCH_TRY(s, false, "reg_image_fwd");
+  return EOGS_OK;
 }
 
-void launch_reg_image_bwd(int H, int W, const float* alt, const float* acc, const float* weights, const float* g_total,
-                          const float* g_terms, float* g_alt, float* g_acc, hipStream_t s) {
-  hipLaunchKernelGGL(reg_image_bwd_kernel, dim3(reg_blocks((int64_t)H * W)), dim3(RT), 0, s, H, W, alt, acc != nullptr, weights,
-                     g_total, g_terms, g_alt, g_acc);
+int eogs_reg_image_backward(int H, int W, const float* altitude, const float* accumulated_opacity, const float* weights,
+                            const float* g_total, const float* g_terms, float* g_altitude, float* g_accumulated_opacity,
+                            void* stream) {
+  clear_error();
+  if (H < 2 || W < 2) return fail(EOGS_ERR_INVALID_ARG, "reg_image_backward: bad sizes (H and W must be at least 2)");
+  if ((!altitude && !accumulated_opacity) || !weights) return fail(EOGS_ERR_INVALID_ARG, "reg_image_backward: NULL argument");
+  if ((altitude != nullptr) != (g_altitude != nullptr) || (accumulated_opacity != nullptr) != (g_accumulated_opacity != nullptr))
+    return fail(EOGS_ERR_INVALID_ARG, "reg_image_backward: a gradient plane goes with its input, NULL with NULL");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps(PS_REG_BWD, s);
+    hipLaunchKernelGGL(reg_image_bwd_kernel, dim3(reg_blocks((int64_t)H * W)), dim3(RT), 0, s, H, W, altitude,
+                       accumulated_opacity != nullptr, weights, g_total, g_terms, g_altitude, g_accumulated_opacity);
+  }
+  LAUNCH_TRY(s, false, "reg_image_bwd");
+  return EOGS_OK;
 }
+
+}  // extern "C"

@@ -41,6 +41,7 @@
 //     pairs behind every pixel's last contributor are never gathered nor written); gaussian_bwd_kernel sums each
 //     Gaussian's live records in fixed order (bitwise reproducible gradients).
 #include "common.h"
+#include "reduce.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -75,21 +76,6 @@ __device__ inline void uv_row8(const float* row, float (&x)[8]) {  // eight cons
 
 // ---- wave64 helpers ----
 __device__ inline uint32_t wave_max_u32(uint32_t v) { return wave_max_u32_dpp(v); }  // (common.h: DPP path, no LDS round trips)
-// wave-uniform sum on the DPP path: four rotations inside each row of 16 lanes, the row totals handed on by row_bcast15 /
-// row_bcast31, lane 63 read back — seven VALU instructions and no LDS round trip (__shfl_xor is a ds_bpermute_b32: six
-// dependent ones cost the quad forward 4 % when this sum sat in its chunk loop, profiles/r05_ab_plain_trips.txt)
-__device__ inline float wave_sum_f32(float v) {
-  auto dpp = [](float x, auto ctrl, auto rows) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, decltype(rows)::value, 0xF, true));
-  };
-  v += dpp(v, std::integral_constant<int, 0x121>{}, std::integral_constant<int, 0xF>{});  // row_ror:1
-  v += dpp(v, std::integral_constant<int, 0x122>{}, std::integral_constant<int, 0xF>{});  // row_ror:2
-  v += dpp(v, std::integral_constant<int, 0x124>{}, std::integral_constant<int, 0xF>{});  // row_ror:4
-  v += dpp(v, std::integral_constant<int, 0x128>{}, std::integral_constant<int, 0xF>{});  // row_ror:8: every lane holds its row's sum
-  v += dpp(v, std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xA>{});  // row_bcast15 into rows 1 and 3
-  v += dpp(v, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xC>{});  // row_bcast31 into rows 2 and 3
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 // The quad forward's plain chunks (render_fwd_quad_kernel): while the bound on T — the product of (1 - opacity) over everything
 // a tile has listed so far — stays above 2^-13 = 1.22e-4 no pixel can reach the reference's stop test T (1 - alpha) < 1e-4
 // (forward.cu:378-382): 22 % of margin against the rounding of a product of a few thousand fp32 factors (relative error
@@ -482,7 +468,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(EOGS_FW, EOG
     for (; c0 < range.y; c0 += 64) {
       if constexpr (PLAIN) {
         // alpha <= o for every pixel: T >= prod (1 - min(o, 0.99)) over everything listed up to and including this chunk
-        const float l = lsum + wave_sum_f32(nxt.hit ? __builtin_amdgcn_logf(1.f - fminf(nxt.q1.y, 0.99f)) : 0.f);
+        const float l = lsum + wave_sum_dpp(nxt.hit ? __builtin_amdgcn_logf(1.f - fminf(nxt.q1.y, 0.99f)) : 0.f);
         if (!(l > PLAIN_LOG2_T) || __builtin_amdgcn_ballot_w64(nxt.hit && nxt.q1.y > 0.99f) != 0ull) return;
         lsum = l;
       }

@@ -7,7 +7,7 @@
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "bucket_gather.h"
-#include "common.h"
+#include "api_util.h"
 
 namespace {
 
@@ -266,19 +266,12 @@ __global__ __launch_bounds__(BLK) void resample_bwd_tile_kernel(int C, int Hv, i
 
 }  // namespace
 
-void launch_resample_fwd(int C, int Hv, int Wv, int H, int W, int n_out, const float* vr, const float* uva,
-                         const float* M, int fill_channel, float fill_value, float* sample, float* uv, hipStream_t s) {
-  const int HW = H * W;
-  hipLaunchKernelGGL(resample_fwd_kernel, dim3((HW + BLK - 1) / BLK), dim3(BLK), 0, s, C, Hv, Wv, HW, n_out, vr, uva, M,
-                     fill_channel, fill_value, sample, uv);
-}
-
-size_t resample_bwd_ws_bytes(int H, int W) {
+static size_t resample_bwd_ws_bytes(int H, int W) {
   const size_t nt = (size_t)((W + OT - 1) / OT) * ((H + OT - 1) / OT);
   return (nt * sizeof(int4) + 255) / 256 * 256 + 256;
 }
 
-void launch_resample_bwd(int C, int Hv, int Wv, int H, int W, int n_out, const float* vr, const float* uva,
+static void launch_resample_bwd(int C, int Hv, int Wv, int H, int W, int n_out, const float* vr, const float* uva,
                          const float* M, int fill_channel, const float* gs, const float* guv, float* gvr, float* guva,
                          void* ws, hipStream_t s) {
   const int ntx = (W + OT - 1) / OT, nty = (H + OT - 1) / OT;
@@ -308,3 +301,53 @@ void launch_resample_bwd(int C, int Hv, int Wv, int H, int W, int n_out, const f
   hipLaunchKernelGGL(kern, dim3((Wv + vx - 1) / vx, (Hv + vy - 1) / vy), dim3(BLK), 0, s, C, Hv, Wv, H, W, n_out,
                      ResampleSrc{uva, M}, fill_channel, gs, bbox, ntx, nty, gvr);
 }
+
+static int resample_check(const char* who, int C, int Hv, int Wv, int H, int W, int n_out, int fill_channel) {
+  if (C <= 0 || Hv <= 0 || Wv <= 0 || H <= 0 || W <= 0 || n_out <= 0 || n_out > C || fill_channel >= n_out ||
+      (int64_t)H * W > 0x7FFFFFFF || (int64_t)Hv * Wv > 0x7FFFFFFF)
+    return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes", who);
+  return EOGS_OK;
+}
+
+extern "C" {
+
+int eogs_resample_forward(int C, int Hv, int Wv, int H, int W, int n_out, const float* virtual_render, const float* uva,
+                          const float* cam2virt, int fill_channel, float fill_value, float* sample, float* uv,
+                          void* stream) {
+  clear_error();
+  const int rc = resample_check("resample_forward", C, Hv, Wv, H, W, n_out, fill_channel);
+  if (rc != EOGS_OK) return rc;
+  if (!virtual_render || !uva || !cam2virt || !sample || !uv) return fail(EOGS_ERR_INVALID_ARG, "resample_forward: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  const int HW = H * W;
+  {
+    ProfScope ps(PS_RESAMPLE_FWD, s);
+    hipLaunchKernelGGL(resample_fwd_kernel, dim3((HW + BLK - 1) / BLK), dim3(BLK), 0, s, C, Hv, Wv, HW, n_out, virtual_render, uva,
+                       cam2virt, fill_channel, fill_value, sample, uv);
+  }
+  LAUNCH_TRY(s, false, "resample_fwd");
+  return EOGS_OK;
+}
+
+int eogs_resample_bytes(int H, int W, size_t* bytes) {
+  if (H <= 0 || W <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "resample_bytes: bad argument");
+  *bytes = resample_bwd_ws_bytes(H, W);
+  return EOGS_OK;
+}
+
+int eogs_resample_backward(int C, int Hv, int Wv, int H, int W, int n_out, const float* virtual_render, const float* uva,
+                           const float* cam2virt, int fill_channel, const float* dL_dsample, const float* dL_duv,
+                           float* dL_dvirtual, float* dL_duva, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const int rc = resample_check("resample_backward", C, Hv, Wv, H, W, n_out, fill_channel);
+  if (rc != EOGS_OK) return rc;
+  if (!virtual_render || !uva || !cam2virt || !dL_dsample || !dL_dvirtual || !dL_duva)
+    return fail(EOGS_ERR_INVALID_ARG, "resample_backward: NULL argument");
+  if (ws && ws_bytes < resample_bwd_ws_bytes(H, W)) return fail(EOGS_ERR_WORKSPACE, "resample_backward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  { ProfScope ps(PS_RESAMPLE_BWD, s); launch_resample_bwd(C, Hv, Wv, H, W, n_out, virtual_render, uva, cam2virt, fill_channel, dL_dsample, dL_duv, dL_dvirtual, dL_duva, ws, s); }
+  LAUNCH_TRY(s, false, "resample_bwd");
+  return EOGS_OK;
+}
+
+}  // extern "C"

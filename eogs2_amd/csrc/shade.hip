@@ -7,23 +7,14 @@
 // a grid-stride loop (dword-coalesced planar loads), nothing is saved between forward and backward (the few values
 // backward needs are recomputed from the inputs), and every sum is reduced per workgroup and then by one small kernel in
 // a fixed order — no atomics, bitwise reproducible.
-#include "common.h"
+#include "api_util.h"
+#include "reduce.h"
 
 namespace {
 
 constexpr int ST = 256;        // threads per workgroup
 constexpr int SMAXBLK = 1024;  // workgroups per launch (4 per CU); partial sums live in the caller's workspace
 constexpr int SK = 16;         // floats per workgroup partial (15 used by shade_bwd)
-
-__device__ inline float wg_sum(float v, float* s_red) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) s_red[w] = v;
-  __syncthreads();
-  return s_red[0] + s_red[1] + s_red[2] + s_red[3];
-}
 
 inline int shade_blocks(int64_t n) {
   const int64_t b = (n + ST - 1) / ST;
@@ -182,7 +173,6 @@ __global__ __launch_bounds__(ST) void mloss_fwd_kernel(int64_t n, int mode, cons
   }
 }
 
-__device__ inline float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
 __global__ __launch_bounds__(ST) void mloss_bwd_kernel(int64_t n, int mode, const float* __restrict__ alt_diff,
                                                        const float* __restrict__ a, const float* __restrict__ b,
@@ -232,48 +222,119 @@ __global__ __launch_bounds__(ST) void tshadow_bwd_kernel(int64_t n, const float*
 
 }  // namespace
 
-size_t shade_ws_bytes() { return (size_t)SMAXBLK * SK * sizeof(float) + 256; }
+static size_t shade_ws_bytes() { return (size_t)SMAXBLK * SK * sizeof(float) + 256; }
 
-void launch_shade_fwd(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow, float* cc,
-                      float* shaded, float* shadow, hipStream_t s) {
-  const int64_t n = (int64_t)H * W;
-  hipLaunchKernelGGL(shade_fwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, raw, alt_diff, M, inshadow, cc, shaded, shadow);
+extern "C" {
+
+int eogs_shade_bytes(int H, int W, size_t* bytes) {
+  clear_error();
+  if (H <= 0 || W <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "shade_bytes: bad argument");
+  *bytes = shade_ws_bytes();
+  return EOGS_OK;
 }
 
-void launch_shade_bwd(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
-                      const float* g_shaded, const float* g_cc, const float* g_shadow, float* g_raw, float* g_alt,
-                      float* g_params, void* ws, hipStream_t s) {
+int eogs_shade_forward(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
+                       float* cc, float* shaded, float* shadow, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "shade_forward: bad sizes");
+  if (!raw || !M || !shaded) return fail(EOGS_ERR_INVALID_ARG, "shade_forward: NULL argument");
+  if ((alt_diff != nullptr) != (shadow != nullptr) || (alt_diff && !inshadow))
+    return fail(EOGS_ERR_INVALID_ARG, "shade_forward: alt_diff, inshadow and shadow go together");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t n = (int64_t)H * W;
+  {
+    ProfScope ps(PS_SHADE_FWD, s);
+    hipLaunchKernelGGL(shade_fwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, raw, alt_diff, M, inshadow, cc, shaded, shadow);
+  }
+  LAUNCH_TRY(s, false, "shade_fwd");
+  return EOGS_OK;
+}
+
+int eogs_shade_backward(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
+                        const float* g_shaded, const float* g_cc, const float* g_shadow, float* g_raw,
+                        float* g_alt_diff, float* g_params, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "shade_backward: bad sizes");
+  if (!raw || !M || !g_shaded || !g_raw || !g_params || !ws) return fail(EOGS_ERR_INVALID_ARG, "shade_backward: NULL argument");
+  if ((alt_diff != nullptr) != (g_alt_diff != nullptr) || (alt_diff && !inshadow) || (!alt_diff && g_shadow))
+    return fail(EOGS_ERR_INVALID_ARG, "shade_backward: alt_diff, inshadow and g_alt_diff go together");
+  if (ws_bytes < shade_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "shade_backward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   const int64_t n = (int64_t)H * W;
   const int nb = shade_blocks(n);
   float* partial = reinterpret_cast<float*>(ws_base(ws));
-  hipLaunchKernelGGL(shade_bwd_kernel, dim3(nb), dim3(ST), 0, s, n, raw, alt_diff, M, inshadow, g_shaded, g_cc, g_shadow, g_raw,
-                     g_alt, partial);
-  hipLaunchKernelGGL(shade_reduce_kernel<0>, dim3(1), dim3(ST), 0, s, partial, nb, 15, 1.f, g_params);
+  {
+    ProfScope ps(PS_SHADE_BWD, s);
+    hipLaunchKernelGGL(shade_bwd_kernel, dim3(nb), dim3(ST), 0, s, n, raw, alt_diff, M, inshadow, g_shaded, g_cc, g_shadow, g_raw,
+                       g_alt_diff, partial);
+    hipLaunchKernelGGL(shade_reduce_kernel<0>, dim3(1), dim3(ST), 0, s, partial, nb, 15, 1.f, g_params);
+  }
+  LAUNCH_TRY(s, false, "shade_bwd");
+  return EOGS_OK;
 }
 
-void launch_mloss_fwd(int H, int W, int mode, const float* alt_diff, const float* a, const float* b, const float* uv, float* out,
-                      void* ws, hipStream_t s) {
+int eogs_mloss_forward(int H, int W, int mode, const float* alt_diff, const float* rgb_a, const float* rgb_b,
+                       const float* uv, float* out, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0 || (mode != EOGS_MLOSS_SUN && mode != EOGS_MLOSS_RANDOM))
+    return fail(EOGS_ERR_INVALID_ARG, "mloss_forward: bad sizes or mode");
+  if (!alt_diff || !rgb_a || !rgb_b || !uv || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "mloss_forward: NULL argument");
+  if (ws_bytes < shade_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "mloss_forward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   const int64_t n = (int64_t)H * W;
   const int nb = shade_blocks(n);
   float* partial = reinterpret_cast<float*>(ws_base(ws));
-  hipLaunchKernelGGL(mloss_fwd_kernel, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, reinterpret_cast<const float2*>(uv), partial);
-  hipLaunchKernelGGL(shade_reduce_kernel<1>, dim3(1), dim3(ST), 0, s, partial, nb, 3, 1.f, out);
+  {
+    ProfScope ps(PS_MLOSS_FWD, s);
+    hipLaunchKernelGGL(mloss_fwd_kernel, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, rgb_a, rgb_b,
+                       reinterpret_cast<const float2*>(uv), partial);
+    hipLaunchKernelGGL(shade_reduce_kernel<1>, dim3(1), dim3(ST), 0, s, partial, nb, 3, 1.f, out);
+  }
+  LAUNCH_TRY(s, false, "mloss_fwd");
+  return EOGS_OK;
 }
 
-void launch_mloss_bwd(int H, int W, int mode, const float* alt_diff, const float* a, const float* b, const float* uv,
-                      const float* out, const float* upstream, float* g_alt, float* g_a, float* g_b, hipStream_t s) {
+int eogs_mloss_backward(int H, int W, int mode, const float* alt_diff, const float* rgb_a, const float* rgb_b,
+                        const float* uv, const float* out, const float* upstream, float* g_alt_diff, float* g_rgb_a,
+                        float* g_rgb_b, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0 || (mode != EOGS_MLOSS_SUN && mode != EOGS_MLOSS_RANDOM))
+    return fail(EOGS_ERR_INVALID_ARG, "mloss_backward: bad sizes or mode");
+  if (!alt_diff || !rgb_a || !rgb_b || !uv || !out || !upstream || !g_alt_diff || !g_rgb_a)
+    return fail(EOGS_ERR_INVALID_ARG, "mloss_backward: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
   const int64_t n = (int64_t)H * W;
-  hipLaunchKernelGGL(mloss_bwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, mode, alt_diff, a, b,
-                     reinterpret_cast<const float2*>(uv), out, upstream, g_alt, g_a, g_b);
+  {
+    ProfScope ps(PS_MLOSS_BWD, s);
+    hipLaunchKernelGGL(mloss_bwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, mode, alt_diff, rgb_a, rgb_b,
+                       reinterpret_cast<const float2*>(uv), out, upstream, g_alt_diff, g_rgb_a, g_rgb_b);
+  }
+  LAUNCH_TRY(s, false, "mloss_bwd");
+  return EOGS_OK;
 }
 
-void launch_tshadow_fwd(int64_t n, const float* a, float* out, void* ws, hipStream_t s) {
+int eogs_tshadow_forward(int64_t n, const float* a, float* out, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (n <= 0) return fail(EOGS_ERR_INVALID_ARG, "tshadow_forward: bad size");
+  if (!a || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "tshadow_forward: NULL argument");
+  if (ws_bytes < shade_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "tshadow_forward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   const int nb = shade_blocks(n);
   float* partial = reinterpret_cast<float*>(ws_base(ws));
   hipLaunchKernelGGL(tshadow_fwd_kernel, dim3(nb), dim3(ST), 0, s, n, a, partial);
   hipLaunchKernelGGL(shade_reduce_kernel<2>, dim3(1), dim3(ST), 0, s, partial, nb, 1, 1.f / (float)n, out);
+  LAUNCH_TRY(s, false, "tshadow_fwd");
+  return EOGS_OK;
 }
 
-void launch_tshadow_bwd(int64_t n, const float* a, const float* upstream, float* g_a, hipStream_t s) {
+int eogs_tshadow_backward(int64_t n, const float* a, const float* upstream, float* g_a, void* stream) {
+  clear_error();
+  if (n <= 0) return fail(EOGS_ERR_INVALID_ARG, "tshadow_backward: bad size");
+  if (!a || !upstream || !g_a) return fail(EOGS_ERR_INVALID_ARG, "tshadow_backward: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(tshadow_bwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, a, upstream, g_a);
+  LAUNCH_TRY(s, false, "tshadow_bwd");
+  return EOGS_OK;
 }
+
+}  // extern "C"

@@ -12,7 +12,7 @@
 //   prior     TSDFVolume.apply_prior (tsdf.py:602-638), two launches: one wave per (x, y) column writes a state byte per
 //             voxel and the column's top occupied z; then one lane per voxel applies the rules from the state bytes only.
 //   surface   TSDFVolume.extract_dsm up to plyflatten (tsdf.py:530-562): one wave per column, top-down 64-voxel chunks.
-#include "common.h"
+#include "api_util.h"
 
 namespace {
 
@@ -256,45 +256,102 @@ __global__ __launch_bounds__(256) void tsdf_surface_kernel(int64_t ncol, int nz,
 
 }  // namespace
 
-void launch_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,
-                           float scale, float trunc, int H, int W, const float* alt, const float* wgt, float* tsdf,
-                           float* wvol, hipStream_t s) {
-  const size_t n = (size_t)nx * ny * nz;
-  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nx, ny, nz, ax, ay, az, affine,
-                     scale, trunc, H, W, alt, wgt, tsdf, wvol);
-}
-
-void launch_tsdf_normals(int H, int W, const float* alt, const float* affine, const float* view_dir, float* normals, float* angle,
-                         float* weights, hipStream_t s) {
-  const size_t hw = (size_t)H * W;
-  // torch.tensor([1 / W, 1 / H, 1]) (tsdf.py:256): the Python quotients rounded once to fp32
-  const float rW = (float)(1.0 / W), rH = (float)(1.0 / H);
-  hipLaunchKernelGGL(tsdf_normals_kernel, dim3((unsigned)((hw + 255) / 256)), dim3(256), 0, s, H, W, rW, rH, alt, affine, view_dir,
-                     normals, angle, weights);
-}
-
 static unsigned column_blocks(int64_t ncol) {  // 4 waves per block, grid-stride beyond 2^20 blocks
   const int64_t b = (ncol + 3) / 4;
   return (unsigned)(b < (1 << 20) ? b : (1 << 20));
 }
 
-size_t tsdf_prior_ws_bytes(int nx, int ny, int nz) {  // state bytes (256-aligned) + int32 top per column
+static size_t tsdf_prior_ws_bytes(int nx, int ny, int nz) {  // state bytes (256-aligned) + int32 top per column
   const size_t n = (size_t)nx * ny * nz;
   return ((n + 255) / 256) * 256 + 4 * (size_t)nx * ny;
 }
 
-void launch_tsdf_prior(int nx, int ny, int nz, float* tsdf, float* wvol, void* ws, hipStream_t s) {
+extern "C" {
+
+int eogs_tsdf_integrate(int nx, int ny, int nz, const float* ax, const float* ay, const float* az, const float* affine,
+                        float model_scale, float trunc_margin, int H, int W, const float* altitude, const float* weight,
+                        float* tsdf_vol, float* weight_vol, void* stream) {
+  clear_error();
+  if (nx < 0 || ny < 0 || nz < 0 || H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "tsdf_integrate: bad sizes");
+  if ((size_t)nx * ny * nz == 0) return EOGS_OK;
+  if ((uint64_t)nx * ny * nz > ((uint64_t)1 << 40)) return fail(EOGS_ERR_OVERFLOW, "tsdf_integrate: volume too large");
+  if (!ax || !ay || !az || !affine || !altitude || !weight || !tsdf_vol || !weight_vol)
+    return fail(EOGS_ERR_INVALID_ARG, "tsdf_integrate: NULL argument");
+  if (!(model_scale != 0.f) || !(trunc_margin > 0.f)) return fail(EOGS_ERR_INVALID_ARG, "tsdf_integrate: bad scale or truncation");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t n = (size_t)nx * ny * nz;
+  {
+    ProfScope ps(PS_TSDF, s);
+    hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, nx, ny, nz, ax, ay, az, affine,
+                       model_scale, trunc_margin, H, W, altitude, weight, tsdf_vol, weight_vol);
+  }
+  LAUNCH_TRY(s, false, "tsdf_integrate");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_normals(int H, int W, const float* altitude, const float* affine, const float* view_dir, float* normals, float* angle,
+                      float* weights, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "tsdf_normals: bad sizes");
+  if (!altitude || !affine || !view_dir || !angle) return fail(EOGS_ERR_INVALID_ARG, "tsdf_normals: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  const size_t hw = (size_t)H * W;
+  // torch.tensor([1 / W, 1 / H, 1]) (tsdf.py:256): the Python quotients rounded once to fp32
+  const float rW = (float)(1.0 / W), rH = (float)(1.0 / H);
+  {
+    ProfScope ps(PS_TSDF_NORMALS, s);
+    hipLaunchKernelGGL(tsdf_normals_kernel, dim3((unsigned)((hw + 255) / 256)), dim3(256), 0, s, H, W, rW, rH, altitude, affine,
+                       view_dir, normals, angle, weights);
+  }
+  LAUNCH_TRY(s, false, "tsdf_normals");
+  return EOGS_OK;
+}
+
+int eogs_tsdf_prior_bytes(int nx, int ny, int nz, size_t* bytes) {
+  clear_error();
+  if (nx < 0 || ny < 0 || nz < 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "tsdf_prior_bytes: bad argument");
+  if ((uint64_t)nx * ny * nz > ((uint64_t)1 << 40)) return fail(EOGS_ERR_OVERFLOW, "tsdf_prior_bytes: volume too large");
+  *bytes = tsdf_prior_ws_bytes(nx, ny, nz);
+  return EOGS_OK;
+}
+
+int eogs_tsdf_prior(int nx, int ny, int nz, float* tsdf_vol, float* weight_vol, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (nx < 0 || ny < 0 || nz < 0) return fail(EOGS_ERR_INVALID_ARG, "tsdf_prior: bad sizes");
+  if ((size_t)nx * ny * nz == 0) return EOGS_OK;
+  if ((uint64_t)nx * ny * nz > ((uint64_t)1 << 40)) return fail(EOGS_ERR_OVERFLOW, "tsdf_prior: volume too large");
+  if (!tsdf_vol || !weight_vol || !ws) return fail(EOGS_ERR_INVALID_ARG, "tsdf_prior: NULL argument");
+  if (ws_bytes < tsdf_prior_ws_bytes(nx, ny, nz)) return fail(EOGS_ERR_WORKSPACE, "tsdf_prior: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)nx * ny * nz;
   const int64_t ncol = (int64_t)nx * ny;
   unsigned char* state = (unsigned char*)ws;
   int* top = (int*)(state + ((n + 255) / 256) * 256);
-  hipLaunchKernelGGL(tsdf_prior_state_kernel, dim3(column_blocks(ncol)), dim3(256), 0, s, ncol, nz, tsdf, wvol, state, top);
   const size_t b = (n + 255) / 256;
-  hipLaunchKernelGGL(tsdf_prior_apply_kernel, dim3((unsigned)(b < (1u << 20) ? b : (1u << 20))), dim3(256), 0, s, nx, ny, nz, state,
-                     top, tsdf, wvol);
+  {
+    ProfScope ps(PS_TSDF_PRIOR, s);
+    hipLaunchKernelGGL(tsdf_prior_state_kernel, dim3(column_blocks(ncol)), dim3(256), 0, s, ncol, nz, tsdf_vol, weight_vol, state, top);
+    hipLaunchKernelGGL(tsdf_prior_apply_kernel, dim3((unsigned)(b < (1u << 20) ? b : (1u << 20))), dim3(256), 0, s, nx, ny, nz, state,
+                       top, tsdf_vol, weight_vol);
+  }
+  LAUNCH_TRY(s, false, "tsdf_prior");
+  return EOGS_OK;
 }
 
-void launch_tsdf_surface(int nx, int ny, int nz, const float* tsdf, const float* az, int64_t* index, float* height, hipStream_t s) {
+int eogs_tsdf_surface(int nx, int ny, int nz, const float* tsdf_vol, const float* az, int64_t* index, float* height, void* stream) {
+  clear_error();
+  if (nx < 0 || ny < 0 || nz <= 0) return fail(EOGS_ERR_INVALID_ARG, "tsdf_surface: bad sizes");
+  if ((size_t)nx * ny == 0) return EOGS_OK;
+  if ((uint64_t)nx * ny * nz > ((uint64_t)1 << 40)) return fail(EOGS_ERR_OVERFLOW, "tsdf_surface: volume too large");
+  if (!tsdf_vol || !az || !index) return fail(EOGS_ERR_INVALID_ARG, "tsdf_surface: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
   const int64_t ncol = (int64_t)nx * ny;
-  hipLaunchKernelGGL(tsdf_surface_kernel, dim3(column_blocks(ncol)), dim3(256), 0, s, ncol, nz, tsdf, az, index, height);
+  {
+    ProfScope ps(PS_TSDF_SURFACE, s);
+    hipLaunchKernelGGL(tsdf_surface_kernel, dim3(column_blocks(ncol)), dim3(256), 0, s, ncol, nz, tsdf_vol, az, index, height);
+  }
+  LAUNCH_TRY(s, false, "tsdf_surface");
+  return EOGS_OK;
 }
+
+}  // extern "C"
