@@ -15,6 +15,7 @@ from . import density  # noqa: F401,E402  (densification statistics and one-pass
 from . import dsm_eval  # noqa: F401,E402  (DSM registration and MAE: eval/dsmr.py, eval/eval_dsm.py)
 from . import dsm_raster  # noqa: F401,E402  (cloud / view / TSDF surface -> DSM: utils/dsm_utils.py, tsdf.py:530-600)
 from . import flow  # noqa: F401,E402  (flow-matching warp, statistics and criteria: flowmatching/flow_matching.py)
+from . import mesh  # noqa: F401,E402  (marching cubes over the TSDF volume: tsdf.py:522-528 without mcubes)
 from . import monitor  # noqa: F401,E402  (training monitor: interval means, PSNR/SSIM, early stopper: train_pan.py:423-597)
 from . import regularizers  # noqa: F401,E402  (opacity, effective-rank, TV and accumulated-opacity terms: loss/opacity.py, main_loss.py)
 

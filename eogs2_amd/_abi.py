@@ -203,6 +203,16 @@ DSM_SIGNATURES = {
     "eogs_dsm_raster_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
     "eogs_dsm_raster": (_i, [_p, C.c_double, C.c_double, C.c_double, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
 }
+# include/eogs_mesh.h, a table of its own for the same reason
+MESH_SIGNATURES = {
+    "eogs_mesh_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+    "eogs_mesh_count": (_i, [_i, _i, _i, _p, C.c_double, _p, _z, _p, _p]),
+    "eogs_mesh_emit": (_i, [_i, _i, _i, _p, C.c_double, _p, _p, _p, C.POINTER(C.c_double), _p, _z, _p, _i64, _p, _i64, _p]),
+    "eogs_mesh_case": (_i, [_i, C.POINTER(C.c_int8), C.POINTER(_i)]),
+}
+MESH_MAX_VERTICES = 1 << 29  # EOGS_MESH_MAX_VERTICES
+MESH_WG_VOXELS = 256  # EOGS_MESH_WG_VOXELS
+MESH_SCAN_ROUND = 256  # EOGS_MESH_SCAN_ROUND
 DSM_Z_QUANTUM = 2.0 ** -20  # EOGS_DSM_Z_QUANTUM
 DSM_Z_MAX = 32768.0  # EOGS_DSM_Z_MAX
 DSM_MAX_RADIUS = 4  # EOGS_DSM_MAX_RADIUS
@@ -229,7 +239,8 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_density_bytes", "eogs_density_decide", "eogs_density_split_rows", "eogs_density_build", "eogs_step_gate",
             "eogs_step_adam_bytes", "eogs_step_adam", "eogs_monitor_state_bytes", "eogs_monitor_reset", "eogs_monitor_observe_bytes",
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
-            "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster")
+            "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
+            "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case")
 
 
 class PackTensor(C.Structure):
@@ -321,7 +332,8 @@ class RastABI:
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
-                                  *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items()):
+                                  *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
+                                  *MESH_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -339,7 +351,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

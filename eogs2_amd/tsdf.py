@@ -13,6 +13,7 @@ The stages around integrate are HIP as well:
   TSDFVolume.surface()               tsdf.py:530-536: the top-most voxel with t < 0 per column and its height
   TSDFVolume.surface_cloud(sp)       tsdf.py:538-556: the float64 point cloud the reference hands to plyflatten
   TSDFVolume.extract_dsm(sp, res)    tsdf.py:530-600 without the file write: the surface rasterised on the device
+  TSDFVolume.extract_mesh(path)      tsdf.py:522-528 without mcubes: marching cubes on the device (eogs2_amd.mesh)
 No CPU / eager fallback: CPU tensors raise.
 """
 import ctypes
@@ -21,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _lib, dsm_raster
+from . import _lib, dsm_raster, mesh
 from .rasterizer import _Ctx, _ptr
 
 
@@ -74,6 +75,19 @@ class TSDFVolume:
         bounds of those points (the one host wait). The profile is dsm_raster.make_profile's plain dict."""
         _, height = self.surface()
         return dsm_raster.dsm_from_surface(height, self.axes[0], self.axes[1], scene_params, resolution)
+
+    def extract_mesh(self, output_mesh_path=None, *, coords="index", scene_params=None, iso=0.0):
+        """tsdf.py:522-528 without mcubes: (vertices float64 [NV, 3], triangles int32 [NT, 3]) on the device, and the OBJ
+        file when a path is given. coords="index": voxel units, what `mcubes.marching_cubes(vol, 0)` returns;
+        coords="world": interpolated between the volume's fp32 axes. `scene_params[0]` is added in double when given, as
+        surface_cloud and extract_dsm add it. Semantics and ordering: include/eogs_mesh.h."""
+        if coords not in ("index", "world"):
+            raise ValueError(f"tsdf extract_mesh: coords is 'index' or 'world', not {coords!r}")
+        vertices, triangles = mesh.marching_cubes(self._tsdf_vol, iso, axes=self.axes if coords == "world" else None,
+                                                  shift=None if scene_params is None else scene_params[0])
+        if output_mesh_path is not None:
+            mesh.export_obj(vertices, triangles, output_mesh_path)
+        return vertices, triangles
 
 
 class RangeImage:
