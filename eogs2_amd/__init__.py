@@ -18,5 +18,6 @@ from . import flow  # noqa: F401,E402  (flow-matching warp, statistics and crite
 from . import mesh  # noqa: F401,E402  (marching cubes over the TSDF volume: tsdf.py:522-528 without mcubes)
 from . import monitor  # noqa: F401,E402  (training monitor: interval means, PSNR/SSIM, early stopper: train_pan.py:423-597)
 from . import regularizers  # noqa: F401,E402  (opacity, effective-rank, TV and accumulated-opacity terms: loss/opacity.py, main_loss.py)
+from . import reset  # noqa: F401,E402  (shadow-based colour reset, in-place opacity reset, render_all_views: color_reset_op.py)
 
 __version__ = "0.1.0"

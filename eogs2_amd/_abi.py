@@ -210,6 +210,16 @@ MESH_SIGNATURES = {
     "eogs_mesh_emit": (_i, [_i, _i, _i, _p, C.c_double, _p, _p, _p, C.POINTER(C.c_double), _p, _z, _p, _i64, _p, _i64, _p]),
     "eogs_mesh_case": (_i, [_i, C.POINTER(C.c_int8), C.POINTER(_i)]),
 }
+# include/eogs_reset.h, a table of its own for the same reason
+RESET_SIGNATURES = {
+    "eogs_reset_erode": (_i, [_i, _i, _p, _p, _p]),
+    "eogs_reset_flags": (_i, [_i64, _p, _p, _f, _i, _p, _i, _p, _p]),
+    "eogs_reset_rows": (_i, [_i64, _p, _i, _p, _p]),
+    "eogs_reset_opacity_cap": (_i, [_i64, _p, _p, _p, _f, _f, _p]),
+}
+RESET_MAX_VIEWS = RESET_MAX_TENSORS = 16  # EOGS_RESET_MAX_*
+RESET_MAX_ROW_ELEMS = 64  # EOGS_RESET_MAX_ROW_ELEMS
+RESET_TILE_H, RESET_TILE_W = 32, 64  # EOGS_RESET_TILE_*: pixels per workgroup of eogs_reset_erode
 MESH_MAX_VERTICES = 1 << 29  # EOGS_MESH_MAX_VERTICES
 MESH_WG_VOXELS = 256  # EOGS_MESH_WG_VOXELS
 MESH_SCAN_ROUND = 256  # EOGS_MESH_SCAN_ROUND
@@ -240,7 +250,8 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_step_adam_bytes", "eogs_step_adam", "eogs_monitor_state_bytes", "eogs_monitor_reset", "eogs_monitor_observe_bytes",
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
             "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
-            "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case")
+            "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case", "eogs_reset_erode", "eogs_reset_flags", "eogs_reset_rows",
+            "eogs_reset_opacity_cap")
 
 
 class PackTensor(C.Structure):
@@ -317,6 +328,18 @@ class DsmBounds(C.Structure):
                 ("count", _i64)]
 
 
+class ResetView(C.Structure):
+    """eogs_reset_view (include/eogs_reset.h)"""
+
+    _fields_ = [("eroded", _p), ("affine", _p), ("H", _i), ("W", _i)]
+
+
+class ResetTensor(C.Structure):
+    """eogs_reset_tensor (include/eogs_reset.h)"""
+
+    _fields_ = [("data", _p), ("row_elems", _i), ("value", _f)]
+
+
 class RastError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -333,7 +356,7 @@ class RastABI:
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
                                   *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
-                                  *MESH_SIGNATURES.items()):
+                                  *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -351,7 +374,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -23,6 +23,8 @@ loss runs on the one PAN plane; `--pan-first` is the reference's `weird_pan_setu
 train_pan.py:423-429,471-495,512-597): every iteration feeds it without a wait, every 10 iterations one record is fetched and printed.
 `--dsm-mae-every N` scores the view's altitude against the unperturbed scene's (`eogs2_amd.dsm_eval.dsm_mae`); with `--dsm-resolution R`
 both are first flattened into DSMs on the device (`eogs2_amd.dsm_raster.dsm_from_view`): render -> DSM -> registered MAE.
+`--opacity-reset-every N` and `--color-reset-at N` are the two resets near the end of the reference's iteration (train_pan.py:726-736)
+in place (`eogs2_amd.reset.reset_opacity_`, `color_reset`): no tensor is replaced, so a recorded step keeps replaying across them.
 """
 import argparse
 import math
@@ -39,6 +41,7 @@ from eogs2_amd.losses import photometric_loss  # noqa: E402
 from eogs2_amd.density import DensityStats, densify_and_prune  # noqa: E402
 from eogs2_amd.optim import FusedAdam, alive_rows, prune_optimizer, retire_rows  # noqa: E402
 from eogs2_amd.rasterizer import captured_gate  # noqa: E402
+from eogs2_amd.reset import color_reset, reset_opacity_  # noqa: E402
 from eogs2_amd.render import render  # noqa: E402
 from eogs2_amd.graph import Branches  # noqa: E402
 from eogs2_amd.resample import render_resample_virtual_camera, resample  # noqa: E402
@@ -208,6 +211,16 @@ def main(argv=None):
                          "photometric loss's own L1 and SSIM, the PSNR, the mean opacity and the two moving averages go into a device "
                          "buffer without a wait (inside the recorded step with --graph, behind the same gate as the optimizers); every "
                          f"{MONITOR_INTERVAL} iterations (tb_log_interval) the interval is closed and ONE record is fetched and printed. Off by default")
+    ap.add_argument("--opacity-reset-every", type=int, default=0, metavar="N",
+                    help="every N iterations the reference's reset_opacity (train_pan.py:726-732, gaussian_model.py:347-352; every 3000 "
+                         "iterations in its flagship configuration) in place: eogs2_amd.reset.reset_opacity_ caps the logits at logit(0.01) "
+                         "and clears the group's Adam moments in one launch, and replaces no tensor, so with --graph the recorded step "
+                         "keeps replaying (main.last_recordings counts the recordings of the run). 0 = off")
+    ap.add_argument("--color-reset-at", type=int, default=0, metavar="N",
+                    help="at iteration N the reference's shadow-based colour reset (train_pan.py:733-736, color_reset_op.py; off in its "
+                         "shipped configuration): eogs2_amd.reset.color_reset renders the training view with render_all_views, erodes its "
+                         "shadow map, samples it at every Gaussian and resets opacity, colour and scale of the flagged rows and their "
+                         "moments in place; no wait for the device and, with --graph, no new recording. 0 = off")
     ap.add_argument("--early-stop-patience", type=int, default=None, metavar="N",
                     help="with --monitor: the reference's early stopper (utils/callback_utils.py) with patience N intervals; the run "
                          "ends at the interval whose record carries the flag. Default: no early stopping (use_early_stopping: False)")
@@ -422,6 +435,19 @@ def main(argv=None):
             kept["altitude"] = out["render"][3].detach()  # (under --graph: the recorded step's output tensor, refilled by a replay)
         return loss.detach(), out.get("radii"), out["viewspace_points"].grad
 
+    reset_cameras = []
+    if a.color_reset_at:  # what render_all_views reads from a training camera (renderer_cc_shadow.py:148-193), over this example's pieces
+        rc = Camera(cam.affine, H, W)
+        rc.image_name = "view"
+        rc.altitude_bounds = torch.stack((bg[3], bg[3]))  # (the lower bound becomes the altitude background, without a readback)
+        rc.UV_grid = (U, V)
+        uva2sun = cam2sun.clone()
+        uva2sun[:2, 2] /= 350.0  # render_all_views stacks the altitude itself, view() the altitude / 350: the same product
+        rc.get_sun_camera = lambda: (sun, uva2sun)
+        rc.render_pipeline = lambda raw_render, sun_altitude_diff=None: pipeline(cc_cam, raw_render, sun_altitude_diff)
+        reset_cameras = [rc]
+    reset_log = []  # (iteration, which reset, recordings of the step so far)
+    recordings = 0
     kept, dsm_scores = {}, []  # --dsm-mae-every: the view's altitude of the last step; (iteration, dx, dy, mae)
     first = last = None
     stopped_at = 0  # --monitor --early-stop-patience: the iteration whose record carried the flag
@@ -449,8 +475,10 @@ def main(argv=None):
                 from eogs2_amd.graph import GraphedStep
 
                 step = GraphedStep(fwd_bwd, warmup=1)  # (the eager warm-up run changes nothing: no optimizer step inside)
+                recordings += 1
             elif stale:
                 step.record_again()  # new parameter tensors, new shapes (fwd_bwd reads them from `model`); same memory pool
+                recordings += 1
             stale = False
             loss, radii, vs_grad = step()
         else:
@@ -491,6 +519,15 @@ def main(argv=None):
                 elif not bool(keep.all()):
                     model.prune(keep)
                     stale = True  # new parameter tensors, new shapes: record again
+        # train_pan.py:726-736, in place: the parameters and moments the recorded step reads keep their addresses
+        if a.opacity_reset_every and it % a.opacity_reset_every == 0:
+            reset_opacity_(model.optimizer)
+            reset_log.append((it, "opacity", recordings + (step.recaptures if step is not None else 0)))
+        if a.color_reset_at and it == a.color_reset_at:
+            flagged = color_reset(model, reset_cameras, pipe)
+            reset_log.append((it, "color", recordings + (step.recaptures if step is not None else 0)))
+            if not a.quiet:
+                print(f"iter {it:4d}  colour reset: {int(flagged.sum())} of {flagged.numel()} Gaussians")
         if a.dsm_mae_every and it % a.dsm_mae_every == 0:
             if dsm_geometry is not None:  # render -> DSM -> registered MAE, all on the device
                 _, pred_dsm = dsm_from_view(kept["altitude"], dsm_cam, dsm_scene, a.dsm_resolution, geometry=dsm_geometry)
@@ -531,6 +568,10 @@ def main(argv=None):
     main.last_ms_per_iter = (t1 - t_steady) / timed * 1e3  # steady state: the last half of the run
     main.last_dsm_mae = dsm_scores
     main.last_stamps, main.last_step = stamps, step  # (step: the GraphedStep of --graph, else None)
+    # --graph: how often the step was recorded (the first recording, after a prune, after an outgrown replay), and what the
+    # count was at each reset: a reset that forced a recording would show as a larger count at the end or at the next reset
+    main.last_recordings = recordings + (step.recaptures if step is not None else 0)
+    main.last_resets = reset_log
     main.last_params = None
     if a.densify_every:  # what callers compare between runs, beside the returned tuple
         main.last_params = {g["name"]: g["params"][0].detach().cpu() for g in model.optimizer.param_groups}
