@@ -580,11 +580,18 @@ struct GaussBwdArgs {
   int lead_cols;
   bool alt_only;           // the records are those of an altitude-only render (REC_ALT)
   int noflag_ok;           // render_bwd_noflag_ok(): the records are flag-free (bit 0) where the scene allows / always (bit 1)
-  int wide;                // records in flight per lane: gaussian_bwd_kernel's WIDE (0, 1, 2), gaussian_bwd_wide()
+  int wide;                // gaussian_bwd_kernel's WIDE, gaussian_bwd_wide(): records in flight per lane (0, 1, 2) or the streaming build (3)
 };
 // Which gaussian_bwd_kernel variant a backward of (R, P) launches (token bit 60: the forward's lists are shallow in opacity).
-// EOGS_GB_WIDE=0|1|2 forces one.
+// EOGS_GB_WIDE=0|1|2|3 forces one. 3, the build that streams each workgroup's records through LDS, takes the place of 1 (shallow
+// lists, fewer than six listed tiles per Gaussian: the headline) from GB_STREAM_MIN_P Gaussians on: a streaming workgroup walks
+// its chunks one round trip after the other, which only other workgroups hide — 2^19 Gaussians are two rounds of the four
+// workgroups that each of the 256 CUs holds. Measured at 2^20 (profiles/r07_ab_gaussian_bwd_stream.txt); longer lists keep 2.
 #define GB_WIDE_DEPTH 256.0f
+#define GB_STREAM_MIN_P (1 << 19)
+// records per chunk of the streaming build's LDS ring: 12 KiB per stage (8 KiB of 32-byte records), three (two) 16-byte loads
+// per lane, and the chunk's 256 flags one dword per lane of one wave
+#define GB_CHUNK 256u
 int gaussian_bwd_wide(int64_t R, int P);
 // per-Gaussian backward over rows [p_begin, p_end) (p_begin a multiple of BLK); the camera sums are finished by the call
 // whose p_end == P

@@ -120,6 +120,27 @@ __device__ inline float raw_activate(float s[3], float q[4], bool* clamped = nul
 #define GB_COOP 64u
 #endif
 
+// LDS of gaussian_bwd_kernel that depends on the build. The gather builds (WIDE 0, 1, 2) park the workgroup's rows of means3D /
+// scales; the streaming build (WIDE 3) has its two-stage ring of record chunks (GB_CHUNK records each, lane-linear: float4 j of
+// a chunk at float4 j of its stage) and the chunks' flags, and parks the rows in the ring once the last chunk is summed.
+template <bool STREAM, bool ALT>
+struct GaussBwdLds {
+  float m[3 * BLK], s[3 * BLK];
+  __device__ float* rows_m() { return m; }
+  __device__ float* rows_s() { return s; }
+};
+template <bool ALT>
+struct GaussBwdLds<true, ALT> {
+  static constexpr uint32_t RQ = (ALT ? REC_ALT : REC) / 4;  // quarters (float4) per record
+  static constexpr uint32_t CH4 = GB_CHUNK * RQ;             // quarters per stage
+  static_assert(CH4 % BLK == 0 && GB_CHUNK == 4 * 64, "a stage is whole 16-byte-per-lane loads of the workgroup; its flags one dword per lane of a wave");
+  static_assert(2 * CH4 * 4 >= 6 * BLK, "the rows of means3D and scales fit in the ring");
+  alignas(16) float ring[2 * CH4 * 4];
+  uint32_t live[2][GB_CHUNK / 4];
+  __device__ float* rows_m() { return ring; }
+  __device__ float* rows_s() { return ring + 3 * BLK; }
+};
+
 }  // namespace
 
 // RAW (EOGS_FLAG_RAW_PARAMS): scales/rotations/opacities/colors are the model's raw parameters; the activations and
@@ -446,6 +467,16 @@ void launch_preprocess_fwd(const FwdPrepArgs& a, const GeomWS& g, hipStream_t s)
 // 2048^2 (9.5) 0.1823 / 0.1544 / 0.1455; 2 M at opacity 0.1 (6.6) 0.2134 / 0.1912 / 0.1887; trained opacities (10.8 listed, most
 // of them dead: flags first, few records) 0.0787 / 0.0827 / 0.0826 — there the seven waves hide the flags -> records chain better
 // than more loads per lane do.
+// 3: the streaming build. The gather builds learn a lane's slot only behind radii / binfo / pblock and then read its 48-byte
+// records through twelve loads whose lanes lie 48 n bytes apart (each 128-byte line requested about eight times). Here the
+// workgroup reads its whole region [pblock[blk], pblock[blk + 1]) — two words that depend on nothing — in chunks of GB_CHUNK
+// records, one KiB of contiguous memory per wave instruction, through a two-stage LDS ring (GaussBwdLds), and every lane adds its
+// own records out of the ring in list order: the same additions in the same order. LDS budget: ring 2 x 12 KiB + 512 B of flags +
+// s_coop 11 KiB + s_red = 36,640 B (28,448 B with 32-byte records): FOUR workgroups per CU (five), the four (five) waves per
+// SIMD the wide builds have — chosen over a three-stage ring (three workgroups) and over keeping s_m / s_s beside the ring
+// (42.8 KB, three workgroups): the rows are parked in the ring after its last chunk. 64 VGPRs; it is the LDS that bounds the
+// waves. One chunk per workgroup is in flight while the one before it is summed (4 x 12 KiB per CU). ms and the decision:
+// below at gaussian_bwd_wide().
 // ALT: the records of an altitude-only render (32 bytes, common.h REC_ALT): only colour 3 has a gradient.
 // (the wide builds sit exactly at the 128 VGPRs that four waves per SIMD leave: said to the compiler, which otherwise takes a
 // 129th for the cooperative section's sake and loses the wave)
@@ -462,8 +493,10 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
     float* __restrict__ dL_drotations, bool want_T, bool want_vm, float* __restrict__ vmpart, uint32_t blk0,
     float* __restrict__ dL_dcolors_lead, int lead_cols, const uint32_t* __restrict__ misc, uint32_t cap_slots,
     uint32_t cap_entries, int noflag_ok) {
-  __shared__ float s_m[3 * BLK];
-  __shared__ float s_s[3 * BLK];
+  constexpr bool STREAM = WIDE == 3;
+  __shared__ GaussBwdLds<STREAM, ALT> s_l;
+  float* const s_m = s_l.rows_m();
+  float* const s_s = s_l.rows_s();
   __shared__ float s_red[BLK / 64][18];
   __shared__ float s_coop[11][BLK];  // record sums of the Gaussians the waves summed cooperatively (GB_COOP)
   // A forward queued on a capacity token (EOGS_FLAG_DEFER_COUNTS) that needed more than its workspaces hold has built no
@@ -471,6 +504,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
   // comparison here: such a backward reads none of them and returns zero gradients (the host repeats the forward).
   constexpr uint32_t GB_DIRECT = WIDE == 2 ? 8u : 4u;  // listed tiles up to which flags and records are read in one trip
   constexpr bool GB_WIDE = WIDE != 0;
+  static_assert(WIDE >= 0 && WIDE <= 3, "narrow, two wide builds, the streaming build");
   const bool fits = misc[MISC_TOTAL_HI] == 0u && misc[MISC_MACRO_HI] == 0u && misc[MISC_TOTAL_LO] <= cap_slots &&
                     misc[MISC_MACRO_LO] <= cap_entries;
   // Where tiles saturate (trained opacities: a tile's pixels stop after a tenth of its list) most listed pairs are DEAD — behind
@@ -509,7 +543,11 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
 
   int radius_in = 0;
   uint4 bi1 = make_uint4(0u, 0u, 0u, 0u);
-  uint32_t pb = 0;
+  uint32_t pb = 0, pe = 0;
+  if (STREAM) {  // the workgroup's region of record slots, [pb, pe): two words that depend on no other load (pblock[nblk]: the scan's total)
+    pb = pblock[blk];
+    pe = pblock[blk + 1];
+  }
   if (t < rows) {
     // Round 4: everything that does not depend on another load is requested up front (the kernel waited 45 % of its wave
     // time, profiles/r03_v30: radii -> binfo -> flags -> records -> rotation / opacity was a chain of five dependent round
@@ -519,7 +557,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
     // but only ever selected away — and only longer lists take the two-trip form (flags, then the live records alone).
     radius_in = radii[idx];
     bi1 = binfo[(size_t)P + idx];  // (its own plane: this kernel reads 16 of a Gaussian's 32 bytes, and fetched all 32 while they shared a line)
-    pb = pblock[blk];
+    if (!STREAM) pb = pblock[blk];
     if (!cov3D_precomp) rot_in = reinterpret_cast<const float4*>(rotations)[idx];
     if (RAW || antialiasing) op_raw = opacities[idx];
   }
@@ -584,7 +622,7 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
     }
   }
 
-  {
+  if constexpr (!STREAM) {
     if (visible) {
       // fixed-order sum of this Gaussian's (tile,Gaussian) records: deterministic, no atomics
       const uint32_t n = is_big ? 0u : n_all;
@@ -695,6 +733,96 @@ __global__ __launch_bounds__(BLK) __attribute__((amdgpu_waves_per_eu(WIDE ? (ALT
         }
       }
     }
+  } else {
+    // ---- the streaming build: the workgroup's records pass through LDS in chunks, fetched as consecutive 16-byte-per-lane loads ----
+    // The region [pb, pe) is walked in chunks of GB_CHUNK records. A chunk is fetched by global -> LDS loads whose wave
+    // instruction covers 1 KiB of contiguous memory (every line requested once, where the gather builds request a line about
+    // eight times through 48 n-byte strides), into the stage the previous chunk but one has left; while it is in flight the
+    // lanes add those of their own records that lie in the chunk before it, in list order. Chunks arrive in ascending slot
+    // order, so every Gaussian's sum is the serial sum of the gather builds: the same additions, the same bits. Dead pairs'
+    // records (never-written memory) and the slots of the Gaussians summed cooperatively above pass through the ring and are
+    // selected away / left alone. Everything the barriers depend on is workgroup-uniform: `fits`, pb, pe.
+    (void)dlim;
+    constexpr uint32_t RQ = GaussBwdLds<true, ALT>::RQ, CH4 = GaussBwdLds<true, ALT>::CH4;
+    const uint32_t L = (fits && pe > pb) ? pe - pb : 0u;  // (a forward that did not fit wrote no record: nothing is read)
+    const uint32_t nch = (L + GB_CHUNK - 1u) / GB_CHUNK;
+    const float4* rsrc = reinterpret_cast<const float4*>(records) + (size_t)pb * RQ;
+    const uint32_t last4 = L * RQ - 1u;  // the region's last quarter: addresses are clamped to it (used while nch > 0 only)
+    uint32_t fl_next = 0;
+    auto fetch = [&](uint32_t k) {
+      const uint32_t st = k & 1u;
+#pragma unroll
+      for (uint32_t i = 0; i < CH4 / BLK; i++) {
+        const uint32_t j = k * CH4 + i * BLK + (uint32_t)t;
+        const float4* src = rsrc + (j < last4 ? j : last4);
+        // The LDS image is lane-linear: M0 holds the wave's base and the hardware adds 16 bytes per lane. Written as the
+        // instruction itself, not as __builtin_amdgcn_global_load_lds: the compiler orders every LDS read behind a builtin's
+        // pending LDS write with vmcnt(0), which would drain chunk k + 1 in front of the sum of chunk k. The loop below waits for
+        // these loads itself, in front of the barrier that publishes them.
+        const uint32_t dst = __builtin_amdgcn_readfirstlane(
+            (int)(uint32_t)(uintptr_t)(__attribute__((address_space(3))) float*)(s_l.ring + 4u * (st * CH4 + i * BLK + ((uint32_t)t & ~63u))));
+        uint32_t keep;
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+      }
+      if (!noflag && t < (int)(GB_CHUNK / 4u)) {  // the chunk's flags: four per lane of the first wave, through a register
+        const uint32_t o = k * GB_CHUNK + 4u * (uint32_t)t;
+        __builtin_memcpy(&fl_next, live + (size_t)pb + (o < L ? o : L), 4);  // (up to 4 bytes past the region: others' flags or the slack)
+      }
+    };
+    auto publish_flags = [&](uint32_t k) {
+      if (!noflag && t < (int)(GB_CHUNK / 4u)) s_l.live[k & 1u][t] = fl_next;
+    };
+    if (nch) {
+      fetch(0u);
+      publish_flags(0u);
+    }
+    const uint32_t n = is_big ? 0u : n_all;
+    const uint32_t rel0 = bi1.y;  // the Gaussian's first slot, counted from pb
+    for (uint32_t k = 0; k < nch; k++) {
+      // chunk k has landed (the LDS writes of the loads count on vmcnt) and every wave is done with the other stage
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (k + 1u < nch) fetch(k + 1u);
+      const uint32_t c0 = k * GB_CHUNK;
+      const uint32_t lo = rel0 > c0 ? rel0 : c0;
+      const uint32_t hi = rel0 + n < c0 + GB_CHUNK ? rel0 + n : c0 + GB_CHUNK;
+      const float4* rg = reinterpret_cast<const float4*>(s_l.ring) + (k & 1u) * CH4;
+      const uint8_t* lf = reinterpret_cast<const uint8_t*>(s_l.live[k & 1u]);
+      // four records per LDS round trip: all reads first (what lies past the lane's last record is read at its first and
+      // selected away, like a dead pair's never-written record), then the additions in list order
+      for (uint32_t q = lo; q < hi; q += 4u) {  // (n == 0: hi <= lo)
+        float4 ra[4], rb[4], rc[4];
+        uint32_t fl[4];
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) {
+          const uint32_t r = (q + u < hi ? q + u : q) - c0;
+          fl[u] = noflag ? 1u : (uint32_t)lf[r];
+          ra[u] = rg[r * RQ];
+          rb[u] = rg[r * RQ + 1u];
+          rc[u] = ALT ? rb[u] : rg[r * RQ + (ALT ? 1u : 2u)];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) {  // (keeps the reads above in front of the flags' branches)
+          asm volatile("" : "+v"(ra[u].x), "+v"(rb[u].x), "+v"(rc[u].x), "+v"(fl[u]));
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < 4u; u++) {
+          if (q + u < hi && fl[u] != 0u) {
+            acc[0] += ra[u].x; acc[1] += ra[u].y; acc[2] += ra[u].z; acc[5] += ra[u].w;
+            acc[3] += rb[u].x; acc[4] += rb[u].y;
+            if (ALT) {
+              acc[9] += rb[u].z;
+            } else {
+              acc[6] += rb[u].z; acc[7] += rb[u].w;
+              acc[8] += rc[u].x; acc[9] += rc[u].y; acc[10] += rc[u].z;
+            }
+          }
+        }
+      }
+      if (k + 1u < nch) publish_flags(k + 1u);
+    }
+    __syncthreads();  // the rows of means3D / scales are parked in the ring: every wave has read its last chunk
   }
   stage_rows3_store(rows, st_m, s_m);
   if (scales) stage_rows3_store(rows, st_s, s_s);
@@ -926,14 +1054,20 @@ __global__ __launch_bounds__(BLK) void camera_sum_kernel(const float* __restrict
 // (1 M / 2 M Gaussians at 1024^2, gaussian_bwd ms narrow / wide by list depth x mean pair opacity): 80: 0.212 / 0.188,
 // 120: 0.118 / 0.101, 195: 0.093 / 0.086, 350: 0.078 / 0.080, trained 1 M: 0.075 / 0.078, trained 2 M: 0.105 / 0.120
 // (profiles/r05_ab_gaussian_bwd_wide.txt). A host that does not know the depth keeps the narrow kernel.
+// The streaming build (3) against the build the rule above picks, gaussian_bwd ms / step ms, same box
+// (profiles/r07_ab_gaussian_bwd_stream.txt): headline 0.078 -> 0.066 / 0.5778 -> 0.5680 over five alternating bench runs (the
+// parent's own runs spread 0.0027): taken, in place of 1. Opacity 0.1 at 1 M 0.138 -> 0.122, 2048^2 0.144 -> 0.129, 2 M at
+// opacity 0.1 0.187 -> 0.182 with step times inside or near three spreads and one of them slower: those keep 2. Trained /
+// surface scenes 0.076 -> 0.154 / 0.102 -> 0.180 (it streams the dead pairs' never-written records): they keep 0.
 int gaussian_bwd_wide(int64_t R, int P) {
   static const int forced = [] {
     const char* e = getenv("EOGS_GB_WIDE");
     return e ? atoi(e) : -1;
   }();
-  if (forced >= 0) return forced > 2 ? 2 : forced;
+  if (forced >= 0) return forced > 3 ? 3 : forced;
   if (!nr_shallow(R) || P <= 0) return 0;
-  return (double)nr_slots(R) >= 6.0 * (double)P ? 2 : 1;
+  if ((double)nr_slots(R) >= 6.0 * (double)P) return 2;
+  return P >= GB_STREAM_MIN_P ? 3 : 1;
 }
 
 void launch_gaussian_bwd(const GaussBwdArgs& a, const GeomWS& g, const BinWS& b, int p_begin, int p_end, hipStream_t s) {
@@ -941,11 +1075,12 @@ void launch_gaussian_bwd(const GaussBwdArgs& a, const GeomWS& g, const BinWS& b,
   const uint32_t blk0 = (uint32_t)p_begin / BLK, nblk = ceil_div_u32((uint64_t)(p_end - p_begin), BLK);
   const bool want_T = a.dL_dT_sum != nullptr, want_vm = a.dL_dvm_mean != nullptr;
   using Kern = decltype(&gaussian_bwd_kernel<false, false, 0>);
-  static Kern const table[3][2][2] = {
+  static Kern const table[4][2][2] = {
       {{gaussian_bwd_kernel<false, false, 0>, gaussian_bwd_kernel<false, true, 0>}, {gaussian_bwd_kernel<true, false, 0>, gaussian_bwd_kernel<true, true, 0>}},
       {{gaussian_bwd_kernel<false, false, 1>, gaussian_bwd_kernel<false, true, 1>}, {gaussian_bwd_kernel<true, false, 1>, gaussian_bwd_kernel<true, true, 1>}},
-      {{gaussian_bwd_kernel<false, false, 2>, gaussian_bwd_kernel<false, true, 2>}, {gaussian_bwd_kernel<true, false, 2>, gaussian_bwd_kernel<true, true, 2>}}};
-  Kern kern = table[a.wide < 0 ? 0 : (a.wide > 2 ? 2 : a.wide)][a.raw ? 1 : 0][a.alt_only ? 1 : 0];
+      {{gaussian_bwd_kernel<false, false, 2>, gaussian_bwd_kernel<false, true, 2>}, {gaussian_bwd_kernel<true, false, 2>, gaussian_bwd_kernel<true, true, 2>}},
+      {{gaussian_bwd_kernel<false, false, 3>, gaussian_bwd_kernel<false, true, 3>}, {gaussian_bwd_kernel<true, false, 3>, gaussian_bwd_kernel<true, true, 3>}}};
+  Kern kern = table[a.wide < 0 ? 0 : (a.wide > 3 ? 3 : a.wide)][a.raw ? 1 : 0][a.alt_only ? 1 : 0];
   if (nblk)
     hipLaunchKernelGGL(kern, dim3(nblk), dim3(BLK), 0, s, a.P, a.H, a.W, a.means3D, a.scales, a.rotations,
                        a.cov3D_precomp, a.opacities, a.viewmatrix, a.projmatrix, a.alt_affine, a.radii, a.scale_modifier,
