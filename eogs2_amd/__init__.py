@@ -16,6 +16,7 @@ from . import dsm_eval  # noqa: F401,E402  (DSM registration and MAE: eval/dsmr.
 from . import dsm_raster  # noqa: F401,E402  (cloud / view / TSDF surface -> DSM: utils/dsm_utils.py, tsdf.py:530-600)
 from . import flow  # noqa: F401,E402  (flow-matching warp, statistics and criteria: flowmatching/flow_matching.py)
 from . import mesh  # noqa: F401,E402  (marching cubes over the TSDF volume: tsdf.py:522-528 without mcubes)
+from . import model  # noqa: F401,E402  (GaussianModel: create_from_pcd, training_setup, PLY and checkpoints: scene/gaussian_model.py)
 from . import monitor  # noqa: F401,E402  (training monitor: interval means, PSNR/SSIM, early stopper: train_pan.py:423-597)
 from . import regularizers  # noqa: F401,E402  (opacity, effective-rank, TV and accumulated-opacity terms: loss/opacity.py, main_loss.py)
 from . import reset  # noqa: F401,E402  (shadow-based colour reset, in-place opacity reset, render_all_views: color_reset_op.py)

@@ -319,6 +319,19 @@ def cat_tensors_to_optimizer(optimizer, tensors_dict):
     return _install(optimizer, plan, new)
 
 
+def replace_tensor(optimizer, tensor, name):
+    """`GaussianModel.replace_tensor_to_optimizer` (gaussian_model.py:451-464): the group called `name` gets `tensor` as a new
+    Parameter and, where the group has stepped, zero moments of its shape; `step` stays, a group without state stays without.
+    Returns {name: new nn.Parameter} ({} when no group has that name)."""
+    out = {}
+    for group, p, st in _groups(optimizer):
+        if group["name"] != name:
+            continue
+        new = [tensor] if st is None else [tensor, torch.zeros_like(tensor), torch.zeros_like(tensor)]
+        out.update(_install(optimizer, [(group, p, st)], new))
+    return out
+
+
 def _selected_rows(optimizer, mask, names, extra=()):
     """{name: rows of that group's parameter where mask} + the same rows of `extra`: ONE scan + ONE gather launch and one
     host sync for all of them (the reference indexes each tensor with the boolean mask: a nonzero + gather + sync each)."""
@@ -446,5 +459,5 @@ def alive_rows(optimizer, name="opacity"):
     raise KeyError(f"alive_rows: no parameter group named {name!r}")
 
 
-__all__ = ["FusedAdam", "compact_rows", "prune_optimizer", "reset_opacity", "cat_tensors_to_optimizer", "densify_and_clone",
+__all__ = ["FusedAdam", "compact_rows", "prune_optimizer", "reset_opacity", "cat_tensors_to_optimizer", "replace_tensor", "densify_and_clone",
            "densify_and_split", "build_rotation", "retire_rows", "alive_rows", "RETIRED_LOGIT"]

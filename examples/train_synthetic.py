@@ -25,6 +25,8 @@ train_pan.py:423-429,471-495,512-597): every iteration feeds it without a wait, 
 both are first flattened into DSMs on the device (`eogs2_amd.dsm_raster.dsm_from_view`): render -> DSM -> registered MAE.
 `--opacity-reset-every N` and `--color-reset-at N` are the two resets near the end of the reference's iteration (train_pan.py:726-736)
 in place (`eogs2_amd.reset.reset_opacity_`, `color_reset`): no tensor is replaced, so a recorded step keeps replaying across them.
+`--save-ply PATH` writes the trained Gaussians as the reference's `point_cloud.ply` (`eogs2_amd.model.GaussianModel.save_ply`: one pack
+launch, one copy, one write); `--load-ply PATH` starts the trainee from such a file instead of the perturbed scene (`load_ply`).
 """
 import argparse
 import math
@@ -50,6 +52,7 @@ from eogs2_amd.dsm_eval import dsm_mae  # noqa: E402
 from eogs2_amd.dsm_raster import dsm_from_view  # noqa: E402
 from eogs2_amd.flow import apply_flow, perform_flow_matching, performOpticalmatching  # noqa: E402
 from eogs2_amd.regularizers import gaussian_regularizers  # noqa: E402
+from eogs2_amd.model import GaussianModel, parse_ply_header  # noqa: E402
 from eogs2_amd.monitor import MONITOR_METRICS, TrainingMonitor  # noqa: E402
 from eogs2_amd.pan import FIXED_PARAMS, KINDS as PAN_KINDS, PanMap, render_pipeline as pan_render_pipeline  # noqa: E402
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
@@ -227,6 +230,13 @@ def main(argv=None):
     ap.add_argument("--early-stop-metric", choices=MONITOR_METRICS, default="photometric", metavar="NAME",
                     help=f"with --monitor: the stopper's metric_name, one of {', '.join(MONITOR_METRICS)} (photometric: "
                          "optimization/early_stopping/l_photom.yaml); PSNR and SSIM are watched with operator max, the losses with min")
+    ap.add_argument("--save-ply", default=None, metavar="PATH",
+                    help="after the last iteration write the trainee as a binary little-endian PLY with the reference's vertex properties "
+                         "(eogs2_amd.model.GaussianModel.save_ply; scene/gaussian_model.py:310-346): what its render_pan.py / tsdf.py chain loads")
+    ap.add_argument("--load-ply", default=None, metavar="PATH",
+                    help="start the trainee from a PLY written by --save-ply (or by the reference at sh_degree 0) instead of the perturbed "
+                         "scene: the raw parameters are the file's, bit for bit (eogs2_amd.model.GaussianModel.load_ply). The file must "
+                         "hold --gaussians rows (that count sizes the target scene and the run's per-row state): any other count is refused")
     a = ap.parse_args(argv)
     if a.early_stop_patience is not None and not a.monitor:
         ap.error("--early-stop-patience needs --monitor")
@@ -236,6 +246,11 @@ def main(argv=None):
         ap.error("--pan-first needs --pan-map")
     if a.pan_map and a.flow_matching:
         ap.error("--flow-matching runs on the three-plane pipeline here: not with --pan-map")
+    if a.load_ply:  # the scene, the noise and the statistics are sized by --gaussians: the file must hold as many rows
+        with open(a.load_ply, "rb") as f:
+            _, file_rows, _ = parse_ply_header(f.read(1 << 16))
+        if file_rows != a.gaussians:
+            ap.error(f"--load-ply: {a.load_ply} holds {file_rows} Gaussians, --gaussians is {a.gaussians}: give the file's count")
     dev = torch.device("cuda:0")
     P, H, W = a.gaussians, a.size, a.size
     sc = make_scene(P, H, W, seed=0, opacity="trained", device=dev)
@@ -370,6 +385,14 @@ def main(argv=None):
     model = Gaussians(sc["means3D"] + 2e-4 * noise(P, 3), (sc["colors"][:, :3] + 0.2 * noise(P, 3)).clamp(0.02, 0.98),
                       torch.full((P,), 0.3, device=dev), torch.sqrt(dist2)[:, None].repeat(1, 3), sc["rotations"],
                       capturable=a.optimizer_in_graph)
+    if a.load_ply:  # the same class over the file's Gaussians; then the file's raw bits under its activations' round trip
+        loaded = GaussianModel(0)
+        loaded.load_ply(a.load_ply)
+        with torch.no_grad():
+            model = Gaussians(loaded.get_xyz, loaded._features_dc.reshape(-1, 3) * C0 + 0.5, loaded.get_opacity.squeeze(1), loaded.get_scaling,
+                              loaded._rotation, capturable=a.optimizer_in_graph)
+            for name in ("_xyz", "_features_dc", "_opacity", "_scaling", "_rotation"):
+                getattr(model, name).copy_(getattr(loaded, name).reshape(getattr(model, name).shape))
     min_logit = math.log(0.005 / 0.995)  # the transparent prune's threshold on the raw logit
     retire_in_step = bool(a.optimizer_in_graph and a.defer_prune and not a.no_prune)
     if retire_in_step:  # train_pan.py:673-678 in its deferred form, every iteration, inside the Adam launch
@@ -575,6 +598,11 @@ def main(argv=None):
     main.last_params = None
     if a.densify_every:  # what callers compare between runs, beside the returned tuple
         main.last_params = {g["name"]: g["params"][0].detach().cpu() for g in model.optimizer.param_groups}
+    if a.save_ply:  # (after the clocks: the file is no part of an iteration)
+        out_model = GaussianModel(0)
+        out_model._xyz, out_model._features_dc, out_model._features_rest = model._xyz, model._features_dc, model._features_rest
+        out_model._opacity, out_model._scaling, out_model._rotation = model._opacity.reshape(-1, 1), model._scaling, model._rotation
+        out_model.save_ply(a.save_ply)
     if not a.quiet:
         print(f"{a.iters} iterations in {dt:.2f} s ({dt / a.iters * 1e3:.2f} ms/iter over all, {main.last_ms_per_iter:.2f} ms/iter over the "
               f"last {timed}; {3 if a.random_camera else 2} renders + resample + render pipeline + losses + Adam each)")
