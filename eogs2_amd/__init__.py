@@ -18,7 +18,9 @@ from . import flow  # noqa: F401,E402  (flow-matching warp, statistics and crite
 from . import mesh  # noqa: F401,E402  (marching cubes over the TSDF volume: tsdf.py:522-528 without mcubes)
 from . import model  # noqa: F401,E402  (GaussianModel: create_from_pcd, training_setup, PLY and checkpoints: scene/gaussian_model.py)
 from . import monitor  # noqa: F401,E402  (training monitor: interval means, PSNR/SSIM, early stopper: train_pan.py:423-597)
+from . import pansharp  # noqa: F401,E402  (pansharpened PAN target, Lpan, Lgradient_pan, Pansharploss: pansharpening/, loss/PAN_loss.py)
 from . import regularizers  # noqa: F401,E402  (opacity, effective-rank, TV and accumulated-opacity terms: loss/opacity.py, main_loss.py)
+from . import rescaler  # noqa: F401,E402  (ground-truth rescalers: utils/rescaler/rescaler.py)
 from . import reset  # noqa: F401,E402  (shadow-based colour reset, in-place opacity reset, render_all_views: color_reset_op.py)
 
 __version__ = "0.1.0"

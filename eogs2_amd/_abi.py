@@ -223,6 +223,23 @@ MODEL_SIGNATURES = {
     "eogs_model_rows_pack": (_i, [_i64, _i] + [_p] * 6 + [_p, _p]),
     "eogs_model_rows_unpack": (_i, [_i64, _i, _p] + [_p] * 6 + [_p]),
 }
+# include/eogs_gtprep.h, a table of its own for the same reason
+GTPREP_SIGNATURES = {
+    "eogs_gtprep_bytes": (_i, [_i, C.POINTER(_z)]),
+    "eogs_gtprep_pansharp": (_i, [_i] * 6 + [_p, _p, _f, _p, _p]),
+    "eogs_gtprep_pansharp_l2_forward": (_i, [_i] * 6 + [_p, _p, _p, _f, _p, _p, _z, _p]),
+    "eogs_gtprep_pansharp_l2_backward": (_i, [_i] * 6 + [_p, _p, _p, _f, _p, _p, _p]),
+    "eogs_gtprep_l2_forward": (_i, [_i64, _p, _p, _p, _p, _z, _p]),
+    "eogs_gtprep_l2_backward": (_i, [_i64, _p, _p, _p, _p, _p]),
+    "eogs_gtprep_grad_l2_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _z, _p]),
+    "eogs_gtprep_grad_l2_backward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p]),
+    "eogs_gtprep_minmax": (_i, [_i, _i64, _p, _p, _p, _z, _p]),
+    "eogs_gtprep_rescale": (_i, [_i, _i64, _p, _p, _p, _p]),
+    "eogs_gtprep_clamp": (_i, [_i64, _p, _f, _f, _p, _p]),
+    "eogs_gtprep_equalize": (_i, [_i, _i64, _p, _p, _p, _z, _p]),
+}
+GTPREP_BROVEY, GTPREP_SIMPLE_BROVEY, GTPREP_IHS = 0, 1, 2  # EOGS_GTPREP_<METHOD>
+GTPREP_MAX_CHANNELS = 8  # EOGS_GTPREP_MAX_CHANNELS
 MODEL_TILE_ROWS = 64  # EOGS_MODEL_TILE_ROWS
 MODEL_MAX_REST = 15  # EOGS_MODEL_MAX_REST
 RESET_MAX_VIEWS = RESET_MAX_TENSORS = 16  # EOGS_RESET_MAX_*
@@ -259,7 +276,7 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
             "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
             "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case", "eogs_reset_erode", "eogs_reset_flags", "eogs_reset_rows",
-            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack")
+            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES)
 
 
 class PackTensor(C.Structure):
@@ -364,7 +381,8 @@ class RastABI:
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
                                   *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
-                                  *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items(), *MODEL_SIGNATURES.items()):
+                                  *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items(), *MODEL_SIGNATURES.items(),
+                                  *GTPREP_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -382,7 +400,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

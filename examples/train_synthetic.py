@@ -27,6 +27,9 @@ both are first flattened into DSMs on the device (`eogs2_amd.dsm_raster.dsm_from
 in place (`eogs2_amd.reset.reset_opacity_`, `color_reset`): no tensor is replaced, so a recorded step keeps replaying across them.
 `--save-ply PATH` writes the trained Gaussians as the reference's `point_cloud.ply` (`eogs2_amd.model.GaussianModel.save_ply`: one pack
 launch, one copy, one write); `--load-ply PATH` starts the trainee from such a file instead of the perturbed scene (`load_ply`).
+`--pansharp-loss METHOD` adds 0.1 x the reference's Pansharploss (`eogs2_amd.pansharp.Pansharploss`; loss/pansharp_loss.py, w_L_pansharp):
+a low-resolution MSI ground truth (the target image, averaged over 4 x 4 blocks) and a PAN ground truth are pansharpened on the fly by
+METHOD (brovey, simple_brovey, ihs) inside the loss kernels, forward and backward, and compared with the rendered image.
 """
 import argparse
 import math
@@ -54,6 +57,7 @@ from eogs2_amd.flow import apply_flow, perform_flow_matching, performOpticalmatc
 from eogs2_amd.regularizers import gaussian_regularizers  # noqa: E402
 from eogs2_amd.model import GaussianModel, parse_ply_header  # noqa: E402
 from eogs2_amd.monitor import MONITOR_METRICS, TrainingMonitor  # noqa: E402
+from eogs2_amd.pansharp import METHODS as PANSHARP_METHODS, Pansharploss  # noqa: E402
 from eogs2_amd.pan import FIXED_PARAMS, KINDS as PAN_KINDS, PanMap, render_pipeline as pan_render_pipeline  # noqa: E402
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
@@ -237,7 +241,18 @@ def main(argv=None):
                     help="start the trainee from a PLY written by --save-ply (or by the reference at sh_degree 0) instead of the perturbed "
                          "scene: the raw parameters are the file's, bit for bit (eogs2_amd.model.GaussianModel.load_ply). The file must "
                          "hold --gaussians rows (that count sizes the target scene and the run's per-row state): any other count is refused")
+    ap.add_argument("--pansharp-loss", choices=sorted(PANSHARP_METHODS), default=None, metavar="METHOD",
+                    help="adds 0.1 x Pansharploss (loss/pansharp_loss.py; pansharp_cfg.method METHOD: brovey, simple_brovey or ihs) through "
+                         "eogs2_amd.pansharp: the ground truth is a synthetic pair, the target image averaged over 4 x 4 blocks as the "
+                         "low-resolution MSI image and a PAN image at full size whose pansharpening gives the target image back up to the "
+                         "upsampling; the pansharpened image is computed inside the loss's forward and backward kernels and never stored. "
+                         "Both images are lifted to 0.9 x + 0.05 first, so that no bicubic undershoot meets brovey's clamp. The term sits "
+                         "inside the recorded step with --graph; main.last_pansharp_loss keeps its first and last value. Default: absent")
     a = ap.parse_args(argv)
+    if a.pansharp_loss and a.pan_map:
+        ap.error("--pansharp-loss compares three-plane images: not with --pan-map")
+    if a.pansharp_loss and a.size % 4:
+        ap.error("--pansharp-loss averages the target over 4 x 4 blocks: --size must be a multiple of 4")
     if a.early_stop_patience is not None and not a.monitor:
         ap.error("--early-stop-patience needs --monitor")
     if a.dsm_resolution and not a.dsm_mae_every:
@@ -361,6 +376,16 @@ def main(argv=None):
         dsm_cam = types.SimpleNamespace(affine=cam.affine, Ainv=torch.inverse(cam.affine[:3, :3].T))  # affine_cameras.py:159
         profile, gt_dsm = dsm_from_view(gt_altitude, dsm_cam, dsm_scene, a.dsm_resolution)  # the one wait: the target's bounds
         dsm_geometry = (profile["transform"][2], profile["transform"][5], profile["width"], profile["height"])
+    pansharp_term = None
+    if a.pansharp_loss:  # train_pan.py:215-224: the MSI ground truth at a quarter of the PAN size, pansharpened by the loss itself
+        lift = lambda x: 0.9 * x + 0.05  # noqa: E731
+        with torch.no_grad():
+            gt_msi_lr = torch.nn.functional.avg_pool2d(lift(gt)[None], 4)[0].contiguous()
+            total = lift(gt).sum(dim=0)
+            gt_pan_hr = {"brovey": 0.1 * total, "simple_brovey": total, "ihs": total / 3.0}[a.pansharp_loss].contiguous()
+        pansharp_args = {"brovey": (gt_pan_hr, gt_msi_lr), "simple_brovey": (gt_pan_hr, gt_msi_lr[None]),
+                         "ihs": (gt_pan_hr[None], gt_msi_lr)}[a.pansharp_loss]
+        pansharp_term = Pansharploss(0.1, types.SimpleNamespace(method=a.pansharp_loss))
     warper = None
     if a.flow_matching:
         shift = torch.tensor(FLOW_SHIFT, device=dev).view(1, 2, 1, 1).expand(1, 2, H, W)
@@ -441,6 +466,10 @@ def main(argv=None):
             loss = loss + 1e-4 * L_new_alt + 1e-3 * L_new_rgb
         if reg_want:  # train_pan.py:450-465: w_L_opacity * L_opacity (+ w_L_erank * L_erank), summed in the kernel
             loss = loss + gaussian_regularizers(model._opacity, model._scaling, n_init=P, weights=reg_weights, want=reg_want)[0]
+        if pansharp_term is not None:  # w_L_pansharp * L_pansharp: one forward and one backward kernel, no full-size temporaries
+            kept["pansharp"] = pansharp_term(lift(final), *pansharp_args)
+            loss = loss + pansharp_term.lambda_L_pansharp * kept["pansharp"]
+            kept["pansharp"] = kept["pansharp"].detach()
         loss.backward()
         # --monitor: like the optimizers, inside the recorded step only with --optimizer-in-graph --graph (gated as they are:
         # an outgrown replay is not counted), else after it, from the tensors kept here (under --graph: refilled by a replay)
@@ -471,6 +500,7 @@ def main(argv=None):
         reset_cameras = [rc]
     reset_log = []  # (iteration, which reset, recordings of the step so far)
     recordings = 0
+    pansharp_values = []  # --pansharp-loss: the unweighted term where the loss is read
     kept, dsm_scores = {}, []  # --dsm-mae-every: the view's altitude of the last step; (iteration, dx, dy, mae)
     first = last = None
     stopped_at = 0  # --monitor --early-stop-patience: the iteration whose record carried the flag
@@ -574,6 +604,8 @@ def main(argv=None):
             v = float(loss)
             first = v if first is None else first
             last = v
+            if pansharp_term is not None:
+                pansharp_values.append(float(kept["pansharp"]))
             if not a.quiet:
                 print(f"iter {it:4d}  loss {v:.5f}  gaussians {model._xyz.shape[0]}  device memory in use "
                       f"{(lambda f, t: (t - f) / 2**20)(*torch.cuda.mem_get_info()):.0f} MiB")
@@ -595,6 +627,7 @@ def main(argv=None):
     # count was at each reset: a reset that forced a recording would show as a larger count at the end or at the next reset
     main.last_recordings = recordings + (step.recaptures if step is not None else 0)
     main.last_resets = reset_log
+    main.last_pansharp_loss = (pansharp_values[0], pansharp_values[-1]) if pansharp_values else None
     main.last_params = None
     if a.densify_every:  # what callers compare between runs, beside the returned tuple
         main.last_params = {g["name"]: g["params"][0].detach().cpu() for g in model.optimizer.param_groups}
