@@ -9,6 +9,7 @@
 // sums are reduced per wave (shuffles), per workgroup (LDS, fixed order) and then column by column over the workgroups'
 // partials by a second kernel, again in a fixed order — no atomics, bitwise reproducible.
 #include "api_util.h"
+#include "reduce.h"  // shadow_clip: the same clamp as shade.hip
 
 namespace {
 
@@ -132,7 +133,7 @@ __global__ __launch_bounds__(PT) void pan_fwd_kernel(int64_t n, const float* __r
 #pragma unroll
     for (int v = 0; v < V; v++) {
       float s = 1.f;
-      if constexpr (SH) ow[v] = s = expf(0.4f * fminf(d[v], 0.f));
+      if constexpr (SH) ow[v] = s = expf(0.4f * shadow_clip(d[v]));
       if constexpr (A) {
         float c[3], x[3];
 #pragma unroll
@@ -216,7 +217,7 @@ __global__ __launch_bounds__(PT) void pan_bwd_kernel(int64_t n, const float* __r
     for (int v = 0; v < V; v++) {
       const float rv[3] = {r[0][v], r[1][v], r[2][v]};
       float s = 1.f;
-      if constexpr (SH) s = expf(0.4f * fminf(d[v], 0.f));
+      if constexpr (SH) s = expf(0.4f * shadow_clip(d[v]));
       float gs = gsw[v];
       if constexpr (A) {
         float c[3], x[3], g3[3], gcc[3];

@@ -1,4 +1,4 @@
-// reduce.h — the fixed-order wave64 / workgroup reductions and two scalar helpers the side modules share (device only).
+// reduce.h — the fixed-order wave64 / workgroup reductions and the scalar helpers the side modules share (device only).
 // The library is built without fast-math and with -ffp-contract=off: each of these is ONE expression tree, so every kernel
 // that sums through it rounds in the same order — what the modules' "same bits on every run" (and monitor.hip's "same
 // bits as reg.hip") rest on.
@@ -54,5 +54,8 @@ __device__ inline float wave_sum_dpp(float v) {
 }
 
 __device__ inline float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+// ShadowMap.forward's `alt_diff.clip(max=0)` (affine_cameras.py:38) for shade.hip and pan.hip, which must agree to the bit: a clamp
+// that keeps a NaN, written as a select (fminf returns its other operand for a NaN). -0 passes, as through torch's clamp.
+__device__ inline float shadow_clip(float d) { return d > 0.f ? 0.f : d; }
 // reg.hip's opacity terms and monitor.hip's mean opacity must agree to the bit
 __device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }

@@ -51,6 +51,9 @@ struct ShadeParams {
   float ins[3];
 };
 
+// Translucentshadows_L's `shadowmap.clip(0.05, 0.95)` (loss/shadow.py:15), NaN kept
+__device__ inline float tshadow_clip(float x) { return x < 0.05f ? 0.05f : (x > 0.95f ? 0.95f : x); }
+
 __global__ __launch_bounds__(ST) void shade_fwd_kernel(int64_t n, const float* __restrict__ raw, const float* __restrict__ alt_diff,
                                                        const float* __restrict__ Mp, const float* __restrict__ insp,
                                                        float* __restrict__ cc, float* __restrict__ shaded,
@@ -72,7 +75,7 @@ __global__ __launch_bounds__(ST) void shade_fwd_kernel(int64_t n, const float* _
       for (int k = 0; k < 3; k++) cc[k * n + p] = c[k];
     }
     if (alt_diff) {
-      const float s = expf(0.4f * fminf(alt_diff[p], 0.f));
+      const float s = expf(0.4f * shadow_clip(alt_diff[p]));
       shadow[p] = s;
 #pragma unroll
       for (int k = 0; k < 3; k++) shaded[k * n + p] = s * c[k] + ((1.f - s) * ins[k]) * c[k];
@@ -85,7 +88,8 @@ __global__ __launch_bounds__(ST) void shade_fwd_kernel(int64_t n, const float* _
 
 // shaded_c = cc_c f_c, f_c = s + (1 - s) ins_c:
 //   d/dcc_c = f_c g_c (+ g_cc_c);  d/ds = sum_c g_c cc_c (1 - ins_c) (+ g_shadow);  d/dins_c = sum_p g_c (1 - s) cc_c
-//   d/dalt_diff = d/ds * 0.4 s [alt_diff <= 0]   (torch.clamp(max=0) passes the gradient at equality)
+//   d/dalt_diff = d/ds * 0.4 s [alt_diff <= 0]   (torch.clamp(max=0) passes the gradient at equality and gives 0 at a NaN,
+//   where s and everything formed from it are NaN)
 //   d/draw_k = sum_c M[c][k] d/dcc_c;  d/dM[c][k] = sum_p d/dcc_c raw_k;  d/dM[c][3] = sum_p d/dcc_c
 __global__ __launch_bounds__(ST) void shade_bwd_kernel(int64_t n, const float* __restrict__ raw, const float* __restrict__ alt_diff,
                                                        const float* __restrict__ Mp, const float* __restrict__ insp,
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(ST) void shade_bwd_kernel(int64_t n, const float* _
     }
     if (alt_diff) {
       const float d = alt_diff[p];
-      const float s = expf(0.4f * fminf(d, 0.f));
+      const float s = expf(0.4f * shadow_clip(d));
       float gs = g_shadow ? g_shadow[p] : 0.f;
 #pragma unroll
       for (int k = 0; k < 3; k++) {
@@ -180,14 +184,27 @@ __global__ __launch_bounds__(ST) void mloss_bwd_kernel(int64_t n, int mode, cons
                                                        const float* __restrict__ upstream, float* __restrict__ g_alt,
                                                        float* __restrict__ g_a, float* __restrict__ g_b) {
   const float cnt = out[2];
-  const float w_alt = cnt > 0.f ? upstream[0] / cnt : 0.f, w_rgb = cnt > 0.f ? upstream[1] / cnt : 0.f;
+  if (!(cnt > 0.f)) {  // an empty mask: the losses are constants with no path to the inputs, +0 everywhere
+    for (int64_t p = (int64_t)blockIdx.x * ST + threadIdx.x; p < n; p += (int64_t)gridDim.x * ST) {
+      g_alt[p] = 0.f;
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        g_a[k * n + p] = 0.f;
+        if (g_b) g_b[k * n + p] = 0.f;
+      }
+    }
+    return;
+  }
+  const float w_alt = upstream[0] / cnt, w_rgb = upstream[1] / cnt;
   for (int64_t p = (int64_t)blockIdx.x * ST + threadIdx.x; p < n; p += (int64_t)gridDim.x * ST) {
     const float d = alt_diff[p];
-    const bool m = mloss_mask(mode, d, uv[p]);
-    g_alt[p] = m ? w_alt * sgn(d) : 0.f;
+    // the reference's (grad * mask) * sign(x): outside the mask a zero with the sign of w sign(x) (NaN under a non-finite w)
+    const float mf = mloss_mask(mode, d, uv[p]) ? 1.f : 0.f;
+    g_alt[p] = (w_alt * mf) * sgn(d);
+    const float wr = w_rgb * mf;
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      const float g = m ? w_rgb * sgn(a[k * n + p] - b[k * n + p]) : 0.f;
+      const float g = wr * sgn(a[k * n + p] - b[k * n + p]);
       g_a[k * n + p] = g;
       if (g_b) g_b[k * n + p] = -g;
     }
@@ -200,7 +217,7 @@ __global__ __launch_bounds__(ST) void tshadow_fwd_kernel(int64_t n, const float*
   float s = 0.f;
   for (int64_t p = (int64_t)blockIdx.x * ST + threadIdx.x; p < n; p += (int64_t)gridDim.x * ST) {
     const float x = a[p];
-    const float b = fminf(fmaxf(x, 0.05f), 0.95f);
+    const float b = tshadow_clip(x);
     s += x * log2f(b) + (1.f - x) * log2f(1.f - b);
   }
   const float t = wg_sum(s, s_red);
@@ -213,7 +230,7 @@ __global__ __launch_bounds__(ST) void tshadow_bwd_kernel(int64_t n, const float*
   const float inv_ln2 = 1.4426950408889634f;
   for (int64_t p = (int64_t)blockIdx.x * ST + threadIdx.x; p < n; p += (int64_t)gridDim.x * ST) {
     const float x = a[p];
-    const float b = fminf(fmaxf(x, 0.05f), 0.95f);
+    const float b = tshadow_clip(x);
     float d = log2f(b) - log2f(1.f - b);
     if (x >= 0.05f && x <= 0.95f) d += (x / b - (1.f - x) / (1.f - b)) * inv_ln2;
     g_a[p] = w * d;

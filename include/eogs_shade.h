@@ -42,6 +42,7 @@ int eogs_shade_forward(int H, int W, const float* raw, const float* alt_diff, co
 /* Backward. Upstream gradients g_shaded (required), g_cc and g_shadow (NULL = zero), same shapes as the outputs.
  *   g_raw      f32[3][H][W], fully overwritten
  *   g_alt_diff f32[H][W], fully overwritten (NULL when alt_diff is NULL); clip(max=0) passes the gradient for alt_diff <= 0
+ *   and keeps a NaN: shadow, shaded, g_raw at that pixel and the parameter sums are NaN there, g_alt_diff is 0
  *   g_params   f32[15] = dL/dM[3][4] then dL/dinshadow[3] (zero when alt_diff is NULL) */
 int eogs_shade_backward(int H, int W, const float* raw, const float* alt_diff, const float* M, const float* inshadow,
                         const float* g_shaded, const float* g_cc, const float* g_shadow, float* g_raw,
@@ -54,7 +55,9 @@ int eogs_shade_backward(int H, int W, const float* raw, const float* alt_diff, c
  *              EOGS_MLOSS_RANDOM: |alt_diff| < 0.30           (main_loss.py:153-155)
  *   L_alt    = sum(|alt_diff| mask) / sum(mask),  L_rgb = sum(|rgb_diff| mask) / sum(mask)   (all 3 channels over the
  *              pixel count, shadow.py:42-48)
- * out f32[3] = {L_alt, L_rgb, sum(mask)}; an empty mask gives {0, 0, 0} (main_loss.py:161-163). */
+ * out f32[3] = {L_alt, L_rgb, sum(mask)}; an empty mask gives {0, 0, 0} (main_loss.py:161-163).
+ * A pixel outside the mask is not read into the sums: a NaN or an infinity there leaves the losses finite, where the
+ * reference's `NaN * 0` makes them NaN; inside the mask it reaches the loss. */
 #define EOGS_MLOSS_SUN 0
 #define EOGS_MLOSS_RANDOM 1
 int eogs_mloss_forward(int H, int W, int mode, const float* alt_diff, const float* rgb_a, const float* rgb_b,
@@ -62,14 +65,15 @@ int eogs_mloss_forward(int H, int W, int mode, const float* alt_diff, const floa
 
 /* Backward: `out` is forward's result (the count is read on the device, no host sync), upstream f32[2] = dL/d{L_alt,
  * L_rgb}. g_alt_diff f32[H][W], g_rgb_a f32[3][H][W] fully overwritten; g_rgb_b (= -g_rgb_a) may be NULL.
- * torch.abs'(0) = 0 is kept (sign). */
+ * torch.abs'(0) = 0 is kept (sign). Outside the mask the gradient is (upstream / count * 0) * sign(x), a zero with that sign,
+ * as autograd forms it; an empty mask gives +0 everywhere. */
 int eogs_mloss_backward(int H, int W, int mode, const float* alt_diff, const float* rgb_a, const float* rgb_b,
                         const float* uv, const float* out, const float* upstream, float* g_alt_diff, float* g_rgb_a,
                         float* g_rgb_b, void* stream);
 
 /* ---- translucent-shadow regulariser ------------------------------------------------------------------------------
  *   out[0] = -mean(a log2 b + (1 - a) log2(1 - b)),  b = clip(a, 0.05, 0.95)       over n elements
- * Backward: g_a fully overwritten; the clip passes its gradient for 0.05 <= a <= 0.95. upstream f32[1]. */
+ * Backward: g_a fully overwritten; the clip passes its gradient for 0.05 <= a <= 0.95 and keeps a NaN (out and g_a there are NaN). upstream f32[1]. */
 int eogs_tshadow_forward(int64_t n, const float* a, float* out, void* ws, size_t ws_bytes, void* stream);
 int eogs_tshadow_backward(int64_t n, const float* a, const float* upstream, float* g_a, void* stream);
 

@@ -14,7 +14,9 @@ def sample_sdf(pts_world_coords, coef, intercept, model_scale, altitude_img, wei
     pts = pts_world_coords / model_scale
     view = F.linear(pts, coef, intercept)
     features = torch.cat([altitude_img, weight_img], dim=1)
-    sampled = F.grid_sample(features, view[None, :, None, :2], mode="bilinear", align_corners=True).squeeze()
+    # the reference's `.squeeze()` (:352) also drops the point axis of a single point and then fails at the next line; indexing
+    # the same two axes away is the same statement for N > 1 and lets a one-voxel volume through
+    sampled = F.grid_sample(features, view[None, :, None, :2], mode="bilinear", align_corners=True)[0, :, :, 0]
     altitude_values, weights = sampled[0, :], sampled[1, :]
     valid_mask = (view[:, :2].abs() <= 1.0).all(dim=1)
     view_new = view.clone()

@@ -267,3 +267,22 @@ def test_example_with_a_pan_camera():
     first, last, _ = train_synthetic.main(args[:-1] + ["learnable_fixed", "--pan-first"])
     print("learnable_fixed, map first:", first, last)
     assert last < first, (first, last)
+
+
+@pytest.mark.parametrize("order,map_name,H,W", [("A", "fixed", 7, 129), ("B", "base", 7, 129), ("A", "identity", 64, 68)])
+def test_nan_altitude_difference_is_kept(dev, order, map_name, H, W):
+    """`alt_diff.clip(max=0)` keeps a NaN (affine_cameras.py:38), as in shade.hip: the shadow, the shaded pixel, that pixel's raw
+    gradient and every parameter sum holding s are NaN, the NaN's own gradient is 0, every other pixel keeps its bits."""
+    c = pan_cases.make_case(order, map_name, H, W, seed=17)
+    base = run_gpu(c, dev)
+    c = dict(c, alt_diff=c["alt_diff"].copy())
+    p = (H // 2, W // 3)
+    c["alt_diff"][p] = np.nan
+    got = run_gpu(c, dev)
+    assert np.isnan(got["out_shadow"][p]) and np.isnan(got["out_shaded"][..., p[0], p[1]]).all()
+    assert got["grad_alt_diff"][p] == 0.0 and np.isnan(got["grad_raw"][:, p[0], p[1]]).all() and np.isnan(got["grad_ins"]).all()
+    assert not np.isnan(got["out_cc"]).any() or order == "B"
+    for k in ("out_shadow", "out_shaded", "out_cc", "grad_alt_diff", "grad_raw"):
+        a, b = got[k].copy(), base[k].copy()
+        a[..., p[0], p[1]] = b[..., p[0], p[1]] = 0
+        assert np.array_equal(a, b), k

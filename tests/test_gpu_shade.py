@@ -1,6 +1,7 @@
 """GPU (MI355X): the fused image chain (include/eogs_shade.h, eogs2_amd/shade.py) through the C-ABI against
 (1) the vectors produced by the reference's own modules (tests/golden/shade_*.npz), (2) the float64 oracle
-(oracle/shade_oracle.py) on odd sizes, (3) size-independent properties at 1024^2, and the reference-named entry points."""
+(oracle/shade_oracle.py) on odd sizes, every element inside its own bound (tests/shade_cases.py; the edge cases are in
+tests/test_gpu_shade_edges.py), (3) size-independent properties at 1024^2, and the reference-named entry points."""
 import types
 
 import numpy as np
@@ -8,7 +9,7 @@ import pytest
 import torch
 
 from oracle import shade_oracle as O
-from shade_cases import close, expected_matrix_grad, fixtures, load, run_shade
+from shade_cases import check_mloss_elementwise, check_shade, close, expected_matrix_grad, fixtures, load, run_shade
 from test_shade_oracle import check_mloss, run_mloss
 
 pytestmark = pytest.mark.gpu
@@ -79,10 +80,8 @@ def test_render_pipeline_vs_oracle_odd_sizes(dev, H, W, shadow):
     fx = _synthetic(H, W, 100 + H, shadow)
     got = run_shade(shade, fx, torch.float32, dev)
     ref = run_shade(O.render_pipeline, fx, torch.float64, "cpu")
-    for k in got:
-        # parameter gradients are sums of H*W signed terms: compare against the magnitude they are reduced from
-        tol = TOL if k not in ("g_M", "g_inshadow") else 2e-5 * max(1.0, (H * W) ** 0.5 / 30)
-        close(got[k], ref[k], tol, k)
+    assert got.keys() == ref.keys()
+    check_shade(got, ref, fx, f"{H}x{W}")  # every element inside its own bound (tests/shade_cases.py)
 
 
 @pytest.mark.parametrize("mode", ["sun", "random"])
@@ -97,6 +96,7 @@ def test_masked_losses_vs_oracle(dev, mode, H, W):
     ref = run_mloss(O.suncamera_l, O.randomcam_l, fx, torch.float64, "cpu")
     got = run_mloss(suncamera_l, randomcam_l, fx, torch.float32, dev)
     check_mloss(got, {**fx, **ref}, TOL)
+    check_mloss_elementwise(got, ref, fx, f"{mode} {H}x{W}")
 
 
 def test_full_size_properties(dev):
