@@ -22,5 +22,6 @@ from . import pansharp  # noqa: F401,E402  (pansharpened PAN target, Lpan, Lgrad
 from . import regularizers  # noqa: F401,E402  (opacity, effective-rank, TV and accumulated-opacity terms: loss/opacity.py, main_loss.py)
 from . import rescaler  # noqa: F401,E402  (ground-truth rescalers: utils/rescaler/rescaler.py)
 from . import reset  # noqa: F401,E402  (shadow-based colour reset, in-place opacity reset, render_all_views: color_reset_op.py)
+from . import views  # noqa: F401,E402  (several views in one recorded step: device-side view bank, train_pan.py:135-138,252-257)
 
 __version__ = "0.1.0"

@@ -238,6 +238,15 @@ GTPREP_SIGNATURES = {
     "eogs_gtprep_clamp": (_i, [_i64, _p, _f, _f, _p, _p]),
     "eogs_gtprep_equalize": (_i, [_i, _i64, _p, _p, _p, _z, _p]),
 }
+# include/eogs_views.h, a table of its own for the same reason
+VIEWS_SIGNATURES = {
+    "eogs_views_wg_bytes": (_i, [C.POINTER(_z)]),
+    "eogs_views_load": (_i, [_i, _p, _p, _p]),
+    "eogs_views_store": (_i, [_i, _p, _p, _p, _p]),
+    "eogs_views_advance": (_i, [_p, _p, _p]),
+}
+VIEWS_MAX_SLOTS = 32  # EOGS_VIEWS_MAX_SLOTS
+VIEWS_LOAD, VIEWS_STORE = 1, 2  # EOGS_VIEWS_LOAD, _STORE
 GTPREP_BROVEY, GTPREP_SIMPLE_BROVEY, GTPREP_IHS = 0, 1, 2  # EOGS_GTPREP_<METHOD>
 GTPREP_MAX_CHANNELS = 8  # EOGS_GTPREP_MAX_CHANNELS
 MODEL_TILE_ROWS = 64  # EOGS_MODEL_TILE_ROWS
@@ -276,7 +285,7 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
             "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
             "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case", "eogs_reset_erode", "eogs_reset_flags", "eogs_reset_rows",
-            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES)
+            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES)
 
 
 class PackTensor(C.Structure):
@@ -365,6 +374,18 @@ class ResetTensor(C.Structure):
     _fields_ = [("data", _p), ("row_elems", _i), ("value", _f)]
 
 
+class ViewsSlot(C.Structure):
+    """eogs_views_slot (include/eogs_views.h)"""
+
+    _fields_ = [("table", _p), ("working", _p), ("row_stride", _z), ("row_bytes", _z), ("flags", C.c_uint32)]
+
+
+class ViewsSchedule(C.Structure):
+    """eogs_views_schedule (include/eogs_views.h)"""
+
+    _fields_ = [("order", _p), ("order_len", _i64), ("cursor", _p), ("current", _p), ("n_views", C.c_int32)]
+
+
 class RastError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -382,7 +403,7 @@ class RastABI:
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
                                   *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
                                   *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items(), *MODEL_SIGNATURES.items(),
-                                  *GTPREP_SIGNATURES.items()):
+                                  *GTPREP_SIGNATURES.items(), *VIEWS_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -400,7 +421,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):
