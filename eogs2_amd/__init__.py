@@ -23,5 +23,6 @@ from . import regularizers  # noqa: F401,E402  (opacity, effective-rank, TV and 
 from . import rescaler  # noqa: F401,E402  (ground-truth rescalers: utils/rescaler/rescaler.py)
 from . import reset  # noqa: F401,E402  (shadow-based colour reset, in-place opacity reset, render_all_views: color_reset_op.py)
 from . import views  # noqa: F401,E402  (several views in one recorded step: device-side view bank, train_pan.py:135-138,252-257)
+from . import draw  # noqa: F401,E402  (per-iteration random background and virtual camera on the device: train_pan.py:272-277,375-378)
 
 __version__ = "0.1.0"

@@ -245,6 +245,13 @@ VIEWS_SIGNATURES = {
     "eogs_views_store": (_i, [_i, _p, _p, _p, _p]),
     "eogs_views_advance": (_i, [_p, _p, _p]),
 }
+# include/eogs_draw.h, a table of its own for the same reason
+DRAW_SIGNATURES = {
+    "eogs_draw_iteration": (_i, [_i, _p, _p, _p]),
+    "eogs_draw_advance": (_i, [_p, _p, _p]),
+}
+DRAW_MAX_CAMERAS = 8  # EOGS_DRAW_MAX_CAMERAS
+DRAW_BG, DRAW_BG_COPY_FIRST, DRAW_CAMERA, DRAW_NADIR = 1, 2, 4, 8  # EOGS_DRAW_*: the flags of a camera
 VIEWS_MAX_SLOTS = 32  # EOGS_VIEWS_MAX_SLOTS
 VIEWS_LOAD, VIEWS_STORE = 1, 2  # EOGS_VIEWS_LOAD, _STORE
 GTPREP_BROVEY, GTPREP_SIMPLE_BROVEY, GTPREP_IHS = 0, 1, 2  # EOGS_GTPREP_<METHOD>
@@ -285,7 +292,7 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
             "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
             "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case", "eogs_reset_erode", "eogs_reset_flags", "eogs_reset_rows",
-            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES)
+            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES, *DRAW_SIGNATURES)
 
 
 class PackTensor(C.Structure):
@@ -386,6 +393,19 @@ class ViewsSchedule(C.Structure):
     _fields_ = [("order", _p), ("order_len", _i64), ("cursor", _p), ("current", _p), ("n_views", C.c_int32)]
 
 
+class DrawStreamDesc(C.Structure):
+    """eogs_draw_stream (include/eogs_draw.h)"""
+
+    _fields_ = [("seed", C.c_uint64), ("counter", _p)]
+
+
+class DrawCamera(C.Structure):
+    """eogs_draw_camera (include/eogs_draw.h)"""
+
+    _fields_ = [("affine", _p), ("center", _p), ("alt_floor", _p), ("bg", _p), ("virt_affine", _p), ("cam2virt", _p), ("shear", _p),
+                ("extent", _f), ("cam2virt_scale", _f), ("flags", C.c_uint32)]
+
+
 class RastError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -403,7 +423,7 @@ class RastABI:
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
                                   *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
                                   *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items(), *MODEL_SIGNATURES.items(),
-                                  *GTPREP_SIGNATURES.items(), *VIEWS_SIGNATURES.items()):
+                                  *GTPREP_SIGNATURES.items(), *VIEWS_SIGNATURES.items(), *DRAW_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -421,7 +441,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_", "draw_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -35,6 +35,10 @@ every camera's parameters on their own Adam moments and step count. The views' g
 parameters and the camera optimizer's state sit in a device-side bank (`eogs2_amd.views.ViewBank`): one launch brings the current view
 into the tensors the iteration reads, one writes the updated state back, so with `--graph --optimizer-in-graph` every replay trains
 another view with no host work in between.
+`--random-background` and `--virtual-camera-extent X` (with `--random-camera`) draw the background and the random virtual camera anew in
+every iteration, as the reference does (train_pan.py:272-277,375-378), on the device (`eogs2_amd.draw.IterationDraws`): one launch
+after `bank.load()`, keyed by `--draw-seed` and the iteration's index, so a recorded step renders against another background and
+another virtual camera on every replay. Without them the background and the `rnd` camera are fixed, as before.
 """
 import argparse
 import math
@@ -67,6 +71,7 @@ from eogs2_amd.pansharp import METHODS as PANSHARP_METHODS, Pansharploss  # noqa
 from eogs2_amd.pan import FIXED_PARAMS, KINDS as PAN_KINDS, PanMap, render_pipeline as pan_render_pipeline  # noqa: E402
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from eogs2_amd.views import ViewBank, ViewSchedule, reference_order  # noqa: E402
+from eogs2_amd.draw import DrawStream, IterationDraws  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
 C0 = 0.28209479177387814
@@ -264,7 +269,25 @@ def main(argv=None):
                          "iteration, bank.store() and schedule.advance() after the optimizers, inside the recorded step with --graph "
                          "--optimizer-in-graph (behind the same gate). The camera optimizer is then a FusedAdam(capturable=True) in every "
                          "mode; main.view_bank exposes the bank. Default 1: one view, no bank")
+    ap.add_argument("--random-background", action="store_true",
+                    help="optimization.random_background (true in the reference's shipped configuration; train_pan.py:272-277): the three "
+                         "colour channels of the background are drawn anew in every iteration, on the device, by a counter-based generator "
+                         "keyed by --draw-seed and the iteration's index (eogs2_amd.draw; another generator than torch's: the sequence "
+                         "differs from the reference's). bg[3], the view's lowest altitude, and bg[4] = 0 stay. One launch per iteration, "
+                         "inside the recorded step with --graph. Default: the scene's one fixed background")
+    ap.add_argument("--virtual-camera-extent", type=float, default=None, metavar="X",
+                    help="with --random-camera: opt.virtual_camera_extent. The random virtual camera becomes the reference's "
+                         "cam.sample_random_camera(X) (affine_cameras.py:403-430) of the current view, sampled anew in every iteration in "
+                         "the same launch as --random-background: the view's affine sheared by randn(2).clip(-1, 1) * X about the "
+                         "origin, cam2rnd its myM (times 350: this example's uva holds altitude / 350). Default: one fixed camera")
+    ap.add_argument("--draw-seed", type=int, default=0, metavar="S", help="the 64-bit seed of --random-background and --virtual-camera-extent")
     a = ap.parse_args(argv)
+    if a.virtual_camera_extent is not None and not a.random_camera:
+        ap.error("--virtual-camera-extent samples the camera of --random-camera")
+    if a.virtual_camera_extent is not None and not (a.virtual_camera_extent >= 0 and math.isfinite(a.virtual_camera_extent)):
+        ap.error("--virtual-camera-extent must be finite and not negative")
+    if not 0 <= a.draw_seed < 1 << 64:
+        ap.error("--draw-seed must fit 64 unsigned bits")
     if a.views < 1:
         ap.error("--views must be at least 1")
     if a.views > 1 and (a.dsm_mae_every or a.pansharp_loss or a.flow_matching or a.color_reset_at or a.pan_map):
@@ -461,6 +484,23 @@ def main(argv=None):
         camera_optimizer.step()
         view_bank.attach_optimizer(camera_optimizer)  # every view starts at step 0 with zero moments, as torch's lazy state does
     main.view_bank = view_bank
+    # --random-background / --virtual-camera-extent: one launch per iteration writes bg[0..2], bg[4] and the rnd camera's affine
+    # and cam2rnd, after the bank's load filled them. The iteration's index is the schedule's cursor (--views) or a counter of
+    # the stream's own, which then moves where the schedule would.
+    draws = draw_stream = draw_shear = None
+    if a.random_background or a.virtual_camera_extent is not None:
+        draw_stream = DrawStream(a.draw_seed, counter=view_schedule.cursor) if view_schedule is not None else DrawStream(a.draw_seed, device=dev)
+        draws = IterationDraws(draw_stream)
+        kw = {}
+        if a.random_background:
+            kw.update(bg=bg)
+        if a.virtual_camera_extent is not None:
+            draw_shear = torch.zeros(2, device=dev)
+            kw.update(virt_affine=rnd.affine, cam2virt=cam2rnd, shear=draw_shear, extent=a.virtual_camera_extent, cam2virt_scale=350.0)
+        draws.add_camera(cam.affine, torch.zeros(3, device=dev), **kw)
+        if not a.quiet:  # what was drawn, per iteration: device-to-device copies, read once after the run
+            draw_log = torch.zeros(a.iters, 5, device=dev)
+    main.draw_stream = draw_stream
 
     # the trainee: perturbed colours / opacities / positions, scales re-initialised from the 3-NN statistic
     g = torch.Generator().manual_seed(1)
@@ -477,6 +517,19 @@ def main(argv=None):
                               loaded._rotation, capturable=a.optimizer_in_graph)
             for name in ("_xyz", "_features_dc", "_opacity", "_scaling", "_rotation"):
                 getattr(model, name).copy_(getattr(loaded, name).reshape(getattr(model, name).shape))
+    if a.virtual_camera_extent and a.graph:
+        # A recorded step's list workspaces are sized from the counts the forwards before the recording have seen, plus a margin
+        # (eogs_rast_capacity_token). The sampled camera's shear moves and widens every footprint, so its count varies from
+        # replay to replay: render it once at the four corners of the shear's range for every view, so that the recording is
+        # sized for the range and not for the one camera of its warm-up run.
+        with torch.no_grad():
+            for vm in (rows["viewmatrix"] if view_bank is not None else [cam.affine.clone()]):
+                for d0, d1 in ((-1, -1), (-1, 1), (1, -1), (1, 1)):
+                    corner = vm.clone()  # (stored transposed: column i is row i of A; the centre is the origin, b stays)
+                    corner[:3, 0] += d0 * a.virtual_camera_extent * vm[:3, 2]
+                    corner[:3, 1] += d1 * a.virtual_camera_extent * vm[:3, 2]
+                    rnd.affine.copy_(corner)
+                    render(rnd, model, pipe, bg)
     min_logit = math.log(0.005 / 0.995)  # the transparent prune's threshold on the raw logit
     retire_in_step = bool(a.optimizer_in_graph and a.defer_prune and not a.no_prune)
     if retire_in_step:  # train_pan.py:673-678 in its deferred form, every iteration, inside the Adam launch
@@ -508,6 +561,8 @@ def main(argv=None):
         """Everything between two optimizer steps; reads the model's and the camera's parameter tensors in place."""
         if view_bank is not None:  # --views: the current view's rows into the tensors everything below reads
             view_bank.load()
+        if draws is not None:  # --random-background / --virtual-camera-extent: this iteration's background and virtual camera
+            draws.draw()
         model.optimizer.zero_grad(set_to_none=True)
         camera_optimizer.zero_grad(set_to_none=True)
         out, img, sun_rgb, sun_uv, sun_altitude_diff, shaded, new = view(model, cc_cam)
@@ -547,6 +602,8 @@ def main(argv=None):
             if view_bank is not None:  # the view's updated camera state back into its rows, the cursor on: gated like the steps
                 view_bank.store(gate)
                 view_schedule.advance(gate)
+            elif draw_stream is not None:  # (one view: the stream counts the iterations itself)
+                draw_stream.advance(gate)
         if a.dsm_mae_every:
             kept["altitude"] = out["render"][3].detach()  # (under --graph: the recorded step's output tensor, refilled by a replay)
         return loss.detach(), out.get("radii"), out["viewspace_points"].grad
@@ -601,6 +658,10 @@ def main(argv=None):
         else:
             loss, radii, vs_grad = fwd_bwd()
         stamps.append((t_in, time.perf_counter()))
+        if draws is not None and not a.quiet:  # (before anything moves the cursor or the next draw overwrites them)
+            draw_log[it - 1, :3].copy_(bg[:3])
+            if draw_shear is not None:
+                draw_log[it - 1, 3:].copy_(draw_shear)
         if not steps_inside:
             if mon is not None:
                 feed_monitor(*kept["monitor"], None)
@@ -609,6 +670,8 @@ def main(argv=None):
             if view_bank is not None:
                 view_bank.store()
                 view_schedule.advance()
+            elif draw_stream is not None:
+                draw_stream.advance()
         with torch.no_grad():
             if model.stats is not None:  # train_pan.py:679-690 in one launch, outside the recorded step: once per iteration
                 model.stats.update(vs_grad, radii)
@@ -706,6 +769,13 @@ def main(argv=None):
     if not a.quiet:
         print(f"{a.iters} iterations in {dt:.2f} s ({dt / a.iters * 1e3:.2f} ms/iter over all, {main.last_ms_per_iter:.2f} ms/iter over the "
               f"last {timed}; {3 if a.random_camera else 2} renders + resample + render pipeline + losses + Adam each)")
+    main.last_draws = None
+    if draws is not None and not a.quiet:
+        main.last_draws = draw_log[:a.iters].cpu().tolist()
+        for k, row in enumerate(main.last_draws):  # iteration k + 1 drew at index k of the stream
+            print(f"draw {k:4d}  bg " + " ".join(f"{x:.9g}" for x in row[:3]) + "  shear " + " ".join(f"{x:.9g}" for x in row[3:]))
+        print(f"draws: seed {a.draw_seed}, random background {'on' if a.random_background else 'off'}, virtual camera extent "
+              f"{a.virtual_camera_extent}; the step was recorded {main.last_recordings} time(s)")
     return first, last, model._xyz.shape[0]
 
 
