@@ -250,6 +250,14 @@ DRAW_SIGNATURES = {
     "eogs_draw_iteration": (_i, [_i, _p, _p, _p]),
     "eogs_draw_advance": (_i, [_p, _p, _p]),
 }
+# include/eogs_randomcam.h, a table of its own for the same reason
+RANDOMCAM_SIGNATURES = {
+    "eogs_randomcam_compose": (_i, [_p, _p, _p, _p]),
+    "eogs_cmloss_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+    "eogs_cmloss_forward": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+    "eogs_cmloss_backward": (_i, [_i, _i, _i] + [_p] * 9 + [_p]),
+}
+CMLOSS_MAX_CHANNELS = 4  # EOGS_CMLOSS_MAX_CHANNELS
 DRAW_MAX_CAMERAS = 8  # EOGS_DRAW_MAX_CAMERAS
 DRAW_BG, DRAW_BG_COPY_FIRST, DRAW_CAMERA, DRAW_NADIR = 1, 2, 4, 8  # EOGS_DRAW_*: the flags of a camera
 VIEWS_MAX_SLOTS = 32  # EOGS_VIEWS_MAX_SLOTS
@@ -292,7 +300,7 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
             "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
             "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case", "eogs_reset_erode", "eogs_reset_flags", "eogs_reset_rows",
-            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES, *DRAW_SIGNATURES)
+            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES, *DRAW_SIGNATURES, *RANDOMCAM_SIGNATURES)
 
 
 class PackTensor(C.Structure):
@@ -423,7 +431,8 @@ class RastABI:
         for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
                                   *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
                                   *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items(), *MODEL_SIGNATURES.items(),
-                                  *GTPREP_SIGNATURES.items(), *VIEWS_SIGNATURES.items(), *DRAW_SIGNATURES.items()):
+                                  *GTPREP_SIGNATURES.items(), *VIEWS_SIGNATURES.items(), *DRAW_SIGNATURES.items(),
+                                  *RANDOMCAM_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -441,7 +450,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_", "draw_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_", "draw_", "randomcam_", "cmloss_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

@@ -39,6 +39,12 @@ another view with no host work in between.
 every iteration, as the reference does (train_pan.py:272-277,375-378), on the device (`eogs2_amd.draw.IterationDraws`): one launch
 after `bank.load()`, keyed by `--draw-seed` and the iteration's index, so a recorded step renders against another background and
 another virtual camera on every replay. Without them the background and the `rnd` camera are fixed, as before.
+`--random-camera-type rawrender_wshadow` and `--random-camera-gt` (with `--random-camera`) are the reference's
+`optimization.random_camera.randomcamera_render_type` and `use_gt` (`eogs2_amd.randomcam.RandomcamRendering_Loss`; loss/main_loss.py:56-221):
+the virtual view goes through the view's whole render pipeline, with a shadow map of its own, before it is resampled and compared with the
+shaded image, or with the ground truth. The loss takes the iteration's own sun render (`sun_render=`) instead of rendering the sun camera
+a second time; `--no-share-sun-render` renders twice, as the reference does. The matrices of the shadow-mapped view are composed on the
+device after `draws.draw()` (`virtual_to_sun`), so a recorded step follows the drawn camera.
 """
 import argparse
 import math
@@ -72,6 +78,7 @@ from eogs2_amd.pan import FIXED_PARAMS, KINDS as PAN_KINDS, PanMap, render_pipel
 from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from eogs2_amd.views import ViewBank, ViewSchedule, reference_order  # noqa: E402
 from eogs2_amd.draw import DrawStream, IterationDraws  # noqa: E402
+from eogs2_amd.randomcam import RENDER_TYPES, RandomcamRendering_Loss  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
 C0 = 0.28209479177387814
@@ -280,12 +287,26 @@ def main(argv=None):
                          "cam.sample_random_camera(X) (affine_cameras.py:403-430) of the current view, sampled anew in every iteration in "
                          "the same launch as --random-background: the view's affine sheared by randn(2).clip(-1, 1) * X about the "
                          "origin, cam2rnd its myM (times 350: this example's uva holds altitude / 350). Default: one fixed camera")
+    ap.add_argument("--random-camera-type", choices=RENDER_TYPES, default="rawrender", metavar="TYPE",
+                    help="with --random-camera: optimization.random_camera.randomcamera_render_type. rawrender_wshadow pushes the virtual "
+                         "view through the view's render pipeline with a shadow map of its own (renderer_cc_shadow.py:57-145) and compares "
+                         "it with the shaded image (eogs2_amd.randomcam.RandomcamRendering_Loss). Default: rawrender")
+    ap.add_argument("--random-camera-gt", action="store_true",
+                    help="with --random-camera: RandomcamRendering_Loss(use_gt=True): the comparison target is the ground-truth image, "
+                         "which takes no gradient")
+    ap.add_argument("--no-share-sun-render", action="store_true",
+                    help="with --random-camera-type rawrender_wshadow: render the sun camera a second time inside the loss, as the "
+                         "reference does, instead of handing it the iteration's own sun render (same camera, Gaussians and background)")
     ap.add_argument("--draw-seed", type=int, default=0, metavar="S", help="the 64-bit seed of --random-background and --virtual-camera-extent")
     a = ap.parse_args(argv)
     if a.virtual_camera_extent is not None and not a.random_camera:
         ap.error("--virtual-camera-extent samples the camera of --random-camera")
     if a.virtual_camera_extent is not None and not (a.virtual_camera_extent >= 0 and math.isfinite(a.virtual_camera_extent)):
         ap.error("--virtual-camera-extent must be finite and not negative")
+    if (a.random_camera_type != "rawrender" or a.random_camera_gt) and not a.random_camera:
+        ap.error("--random-camera-type and --random-camera-gt belong to --random-camera")
+    if a.no_share_sun_render and a.random_camera_type != "rawrender_wshadow":
+        ap.error("--no-share-sun-render belongs to --random-camera-type rawrender_wshadow")
     if not 0 <= a.draw_seed < 1 << 64:
         ap.error("--draw-seed must fit 64 unsigned bits")
     if a.views < 1:
@@ -326,6 +347,21 @@ def main(argv=None):
     U, V = torch.meshgrid(torch.linspace(-1, 1, W, device=dev), torch.linspace(-1, 1, H, device=dev), indexing="xy")
 
     branches = Branches(3, device=dev) if a.parallel_renders else None
+    # --random-camera-type rawrender_wshadow / --random-camera-gt: the reference's loss class; else the comparison alone, as before
+    rc_loss = None
+    if a.random_camera and (a.random_camera_type != "rawrender" or a.random_camera_gt):
+        rc_loss = RandomcamRendering_Loss(1e-4, 1e-3, a.random_camera_type, use_gt=a.random_camera_gt)
+    share_sun = a.random_camera_type == "rawrender_wshadow" and not a.no_share_sun_render
+
+    def random_camera_loss(m, cc_cam, uva, altitude, img, shaded, sun_img, rnd_img):
+        """train_pan.py:375-391 through RandomcamRendering_Loss: (L_new_altitude_resample, L_new_rgb_resample). The target's own
+        views (no grad) have no use for it."""
+        if not torch.is_grad_enabled():
+            return None
+        kw = dict(virtual_render=rnd_img)
+        if a.random_camera_type == "rawrender_wshadow":
+            kw.update(sun_render=sun_img if share_sun else None)
+        return rc_loss(rnd, cc_cam, cam2rnd, uva, m, pipe, bg, altitude, img, gt, shaded["shaded"], **kw)
 
     def view(m, cc_cam):
         """train_pan.py:279-330: view render, sun render resampled onto the view, camera render pipeline."""
@@ -347,19 +383,23 @@ def main(argv=None):
             sun_altitude_diff = altitude - sun_alt
             shaded = pipeline(cc_cam, img, sun_altitude_diff)
             new = None
-            if a.random_camera:
+            if rc_loss is not None:
+                new = random_camera_loss(m, cc_cam, uva, altitude, img, shaded, sun_img, rnd_img)
+            elif a.random_camera:
                 smp, new_uv = resample(rnd_img, cam2rnd, uva)
                 new = (altitude - smp[3], smp[:3], new_uv)
             return out, img, sun_rgb, sun_uv, sun_altitude_diff, shaded, new
         out = render(cam, m, pipe, bg)
         img, altitude = out["render"][:3], out["render"][3]
         uva = torch.stack((U, V, altitude / 350.0), dim=-1)
-        sun_rgb, sun_alt, sun_uv = render_resample_virtual_camera(sun, cam2sun, uva, m, pipe, bg,
-                                                                  altitude_only=a.sun_altitude_only)
+        sun_rgb, sun_alt, sun_uv, sun_img = render_resample_virtual_camera(sun, cam2sun, uva, m, pipe, bg, return_extra=True,
+                                                                           altitude_only=a.sun_altitude_only)
         sun_altitude_diff = altitude - sun_alt
         shaded = pipeline(cc_cam, img, sun_altitude_diff)
         new = None
-        if a.random_camera:  # train_pan.py:375-391 / loss/main_loss.py:123-164
+        if rc_loss is not None:  # (the virtual camera is rendered inside the loss)
+            new = random_camera_loss(m, cc_cam, uva, altitude, img, shaded, sun_img, None)
+        elif a.random_camera:  # train_pan.py:375-391 / loss/main_loss.py:123-164
             new_rgb, new_alt, new_uv = render_resample_virtual_camera(rnd, cam2rnd, uva, m, pipe, bg)
             new = (altitude - new_alt, new_rgb, new_uv)
         return out, img, sun_rgb, sun_uv, sun_altitude_diff, shaded, new
@@ -391,6 +431,7 @@ def main(argv=None):
             c.color_correction.bias.zero_()
         c.inshadow_color_correction = torch.nn.Parameter(torch.full((n, 1, 1), 0.05, device=dev))
         c.msi_to_pan = pan_map(perturb)
+        c.get_sun_camera = lambda: (sun, cam2sun)
         m = c.msi_to_pan
         c.map_parameters = [t for t in (m.params, m.weight, m.bias) if isinstance(t, torch.nn.Parameter)]
         return c
@@ -404,6 +445,7 @@ def main(argv=None):
             c.color_correction.weight.copy_((torch.eye(3) + perturb * torch.randn(3, 3, generator=gcam)).reshape(3, 3, 1, 1))
             c.color_correction.bias.zero_()
         c.inshadow_color_correction = torch.nn.Parameter(torch.full((3, 1, 1), 0.05, device=dev))
+        c.get_sun_camera = lambda: (sun, cam2sun)  # affine_cameras.py:350-370: what RandomcamRendering_Loss asks the true camera for
         return c
 
     gcam = torch.Generator().manual_seed(2)
@@ -578,8 +620,10 @@ def main(argv=None):
             L_sun_alt, L_sun_rgb = suncamera_l(img, sun_rgb, sun_altitude_diff, sun_uv)
             loss = loss + 1e-4 * L_sun_alt + 1e-3 * L_sun_rgb
         if new is not None:
-            L_new_alt, L_new_rgb = randomcam_l(new[0], img, new[1], new[2])
+            L_new_alt, L_new_rgb = new if rc_loss is not None else randomcam_l(new[0], img, new[1], new[2])
             loss = loss + 1e-4 * L_new_alt + 1e-3 * L_new_rgb
+            if rc_loss is not None:
+                kept["random_camera"] = (L_new_alt.detach(), L_new_rgb.detach())
         if reg_want:  # train_pan.py:450-465: w_L_opacity * L_opacity (+ w_L_erank * L_erank), summed in the kernel
             loss = loss + gaussian_regularizers(model._opacity, model._scaling, n_init=P, weights=reg_weights, want=reg_want)[0]
         if pansharp_term is not None:  # w_L_pansharp * L_pansharp: one forward and one backward kernel, no full-size temporaries
@@ -769,6 +813,11 @@ def main(argv=None):
     if not a.quiet:
         print(f"{a.iters} iterations in {dt:.2f} s ({dt / a.iters * 1e3:.2f} ms/iter over all, {main.last_ms_per_iter:.2f} ms/iter over the "
               f"last {timed}; {3 if a.random_camera else 2} renders + resample + render pipeline + losses + Adam each)")
+    main.last_random_camera = tuple(float(v) for v in kept["random_camera"]) if "random_camera" in kept else None
+    if rc_loss is not None and not a.quiet:
+        print(f"random camera: {a.random_camera_type}, target {'ground truth' if a.random_camera_gt else 'the view itself'}, sun render "
+              f"{'shared' if share_sun else 'rendered twice' if a.random_camera_type == 'rawrender_wshadow' else 'not used'}; last L_new_altitude_resample "
+              f"{main.last_random_camera[0]:.6g} L_new_rgb_resample {main.last_random_camera[1]:.6g}; the step was recorded {main.last_recordings} time(s)")
     main.last_draws = None
     if draws is not None and not a.quiet:
         main.last_draws = draw_log[:a.iters].cpu().tolist()
