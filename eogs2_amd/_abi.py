@@ -257,6 +257,25 @@ RANDOMCAM_SIGNATURES = {
     "eogs_cmloss_forward": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
     "eogs_cmloss_backward": (_i, [_i, _i, _i] + [_p] * 9 + [_p]),
 }
+# include/eogs_report.h, a table of its own for the same reason
+REPORT_SIGNATURES = {
+    "eogs_report_normalize_rows": (_i, [_i64, _p, _p, _p, _p]),
+    "eogs_report_recompose": (_i, [_i, _p, _p, _p, _p]),
+    "eogs_report_cc_to_test": (_i, [_i, _i, _p, _i, _p, _i, _i, _p]),
+    "eogs_report_metrics_bytes": (_i, [C.POINTER(_z)]),
+    "eogs_report_metrics_reset": (_i, [_p, _p]),
+    "eogs_report_metrics_accumulate": (_i, [_i, _i, _i, _p, _p, _i, _p, _p, _p, _z, _p]),
+    "eogs_report_pack": (_i, [_i, _p, _p, _z, _p]),
+}
+REPORT_MAX_CAMERAS = 64  # EOGS_REPORT_MAX_CAMERAS
+REPORT_MAX_CC_ELEMS = 16  # EOGS_REPORT_MAX_CC_ELEMS
+REPORT_MAX_ITEMS = 16  # EOGS_REPORT_MAX_ITEMS
+REPORT_MAX_CHANNELS = 4  # EOGS_REPORT_MAX_CHANNELS
+REPORT_PACK_MAX_CHANNELS = 5  # EOGS_REPORT_PACK_MAX_CHANNELS
+REPORT_CC_REF, REPORT_CC_AVERAGE = 0, 1  # EOGS_REPORT_CC_*
+REPORT_KINDS = ("pan", "msi")  # EOGS_REPORT_KIND_*: the index
+REPORT_FLOAT_HWC, REPORT_U8_ROUND, REPORT_U8_TRUNC = 0, 1, 2  # EOGS_REPORT_<MODE>
+REPORT_REVERSE, REPORT_REPLICATE, REPORT_PREMAP = 1, 2, 4  # the flags of an item
 CMLOSS_MAX_CHANNELS = 4  # EOGS_CMLOSS_MAX_CHANNELS
 DRAW_MAX_CAMERAS = 8  # EOGS_DRAW_MAX_CAMERAS
 DRAW_BG, DRAW_BG_COPY_FIRST, DRAW_CAMERA, DRAW_NADIR = 1, 2, 4, 8  # EOGS_DRAW_*: the flags of a camera
@@ -300,7 +319,8 @@ HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_
             "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
             "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
             "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case", "eogs_reset_erode", "eogs_reset_flags", "eogs_reset_rows",
-            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES, *DRAW_SIGNATURES, *RANDOMCAM_SIGNATURES)
+            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES, *DRAW_SIGNATURES, *RANDOMCAM_SIGNATURES,
+            *REPORT_SIGNATURES)
 
 
 class PackTensor(C.Structure):
@@ -414,6 +434,26 @@ class DrawCamera(C.Structure):
                 ("extent", _f), ("cam2virt_scale", _f), ("flags", C.c_uint32)]
 
 
+class ReportCamera(C.Structure):
+    """eogs_report_camera (include/eogs_report.h)"""
+
+    _fields_ = [("weight", _p), ("bias", _p)]
+
+
+class ReportTable(C.Structure):
+    """eogs_report_table (include/eogs_report.h)"""
+
+    _fields_ = [("l1", C.c_double * 2), ("psnr", C.c_double * 2), ("views", _i64 * 2), ("last_l1", _f), ("last_psnr", _f),
+                ("reserved", _i64)]
+
+
+class ReportItem(C.Structure):
+    """eogs_report_item (include/eogs_report.h)"""
+
+    _fields_ = [("src", _p), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("mode", C.c_int32), ("dst_offset", C.c_uint64),
+                ("dst_pitch", C.c_uint64), ("flags", C.c_uint32), ("lo", _f), ("d", _f)]
+
+
 class RastError(RuntimeError):
     """A C-ABI call returned a negative status."""
 
@@ -432,7 +472,7 @@ class RastABI:
                                   *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
                                   *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items(), *MODEL_SIGNATURES.items(),
                                   *GTPREP_SIGNATURES.items(), *VIEWS_SIGNATURES.items(), *DRAW_SIGNATURES.items(),
-                                  *RANDOMCAM_SIGNATURES.items()):
+                                  *RANDOMCAM_SIGNATURES.items(), *REPORT_SIGNATURES.items()):
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -450,7 +490,7 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_", "draw_", "randomcam_", "cmloss_"))
+        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_", "draw_", "randomcam_", "cmloss_", "report_"))
         return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
 
     def path_info(self, P, num_rendered):

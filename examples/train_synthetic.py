@@ -45,6 +45,13 @@ the virtual view goes through the view's whole render pipeline, with a shadow ma
 shaded image, or with the ground truth. The loss takes the iteration's own sun render (`sun_render=`) instead of rendering the sun camera
 a second time; `--no-share-sun-render` renders twice, as the reference does. The matrices of the shadow-mapped view are composed on the
 device after `draws.draw()` (`virtual_to_sun`), so a recorded step follows the drawn camera.
+`--test-views N --report-every K` hold out N synthetic views and every K iterations do what the reference's `training_report` does
+(train_pan.py:838-951): the train cameras' colour correction goes to the test cameras by `--cc-to-test ref|average`
+(`eogs2_amd.report.load_convert_color_correction_train_to_test`), then the test and the train views are rendered through sun resample
+and render pipeline and their L1 and PSNR summed on the device (`evaluate_views`: no wait per camera, one copy per report).
+`--normalize-colors` is the reference's `normalize_before_saving` before the final save (train_pan.py:614-620) in place, and
+`--render-set DIR` writes `render_set`'s products of every view (render_pan.py) as DIR/<product>/<view>.npy — one packing launch and
+one copy per view (`view_products`, `fetch_products`) — and render_video.py's frame `[final | elevation]` as DIR/frames/<view>.npy.
 """
 import argparse
 import math
@@ -54,6 +61,7 @@ import sys
 import time
 import types
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -79,6 +87,9 @@ from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
 from eogs2_amd.views import ViewBank, ViewSchedule, reference_order  # noqa: E402
 from eogs2_amd.draw import DrawStream, IterationDraws  # noqa: E402
 from eogs2_amd.randomcam import RENDER_TYPES, RandomcamRendering_Loss  # noqa: E402
+from eogs2_amd.report import (evaluate_views, fetch_products, load_convert_color_correction_train_to_test, normalize_before_saving,  # noqa: E402
+                              video_frame, view_products)
+from eogs2_amd.reset import render_all_views  # noqa: E402
 from simple_knn._C import distCUDA2  # noqa: E402
 
 C0 = 0.28209479177387814
@@ -298,7 +309,34 @@ def main(argv=None):
                     help="with --random-camera-type rawrender_wshadow: render the sun camera a second time inside the loss, as the "
                          "reference does, instead of handing it the iteration's own sun render (same camera, Gaussians and background)")
     ap.add_argument("--draw-seed", type=int, default=0, metavar="S", help="the 64-bit seed of --random-background and --virtual-camera-extent")
+    ap.add_argument("--test-views", type=int, default=0, metavar="N",
+                    help="hold out N synthetic views (make_camera(seed 100 + t), a sun camera and a perturbed colour camera of their own, "
+                         "the target from the unperturbed scene) for --report-every and --render-set. Default 0: none")
+    ap.add_argument("--report-every", type=int, default=0, metavar="K",
+                    help="every K iterations the reference's training_report (train_pan.py:838-951) over the test and the train views: "
+                         "--cc-to-test, then eogs2_amd.report.evaluate_views per set, printed as the reference prints it and kept in "
+                         "main.last_reports. No wait per camera: the sums stay on the device until the one copy. 0 = off")
+    ap.add_argument("--cc-to-test", choices=("ref", "average"), default="average", metavar="RULE",
+                    help="with --report-every: scene.train_to_test_cc_converter, how the test cameras get their colour correction from the "
+                         "train cameras (utils/convert_color_correction.py): view 0's (ref) or the mean over the train views (average)")
+    ap.add_argument("--normalize-colors", action="store_true",
+                    help="after the last iteration and before --save-ply the reference's normalize_before_saving (utils/save_utils.py; "
+                         "train_pan.py:614-620) with view 0 as the reference camera: its colour correction becomes the identity, every "
+                         "Gaussian's colour and every other view's correction are mapped so that renders stay the same. In place "
+                         "(eogs2_amd.report): the parameter, its address and the optimizer state stay; main.last_alignment keeps the "
+                         "colours before and after")
+    ap.add_argument("--render-set", default=None, metavar="DIR",
+                    help="after the last iteration write the products the reference's render_set writes per camera (render_pan.py:94-476) "
+                         "for every train and test view as DIR/<product>/<view>.npy in file layout, and render_video.py's frame "
+                         "[final | normalised elevation] (8-bit BGR) as DIR/frames/<view>.npy: eogs2_amd.report.view_products, "
+                         "fetch_products (one packing launch and one copy per view) and video_frame")
     a = ap.parse_args(argv)
+    if a.test_views < 0 or a.report_every < 0:
+        ap.error("--test-views and --report-every are not negative")
+    if a.report_every and not a.test_views:
+        ap.error("--report-every evaluates held-out views: give --test-views N")
+    if a.normalize_colors and a.pan_first:
+        ap.error("--normalize-colors recomposes 3 x 3 colour corrections: not with --pan-first, whose correction is 1 x 1")
     if a.virtual_camera_extent is not None and not a.random_camera:
         ap.error("--virtual-camera-extent samples the camera of --random-camera")
     if a.virtual_camera_extent is not None and not (a.virtual_camera_extent >= 0 and math.isfinite(a.virtual_camera_extent)):
@@ -544,6 +582,54 @@ def main(argv=None):
             draw_log = torch.zeros(a.iters, 5, device=dev)
     main.draw_stream = draw_stream
 
+    # --test-views / --report-every / --normalize-colors / --render-set: every view as a camera of the reference's kind, with what
+    # training_report, normalize_before_saving and render_set read from one (a viewpoint here is its own MSI or PAN camera)
+    train_viewpoints, test_viewpoints, report_opt, converter = [], [], None, None
+    if a.test_views or a.normalize_colors or a.render_set:
+        kind = "pan" if a.pan_map else "msi"
+        report_opt = types.SimpleNamespace(load_msi=kind == "msi", load_pan=kind == "pan", random_background=False)
+        converter = load_convert_color_correction_train_to_test(a.cc_to_test)
+
+        def report_camera(name, vm, sun_vm, colour, bg3, is_reference=False):
+            rc = Camera(vm, H, W)
+            rc.image_name, rc.image_type, rc.is_reference_camera = name, kind, is_reference
+            rc.altitude_bounds = torch.stack((bg3, bg3)).detach()  # (the lower bound becomes the altitude background, without a readback)
+            rc.UV_grid = (U, V)
+            for which, other in (("sun", Camera(sun_vm, 2 * H, 2 * W)), ("nadir", Camera(rnd.affine.clone(), H, W))):
+                m = torch.eye(3, device=dev)  # (the report stacks the altitude itself, view() the altitude / 350: the same product)
+                m[:2, 2] = (other.affine[2, :2] - vm[2, :2]) / 350.0 / 350.0
+                setattr(rc, f"get_{which}_camera", lambda other=other, m=m: (other, m))
+            rc.color_correction = colour.color_correction
+            rc.render_pipeline = lambda raw_render, sun_altitude_diff=None: pipeline(colour, raw_render, sun_altitude_diff)
+            rc.get_msi_cameras = rc.get_pan_cameras = lambda: rc
+            return rc
+
+        def target_image(rc_of):
+            """The view's target: the unperturbed scene under an identity colour camera."""
+            c = rc_of(colour_camera(0.0))
+            return render_all_views([c], target_model, pipe, bg=bg.clone())[0]["render"].clone()
+
+        if view_bank is not None:  # the views' colour parameters are the bank's rows: cameras over them, no copies
+            for v in range(a.views):
+                colour = types.SimpleNamespace(use_cc=True, use_exposure=False, use_shadow=True, inshadow_color_correction=view_bank.row("camera.2", v),
+                                               color_correction=types.SimpleNamespace(weight=view_bank.row("camera.0", v), bias=view_bank.row("camera.1", v)))
+                rc = report_camera(f"train_{v}", rows["viewmatrix"][v], rows["sun_viewmatrix"][v], colour, rows["bg"][v][3], is_reference=v == 0)
+                rc.original_image = rows["gt"][v]
+                train_viewpoints.append(rc)
+        else:
+            rc = report_camera("train_0", cam.affine, sun.affine, cc_cam, bg[3], is_reference=True)
+            rc.original_image = gt
+            train_viewpoints.append(rc)
+        for k in range(a.test_views):
+            vm, sun_vm = make_camera(H, W, seed=100 + k, device=dev), make_camera(2 * H, 2 * W, seed=105 + 10 * k, device=dev)
+            bg3 = (sc["means3D"] @ vm[:3, 2] + vm[3, 2]).min()
+            rc_of = lambda colour, k=k, vm=vm, sun_vm=sun_vm, bg3=bg3: report_camera(f"test_{k}", vm, sun_vm, colour, bg3)  # noqa: E731
+            rc = rc_of(colour_camera(0.15))
+            with torch.no_grad():
+                rc.original_image = target_image(rc_of)
+            test_viewpoints.append(rc)
+    main.last_reports = []  # --report-every: (iteration, "test" | "train", evaluate_views' dict)
+
     # the trainee: perturbed colours / opacities / positions, scales re-initialised from the 3-NN statistic
     g = torch.Generator().manual_seed(1)
     noise = lambda *s: torch.randn(*s, generator=g).to(dev)
@@ -774,6 +860,13 @@ def main(argv=None):
                 if not a.quiet:
                     print(f"iter {it:4d}  early stop: {a.early_stop_metric} has not improved on {rec['best']:.5g} for {rec['counter']} intervals")
                 stopped_at = it
+        if a.report_every and it % a.report_every == 0:  # train_pan.py:838-951 (its nadir DSM tail is --dsm-mae-every's)
+            converter.perform_cc_to_test(train_viewpoints=train_viewpoints, test_cameras=test_viewpoints, opt=report_opt)
+            for name, cameras in (("test", test_viewpoints), ("train", train_viewpoints)):
+                res = evaluate_views(cameras, model, pipe, report_opt, bg.clone())
+                main.last_reports.append((it, name, res))
+                if not a.quiet:
+                    print(f"[ITER {it}] Evaluating {name}: L1 {res['l1']} PSNR {res['psnr']}")
         if it == 1 or it % 25 == 0 or it == a.iters or stopped_at:
             v = float(loss)
             first = v if first is None else first
@@ -805,6 +898,35 @@ def main(argv=None):
     main.last_params = None
     if a.densify_every or a.views > 1:  # what callers compare between runs, beside the returned tuple
         main.last_params = {g["name"]: g["params"][0].detach().cpu() for g in model.optimizer.param_groups}
+    main.last_alignment = None
+    if a.normalize_colors:  # train_pan.py:614-620, in place: the same Parameter at the same address, the cameras' own storage
+        ref_cc = train_viewpoints[0].color_correction
+        main.last_alignment = dict(f_dc_before=model._features_dc.detach().cpu().clone(), A1=ref_cc.weight.detach().cpu().reshape(3, 3).clone(),
+                                   b1=ref_cc.bias.detach().cpu().clone(), data_ptr=model._features_dc.data_ptr())
+        normalize_before_saving(types.SimpleNamespace(getTrainCameras=lambda: train_viewpoints), model)
+        main.last_alignment["f_dc_after"] = model._features_dc.detach().cpu().clone()
+        if not a.quiet:
+            print("colours aligned to view 0: its colour correction is now " + " ".join(f"{x:.6g}" for x in ref_cc.weight.detach().reshape(-1).tolist())
+                  + " | " + " ".join(f"{x:.6g}" for x in ref_cc.bias.detach().tolist()))
+    main.last_render_set = None
+    if a.render_set:  # render_pan.py:94-476 per view, render_video.py:138-164's frame
+        alt = sc["means3D"] @ cam.affine[:3, 2] + cam.affine[3, 2]
+        alt_min, alt_max = float(alt.min()), float(alt.max())  # (render_video.py's altitude_min / altitude_max: once)
+        written = []
+        for rc in train_viewpoints + test_viewpoints:
+            bg_v = bg.clone()
+            bg_v[3], bg_v[4] = rc.altitude_bounds[0], 0.0
+            products = view_products(rc, model, pipe, bg_v)
+            frame = video_frame(products["final"], products["altitude"], alt_min, alt_max)
+            arrays = fetch_products(products)  # one launch, one copy
+            arrays["frames"] = frame.cpu().numpy()
+            for key, arr in arrays.items():
+                os.makedirs(os.path.join(a.render_set, key), exist_ok=True)
+                np.save(os.path.join(a.render_set, key, rc.image_name + ".npy"), arr)
+                written.append((key, rc.image_name, arr.shape, str(arr.dtype)))
+        main.last_render_set = written
+        if not a.quiet:
+            print(f"render set: {len(written)} arrays of {len(train_viewpoints) + len(test_viewpoints)} views under {a.render_set}")
     if a.save_ply:  # (after the clocks: the file is no part of an iteration)
         out_model = GaussianModel(0)
         out_model._xyz, out_model._features_dc, out_model._features_rest = model._xyz, model._features_dc, model._features_rest
