@@ -1,8 +1,8 @@
-"""ctypes prototypes for the C-ABI declared in include/eogs_rast.h.
+"""ctypes prototypes for the C-ABI declared in include/*.h: one table, `HEADERS`, keyed by header file.
 
 One `RastABI` instance wraps one loaded shared library. The product path only
 ever wraps the HIP library (see `_lib.py`); tests may wrap the CPU oracle, which
-exports the same symbols over host pointers.
+exports the symbols of include/eogs_rast.h over host pointers.
 """
 import ctypes as C
 
@@ -42,231 +42,6 @@ PAN_TRANSLATE_FROZEN = 6
 PAN_ORDER_CC_FIRST = 0  # EOGS_PAN_ORDER_*
 PAN_ORDER_MAP_FIRST = 1
 PAN_NPARAMS = 20
-
-_p = C.c_void_p
-_i = C.c_int
-_f = C.c_float
-_u = C.c_uint
-_z = C.c_size_t
-_i64 = C.c_int64
-
-# name -> (restype, argtypes); the order is exactly include/eogs_rast.h
-SIGNATURES = {
-    "eogs_rast_last_error": (C.c_char_p, []),
-    "eogs_rast_abi_version": (_i, []),
-    "eogs_rast_backend": (C.c_char_p, []),
-    "eogs_rast_geom_bytes": (_i, [_i, C.POINTER(_z)]),
-    "eogs_rast_image_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_rast_binning_bytes": (_i, [_i, _i, _i, _i64, C.POINTER(_z)]),
-    "eogs_rast_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
-    "eogs_rast_forward_prepare": (
-        _i,
-        [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _u, _p, _p, _z, _p, _z, C.POINTER(_i64), _p],
-    ),
-    "eogs_rast_forward_counts": (_i, [C.POINTER(_i64)]),
-    "eogs_rast_read_counts": (_i, [_i, _i, _i, _p, _z, _i, _p, C.POINTER(_i64)]),
-    "eogs_rast_mirror_arm": (_i, [_p]),
-    "eogs_rast_mirror_counts": (_i, [_i, _p, _z, _p, _p]),
-    "eogs_rast_mirror_token": (_i, [_i, _i, _i, _p, _i, C.POINTER(_i64), C.POINTER(_i)]),
-    "eogs_rast_capacity_token": (_i, [_i, _i64, C.c_double, _i, _i64, C.POINTER(_i64), C.POINTER(_i)]),
-    "eogs_rast_forward_render": (
-        _i,
-        [_i, _i, _i, _i64, _p, _u, _p, _z, _p, _z, _p, _z, _p, _z, _p, _p, _p],
-    ),
-    "eogs_rast_backward": (
-        _i,
-        [_i, _i, _i, _i64]
-        + [_p] * 7  # bg, means3D, radii, colors, opacities, scales, rotations
-        + [_f, _p, _p, _p, _p, _u]  # scale_modifier, cov3D_precomp, viewmatrix, projmatrix, alt_affine, flags
-        + [_p] * 4  # out_color, out_invdepth, dL_dout_color, dL_dout_invdepth
-        + [_p, _z, _p, _z, _p, _z]  # geom, binning, image workspaces
-        + [_p] * 9  # 7 gradients + dL_dT_sum + dL_dvm_mean
-        + [_p, _i]  # dL_dcolors_lead, lead_cols
-        + [_p],  # stream
-    ),
-    "eogs_rast_backward_range": (
-        _i,
-        [_i, _i, _i, _i64]
-        + [_p] * 7
-        + [_f, _p, _p, _p, _p, _u]
-        + [_p] * 4
-        + [_p, _z, _p, _z, _p, _z]
-        + [_p] * 9
-        + [_p, _i]  # dL_dcolors_lead, lead_cols
-        + [_i, _i]  # p_begin, p_end
-        + [_p],
-    ),
-    "eogs_rast_mark_visible": (_i, [_i, _p, _p, _p, _p, _p]),
-    "eogs_rast_path_info": (_i, [_i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
-    "eogs_rast_backward_info": (_i, [_i, _i64, C.POINTER(_i)]),
-    "eogs_rast_profile_enable": (_i, [_i]),
-    "eogs_rast_profile_select": (_i, [_u]),
-    "eogs_rast_profile_reset": (_i, []),
-    "eogs_rast_profile_slots": (_i, []),
-    "eogs_rast_profile_get": (_i, [_i, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_char_p)]),
-    "eogs_rast_selftest": (_i, [_p, C.POINTER(_u), _p]),
-    # include/eogs_loss.h
-    "eogs_loss_bytes": (_i, [_i, _i, _i, _u, C.POINTER(_z)]),
-    "eogs_loss_tile_shape": (_i, [C.POINTER(_i), C.POINTER(_i)]),
-    "eogs_loss_window": (_i, [C.POINTER(C.c_float)]),
-    "eogs_loss_forward": (_i, [_i, _i, _i, _p, _p, _u, _f, _f, _f, _p, _p, _p, _z, _p]),
-    "eogs_loss_backward": (_i, [_i, _i, _i, _p, _p, _u, _f, _f, _p, _p, _p, _z, _p, _p]),
-    # include/eogs_optim.h
-    "eogs_adam_step": (_i, [_i, _p, C.c_double, C.c_double, C.c_double, _i64, _p]),
-    "eogs_sum_into": (_i, [_i, _p, _i, _p]),
-    "eogs_pack_columns": (_i, [_i64, _i, _p, _p, _i, _i, _p]),
-    "eogs_compact_bytes": (_i, [_i64, C.POINTER(_z)]),
-    "eogs_compact_plan": (_i, [_i64, _p, _p, _z, C.POINTER(_i64), _p]),
-    "eogs_compact_apply": (_i, [_i64, _p, _i, _p, _p, _p, _p, _z, _p]),
-    # include/eogs_resample.h
-    "eogs_resample_forward": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _p]),
-    "eogs_resample_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_resample_backward": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
-    # include/eogs_resample.h: flow-matching warp
-    "eogs_resample_flow_forward": (_i, [_i, _i, _i, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
-    "eogs_resample_flow_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_resample_flow_backward": (_i, [_i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _z, _p]),
-    "eogs_resample_flow_stats_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_resample_flow_stats": (_i, [_i, _i, _p, _i64, _i64, _i64, _p, _p, _z, _p]),
-    # include/eogs_knn.h
-    "eogs_knn_bytes": (_i, [_i, C.POINTER(_z)]),
-    "eogs_knn_mean_dist2": (_i, [_i, _p, _p, _p, _z, _p]),
-    # include/eogs_shade.h
-    "eogs_shade_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_shade_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
-    "eogs_shade_backward": (_i, [_i, _i] + [_p] * 10 + [_p, _z, _p]),
-    "eogs_mloss_forward": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "eogs_mloss_backward": (_i, [_i, _i, _i] + [_p] * 9 + [_p]),
-    "eogs_tshadow_forward": (_i, [_i64, _p, _p, _p, _z, _p]),
-    "eogs_tshadow_backward": (_i, [_i64, _p, _p, _p, _p]),
-    # include/eogs_tsdf.h
-    "eogs_tsdf_integrate": (_i, [_i, _i, _i, _p, _p, _p, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p]),
-    "eogs_tsdf_normals": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p]),
-    "eogs_tsdf_prior_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
-    "eogs_tsdf_prior": (_i, [_i, _i, _i, _p, _p, _p, _z, _p]),
-    "eogs_tsdf_surface": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
-    # include/eogs_tsdf.h: DSM evaluation
-    "eogs_tsdf_dsm_downsample": (_i, [_i, _i, _p, _i, _p, _p]),
-    "eogs_tsdf_dsm_ncc_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
-    "eogs_tsdf_dsm_ncc": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _z, _p]),
-    "eogs_tsdf_dsm_shift_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_z), C.POINTER(_i)]),
-    "eogs_tsdf_dsm_shift": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
-    "eogs_tsdf_dsm_apply_shift": (_i, [_i, _i, _p, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
-    "eogs_tsdf_dsm_mae_bytes": (_i, [C.POINTER(_z)]),
-    "eogs_tsdf_dsm_mae": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
-}
-# include/eogs_reg.h, bound like the entries above. A table of its own: tests/test_abi.py pins SIGNATURES to the symbols
-# of the seven headers it names.
-REG_SIGNATURES = {
-    "eogs_reg_gauss_bytes": (_i, [_i64, C.POINTER(_z)]),
-    "eogs_reg_gauss_forward": (_i, [_i64, _u, _p, _p, _p, _f, _p, _p, _p, _z, _p]),
-    "eogs_reg_gauss_backward": (_i, [_i64, _u, _p, _p, _p, _f] + [_p] * 6 + [_p]),
-    "eogs_reg_image_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_reg_image_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _z, _p]),
-    "eogs_reg_image_backward": (_i, [_i, _i] + [_p] * 7 + [_p]),
-}
-# include/eogs_pan.h, a table of its own for the same reason
-PAN_SIGNATURES = {
-    "eogs_pan_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_pan_forward": (_i, [_i, _i, _i, _i] + [_p] * 8 + [_p]),
-    "eogs_pan_backward": (_i, [_i, _i, _i, _i] + [_p] * 11 + [_p, _z, _p]),
-}
-# include/eogs_density.h, a table of its own for the same reason
-DENSITY_SIGNATURES = {
-    "eogs_density_stats_update": (_i, [_i64, _p, _p, _i, _p, _p, _p, _p]),
-    "eogs_density_bytes": (_i, [_i64, C.POINTER(_z)]),
-    "eogs_density_decide": (_i, [_i64, _p, _p, _p, _p, _f, _f, _f, _i, _f, _f, _p, _p, _z, C.POINTER(_i64), _p]),
-    "eogs_density_split_rows": (_i, [_i64, _p, _p, _p, _i, _p, _z, _p]),
-    "eogs_density_build": (_i, [_i64, _i, _p, C.POINTER(_i64), _i, _p, _p, _p, _f, _p, _z, _p]),
-}
-# include/eogs_step.h, a table of its own for the same reason
-STEP_SIGNATURES = {
-    "eogs_step_gate": (_i, [_i, _p, _i, _p, _p]),
-    "eogs_step_adam_bytes": (_i, [_i, C.POINTER(_z)]),
-    "eogs_step_adam": (_i, [_i, _p, C.c_double, C.c_double, C.c_double, _p, _p, _z, _p]),
-}
-# include/eogs_monitor.h, a table of its own for the same reason
-MONITOR_SIGNATURES = {
-    "eogs_monitor_state_bytes": (_i, [C.POINTER(_z)]),
-    "eogs_monitor_reset": (_i, [_p, _z, _i, _p]),
-    "eogs_monitor_observe_bytes": (_i, [_i, _i, _i, _i, C.POINTER(_z)]),
-    "eogs_monitor_observe": (_i, [_i, _i, _i, _p, _p, _p, C.c_double, _i, _i, _p, _p, _p, _z, _p]),
-    "eogs_monitor_model_bytes": (_i, [_i64, C.POINTER(_z)]),
-    "eogs_monitor_observe_model": (_i, [_i64, _p, _p, _p, _p, _z, _p]),
-    "eogs_monitor_end_iteration": (_i, [_p, _p, _p, _p]),
-    "eogs_monitor_close_interval": (_i, [_i, _i, _i64, _p, _p, _p]),
-}
-# include/eogs_dsm.h, a table of its own for the same reason
-DSM_SIGNATURES = {
-    "eogs_dsm_bounds_bytes": (_i, [C.POINTER(_z)]),
-    "eogs_dsm_bounds": (_i, [_p, _p, _p, _z, _p]),
-    "eogs_dsm_raster_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
-    "eogs_dsm_raster": (_i, [_p, C.c_double, C.c_double, C.c_double, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
-}
-# include/eogs_mesh.h, a table of its own for the same reason
-MESH_SIGNATURES = {
-    "eogs_mesh_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
-    "eogs_mesh_count": (_i, [_i, _i, _i, _p, C.c_double, _p, _z, _p, _p]),
-    "eogs_mesh_emit": (_i, [_i, _i, _i, _p, C.c_double, _p, _p, _p, C.POINTER(C.c_double), _p, _z, _p, _i64, _p, _i64, _p]),
-    "eogs_mesh_case": (_i, [_i, C.POINTER(C.c_int8), C.POINTER(_i)]),
-}
-# include/eogs_reset.h, a table of its own for the same reason
-RESET_SIGNATURES = {
-    "eogs_reset_erode": (_i, [_i, _i, _p, _p, _p]),
-    "eogs_reset_flags": (_i, [_i64, _p, _p, _f, _i, _p, _i, _p, _p]),
-    "eogs_reset_rows": (_i, [_i64, _p, _i, _p, _p]),
-    "eogs_reset_opacity_cap": (_i, [_i64, _p, _p, _p, _f, _f, _p]),
-}
-# include/eogs_model.h, a table of its own for the same reason
-MODEL_SIGNATURES = {
-    "eogs_model_init": (_i, [_i64, _i, _p, _p, _p, _f] + [_p] * 7 + [_p]),
-    "eogs_model_rows_pack": (_i, [_i64, _i] + [_p] * 6 + [_p, _p]),
-    "eogs_model_rows_unpack": (_i, [_i64, _i, _p] + [_p] * 6 + [_p]),
-}
-# include/eogs_gtprep.h, a table of its own for the same reason
-GTPREP_SIGNATURES = {
-    "eogs_gtprep_bytes": (_i, [_i, C.POINTER(_z)]),
-    "eogs_gtprep_pansharp": (_i, [_i] * 6 + [_p, _p, _f, _p, _p]),
-    "eogs_gtprep_pansharp_l2_forward": (_i, [_i] * 6 + [_p, _p, _p, _f, _p, _p, _z, _p]),
-    "eogs_gtprep_pansharp_l2_backward": (_i, [_i] * 6 + [_p, _p, _p, _f, _p, _p, _p]),
-    "eogs_gtprep_l2_forward": (_i, [_i64, _p, _p, _p, _p, _z, _p]),
-    "eogs_gtprep_l2_backward": (_i, [_i64, _p, _p, _p, _p, _p]),
-    "eogs_gtprep_grad_l2_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _z, _p]),
-    "eogs_gtprep_grad_l2_backward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p]),
-    "eogs_gtprep_minmax": (_i, [_i, _i64, _p, _p, _p, _z, _p]),
-    "eogs_gtprep_rescale": (_i, [_i, _i64, _p, _p, _p, _p]),
-    "eogs_gtprep_clamp": (_i, [_i64, _p, _f, _f, _p, _p]),
-    "eogs_gtprep_equalize": (_i, [_i, _i64, _p, _p, _p, _z, _p]),
-}
-# include/eogs_views.h, a table of its own for the same reason
-VIEWS_SIGNATURES = {
-    "eogs_views_wg_bytes": (_i, [C.POINTER(_z)]),
-    "eogs_views_load": (_i, [_i, _p, _p, _p]),
-    "eogs_views_store": (_i, [_i, _p, _p, _p, _p]),
-    "eogs_views_advance": (_i, [_p, _p, _p]),
-}
-# include/eogs_draw.h, a table of its own for the same reason
-DRAW_SIGNATURES = {
-    "eogs_draw_iteration": (_i, [_i, _p, _p, _p]),
-    "eogs_draw_advance": (_i, [_p, _p, _p]),
-}
-# include/eogs_randomcam.h, a table of its own for the same reason
-RANDOMCAM_SIGNATURES = {
-    "eogs_randomcam_compose": (_i, [_p, _p, _p, _p]),
-    "eogs_cmloss_bytes": (_i, [_i, _i, C.POINTER(_z)]),
-    "eogs_cmloss_forward": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
-    "eogs_cmloss_backward": (_i, [_i, _i, _i] + [_p] * 9 + [_p]),
-}
-# include/eogs_report.h, a table of its own for the same reason
-REPORT_SIGNATURES = {
-    "eogs_report_normalize_rows": (_i, [_i64, _p, _p, _p, _p]),
-    "eogs_report_recompose": (_i, [_i, _p, _p, _p, _p]),
-    "eogs_report_cc_to_test": (_i, [_i, _i, _p, _i, _p, _i, _i, _p]),
-    "eogs_report_metrics_bytes": (_i, [C.POINTER(_z)]),
-    "eogs_report_metrics_reset": (_i, [_p, _p]),
-    "eogs_report_metrics_accumulate": (_i, [_i, _i, _i, _p, _p, _i, _p, _p, _p, _z, _p]),
-    "eogs_report_pack": (_i, [_i, _p, _p, _z, _p]),
-}
 REPORT_MAX_CAMERAS = 64  # EOGS_REPORT_MAX_CAMERAS
 REPORT_MAX_CC_ELEMS = 16  # EOGS_REPORT_MAX_CC_ELEMS
 REPORT_MAX_ITEMS = 16  # EOGS_REPORT_MAX_ITEMS
@@ -303,24 +78,230 @@ STEP_MAX_FORWARDS = STEP_MAX_TENSORS = 16  # EOGS_STEP_MAX_*
 DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP = 1, 2, 4, 8  # EOGS_DENSITY_*: the flag byte
 DENSITY_COPY, DENSITY_ZERO, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2, 3  # the tensor kinds of eogs_density_build
 DENSITY_MAX_N = 8
-# symbols only the HIP library exports (the CPU oracle of the loss is oracle/loss_oracle.py, not a C-ABI twin)
-HIP_ONLY = ("eogs_sum_into", "eogs_pack_columns", "eogs_loss_bytes", "eogs_loss_tile_shape", "eogs_loss_window", "eogs_loss_forward", "eogs_loss_backward", "eogs_adam_step", "eogs_compact_bytes",
-            "eogs_compact_plan", "eogs_compact_apply", "eogs_resample_forward", "eogs_resample_bytes", "eogs_resample_backward", "eogs_knn_bytes",
-            "eogs_knn_mean_dist2", "eogs_shade_bytes", "eogs_shade_forward", "eogs_shade_backward", "eogs_mloss_forward",
-            "eogs_mloss_backward", "eogs_tshadow_forward", "eogs_tshadow_backward", "eogs_tsdf_integrate", "eogs_tsdf_normals",
-            "eogs_tsdf_prior_bytes", "eogs_tsdf_prior", "eogs_tsdf_surface", "eogs_tsdf_dsm_downsample", "eogs_tsdf_dsm_ncc_bytes",
-            "eogs_tsdf_dsm_ncc", "eogs_tsdf_dsm_shift_bytes", "eogs_tsdf_dsm_shift", "eogs_tsdf_dsm_apply_shift",
-            "eogs_tsdf_dsm_mae_bytes", "eogs_tsdf_dsm_mae", "eogs_resample_flow_forward", "eogs_resample_flow_bytes",
-            "eogs_resample_flow_backward", "eogs_resample_flow_stats_bytes", "eogs_resample_flow_stats", "eogs_reg_gauss_bytes",
-            "eogs_reg_gauss_forward", "eogs_reg_gauss_backward", "eogs_reg_image_bytes", "eogs_reg_image_forward",
-            "eogs_reg_image_backward", "eogs_pan_bytes", "eogs_pan_forward", "eogs_pan_backward", "eogs_density_stats_update",
-            "eogs_density_bytes", "eogs_density_decide", "eogs_density_split_rows", "eogs_density_build", "eogs_step_gate",
-            "eogs_step_adam_bytes", "eogs_step_adam", "eogs_monitor_state_bytes", "eogs_monitor_reset", "eogs_monitor_observe_bytes",
-            "eogs_monitor_observe", "eogs_monitor_model_bytes", "eogs_monitor_observe_model", "eogs_monitor_end_iteration",
-            "eogs_monitor_close_interval", "eogs_dsm_bounds_bytes", "eogs_dsm_bounds", "eogs_dsm_raster_bytes", "eogs_dsm_raster", "eogs_mesh_bytes",
-            "eogs_mesh_count", "eogs_mesh_emit", "eogs_mesh_case", "eogs_reset_erode", "eogs_reset_flags", "eogs_reset_rows",
-            "eogs_reset_opacity_cap", "eogs_model_init", "eogs_model_rows_pack", "eogs_model_rows_unpack", *GTPREP_SIGNATURES, *VIEWS_SIGNATURES, *DRAW_SIGNATURES, *RANDOMCAM_SIGNATURES,
-            *REPORT_SIGNATURES)
+
+_p = C.c_void_p
+_i = C.c_int
+_f = C.c_float
+_u = C.c_uint
+_z = C.c_size_t
+_i64 = C.c_int64
+
+# header -> name -> (restype, argtypes), every header of include/ in the order of its declarations. The one table:
+# tests/test_abi.py holds it against the headers and the built library, symbol by symbol.
+HEADERS = {
+    "eogs_rast.h": {
+        "eogs_rast_last_error": (C.c_char_p, []),
+        "eogs_rast_abi_version": (_i, []),
+        "eogs_rast_backend": (C.c_char_p, []),
+        "eogs_rast_geom_bytes": (_i, [_i, C.POINTER(_z)]),
+        "eogs_rast_image_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_rast_binning_bytes": (_i, [_i, _i, _i, _i64, C.POINTER(_z)]),
+        "eogs_rast_scratch_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_rast_forward_prepare": (
+            _i,
+            [_i, _i, _i, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _u, _p, _p, _z, _p, _z, C.POINTER(_i64), _p],
+        ),
+        "eogs_rast_forward_counts": (_i, [C.POINTER(_i64)]),
+        "eogs_rast_read_counts": (_i, [_i, _i, _i, _p, _z, _i, _p, C.POINTER(_i64)]),
+        "eogs_rast_mirror_arm": (_i, [_p]),
+        "eogs_rast_mirror_counts": (_i, [_i, _p, _z, _p, _p]),
+        "eogs_rast_mirror_token": (_i, [_i, _i, _i, _p, _i, C.POINTER(_i64), C.POINTER(_i)]),
+        "eogs_rast_capacity_token": (_i, [_i, _i64, C.c_double, _i, _i64, C.POINTER(_i64), C.POINTER(_i)]),
+        "eogs_rast_forward_render": (
+            _i,
+            [_i, _i, _i, _i64, _p, _u, _p, _z, _p, _z, _p, _z, _p, _z, _p, _p, _p],
+        ),
+        "eogs_rast_backward": (
+            _i,
+            [_i, _i, _i, _i64]
+            + [_p] * 7  # bg, means3D, radii, colors, opacities, scales, rotations
+            + [_f, _p, _p, _p, _p, _u]  # scale_modifier, cov3D_precomp, viewmatrix, projmatrix, alt_affine, flags
+            + [_p] * 4  # out_color, out_invdepth, dL_dout_color, dL_dout_invdepth
+            + [_p, _z, _p, _z, _p, _z]  # geom, binning, image workspaces
+            + [_p] * 9  # 7 gradients + dL_dT_sum + dL_dvm_mean
+            + [_p, _i]  # dL_dcolors_lead, lead_cols
+            + [_p],  # stream
+        ),
+        "eogs_rast_backward_range": (
+            _i,
+            [_i, _i, _i, _i64]
+            + [_p] * 7
+            + [_f, _p, _p, _p, _p, _u]
+            + [_p] * 4
+            + [_p, _z, _p, _z, _p, _z]
+            + [_p] * 9
+            + [_p, _i]  # dL_dcolors_lead, lead_cols
+            + [_i, _i]  # p_begin, p_end
+            + [_p],
+        ),
+        "eogs_rast_mark_visible": (_i, [_i, _p, _p, _p, _p, _p]),
+        "eogs_rast_path_info": (_i, [_i, _i64, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+        "eogs_rast_backward_info": (_i, [_i, _i64, C.POINTER(_i)]),
+        "eogs_rast_profile_enable": (_i, [_i]),
+        "eogs_rast_profile_select": (_i, [_u]),
+        "eogs_rast_profile_reset": (_i, []),
+        "eogs_rast_profile_slots": (_i, []),
+        "eogs_rast_profile_get": (_i, [_i, C.POINTER(C.c_double), C.POINTER(_i64), C.POINTER(C.c_char_p)]),
+        "eogs_rast_selftest": (_i, [_p, C.POINTER(_u), _p]),
+    },
+    "eogs_loss.h": {
+        "eogs_loss_bytes": (_i, [_i, _i, _i, _u, C.POINTER(_z)]),
+        "eogs_loss_tile_shape": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+        "eogs_loss_window": (_i, [C.POINTER(C.c_float)]),
+        "eogs_loss_forward": (_i, [_i, _i, _i, _p, _p, _u, _f, _f, _f, _p, _p, _p, _z, _p]),
+        "eogs_loss_backward": (_i, [_i, _i, _i, _p, _p, _u, _f, _f, _p, _p, _p, _z, _p, _p]),
+    },
+    "eogs_optim.h": {
+        "eogs_adam_step": (_i, [_i, _p, C.c_double, C.c_double, C.c_double, _i64, _p]),
+        "eogs_sum_into": (_i, [_i, _p, _i, _p]),
+        "eogs_pack_columns": (_i, [_i64, _i, _p, _p, _i, _i, _p]),
+        "eogs_compact_bytes": (_i, [_i64, C.POINTER(_z)]),
+        "eogs_compact_plan": (_i, [_i64, _p, _p, _z, C.POINTER(_i64), _p]),
+        "eogs_compact_apply": (_i, [_i64, _p, _i, _p, _p, _p, _p, _z, _p]),
+    },
+    "eogs_resample.h": {
+        "eogs_resample_forward": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _f, _p, _p, _p]),
+        "eogs_resample_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_resample_backward": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
+        # the flow-matching warp
+        "eogs_resample_flow_forward": (_i, [_i, _i, _i, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+        "eogs_resample_flow_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_resample_flow_backward": (_i, [_i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _z, _p]),
+        "eogs_resample_flow_stats_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_resample_flow_stats": (_i, [_i, _i, _p, _i64, _i64, _i64, _p, _p, _z, _p]),
+    },
+    "eogs_knn.h": {
+        "eogs_knn_bytes": (_i, [_i, C.POINTER(_z)]),
+        "eogs_knn_mean_dist2": (_i, [_i, _p, _p, _p, _z, _p]),
+    },
+    "eogs_shade.h": {
+        "eogs_shade_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_shade_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+        "eogs_shade_backward": (_i, [_i, _i] + [_p] * 10 + [_p, _z, _p]),
+        "eogs_mloss_forward": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+        "eogs_mloss_backward": (_i, [_i, _i, _i] + [_p] * 9 + [_p]),
+        "eogs_tshadow_forward": (_i, [_i64, _p, _p, _p, _z, _p]),
+        "eogs_tshadow_backward": (_i, [_i64, _p, _p, _p, _p]),
+    },
+    "eogs_tsdf.h": {
+        "eogs_tsdf_integrate": (_i, [_i, _i, _i, _p, _p, _p, _p, _f, _f, _i, _i, _p, _p, _p, _p, _p]),
+        "eogs_tsdf_normals": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, _p]),
+        "eogs_tsdf_prior_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_tsdf_prior": (_i, [_i, _i, _i, _p, _p, _p, _z, _p]),
+        "eogs_tsdf_surface": (_i, [_i, _i, _i, _p, _p, _p, _p, _p]),
+        # DSM evaluation
+        "eogs_tsdf_dsm_downsample": (_i, [_i, _i, _p, _i, _p, _p]),
+        "eogs_tsdf_dsm_ncc_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_tsdf_dsm_ncc": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _i, _p, _p, _p, _z, _p]),
+        "eogs_tsdf_dsm_shift_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_z), C.POINTER(_i)]),
+        "eogs_tsdf_dsm_shift": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
+        "eogs_tsdf_dsm_apply_shift": (_i, [_i, _i, _p, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
+        "eogs_tsdf_dsm_mae_bytes": (_i, [C.POINTER(_z)]),
+        "eogs_tsdf_dsm_mae": (_i, [_i, _i, _p, _i, _i, _p, _i, _i, _p, _p, _p, _z, _p]),
+    },
+    "eogs_reg.h": {
+        "eogs_reg_gauss_bytes": (_i, [_i64, C.POINTER(_z)]),
+        "eogs_reg_gauss_forward": (_i, [_i64, _u, _p, _p, _p, _f, _p, _p, _p, _z, _p]),
+        "eogs_reg_gauss_backward": (_i, [_i64, _u, _p, _p, _p, _f] + [_p] * 6 + [_p]),
+        "eogs_reg_image_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_reg_image_forward": (_i, [_i, _i, _p, _p, _p, _p, _p, _z, _p]),
+        "eogs_reg_image_backward": (_i, [_i, _i] + [_p] * 7 + [_p]),
+    },
+    "eogs_pan.h": {
+        "eogs_pan_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_pan_forward": (_i, [_i, _i, _i, _i] + [_p] * 8 + [_p]),
+        "eogs_pan_backward": (_i, [_i, _i, _i, _i] + [_p] * 11 + [_p, _z, _p]),
+    },
+    "eogs_density.h": {
+        "eogs_density_stats_update": (_i, [_i64, _p, _p, _i, _p, _p, _p, _p]),
+        "eogs_density_bytes": (_i, [_i64, C.POINTER(_z)]),
+        "eogs_density_decide": (_i, [_i64, _p, _p, _p, _p, _f, _f, _f, _i, _f, _f, _p, _p, _z, C.POINTER(_i64), _p]),
+        "eogs_density_split_rows": (_i, [_i64, _p, _p, _p, _i, _p, _z, _p]),
+        "eogs_density_build": (_i, [_i64, _i, _p, C.POINTER(_i64), _i, _p, _p, _p, _f, _p, _z, _p]),
+    },
+    "eogs_step.h": {
+        "eogs_step_gate": (_i, [_i, _p, _i, _p, _p]),
+        "eogs_step_adam_bytes": (_i, [_i, C.POINTER(_z)]),
+        "eogs_step_adam": (_i, [_i, _p, C.c_double, C.c_double, C.c_double, _p, _p, _z, _p]),
+    },
+    "eogs_monitor.h": {
+        "eogs_monitor_state_bytes": (_i, [C.POINTER(_z)]),
+        "eogs_monitor_reset": (_i, [_p, _z, _i, _p]),
+        "eogs_monitor_observe_bytes": (_i, [_i, _i, _i, _i, C.POINTER(_z)]),
+        "eogs_monitor_observe": (_i, [_i, _i, _i, _p, _p, _p, C.c_double, _i, _i, _p, _p, _p, _z, _p]),
+        "eogs_monitor_model_bytes": (_i, [_i64, C.POINTER(_z)]),
+        "eogs_monitor_observe_model": (_i, [_i64, _p, _p, _p, _p, _z, _p]),
+        "eogs_monitor_end_iteration": (_i, [_p, _p, _p, _p]),
+        "eogs_monitor_close_interval": (_i, [_i, _i, _i64, _p, _p, _p]),
+    },
+    "eogs_dsm.h": {
+        "eogs_dsm_bounds_bytes": (_i, [C.POINTER(_z)]),
+        "eogs_dsm_bounds": (_i, [_p, _p, _p, _z, _p]),
+        "eogs_dsm_raster_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_dsm_raster": (_i, [_p, C.c_double, C.c_double, C.c_double, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    },
+    "eogs_mesh.h": {
+        "eogs_mesh_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_mesh_count": (_i, [_i, _i, _i, _p, C.c_double, _p, _z, _p, _p]),
+        "eogs_mesh_emit": (_i, [_i, _i, _i, _p, C.c_double, _p, _p, _p, C.POINTER(C.c_double), _p, _z, _p, _i64, _p, _i64, _p]),
+        "eogs_mesh_case": (_i, [_i, C.POINTER(C.c_int8), C.POINTER(_i)]),
+    },
+    "eogs_reset.h": {
+        "eogs_reset_erode": (_i, [_i, _i, _p, _p, _p]),
+        "eogs_reset_flags": (_i, [_i64, _p, _p, _f, _i, _p, _i, _p, _p]),
+        "eogs_reset_rows": (_i, [_i64, _p, _i, _p, _p]),
+        "eogs_reset_opacity_cap": (_i, [_i64, _p, _p, _p, _f, _f, _p]),
+    },
+    "eogs_model.h": {
+        "eogs_model_init": (_i, [_i64, _i, _p, _p, _p, _f] + [_p] * 7 + [_p]),
+        "eogs_model_rows_pack": (_i, [_i64, _i] + [_p] * 6 + [_p, _p]),
+        "eogs_model_rows_unpack": (_i, [_i64, _i, _p] + [_p] * 6 + [_p]),
+    },
+    "eogs_gtprep.h": {
+        "eogs_gtprep_bytes": (_i, [_i, C.POINTER(_z)]),
+        "eogs_gtprep_pansharp": (_i, [_i] * 6 + [_p, _p, _f, _p, _p]),
+        "eogs_gtprep_pansharp_l2_forward": (_i, [_i] * 6 + [_p, _p, _p, _f, _p, _p, _z, _p]),
+        "eogs_gtprep_pansharp_l2_backward": (_i, [_i] * 6 + [_p, _p, _p, _f, _p, _p, _p]),
+        "eogs_gtprep_l2_forward": (_i, [_i64, _p, _p, _p, _p, _z, _p]),
+        "eogs_gtprep_l2_backward": (_i, [_i64, _p, _p, _p, _p, _p]),
+        "eogs_gtprep_grad_l2_forward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _z, _p]),
+        "eogs_gtprep_grad_l2_backward": (_i, [_i64, _i, _i, _p, _p, _p, _p, _p]),
+        "eogs_gtprep_minmax": (_i, [_i, _i64, _p, _p, _p, _z, _p]),
+        "eogs_gtprep_rescale": (_i, [_i, _i64, _p, _p, _p, _p]),
+        "eogs_gtprep_clamp": (_i, [_i64, _p, _f, _f, _p, _p]),
+        "eogs_gtprep_equalize": (_i, [_i, _i64, _p, _p, _p, _z, _p]),
+    },
+    "eogs_views.h": {
+        "eogs_views_wg_bytes": (_i, [C.POINTER(_z)]),
+        "eogs_views_load": (_i, [_i, _p, _p, _p]),
+        "eogs_views_store": (_i, [_i, _p, _p, _p, _p]),
+        "eogs_views_advance": (_i, [_p, _p, _p]),
+    },
+    "eogs_draw.h": {
+        "eogs_draw_iteration": (_i, [_i, _p, _p, _p]),
+        "eogs_draw_advance": (_i, [_p, _p, _p]),
+    },
+    "eogs_randomcam.h": {
+        "eogs_randomcam_compose": (_i, [_p, _p, _p, _p]),
+        "eogs_cmloss_bytes": (_i, [_i, _i, C.POINTER(_z)]),
+        "eogs_cmloss_forward": (_i, [_i, _i, _i, _p, _p, _p, _p, _p, _p, _z, _p]),
+        "eogs_cmloss_backward": (_i, [_i, _i, _i] + [_p] * 9 + [_p]),
+    },
+    "eogs_report.h": {
+        "eogs_report_normalize_rows": (_i, [_i64, _p, _p, _p, _p]),
+        "eogs_report_recompose": (_i, [_i, _p, _p, _p, _p]),
+        "eogs_report_cc_to_test": (_i, [_i, _i, _p, _i, _p, _i, _i, _p]),
+        "eogs_report_metrics_bytes": (_i, [C.POINTER(_z)]),
+        "eogs_report_metrics_reset": (_i, [_p, _p]),
+        "eogs_report_metrics_accumulate": (_i, [_i, _i, _i, _p, _p, _i, _p, _p, _p, _z, _p]),
+        "eogs_report_pack": (_i, [_i, _p, _p, _z, _p]),
+    },
+}
+# name -> (restype, argtypes) of every header
+SIGNATURES = {name: sig for table in HEADERS.values() for name, sig in table.items()}
+# symbols only the HIP library exports: the CPU oracle is the twin of include/eogs_rast.h alone (the oracle of the loss, say,
+# is oracle/loss_oracle.py, not a C-ABI twin)
+HIP_ONLY = tuple(name for name in SIGNATURES if name not in HEADERS["eogs_rast.h"])
 
 
 class PackTensor(C.Structure):
@@ -468,11 +449,7 @@ class RastABI:
         self.cdll = C.CDLL(self.path)
         self.cdll.eogs_rast_backend.restype = C.c_char_p
         oracle_lib = self.cdll.eogs_rast_backend().decode() == "cpu-oracle"
-        for name, (res, args) in (*SIGNATURES.items(), *REG_SIGNATURES.items(), *PAN_SIGNATURES.items(), *DENSITY_SIGNATURES.items(),
-                                  *STEP_SIGNATURES.items(), *MONITOR_SIGNATURES.items(), *DSM_SIGNATURES.items(),
-                                  *MESH_SIGNATURES.items(), *RESET_SIGNATURES.items(), *MODEL_SIGNATURES.items(),
-                                  *GTPREP_SIGNATURES.items(), *VIEWS_SIGNATURES.items(), *DRAW_SIGNATURES.items(),
-                                  *RANDOMCAM_SIGNATURES.items(), *REPORT_SIGNATURES.items()):
+        for name, (res, args) in SIGNATURES.items():
             if oracle_lib and name in HIP_ONLY:
                 continue
             fn = getattr(self.cdll, name)  # AttributeError if the library lacks a declared symbol
@@ -490,8 +467,12 @@ class RastABI:
             raise RastError(code, self.cdll.eogs_rast_last_error().decode())
 
     def __getattr__(self, name):
-        short = name.startswith(("loss_", "adam_", "sum_", "pack_", "compact_", "resample_", "knn_", "shade_", "mloss_", "tshadow_", "tsdf_", "reg_", "pan_", "density_", "step_", "monitor_", "dsm_", "mesh_", "reset_", "model_", "gtprep_", "views_", "draw_", "randomcam_", "cmloss_", "report_"))
-        return getattr(self.cdll, ("eogs_" if short else "eogs_rast_") + name)
+        """`abi.loss_forward` is eogs_loss_forward, `abi.geom_bytes` eogs_rast_geom_bytes: a name the table holds behind
+        "eogs_", else the rasterizer's. Kept on the instance, so this runs once per name."""
+        full = "eogs_" + name
+        fn = getattr(self.cdll, full if full in SIGNATURES else "eogs_rast_" + name)
+        setattr(self, name, fn)
+        return fn
 
     def path_info(self, P, num_rendered):
         """(list block in pixels, forward kernel variant, backward kernel variant) of a forward (include/eogs_rast.h)."""

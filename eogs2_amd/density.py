@@ -14,6 +14,7 @@
 No CPU / eager fallback: arithmetic only in the HIP library.
 """
 import ctypes
+import functools
 
 import torch
 
@@ -21,18 +22,14 @@ from . import _lib
 from . import optim as _optim
 from ._abi import (DENSITY_CLONE, DENSITY_COPY, DENSITY_MAX_N, DENSITY_PRUNE_SAMP, DENSITY_PRUNE_SELF, DENSITY_SCALING,
                    DENSITY_SPLIT, DENSITY_XYZ, DENSITY_ZERO, DensityTensor)
-from .flow import _call
-from .rasterizer import _Ctx
+from ._host import Ctx, call, on_device, query_bytes
 
 STATS = ("xyz_gradient_accum", "denom", "max_radii2D")
 # the bit layout of DensifyInfo.flags, one byte per ORIGINAL row (include/eogs_density.h EOGS_DENSITY_*)
 FLAG_CLONE, FLAG_SPLIT, FLAG_PRUNE_SELF, FLAG_PRUNE_SAMPLES = DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP
 
 
-def _on_device(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"density {what}: tensors live on '{t.device.type}'; density control runs on the GPU only, there is "
-                           "no CPU fallback")
+_on_device = functools.partial(on_device, "density", "density control runs")
 
 
 def _check_stats(accum, denom, maxr, what):
@@ -86,8 +83,8 @@ def add_densification_stats(xyz_gradient_accum, denom, max_radii2D, viewspace_gr
     vg = viewspace_grad.detach()
     vg = vg if vg.is_contiguous() else vg.contiguous()
     r = radii if radii.is_contiguous() else radii.contiguous()
-    _call("eogs_density_stats_update", dev, P, vg.data_ptr(), r.data_ptr(), int(r.dtype == torch.float32),
-          xyz_gradient_accum.data_ptr(), denom.data_ptr(), max_radii2D.data_ptr())
+    call("eogs_density_stats_update", dev, P, vg.data_ptr(), r.data_ptr(), int(r.dtype == torch.float32),
+         xyz_gradient_accum.data_ptr(), denom.data_ptr(), max_radii2D.data_ptr())
 
 
 class DensityStats:
@@ -249,10 +246,8 @@ def densify_and_prune(optimizer, stats, grad_threshold, min_opacity=0.005, scree
     thr_dense = percent_dense * scene_extent  # doubles, as Python forms them; ctypes rounds each once to fp32
     thr_big = 0.1 * screen_size_threshold if max_screen_size else 0.0
     split_div = 0.8 * N
-    with _Ctx(abi, dev) as cx, torch.no_grad():
-        n = ctypes.c_size_t()
-        abi.check(abi.density_bytes(P, ctypes.byref(n)))
-        ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+    with Ctx(abi, dev) as cx, torch.no_grad():
+        ws = torch.empty((query_bytes(abi, "density_bytes", P),), dtype=torch.uint8, device=dev)
         flags = torch.empty((P,), dtype=torch.uint8, device=dev)
         counts = (ctypes.c_int64 * 4)()
         ptr = lambda t: t.data_ptr() if t.numel() else None  # noqa: E731

@@ -34,7 +34,7 @@ import torch
 
 from . import _lib
 from ._abi import DRAW_BG, DRAW_BG_COPY_FIRST, DRAW_CAMERA, DRAW_MAX_CAMERAS, DRAW_NADIR, DrawCamera, DrawStreamDesc
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, ptr
 from .views import _check_gate
 
 PURPOSE_BG, PURPOSE_SHEAR = 0, 1
@@ -140,8 +140,8 @@ class DrawStream:
             raise RuntimeError("DrawStream.advance: the counter is not this stream's own (a schedule's cursor): its owner advances it")
         _check_gate(gate, self.device, "DrawStream.advance")
         abi = _lib.get()
-        with _Ctx(abi, self.device) as cx:
-            abi.check(abi.draw_advance(_ptr(self.counter), _ptr(gate), cx.stream))
+        with Ctx(abi, self.device) as cx:
+            abi.check(abi.draw_advance(ptr(self.counter), ptr(gate), cx.stream))
 
     def seek(self, k):
         """counter = k: a device write, no wait."""
@@ -304,7 +304,7 @@ class IterationDraws:
         """One launch: every camera's draws at the stream's current iteration."""
         abi = _lib.get()
         arr = self._descriptors()
-        with _Ctx(abi, self.device) as cx:
+        with Ctx(abi, self.device) as cx:
             abi.check(abi.draw_iteration(len(self._cameras), ctypes.cast(arr, ctypes.c_void_p), ctypes.byref(self.stream._struct), cx.stream))
 
 

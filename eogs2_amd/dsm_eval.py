@@ -26,17 +26,19 @@ truth makes both NaN, `np.clip` then returns NaN everywhere and the MAE raises V
 masked ground truth. `clip="finite"` takes the bounds from the ground truth's non-NaN pixels (an explicit deviation).
 """
 import ctypes
+import functools
 
 import numpy as np
 import torch
 
 from . import _lib
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, Workspaces, nbytes, on_device, ptr
 
 MAX_IRANGE = 8  # include/eogs_tsdf.h EOGS_TSDF_DSM_MAX_IRANGE
 RESULT_DTYPE = np.dtype([("dx", "<i4"), ("dy", "<i4"), ("valid", "<i4"), ("reserved", "<i4"), ("count", "<f8"), ("muu", "<f8"),
                          ("muv", "<f8"), ("sigu", "<f8"), ("sigv", "<f8"), ("xcorr", "<f8"), ("ncc", "<f8")])  # eogs_tsdf_dsm_result
-_ws_cache = {}
+_ws_cache = Workspaces()
+_on_device = functools.partial(on_device, "dsm_eval", "the DSM evaluation runs")
 
 
 def _image(t, what):
@@ -45,12 +47,6 @@ def _image(t, what):
     if t.dtype not in (torch.float32, torch.float64):
         raise TypeError(f"dsm_eval {what}: images are float32 or float64, not {t.dtype}")
     return t.detach().contiguous()
-
-
-def _on_device(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"dsm_eval {what}: tensors live on '{t.device.type}'; the DSM evaluation runs on the GPU only, there is "
-                           "no CPU fallback")
 
 
 def _pair(ref, sec, irange, what):
@@ -69,22 +65,10 @@ def _pair(ref, sec, irange, what):
     return ref, sec
 
 
-def _workspace(key, dev, make):
-    """One set of buffers per (device, stream, call shape), reused by later calls."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) + key
-    if key not in _ws_cache:
-        _ws_cache[key] = make()
-    return _ws_cache[key]
-
-
 def clear_workspaces():
     """Drops every cached workspace (a caller that scores DSMs of many sizes, or on short-lived streams). Buffers returned
     by compute_shift_device stay valid as long as the caller holds them; a captured graph holds none of them."""
     _ws_cache.clear()
-
-
-def _bytes(dev, n):
-    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=dev)
 
 
 def read_results(results):
@@ -100,8 +84,8 @@ def downsample2x(u):
     abi = _lib.get()
     H, W = u.shape
     out = torch.empty(((H + 1) // 2, (W + 1) // 2), dtype=torch.float64, device=u.device)
-    with _Ctx(abi, u.device) as cx:
-        abi.check(abi.tsdf_dsm_downsample(H, W, _ptr(u), int(u.dtype == torch.float64), _ptr(out), cx.stream))
+    with Ctx(abi, u.device) as cx:
+        abi.check(abi.tsdf_dsm_downsample(H, W, ptr(u), int(u.dtype == torch.float64), ptr(out), cx.stream))
     return out
 
 
@@ -115,16 +99,15 @@ def ncc_search(ref, sec, irange=5, dx=0, dy=0):
     (Hu, Wu), (Hv, Wv), n = ref.shape, sec.shape, 2 * int(irange) + 1
 
     def make():
-        nb = ctypes.c_size_t()
-        abi.check(abi.tsdf_dsm_ncc_bytes(Hu, Wu, int(irange), ctypes.byref(nb)))
-        return _bytes(dev, nb.value), _bytes(dev, RESULT_DTYPE.itemsize)
+        return (Workspaces.bytes(dev, nbytes(abi, "tsdf_dsm_ncc_bytes", Hu, Wu, int(irange))),
+                Workspaces.bytes(dev, RESULT_DTYPE.itemsize))
 
-    ws, res = _workspace(("ncc", Hu, Wu, int(irange)), dev, make)
+    ws, res = _ws_cache.of(("ncc", Hu, Wu, int(irange)), dev, make)
     table = torch.empty((n, n), dtype=torch.float64, device=dev)
     centre = torch.tensor([int(dx), int(dy)], dtype=torch.int32, device=dev)
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.tsdf_dsm_ncc(Hu, Wu, _ptr(ref), Hv, Wv, _ptr(sec), int(ref.dtype == torch.float64), int(irange),
-                                   _ptr(centre), 1, _ptr(table), _ptr(res), _ptr(ws), ws.numel(), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_dsm_ncc(Hu, Wu, ptr(ref), Hv, Wv, ptr(sec), int(ref.dtype == torch.float64), int(irange),
+                                   ptr(centre), 1, ptr(table), ptr(res), ptr(ws), ws.numel(), cx.stream))
     r = read_results(res)[0]
     if not r["valid"]:
         raise ValueError("dsm_eval ncc_search: no candidate shift has a finite NCC")
@@ -142,15 +125,15 @@ def compute_shift_device(dsm_ref, dsm_sec, irange=5):
     (Hu, Wu), (Hv, Wv), n = ref.shape, sec.shape, 2 * int(irange) + 1
 
     def make():
-        nb, lv = ctypes.c_size_t(), ctypes.c_int()
+        nb, lv = ctypes.c_size_t(), ctypes.c_int()  # (a size and a level count: not a plain size query)
         abi.check(abi.tsdf_dsm_shift_bytes(Hu, Wu, Hv, Wv, int(irange), ctypes.byref(nb), ctypes.byref(lv)))
-        return (_bytes(dev, nb.value), _bytes(dev, lv.value * RESULT_DTYPE.itemsize),
+        return (Workspaces.bytes(dev, nb.value), Workspaces.bytes(dev, lv.value * RESULT_DTYPE.itemsize),
                 torch.empty((lv.value, n, n), dtype=torch.float64, device=dev))
 
-    ws, results, tables = _workspace(("shift", Hu, Wu, Hv, Wv, int(irange)), dev, make)
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.tsdf_dsm_shift(Hu, Wu, _ptr(ref), Hv, Wv, _ptr(sec), int(ref.dtype == torch.float64), int(irange),
-                                     _ptr(tables), _ptr(results), _ptr(ws), ws.numel(), cx.stream))
+    ws, results, tables = _ws_cache.of(("shift", Hu, Wu, Hv, Wv, int(irange)), dev, make)
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_dsm_shift(Hu, Wu, ptr(ref), Hv, Wv, ptr(sec), int(ref.dtype == torch.float64), int(irange),
+                                     ptr(tables), ptr(results), ptr(ws), ws.numel(), cx.stream))
     return results, tables
 
 
@@ -174,9 +157,9 @@ def apply_shift(in_dsm, dx=0, dy=0, a=1, b=0, c=0, d=0):
     abi = _lib.get()
     H, W = v.shape
     out = torch.empty_like(v)
-    with _Ctx(abi, v.device) as cx:
-        abi.check(abi.tsdf_dsm_apply_shift(H, W, _ptr(v), int(v.dtype == torch.float64), int(dx), int(dy), float(a), float(b),
-                                           float(c), float(d), _ptr(out), cx.stream))
+    with Ctx(abi, v.device) as cx:
+        abi.check(abi.tsdf_dsm_apply_shift(H, W, ptr(v), int(v.dtype == torch.float64), int(dx), int(dy), float(a), float(b),
+                                           float(c), float(d), ptr(out), cx.stream))
     return out
 
 
@@ -209,17 +192,12 @@ def _pointwise(pred_dsm, gt_dsm, clip):
     (Hp, Wp), (Hg, Wg) = pred_r.shape, gt.shape
     h, w = min(Hp, Hg), min(Wp, Wg)
 
-    def make():
-        nb = ctypes.c_size_t()
-        abi.check(abi.tsdf_dsm_mae_bytes(ctypes.byref(nb)))
-        return (_bytes(dev, nb.value),)
-
-    (ws,) = _workspace(("mae",), dev, make)
+    (ws,) = _ws_cache.of(("mae",), dev, lambda: (Workspaces.bytes(dev, nbytes(abi, "tsdf_dsm_mae_bytes")),))
     diff = torch.empty((h, w), dtype=pred_r.dtype, device=dev)
     out = torch.empty(4, dtype=torch.float64, device=dev)
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.tsdf_dsm_mae(Hp, Wp, _ptr(pred_r), Hg, Wg, _ptr(gt), int(gt.dtype == torch.float64), int(clip == "finite"),
-                                   _ptr(diff), _ptr(out), _ptr(ws), ws.numel(), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_dsm_mae(Hp, Wp, ptr(pred_r), Hg, Wg, ptr(gt), int(gt.dtype == torch.float64), int(clip == "finite"),
+                                   ptr(diff), ptr(out), ptr(ws), ws.numel(), cx.stream))
     return diff, pred_r, transform, out
 
 

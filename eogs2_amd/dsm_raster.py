@@ -23,6 +23,7 @@ one warm-up call on the capture stream (workspaces are allocated per (device, st
 `clear_workspaces()` drops them). With `geometry=None` there is one wait, for the bounds, as in the reference.
 """
 import ctypes
+import functools
 import math
 
 import numpy as np
@@ -30,39 +31,20 @@ import torch
 
 from . import _lib
 from ._abi import DSM_MAX_RADIUS, DSM_SRC_CLOUD, DSM_SRC_GRID, DSM_SRC_VIEW, DSM_Z_MAX, DSM_Z_QUANTUM, DsmBounds, DsmSource
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, Workspaces, nbytes, on_device, ptr
 
 Z_QUANTUM = DSM_Z_QUANTUM  # include/eogs_dsm.h EOGS_DSM_Z_QUANTUM
 Z_MAX = DSM_Z_MAX  # EOGS_DSM_Z_MAX
 MAX_RADIUS = DSM_MAX_RADIUS  # EOGS_DSM_MAX_RADIUS
-_ws_cache = {}
+_ws_cache = Workspaces()
 _axes_cache = {}
-
-
-def _on_device(t, what):
-    if not torch.is_tensor(t):
-        raise TypeError(f"dsm_raster {what}: expected a tensor, not {type(t).__name__}")
-    if t.device.type != "cuda":
-        raise RuntimeError(f"dsm_raster {what}: tensors live on '{t.device.type}'; the DSM raster runs on the GPU only, there is "
-                           "no CPU fallback")
-
-
-def _workspace(key, dev, make):
-    """One set of buffers per (device, stream, call shape), reused by later calls."""
-    key = (dev, torch.cuda.current_stream(dev).cuda_stream) + key
-    if key not in _ws_cache:
-        _ws_cache[key] = make()
-    return _ws_cache[key]
+_on_device = functools.partial(on_device, "dsm_raster", "the DSM raster runs", non_tensor="not")
 
 
 def clear_workspaces():
     """Drops every cached workspace (not while a captured graph that uses them is alive)."""
     _ws_cache.clear()
     _axes_cache.clear()
-
-
-def _bytes(dev, n):
-    return torch.empty(max(int(n), 1), dtype=torch.uint8, device=dev)
 
 
 def _cloud_source(cloud, what):
@@ -137,14 +119,10 @@ def _grid_source(height, axis0, axis1, scene_params, what="extract_dsm"):
 def _bounds(src, dev, what):
     abi = _lib.get()
 
-    def make():
-        nb = ctypes.c_size_t()
-        abi.check(abi.dsm_bounds_bytes(ctypes.byref(nb)))
-        return _bytes(dev, nb.value), _bytes(dev, ctypes.sizeof(DsmBounds))
-
-    ws, res = _workspace(("bounds",), dev, make)
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.dsm_bounds(ctypes.byref(src), _ptr(res), _ptr(ws), ws.numel(), cx.stream))
+    ws, res = _ws_cache.of(("bounds",), dev, lambda: (Workspaces.bytes(dev, nbytes(abi, "dsm_bounds_bytes")),
+                                                      Workspaces.bytes(dev, ctypes.sizeof(DsmBounds))))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.dsm_bounds(ctypes.byref(src), ptr(res), ptr(ws), ws.numel(), cx.stream))
     r = DsmBounds.from_buffer_copy(res.cpu().numpy().tobytes())  # the one read-back
     if r.count == 0:
         raise ValueError(f"dsm_raster {what}: the cloud is empty, it has no bounds")
@@ -184,22 +162,17 @@ def _check_grid(xoff, yoff, resolution, xsize, ysize, radius, what):
 def _raster(src, dev, xoff, yoff, resolution, xsize, ysize, radius, return_count, skipped_out):
     abi = _lib.get()
     xsize, ysize, radius = int(xsize), int(ysize), int(radius)
-
-    def make():
-        nb = ctypes.c_size_t()
-        abi.check(abi.dsm_raster_bytes(xsize, ysize, radius, ctypes.byref(nb)))
-        return (_bytes(dev, nb.value),)
-
-    (ws,) = _workspace(("raster", xsize, ysize, radius), dev, make)
+    (ws,) = _ws_cache.of(("raster", xsize, ysize, radius), dev,
+                         lambda: (Workspaces.bytes(dev, nbytes(abi, "dsm_raster_bytes", xsize, ysize, radius)),))
     out = torch.empty((ysize, xsize, 1), dtype=torch.float32, device=dev)
     count = torch.empty((ysize, xsize), dtype=torch.int32, device=dev) if return_count else None
     if skipped_out is not None:
         _on_device(skipped_out, "plyflatten")
         if skipped_out.dtype != torch.int64 or skipped_out.numel() != 1 or skipped_out.device != dev:
             raise TypeError("dsm_raster plyflatten: skipped_out is one int64 on the cloud's device")
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.dsm_raster(ctypes.byref(src), float(xoff), float(yoff), float(resolution), xsize, ysize, radius, _ptr(out),
-                                 _ptr(count), _ptr(skipped_out), _ptr(ws), ws.numel(), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.dsm_raster(ctypes.byref(src), float(xoff), float(yoff), float(resolution), xsize, ysize, radius, ptr(out),
+                                 ptr(count), ptr(skipped_out), ptr(ws), ws.numel(), cx.stream))
     return (out, count) if return_count else out
 
 

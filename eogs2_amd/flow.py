@@ -20,35 +20,12 @@ switches the warp off where it is zero: output and gradient are then copies, bit
 `perform_flow_matching(..., on_device=True)` makes the reference's `if abs(flow).mean() < max_value_flow` without waiting
 for the device, so the step can be recorded into a HIP graph. fp32 only; CPU tensors raise (no CPU fallback).
 """
-import ctypes
+import functools
 
 import torch
 
 from . import _lib
-from .rasterizer import _Ctx, _ptr
-
-# The calls sit at the launch floor (the kernels take a few microseconds), so the path of apply_flow through this file is
-# kept short: entry points resolved once, raw pointers, the current stream's handle without a Stream object, and a device
-# guard only when the tensors' device is not the current one.
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-_entry = {}
-
-
-def _call(name, dev, *args):
-    """One launch entry of the library on `dev`'s current stream (appended as the last argument)."""
-    fn = _entry.get(name)
-    if fn is None:
-        fn = _entry[name] = getattr(_lib.get().cdll, name)
-    idx = dev.index
-    if idx is not None and idx != torch.cuda.current_device():
-        with torch.cuda.device(idx):
-            return _call(name, torch.device("cuda"), *args)
-    if idx is None:
-        idx = torch.cuda.current_device()
-    stream = _raw_stream(idx) if _raw_stream is not None else torch.cuda.current_stream(idx).cuda_stream
-    rc = fn(*args, stream)
-    if rc:
-        _lib.get().check(rc)
+from ._host import Ctx, call, nbytes, on_device, ptr
 
 
 def pgd8(n, k=8):
@@ -61,10 +38,7 @@ def ppcm8(n, k=8):
     return ((n + k - 1) // k) * k
 
 
-def _on_device(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"flow {what}: tensors live on '{t.device.type}'; the flow warp runs on the GPU only, there is no CPU "
-                           "fallback")
+_on_device = functools.partial(on_device, "flow", "the flow warp runs")
 
 
 def _check_flow(flow, what, H=None, W=None):
@@ -83,19 +57,6 @@ def _strides(flow):
     return int(flow.stride(1)), int(flow.stride(2)), int(flow.stride(3))
 
 
-_sizes = {}
-
-
-def _bytes(query, H, W):
-    """A workspace size query of the library, asked once per shape."""
-    key = (query.__name__, H, W)
-    if key not in _sizes:
-        n = ctypes.c_size_t()
-        _lib.get().check(query(H, W, ctypes.byref(n)))
-        _sizes[key] = n.value
-    return _sizes[key]
-
-
 def _check_gate(gate, dev):
     if gate is None:
         return None
@@ -111,8 +72,8 @@ class _ApplyFlow(torch.autograd.Function):
         C, H, W = img.shape
         x = img if img.is_contiguous() else img.contiguous()
         out = torch.empty_like(x)
-        _call("eogs_resample_flow_forward", x.device, C, H, W, x.data_ptr(), flow.data_ptr(), *flow.stride()[1:],
-              None if gate is None else gate.data_ptr(), out.data_ptr())
+        call("eogs_resample_flow_forward", x.device, C, H, W, x.data_ptr(), flow.data_ptr(), *flow.stride()[1:],
+             None if gate is None else gate.data_ptr(), out.data_ptr())
         ctx.flow, ctx.gate = flow, gate  # (not save_for_backward: a network run under inference_mode returns inference tensors)
         return out
 
@@ -127,11 +88,11 @@ class _ApplyFlow(torch.autograd.Function):
         g_img = torch.empty_like(g)
         ws, ws_ptr, ws_bytes = None, None, 0
         if sy or sx:  # a field: the boxes of the bucketed gather (a constant displacement needs no workspace)
-            ws_bytes = _bytes(_lib.get().resample_flow_bytes, H, W)
+            ws_bytes = nbytes(_lib.get(), "resample_flow_bytes", H, W)
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=g.device)
             ws_ptr = ws.data_ptr()
-        _call("eogs_resample_flow_backward", g.device, C, H, W, flow.data_ptr(), sc, sy, sx,
-              None if gate is None else gate.data_ptr(), g.data_ptr(), g_img.data_ptr(), ws_ptr, ws_bytes)
+        call("eogs_resample_flow_backward", g.device, C, H, W, flow.data_ptr(), sc, sy, sx,
+             None if gate is None else gate.data_ptr(), g.data_ptr(), g_img.data_ptr(), ws_ptr, ws_bytes)
         return g_img, None, None
 
 
@@ -167,10 +128,10 @@ def flow_stats(flow):
     abi = _lib.get()
     H, W = int(flow.shape[2]), int(flow.shape[3])
     dev = flow.device
-    with _Ctx(abi, dev) as cx:
-        ws = torch.empty((_bytes(abi.resample_flow_stats_bytes, H, W),), dtype=torch.uint8, device=dev)
+    with Ctx(abi, dev) as cx:
+        ws = torch.empty((nbytes(abi, "resample_flow_stats_bytes", H, W),), dtype=torch.uint8, device=dev)
         stats = torch.empty((5,), dtype=torch.float32, device=dev)
-        abi.check(abi.resample_flow_stats(H, W, _ptr(flow), *_strides(flow), _ptr(stats), _ptr(ws), ws.numel(), cx.stream))
+        abi.check(abi.resample_flow_stats(H, W, ptr(flow), *_strides(flow), ptr(stats), ptr(ws), ws.numel(), cx.stream))
     return stats
 
 

@@ -5,12 +5,10 @@ float [P,3] tensor on the GPU, returns float32 [P] = mean squared distance to th
 package `simple_knn` re-exports it as `simple_knn._C.distCUDA2`, the name scene/gaussian_model.py:20 imports.
 No CPU fallback.
 """
-import ctypes
-
 import torch
 
 from . import _lib
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, ptr, query_bytes
 
 
 def distCUDA2(points):
@@ -20,11 +18,9 @@ def distCUDA2(points):
     dev, P = points.device, points.shape[0]
     pts = points.detach().to(torch.float32).contiguous()
     means = torch.full((P,), 0.0, dtype=torch.float32, device=dev)  # spatial.cu:21
-    with _Ctx(abi, dev) as cx:
-        n = ctypes.c_size_t()
-        abi.check(abi.knn_bytes(P, ctypes.byref(n)))
-        ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
-        abi.check(abi.knn_mean_dist2(P, _ptr(pts), _ptr(means), _ptr(ws), ws.numel(), cx.stream))
+    with Ctx(abi, dev) as cx:
+        ws = torch.empty((query_bytes(abi, "knn_bytes", P),), dtype=torch.uint8, device=dev)
+        abi.check(abi.knn_mean_dist2(P, ptr(pts), ptr(means), ptr(ws), ws.numel(), cx.stream))
     return means
 
 

@@ -12,19 +12,16 @@ Same names, arguments and return values as the reference:
 Gradients flow to the first argument only (the rendered image); the reference never differentiates the ground truth.
 PyTorch is plumbing (memory, streams, autograd wiring); there is no CPU or eager fallback.
 """
-import ctypes
+import functools
 
 import torch
 
 from . import _lib
 from ._abi import LOSS_L1, LOSS_SSIM
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, f32c, nbytes, ptr
 
 
-def _f32c(t, dev):
-    if t.device != dev:
-        raise RuntimeError(f"loss input on {t.device}, expected {dev}")
-    return t.detach().to(torch.float32).contiguous()
+_f32c = functools.partial(f32c, label="loss input")
 
 
 class _Photometric(torch.autograd.Function):
@@ -41,14 +38,12 @@ class _Photometric(torch.autograd.Function):
         planes = img.numel() // (H * W)
         dev = img.device
         x, y = _f32c(img, dev), _f32c(gt, dev)
-        with _Ctx(abi, dev) as cx:
-            n = ctypes.c_size_t()
-            abi.check(abi.loss_bytes(planes, H, W, mode, ctypes.byref(n)))
-            ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+        with Ctx(abi, dev) as cx:
+            ws = torch.empty((nbytes(abi, "loss_bytes", planes, H, W, mode),), dtype=torch.uint8, device=dev)
             out = torch.empty((3,), dtype=torch.float32, device=dev)
             psum = torch.empty((planes, 2) if want_plane_sums else (0, 2), dtype=torch.float32, device=dev)
-            abi.check(abi.loss_forward(planes, H, W, _ptr(x), _ptr(y), mode, w_l1, w_ssim, bias, _ptr(out),
-                                       _ptr(psum) if want_plane_sums else None, _ptr(ws), ws.numel(), cx.stream))
+            abi.check(abi.loss_forward(planes, H, W, ptr(x), ptr(y), mode, w_l1, w_ssim, bias, ptr(out),
+                                       ptr(psum) if want_plane_sums else None, ptr(ws), ws.numel(), cx.stream))
         ctx.cfg = (planes, H, W, mode, w_l1, w_ssim)
         ctx.img_shape, ctx.img_dtype = img.shape, img.dtype
         ctx.save_for_backward(x, y, ws)
@@ -64,18 +59,18 @@ class _Photometric(torch.autograd.Function):
         planes, H, W, mode, w_l1, w_ssim = ctx.cfg
         x, y, ws = ctx.saved_tensors
         dev = x.device
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             d = torch.empty((planes, H, W), dtype=torch.float32, device=dev)
             if g_psum is not None and g_psum.numel():
                 if g_out is not None:
                     raise RuntimeError("loss: use either the scalar outputs or the per-plane sums of one call, not both")
                 pg = _f32c(g_psum, dev)
-                abi.check(abi.loss_backward(planes, H, W, _ptr(x), _ptr(y), mode, 0.0, 0.0, None, _ptr(pg),
-                                            _ptr(ws), ws.numel(), _ptr(d), cx.stream))
+                abi.check(abi.loss_backward(planes, H, W, ptr(x), ptr(y), mode, 0.0, 0.0, None, ptr(pg),
+                                            ptr(ws), ws.numel(), ptr(d), cx.stream))
             else:
                 g = _f32c(g_out, dev)
-                abi.check(abi.loss_backward(planes, H, W, _ptr(x), _ptr(y), mode, w_l1, w_ssim, _ptr(g), None,
-                                            _ptr(ws), ws.numel(), _ptr(d), cx.stream))
+                abi.check(abi.loss_backward(planes, H, W, ptr(x), ptr(y), mode, w_l1, w_ssim, ptr(g), None,
+                                            ptr(ws), ws.numel(), ptr(d), cx.stream))
         return (d.view(ctx.img_shape).to(ctx.img_dtype),) + none7[1:]
 
 

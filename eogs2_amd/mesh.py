@@ -16,23 +16,19 @@ non-finite voxels (mcubes hands back NaN vertices).
 Two phases with one host wait between them, for the sizes (four integers), as `density.densify_and_prune` has.
 """
 import ctypes
+import functools
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._abi import MESH_MAX_VERTICES
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, on_device, ptr, query_bytes
 
 MAX_VERTICES = MESH_MAX_VERTICES  # include/eogs_mesh.h EOGS_MESH_MAX_VERTICES
 
 
-def _on_device(t, what):
-    if not torch.is_tensor(t):
-        raise TypeError(f"mesh {what}: expected a tensor, not {type(t).__name__}")
-    if t.device.type != "cuda":
-        raise RuntimeError(f"mesh {what}: tensors live on '{t.device.type}'; the mesh extraction runs on the GPU only, there is "
-                           "no CPU fallback")
+_on_device = functools.partial(on_device, "mesh", "the mesh extraction runs", non_tensor="not")
 
 
 def _shift3(shift):
@@ -65,12 +61,10 @@ def marching_cubes(volume, iso=0.0, *, axes=None, shift=None):
             raise ValueError("mesh marching_cubes: the axes do not match the volume")
     sh = None if shift is None else _shift3(shift)
     abi = _lib.get()
-    nb = ctypes.c_size_t()
-    abi.check(abi.mesh_bytes(nx, ny, nz, ctypes.byref(nb)))
-    ws = torch.empty(nb.value, dtype=torch.uint8, device=dev)
+    ws = torch.empty(query_bytes(abi, "mesh_bytes", nx, ny, nz), dtype=torch.uint8, device=dev)
     counts = torch.empty(4, dtype=torch.int32, device=dev)
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.mesh_count(nx, ny, nz, _ptr(vol), iso, _ptr(ws), ws.numel(), _ptr(counts), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.mesh_count(nx, ny, nz, ptr(vol), iso, ptr(ws), ws.numel(), ptr(counts), cx.stream))
         nv, nt, bad, _ = (int(c) for c in counts.cpu().numpy().view(np.uint32))  # the one wait
         if bad:
             raise ValueError(f"mesh marching_cubes: {bad} of {nx * ny * nz} voxels are not finite")
@@ -79,8 +73,8 @@ def marching_cubes(volume, iso=0.0, *, axes=None, shift=None):
         vertices = torch.empty((nv, 3), dtype=torch.float64, device=dev)
         triangles = torch.empty((nt, 3), dtype=torch.int32, device=dev)
         if nv:
-            abi.check(abi.mesh_emit(nx, ny, nz, _ptr(vol), iso, _ptr(ax), _ptr(ay), _ptr(az), sh, _ptr(ws), ws.numel(),
-                                    _ptr(vertices), nv, _ptr(triangles), nt, cx.stream))
+            abi.check(abi.mesh_emit(nx, ny, nz, ptr(vol), iso, ptr(ax), ptr(ay), ptr(az), sh, ptr(ws), ws.numel(),
+                                    ptr(vertices), nv, ptr(triangles), nt, cx.stream))
     return vertices, triangles
 
 

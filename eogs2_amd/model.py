@@ -36,7 +36,7 @@ from . import density as _density
 from . import optim as _optim
 from . import reset as _reset
 from ._abi import MODEL_MAX_REST
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, ptr
 
 C0 = 0.28209479177387814  # utils/sh_utils.py
 GROUPS = _optim.GROUPS
@@ -128,12 +128,12 @@ def init_tensors(points, colors, dist2, sh_degree, opacity_init_value=0.01):
     _need_gpu(dev, "init_tensors")
     logit = opacity_logit(opacity_init_value)
     abi = _lib.get()
-    with _Ctx(abi, dev) as cx, torch.no_grad():
+    with Ctx(abi, dev) as cx, torch.no_grad():
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
         out = {"xyz": new(P, 3), "f_dc": new(P, 1, 3), "f_rest": new(P, n_rest, 3), "scaling": new(P, 3), "rotation": new(P, 4),
                "opacity": new(P, 1), "max_radii2D": new(P)}
-        ptr = lambda t: _ptr(t) if t.numel() else None  # noqa: E731
-        abi.check(abi.model_init(P, n_rest, ptr(points), ptr(colors), ptr(dist2), logit, *(ptr(out[k]) for k in
+        ptr0 = lambda t: ptr(t) if t.numel() else None  # noqa: E731
+        abi.check(abi.model_init(P, n_rest, ptr0(points), ptr0(colors), ptr0(dist2), logit, *(ptr0(out[k]) for k in
                                  ("xyz", "f_dc", "f_rest", "scaling", "rotation", "opacity", "max_radii2D")), cx.stream))
     return out
 
@@ -147,10 +147,10 @@ def pack_rows(xyz, f_dc, f_rest, opacity, scaling, rotation, out=None):
             raise RuntimeError("pack_rows: out must be contiguous")
     _need_gpu(dev, "pack_rows")
     abi = _lib.get()
-    with _Ctx(abi, dev) as cx, torch.no_grad():
+    with Ctx(abi, dev) as cx, torch.no_grad():
         rows = out if out is not None else torch.empty((P, row_cols(n_rest)), dtype=torch.float32, device=dev)
-        ptr = lambda t: _ptr(t) if t.numel() else None  # noqa: E731
-        abi.check(abi.model_rows_pack(P, n_rest, *(ptr(t) for t in six), ptr(rows), cx.stream))
+        ptr0 = lambda t: ptr(t) if t.numel() else None  # noqa: E731
+        abi.check(abi.model_rows_pack(P, n_rest, *(ptr0(t) for t in six), ptr0(rows), cx.stream))
     return rows
 
 
@@ -162,11 +162,11 @@ def unpack_rows(rows, n_rest):
     P, dev = rows.shape[0], rows.device
     _need_gpu(dev, "unpack_rows")
     abi = _lib.get()
-    with _Ctx(abi, dev) as cx, torch.no_grad():
+    with Ctx(abi, dev) as cx, torch.no_grad():
         new = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)  # noqa: E731
         six = (new(P, 3), new(P, 1, 3), new(P, n_rest, 3), new(P, 1), new(P, 3), new(P, 4))
-        ptr = lambda t: _ptr(t) if t.numel() else None  # noqa: E731
-        abi.check(abi.model_rows_unpack(P, n_rest, ptr(rows), *(ptr(t) for t in six), cx.stream))
+        ptr0 = lambda t: ptr(t) if t.numel() else None  # noqa: E731
+        abi.check(abi.model_rows_unpack(P, n_rest, ptr0(rows), *(ptr0(t) for t in six), cx.stream))
     return six
 
 

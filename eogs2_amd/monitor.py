@@ -23,23 +23,20 @@ tensors raise: there is no CPU fallback.
 """
 import collections
 import ctypes
+import functools
 
 import torch
 
 from . import _lib
 from ._abi import MONITOR_KINDS, MONITOR_METRICS, MONITOR_OPERATORS, MONITOR_RING, MonitorRecord, MonitorState
-from .flow import _call
+from ._host import call, on_device, query_bytes
 
 HOST_METRICS = ("mae", "mae_wtree")  # what the reference's metric_dict holds beside the six: computed on the host there
 _RECORD_BYTES = ctypes.sizeof(MonitorRecord)
 _LATEST_OFFSET = MonitorState.latest.offset
 
 
-def _on_device(t, what):
-    if not torch.is_tensor(t):
-        raise TypeError(f"monitor {what}: expected a tensor, got {type(t).__name__}")
-    if t.device.type != "cuda":
-        raise RuntimeError(f"monitor {what}: tensors live on '{t.device.type}'; the monitor runs on the GPU only, there is no CPU fallback")
+_on_device = functools.partial(on_device, "monitor", "the monitor runs", non_tensor="got")
 
 
 def _record_dict(r):
@@ -111,7 +108,7 @@ class TrainingMonitor:
     def reset(self):
         """Zero sums, counts, averages and ring; best = +inf (min) or -inf (max). One launch."""
         st = self.state if self._state is None else self._state  # (the first access resets by itself)
-        _call("eogs_monitor_reset", self.device, st.data_ptr(), st.numel(), self.op)
+        call("eogs_monitor_reset", self.device, st.data_ptr(), st.numel(), self.op)
 
     def _gate(self, gate, what):
         if gate is None:
@@ -124,10 +121,7 @@ class TrainingMonitor:
     def _workspace(self, key, query, *args):
         ws = self._ws.get(key)
         if ws is None:
-            n = ctypes.c_size_t()
-            abi = _lib.get()
-            abi.check(getattr(abi, query)(*args, ctypes.byref(n)))
-            ws = self._ws[key] = torch.empty((n.value,), dtype=torch.uint8, device=self.device)
+            ws = self._ws[key] = torch.empty((query_bytes(_lib.get(), query, *args),), dtype=torch.uint8, device=self.device)
         return ws
 
     def observe(self, image, gt, kind, loss_out=None, lambda_dssim=0.2, photometric_on=True, gate=None):
@@ -157,8 +151,8 @@ class TrainingMonitor:
             lo = loss_out.detach().contiguous()
         g = self._gate(gate, what)
         ws = self._workspace(("observe", planes, H, W, lo is None), "monitor_observe_bytes", planes, H, W, int(lo is None))
-        _call("eogs_monitor_observe", self.device, planes, H, W, x.data_ptr(), y.data_ptr(), None if lo is None else lo.data_ptr(),
-              float(lambda_dssim), k, int(bool(photometric_on)), g, self.state.data_ptr(), ws.data_ptr(), ws.numel())
+        call("eogs_monitor_observe", self.device, planes, H, W, x.data_ptr(), y.data_ptr(), None if lo is None else lo.data_ptr(),
+             float(lambda_dssim), k, int(bool(photometric_on)), g, self.state.data_ptr(), ws.data_ptr(), ws.numel())
 
     def observe_model(self, opacity_logits, gate=None):
         """Mean opacity and number of rows over the raw `_opacity` [P,1] or [P]; rows that eogs2_amd.optim.retire_rows parked are
@@ -176,7 +170,7 @@ class TrainingMonitor:
         P = o.shape[0]
         g = self._gate(gate, what)
         ws = self._workspace(("model",), "monitor_model_bytes", 1 << 40)  # (one size from 2^20 rows on: the grid is capped)
-        _call("eogs_monitor_observe_model", self.device, P, o.data_ptr(), g, self.state.data_ptr(), ws.data_ptr(), ws.numel())
+        call("eogs_monitor_observe_model", self.device, P, o.data_ptr(), g, self.state.data_ptr(), ws.data_ptr(), ws.numel())
 
     def end_iteration(self, loss, gate=None):
         """`loss` is the iteration's total loss as a device scalar (train_pan.py:467,492-495)."""
@@ -186,12 +180,12 @@ class TrainingMonitor:
             raise ValueError(f"monitor {what}: the loss is one float32 on {self.device}, got {tuple(loss.shape)} {loss.dtype} on {loss.device}")
         g = self._gate(gate, what)
         lv = loss.detach()
-        _call("eogs_monitor_end_iteration", self.device, lv.data_ptr(), g, self.state.data_ptr())
+        call("eogs_monitor_end_iteration", self.device, lv.data_ptr(), g, self.state.data_ptr())
 
     def close_interval(self, gate=None):
         """train_pan.py:512-519, 572-597: means, early stopper, one record, sums cleared. One launch."""
         g = self._gate(gate, "close_interval")
-        _call("eogs_monitor_close_interval", self.device, self.metric, self.op, self.patience, g, self.state.data_ptr())
+        call("eogs_monitor_close_interval", self.device, self.metric, self.op, self.patience, g, self.state.data_ptr())
 
     # ---- reading -----------------------------------------------------------------------------------------------------
     def _latest_view(self):

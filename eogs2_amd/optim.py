@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from . import _lib
 from ._abi import AdamTensor, StepAdamTensor, SumTensor
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, ptr, query_bytes
 
 MAX_TENSORS = 16  # EOGS_ADAM_MAX_TENSORS
 SUM_MAX_TENSORS, SUM_MAX_SOURCES = 8, 4  # EOGS_SUM_MAX_TENSORS / _SOURCES
@@ -44,7 +44,7 @@ def sum_into_(dsts, sources):
             if t.device != dev or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != d.numel():
                 raise RuntimeError("sum_into_: contiguous fp32 tensors of equal size on one device")
     abi = _lib.get()
-    with _Ctx(abi, dev) as cx, torch.no_grad():
+    with Ctx(abi, dev) as cx, torch.no_grad():
         for s0 in range(0, len(sources), SUM_MAX_SOURCES):
             srcs = sources[s0:s0 + SUM_MAX_SOURCES]
             for k0 in range(0, len(dsts), SUM_MAX_TENSORS):
@@ -151,7 +151,7 @@ class FusedAdam(torch.optim.Adam):
                 if not (isinstance(gate, torch.Tensor) and gate.device == dev and gate.numel() == 2 and gate.is_contiguous()
                         and gate.dtype in (torch.uint32, torch.int32)):
                     raise RuntimeError("FusedAdam.step: gate must be a contiguous uint32[2] tensor on the parameters' device")
-            with _Ctx(abi, dev) as cx:
+            with Ctx(abi, dev) as cx:
                 for i0 in range(0, len(items), MAX_TENSORS):
                     chunk = items[i0:i0 + MAX_TENSORS]
                     key = (dev, (b1, b2), eps, i0)
@@ -164,7 +164,7 @@ class FusedAdam(torch.optim.Adam):
                         a.exp_avg, a.exp_avg_sq = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
                         a.numel, a.lr, a.step, a.retire_below = p.numel(), lr_t.data_ptr(), st["step"].data_ptr(), below
                         self._ws_row[p] = (ws, row)
-                    abi.check(abi.step_adam(len(chunk), ctypes.cast(arr, ctypes.c_void_p), b1, b2, eps, _ptr(gate), _ptr(ws),
+                    abi.check(abi.step_adam(len(chunk), ctypes.cast(arr, ctypes.c_void_p), b1, b2, eps, ptr(gate), ptr(ws),
                                             ws.numel() * 4, cx.stream))
 
     @torch.no_grad()
@@ -201,7 +201,7 @@ class FusedAdam(torch.optim.Adam):
                 key = (p.device, group["betas"], group["eps"], t)
                 batches.setdefault(key, []).append((p, p.grad.contiguous(), state, float(group["lr"])))
         for (dev, (b1, b2), eps, t), items in batches.items():
-            with _Ctx(abi, dev) as cx:
+            with Ctx(abi, dev) as cx:
                 for i0 in range(0, len(items), MAX_TENSORS):
                     chunk = items[i0:i0 + MAX_TENSORS]
                     arr = (AdamTensor * len(chunk))()
@@ -227,12 +227,10 @@ def compact_rows(mask, tensors):
             raise RuntimeError("compact_rows: 4-byte element types only")
         srcs.append(t.detach().contiguous())
     keep = mask.contiguous().view(torch.uint8)
-    with _Ctx(abi, dev) as cx:
-        n = ctypes.c_size_t()
-        abi.check(abi.compact_bytes(N, ctypes.byref(n)))
-        ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
+    with Ctx(abi, dev) as cx:
+        ws = torch.empty((query_bytes(abi, "compact_bytes", N),), dtype=torch.uint8, device=dev)
         n_keep = ctypes.c_int64()
-        abi.check(abi.compact_plan(N, _ptr(keep), _ptr(ws), ws.numel(), ctypes.byref(n_keep), cx.stream))
+        abi.check(abi.compact_plan(N, ptr(keep), ptr(ws), ws.numel(), ctypes.byref(n_keep), cx.stream))
         K = n_keep.value
         outs = [torch.empty((K,) + tuple(t.shape[1:]), dtype=t.dtype, device=dev) for t in srcs]
         row_bytes = [(t.numel() // N if N else 0) * 4 for t in srcs]
@@ -243,8 +241,8 @@ def compact_rows(mask, tensors):
             S = (ctypes.c_void_p * k)(*[t.data_ptr() if t.numel() else None for t in srcs])
             D = (ctypes.c_void_p * k)(*[o.data_ptr() if o.numel() else None for o in outs])
             RB = (ctypes.c_int * k)(*[rb if K else 0 for rb in row_bytes])
-            abi.check(abi.compact_apply(N, _ptr(keep), k, ctypes.cast(S, ctypes.c_void_p), ctypes.cast(D, ctypes.c_void_p),
-                                        ctypes.cast(RB, ctypes.c_void_p), _ptr(ws), ws.numel(), cx.stream))
+            abi.check(abi.compact_apply(N, ptr(keep), k, ctypes.cast(S, ctypes.c_void_p), ctypes.cast(D, ctypes.c_void_p),
+                                        ctypes.cast(RB, ctypes.c_void_p), ptr(ws), ws.numel(), cx.stream))
     return outs
 
 

@@ -16,14 +16,12 @@ One forward and one backward kernel (plus a tiny fixed-order reduction) where th
 PyTorch kernels and autograd replays them; parameter gradients are reproducible bit for bit. Gradients reach the
 camera's and the map's own Parameters. PyTorch is plumbing; there is no CPU or eager fallback.
 """
-import ctypes
-
 import torch
 
 from . import _lib, shade as _shade
 from ._abi import (PAN_AVERAGE, PAN_BASE, PAN_BASE_SIGMOID, PAN_FIXED, PAN_NPARAMS, PAN_ONE_CHANNEL, PAN_ORDER_CC_FIRST,
                    PAN_ORDER_MAP_FIRST, PAN_TRANSLATE, PAN_TRANSLATE_FROZEN)
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, f32c, nbytes, ptr
 
 ORDER_CC_FIRST = "cc_first"  # PANAffineCamera._render_pipeline
 ORDER_MAP_FIRST = "map_first"  # PANAffineCamera._render_pipeline_weird (weird_pan_setup)
@@ -157,12 +155,6 @@ def pan_map_of(module):
     raise RuntimeError(f"pan_map_of: unknown MSI->PAN module {name}")
 
 
-def _f32c(t, dev, what):
-    if t.device != dev:
-        raise RuntimeError(f"pan_shade: {what} on {t.device}, expected {dev}")
-    return t.detach().to(torch.float32).contiguous()
-
-
 class _PanShade(torch.autograd.Function):
     """(cc, shaded, shadow) = pan(raw[3,H,W], alt_diff[H,W] | None, M, inshadow, map_params | None; order, kind)"""
 
@@ -172,17 +164,17 @@ class _PanShade(torch.autograd.Function):
         _, H, W = raw.shape
         dev = raw.device
         a_first = order == PAN_ORDER_CC_FIRST
-        x = _f32c(raw, dev, "raw_render")
-        m = _f32c(M, dev, "the colour correction").reshape(-1)
-        d = _f32c(alt_diff, dev, "sun_altitude_diff") if alt_diff is not None else None
-        ins = _f32c(inshadow, dev, "inshadow_color_correction").reshape(-1) if alt_diff is not None else None
-        p = _f32c(mp, dev, "the map's parameters") if mp is not None else None
-        with _Ctx(abi, dev) as cx:
+        x = f32c(raw, dev, "pan_shade: raw_render")
+        m = f32c(M, dev, "pan_shade: the colour correction").reshape(-1)
+        d = f32c(alt_diff, dev, "pan_shade: sun_altitude_diff") if alt_diff is not None else None
+        ins = f32c(inshadow, dev, "pan_shade: inshadow_color_correction").reshape(-1) if alt_diff is not None else None
+        p = f32c(mp, dev, "pan_shade: the map's parameters") if mp is not None else None
+        with Ctx(abi, dev) as cx:
             cc = torch.empty((3 if a_first else 1, H, W), dtype=torch.float32, device=dev)
             shaded = torch.empty((1, H, W), dtype=torch.float32, device=dev)
             shadow = torch.empty((H, W), dtype=torch.float32, device=dev) if d is not None else None
-            abi.check(abi.pan_forward(H, W, order, kind, _ptr(x), _ptr(d), _ptr(m), _ptr(ins), _ptr(p), _ptr(cc), _ptr(shaded),
-                                      _ptr(shadow), cx.stream))
+            abi.check(abi.pan_forward(H, W, order, kind, ptr(x), ptr(d), ptr(m), ptr(ins), ptr(p), ptr(cc), ptr(shaded),
+                                      ptr(shadow), cx.stream))
         ctx.cfg = (H, W, order, kind, d is not None, M.shape, inshadow.shape if inshadow is not None else None)
         ctx.save_for_backward(x, d, m, ins, p)
         ctx.set_materialize_grads(False)
@@ -200,18 +192,16 @@ class _PanShade(torch.autograd.Function):
         H, W, order, kind, has_shadow, m_shape, ins_shape = ctx.cfg
         x, d, m, ins, p = ctx.saved_tensors
         dev = x.device
-        with _Ctx(abi, dev) as cx:
-            gs = _f32c(g_shaded, dev, "the gradient of shaded") if g_shaded is not None else None
-            gc = _f32c(g_cc, dev, "the gradient of cc") if g_cc is not None else None
-            gsh = _f32c(g_shadow, dev, "the gradient of shadowmap") if (g_shadow is not None and has_shadow) else None
+        with Ctx(abi, dev) as cx:
+            gs = f32c(g_shaded, dev, "pan_shade: the gradient of shaded") if g_shaded is not None else None
+            gc = f32c(g_cc, dev, "pan_shade: the gradient of cc") if g_cc is not None else None
+            gsh = f32c(g_shadow, dev, "pan_shade: the gradient of shadowmap") if (g_shadow is not None and has_shadow) else None
             g_raw = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             g_alt = torch.empty((H, W), dtype=torch.float32, device=dev) if has_shadow else None
             g_par = torch.empty((PAN_NPARAMS,), dtype=torch.float32, device=dev)
-            n = ctypes.c_size_t()
-            abi.check(abi.pan_bytes(H, W, ctypes.byref(n)))
-            ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
-            abi.check(abi.pan_backward(H, W, order, kind, _ptr(x), _ptr(d), _ptr(m), _ptr(ins), _ptr(p), _ptr(gs), _ptr(gc),
-                                       _ptr(gsh), _ptr(g_raw), _ptr(g_alt), _ptr(g_par), _ptr(ws), ws.numel(), cx.stream))
+            ws = torch.empty((nbytes(abi, "pan_bytes", H, W),), dtype=torch.uint8, device=dev)
+            abi.check(abi.pan_backward(H, W, order, kind, ptr(x), ptr(d), ptr(m), ptr(ins), ptr(p), ptr(gs), ptr(gc),
+                                       ptr(gsh), ptr(g_raw), ptr(g_alt), ptr(g_par), ptr(ws), ws.numel(), cx.stream))
         g_M = g_par[:m.numel()].reshape(m_shape)
         g_ins = g_par[12:12 + ins.numel()].reshape(ins_shape) if has_shadow else None
         g_mp = None

@@ -19,33 +19,22 @@ stores it; the gradient of every loss reaches the rendered image only (the first
 same bits on every run. Every call only queues launches, so a recorded step holds it. fp32 only; CPU tensors raise (no CPU
 fallback).
 """
-import ctypes
+import functools
 
 import torch
 
 from . import _lib
 from ._abi import GTPREP_BROVEY, GTPREP_IHS, GTPREP_MAX_CHANNELS, GTPREP_SIMPLE_BROVEY
-from .flow import _call
+from ._host import call, nbytes, on_device
 
 METHODS = {"brovey": GTPREP_BROVEY, "simple_brovey": GTPREP_SIMPLE_BROVEY, "ihs": GTPREP_IHS}
 _OUT_BYTES = 32
-_ws_bytes = {}
-
-
-def _on_device(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"pansharp {what}: tensors live on '{t.device.type}'; ground-truth preparation runs on the GPU only, "
-                           "there is no CPU fallback")
+_on_device = functools.partial(on_device, "pansharp", "ground-truth preparation runs")
 
 
 def _buffer(dev, C=1):
     """(float32 tensor, workspace bytes): the result float at its start, the reduction workspace from byte _OUT_BYTES on."""
-    n = _ws_bytes.get(C)
-    if n is None:
-        size = ctypes.c_size_t()
-        abi = _lib.get()
-        abi.check(abi.gtprep_bytes(C, ctypes.byref(size)))
-        n = _ws_bytes[C] = int(size.value)
+    n = nbytes(_lib.get(), "gtprep_bytes", C)
     return torch.empty(((_OUT_BYTES + n + 3) // 4,), dtype=torch.float32, device=dev), n
 
 
@@ -80,7 +69,7 @@ def _fuse(method, pan, msi, weight):
     C, h, w = msi.shape
     H, W = pan.shape
     out = torch.empty((C, H, W), dtype=torch.float32, device=pan.device)
-    _call("eogs_gtprep_pansharp", pan.device, method, C, h, w, H, W, msi.data_ptr(), pan.data_ptr(), float(weight), out.data_ptr())
+    call("eogs_gtprep_pansharp", pan.device, method, C, h, w, H, W, msi.data_ptr(), pan.data_ptr(), float(weight), out.data_ptr())
     return out
 
 
@@ -163,8 +152,8 @@ class _PansharpL2(torch.autograd.Function):
         H, W = pan.shape
         buf, ws_bytes = _buffer(s.device, C)
         p = buf.data_ptr()
-        _call("eogs_gtprep_pansharp_l2_forward", s.device, method, C, h, w, H, W, s.data_ptr(), msi.data_ptr(), pan.data_ptr(), weight,
-              p, p + _OUT_BYTES, ws_bytes)
+        call("eogs_gtprep_pansharp_l2_forward", s.device, method, C, h, w, H, W, s.data_ptr(), msi.data_ptr(), pan.data_ptr(), weight,
+             p, p + _OUT_BYTES, ws_bytes)
         ctx.cfg = (method, weight)
         ctx.save_for_backward(s, pan, msi)
         return buf[0]
@@ -177,8 +166,8 @@ class _PansharpL2(torch.autograd.Function):
         H, W = pan.shape
         up, keep = _upstream(g)
         g_syn = torch.empty_like(s)
-        _call("eogs_gtprep_pansharp_l2_backward", s.device, method, C, h, w, H, W, s.data_ptr(), msi.data_ptr(), pan.data_ptr(), weight,
-              up, g_syn.data_ptr())
+        call("eogs_gtprep_pansharp_l2_backward", s.device, method, C, h, w, H, W, s.data_ptr(), msi.data_ptr(), pan.data_ptr(), weight,
+             up, g_syn.data_ptr())
         return g_syn, None, None, None, None
 
 
@@ -190,7 +179,7 @@ class _L2(torch.autograd.Function):
         a = image.contiguous()
         buf, ws_bytes = _buffer(a.device)
         p = buf.data_ptr()
-        _call("eogs_gtprep_l2_forward", a.device, a.numel(), a.data_ptr(), target.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
+        call("eogs_gtprep_l2_forward", a.device, a.numel(), a.data_ptr(), target.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
         ctx.save_for_backward(a, target)
         return buf[0]
 
@@ -199,7 +188,7 @@ class _L2(torch.autograd.Function):
         a, target = ctx.saved_tensors
         up, keep = _upstream(g)
         g_a = torch.empty_like(a)
-        _call("eogs_gtprep_l2_backward", a.device, a.numel(), a.data_ptr(), target.data_ptr(), up, g_a.data_ptr())
+        call("eogs_gtprep_l2_backward", a.device, a.numel(), a.data_ptr(), target.data_ptr(), up, g_a.data_ptr())
         return g_a, None
 
 
@@ -213,7 +202,7 @@ class _GradL2(torch.autograd.Function):
         B = a.numel() // (H * W)
         buf, ws_bytes = _buffer(a.device)
         p = buf.data_ptr()
-        _call("eogs_gtprep_grad_l2_forward", a.device, B, H, W, a.data_ptr(), target.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
+        call("eogs_gtprep_grad_l2_forward", a.device, B, H, W, a.data_ptr(), target.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
         ctx.save_for_backward(a, target)
         return buf[0]
 
@@ -223,7 +212,7 @@ class _GradL2(torch.autograd.Function):
         H, W = a.shape[-2:]
         up, keep = _upstream(g)
         g_a = torch.empty_like(a)
-        _call("eogs_gtprep_grad_l2_backward", a.device, a.numel() // (H * W), H, W, a.data_ptr(), target.data_ptr(), up, g_a.data_ptr())
+        call("eogs_gtprep_grad_l2_backward", a.device, a.numel() // (H * W), H, W, a.data_ptr(), target.data_ptr(), up, g_a.data_ptr())
         return g_a, None
 
 

@@ -22,13 +22,11 @@ where the reference chains two fp32 products per pixel. The refe
 indexed by the TRUE camera's pixel, is subtracted from the VIRTUAL camera's altitude at the same index
 (renderer_cc_shadow.py:85-109). PyTorch is plumbing; there is no CPU or eager fallback.
 """
-import ctypes
-
 import torch
 
 from . import _lib, pan as _pan, shade as _shade
 from ._abi import CMLOSS_MAX_CHANNELS
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, f32c, nbytes, ptr
 from .resample import render_resample_virtual_camera, resample
 
 RENDER_TYPES = ("rawrender", "rawrender_wshadow")
@@ -39,12 +37,6 @@ def _on_gpu(what, name, t):
         raise TypeError(f"{what}: {name} must be a tensor, got {type(t).__name__}")
     if t.device.type != "cuda":
         raise RuntimeError(f"{what}: {name} on '{t.device}': this runs on the GPU, there is no CPU fallback")
-
-
-def _f32c(t, dev, what, name):
-    if t.device != dev:
-        raise RuntimeError(f"{what}: {name} on {t.device}, expected {dev}")
-    return t.detach().to(torch.float32).contiguous()
 
 
 # ---- the composed matrices ----------------------------------------------------------------------------------------------
@@ -85,10 +77,10 @@ def virtual_to_sun(cam2virt, camera_to_sun, out=None):
     abi = _lib.get()
     c = cam2virt.detach().contiguous()
     s = camera_to_sun.detach().contiguous()
-    with _Ctx(abi, dev) as cx:
+    with Ctx(abi, dev) as cx:
         if out is None:
             out = torch.empty((18,), dtype=torch.float32, device=dev)
-        abi.check(abi.randomcam_compose(_ptr(c), _ptr(s), _ptr(out), cx.stream))
+        abi.check(abi.randomcam_compose(ptr(c), ptr(s), ptr(out), cx.stream))
     flat = out.view(-1)
     return flat[:9].view(3, 3), flat[9:].view(3, 3)
 
@@ -126,14 +118,12 @@ class _CMLoss(torch.autograd.Function):
         C, H, W = check_cmloss(alt_diff, rgb_a, rgb_b, uv)
         abi = _lib.get()
         dev = alt_diff.device
-        d, a, b, u = (_f32c(t, dev, "cmloss", n) for n, t in (("new_altitude_diff", alt_diff), ("rgb_render", rgb_a),
+        d, a, b, u = (f32c(t, dev, f"cmloss: {n}") for n, t in (("new_altitude_diff", alt_diff), ("rgb_render", rgb_a),
                                                               ("new_rgb_sample", rgb_b), ("new_uv", uv)))
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             out = torch.empty((3,), dtype=torch.float32, device=dev)
-            n = ctypes.c_size_t()
-            abi.check(abi.cmloss_bytes(H, W, ctypes.byref(n)))
-            ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
-            abi.check(abi.cmloss_forward(H, W, C, _ptr(d), _ptr(a), _ptr(b), _ptr(u), _ptr(out), _ptr(ws), ws.numel(), cx.stream))
+            ws = torch.empty((nbytes(abi, "cmloss_bytes", H, W),), dtype=torch.uint8, device=dev)
+            abi.check(abi.cmloss_forward(H, W, C, ptr(d), ptr(a), ptr(b), ptr(u), ptr(out), ptr(ws), ws.numel(), cx.stream))
         ctx.cfg = (H, W, C)
         ctx.save_for_backward(d, a, b, u, out)
         ctx.set_materialize_grads(False)
@@ -147,13 +137,13 @@ class _CMLoss(torch.autograd.Function):
         H, W, C = ctx.cfg
         d, a, b, u, out = ctx.saved_tensors
         dev = d.device
-        with _Ctx(abi, dev) as cx:
-            up = _f32c(g_out, dev, "cmloss", "the upstream gradient")[:2].contiguous()
+        with Ctx(abi, dev) as cx:
+            up = f32c(g_out, dev, "cmloss: the upstream gradient")[:2].contiguous()
             g_alt = torch.empty((H, W), dtype=torch.float32, device=dev)
             g_a = torch.empty((C, H, W), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
             g_b = torch.empty((C, H, W), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-            abi.check(abi.cmloss_backward(H, W, C, _ptr(d), _ptr(a), _ptr(b), _ptr(u), _ptr(out), _ptr(up), _ptr(g_alt), _ptr(g_a),
-                                          _ptr(g_b), cx.stream))
+            abi.check(abi.cmloss_backward(H, W, C, ptr(d), ptr(a), ptr(b), ptr(u), ptr(out), ptr(up), ptr(g_alt), ptr(g_a),
+                                          ptr(g_b), cx.stream))
         return g_alt, g_a, g_b, None
 
 

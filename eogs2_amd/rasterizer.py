@@ -28,6 +28,7 @@ import torch.nn as nn
 from . import _lib
 from ._abi import (FLAG_ALT_ONLY, FLAG_ANTIALIASING, FLAG_DEBUG, FLAG_DEFER_COUNTS, FLAG_NO_READBACK, FLAG_RAW_PARAMS, MIRROR_BYTES,
                    STEP_MAX_FORWARDS, RastError, StepForward)
+from ._host import Ctx, ptr, query_bytes
 
 NUM_CHANNELS = 5  # DGR/cuda_rasterizer/config.h:15
 
@@ -65,36 +66,6 @@ def _f32(t, dev):
     if t.dtype == torch.float32 and t.is_contiguous():
         return t  # the common case: only the data pointer is used, nothing to convert
     return t.detach().to(torch.float32).contiguous()
-
-
-def _ptr(t):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-class _Ctx:
-    """device guard + stream for one call"""
-
-    def __init__(self, abi, dev):
-        self.abi = abi
-        if dev.type != abi.device_type:
-            raise RuntimeError(
-                f"rasterizer tensors live on '{dev.type}' but the loaded library ({abi.backend}) works on "
-                f"'{abi.device_type}' memory; there is no CPU fallback"
-            )
-        self.dev = dev
-        self.guard = torch.cuda.device(dev) if dev.type == "cuda" else None
-
-    def __enter__(self):
-        if self.guard is not None:
-            self.guard.__enter__()
-            self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        else:
-            self.stream = None
-        return self
-
-    def __exit__(self, *a):
-        if self.guard is not None:
-            self.guard.__exit__(*a)
 
 
 _scratch_lock = threading.Lock()
@@ -179,7 +150,7 @@ class CapturedForward:
         if not arrived.value:
             with torch.cuda.device(dev):
                 stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-                self.abi.check(self.abi.read_counts(P, H, W, _ptr(self.geom), self.geom.numel(), int(self.have_scratch), stream,
+                self.abi.check(self.abi.read_counts(P, H, W, ptr(self.geom), self.geom.numel(), int(self.have_scratch), stream,
                                                     ctypes.byref(R)))
         exact = R.value
         _peak[self.key] = _merge_counts(_peak.get(self.key), exact)
@@ -236,13 +207,13 @@ def captured_gate():
     gate = rec.gate.get(dev)
     if gate is None:
         gate = rec.gate[dev] = torch.empty((2,), dtype=torch.int32, device=dev).view(torch.uint32)
-    with _Ctx(abi, dev) as cx:
+    with Ctx(abi, dev) as cx:
         for i0 in range(0, max(1, len(rec.forwards)), STEP_MAX_FORWARDS):
             chunk = rec.forwards[i0:i0 + STEP_MAX_FORWARDS]
             arr = (StepForward * max(1, len(chunk)))()
             for a, f in zip(arr, chunk):
                 a.geom, a.geom_bytes, a.P, a.capacity = f.geom.data_ptr(), f.geom.numel(), f.key[1], f.capacity
-            abi.check(abi.step_gate(len(chunk), ctypes.cast(arr, ctypes.c_void_p), int(i0 > 0), _ptr(gate), cx.stream))
+            abi.check(abi.step_gate(len(chunk), ctypes.cast(arr, ctypes.c_void_p), int(i0 > 0), ptr(gate), cx.stream))
     return gate
 
 
@@ -254,16 +225,15 @@ def last_exact_token(device):
 def _scratch_for(abi, dev, stream_id, P, H, W):
     """The transient entry-sort buffer of a forward (include/eogs_rast.h `scratch`): one per device and stream, grown on
     demand, never saved for backward (work on a stream is ordered, so the next forward may overwrite it)."""
-    n = ctypes.c_size_t()
-    abi.check(abi.scratch_bytes(P, H, W, ctypes.byref(n)))
-    if n.value == 0:
+    n = query_bytes(abi, "scratch_bytes", P, H, W)
+    if n == 0:
         return None
     key = (dev, stream_id)
     with _scratch_lock:
         t = _scratch.get(key)
         # grown on demand; given back when the scene shrank to less than half of it (pruning) instead of staying at its peak
-        if t is None or t.numel() < n.value or t.numel() > 2 * (n.value + n.value // 4):
-            t = _scratch[key] = torch.empty((n.value + n.value // 4,), dtype=torch.uint8, device=dev)
+        if t is None or t.numel() < n or t.numel() > 2 * (n + n // 4):
+            t = _scratch[key] = torch.empty((n + n // 4,), dtype=torch.uint8, device=dev)
     return t
 
 
@@ -325,7 +295,7 @@ def _run_forward(rs, viewmat, means3D, colors, opacities, scales, rotations, cov
     flags = _flags(rs) | (FLAG_RAW_PARAMS if raw else 0) | (FLAG_ALT_ONLY if alt_only else 0)
     ncol = 3 if raw else NUM_CHANNELS
 
-    with _Ctx(abi, dev) as cx:
+    with Ctx(abi, dev) as cx:
         # outputs as DGR/rasterize_points.cu:69-76 (zero images when P == 0: forward is skipped)
         color = torch.empty((1 if alt_only else NUM_CHANNELS, H, W), dtype=torch.float32, device=dev)
         # (alt_only: no such output; want_invdepth=False: the caller drops it, as the reference's render() does)
@@ -361,16 +331,13 @@ def _run_forward(rs, viewmat, means3D, colors, opacities, scales, rotations, cov
             if raw and (alt is None or alt.numel() != 4 or sc is None or rot is None):
                 raise RuntimeError("raw-parameter mode needs log-scales, raw rotations and a 4-element alt_affine")
 
-            nbytes = ctypes.c_size_t()
-            abi.check(abi.geom_bytes(P, ctypes.byref(nbytes)))
-            geom = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-            abi.check(abi.image_bytes(H, W, ctypes.byref(nbytes)))
-            img = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+            geom = torch.empty((query_bytes(abi, "geom_bytes", P),), dtype=torch.uint8, device=dev)
+            img = torch.empty((query_bytes(abi, "image_bytes", H, W),), dtype=torch.uint8, device=dev)
 
             capturing = dev.type == "cuda" and torch.cuda.is_current_stream_capturing()
             if capturing:  # a buffer of the graph's own pool (the cached one belongs to eager work on another stream)
-                abi.check(abi.scratch_bytes(P, H, W, ctypes.byref(nbytes)))
-                scratch = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev) if nbytes.value else None
+                n = query_bytes(abi, "scratch_bytes", P, H, W)
+                scratch = torch.empty((n,), dtype=torch.uint8, device=dev) if n else None
             else:
                 scratch = _scratch_for(abi, dev, cx.stream.value if cx.stream is not None else 0, P, H, W)
             n_scratch = 0 if scratch is None else scratch.numel()
@@ -379,20 +346,19 @@ def _run_forward(rs, viewmat, means3D, colors, opacities, scales, rotations, cov
             def prepare(extra_flags):
                 abi.check(
                     abi.forward_prepare(
-                        P, H, W, _ptr(m3), _ptr(sc), _ptr(rot), _ptr(cov), _ptr(opa), _ptr(col),
-                        float(rs.scale_modifier), _ptr(vm), _ptr(pm), _ptr(alt), flags | extra_flags,
-                        _ptr(radii), _ptr(geom), geom.numel(), _ptr(scratch), n_scratch, ctypes.byref(R), cx.stream,
+                        P, H, W, ptr(m3), ptr(sc), ptr(rot), ptr(cov), ptr(opa), ptr(col),
+                        float(rs.scale_modifier), ptr(vm), ptr(pm), ptr(alt), flags | extra_flags,
+                        ptr(radii), ptr(geom), geom.numel(), ptr(scratch), n_scratch, ctypes.byref(R), cx.stream,
                     )
                 )
 
             def render(token):
-                abi.check(abi.binning_bytes(P, H, W, token, ctypes.byref(nbytes)))
-                ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+                ws = torch.empty((query_bytes(abi, "binning_bytes", P, H, W, token),), dtype=torch.uint8, device=dev)
                 abi.check(
                     abi.forward_render(
-                        P, H, W, token, _ptr(bg), flags,
-                        _ptr(geom), geom.numel(), _ptr(ws), ws.numel(), _ptr(img), img.numel(),
-                        _ptr(scratch), n_scratch, _ptr(color), None if invdepths is None else _ptr(invdepths), cx.stream,
+                        P, H, W, token, ptr(bg), flags,
+                        ptr(geom), geom.numel(), ptr(ws), ws.numel(), ptr(img), img.numel(),
+                        ptr(scratch), n_scratch, ptr(color), None if invdepths is None else ptr(invdepths), cx.stream,
                     )
                 )
                 return ws
@@ -423,7 +389,7 @@ def _run_forward(rs, viewmat, means3D, colors, opacities, scales, rotations, cov
                 if _recording is not None:
                     slot = _recording.take_slot()
                     if slot is not None:  # the counts reach the host while the rest of the graph runs
-                        abi.check(abi.mirror_counts(P, _ptr(geom), geom.numel(), slot, cx.stream))
+                        abi.check(abi.mirror_counts(P, ptr(geom), geom.numel(), slot, cx.stream))
                     _recording.forwards.append(CapturedForward(abi, key, geom, num_rendered, hs(), slot))
             elif last is None:
                 prepare(0)
@@ -518,7 +484,7 @@ def _run_backward(rs, num_rendered, grad_out_color, grad_out_depth, means3D, col
     flags = _flags(rs) | (FLAG_RAW_PARAMS if raw else 0)
     grad_viewmatrix = torch.zeros_like(rs.viewmatrix) if want_vm else None
 
-    with _Ctx(abi, dev) as cx:
+    with Ctx(abi, dev) as cx:
         g_color = _f32(grad_out_color, dev)
         if g_color is None:
             g_color = torch.zeros((1 if alt_only else NUM_CHANNELS, H, W), **f32)
@@ -558,14 +524,14 @@ def _run_backward(rs, num_rendered, grad_out_color, grad_out_depth, means3D, col
         grads = {"means3D": d_means3D, "colors": d_colors, "opacities": d_opacity, "scales": d_scales, "rotations": d_rot}
         args = (
             P, H, W, num_rendered,
-            _ptr(_f32(rs.bg, dev)), _ptr(_f32(means3D, dev)), _ptr(radii), _ptr(_f32(colors, dev)),
-            _ptr(_f32(opacities, dev)), _ptr(_f32(scales, dev)), _ptr(_f32(rotations, dev)),
-            float(rs.scale_modifier), _ptr(_f32(cov3Ds_precomp, dev)),
-            _ptr(_f32(rs.viewmatrix, dev)), _ptr(_f32(rs.projmatrix, dev)), _ptr(_f32(alt_affine, dev)), flags,
-            _ptr(color), _ptr(invdepths), _ptr(g_color), _ptr(g_depth),
-            _ptr(geom), geom.numel(), _ptr(binning), binning.numel(), _ptr(img), img.numel(),
-            _ptr(d_means2D), _ptr(d_colors), _ptr(d_opacity), _ptr(d_means3D), _ptr(d_cov3D),
-            _ptr(d_scales), _ptr(d_rot), _ptr(dT_sum), _ptr(dvm_mean), _ptr(lead), 0 if lead is None else int(lead.shape[1]),
+            ptr(_f32(rs.bg, dev)), ptr(_f32(means3D, dev)), ptr(radii), ptr(_f32(colors, dev)),
+            ptr(_f32(opacities, dev)), ptr(_f32(scales, dev)), ptr(_f32(rotations, dev)),
+            float(rs.scale_modifier), ptr(_f32(cov3Ds_precomp, dev)),
+            ptr(_f32(rs.viewmatrix, dev)), ptr(_f32(rs.projmatrix, dev)), ptr(_f32(alt_affine, dev)), flags,
+            ptr(color), ptr(invdepths), ptr(g_color), ptr(g_depth),
+            ptr(geom), geom.numel(), ptr(binning), binning.numel(), ptr(img), img.numel(),
+            ptr(d_means2D), ptr(d_colors), ptr(d_opacity), ptr(d_means3D), ptr(d_cov3D),
+            ptr(d_scales), ptr(d_rot), ptr(dT_sum), ptr(dvm_mean), ptr(lead), 0 if lead is None else int(lead.shape[1]),
         )
         if plan is None or plan.chunks <= 1:
             abi.check(abi.backward(*args, cx.stream))
@@ -668,11 +634,11 @@ class GaussianRasterizer(nn.Module):
             P = positions.shape[0]
             present = torch.empty((P,), dtype=torch.bool, device=positions.device)
             if P:
-                with _Ctx(abi, positions.device) as cx:
+                with Ctx(abi, positions.device) as cx:
                     abi.check(
                         abi.mark_visible(
-                            P, _ptr(_f32(positions, positions.device)), _ptr(_f32(rs.viewmatrix, positions.device)),
-                            _ptr(_f32(rs.projmatrix, positions.device)), _ptr(present), cx.stream,
+                            P, ptr(_f32(positions, positions.device)), ptr(_f32(rs.viewmatrix, positions.device)),
+                            ptr(_f32(rs.projmatrix, positions.device)), ptr(present), cx.stream,
                         )
                     )
         return present

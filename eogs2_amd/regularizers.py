@@ -22,40 +22,29 @@ replaying across the switch (the idea of the device gate of eogs2_amd.flow). Row
 contribute nothing, receive no gradient and are left out of erank's mean; the count is made on the device. fp32 only; CPU
 tensors raise (no CPU fallback).
 """
-import ctypes
+import functools
 
 import torch
 
 from . import _lib
 from ._abi import REG_ERANK, REG_OPACITY, REG_OPACITY_RADII
-from .flow import _call
+from ._host import call, nbytes, on_device
 
 GAUSSIAN_TERMS = ("opacity", "opacity_radii", "erank")  # the order of terms[] and weights[]
 RENDER_TERMS = ("tv_altitude", "accumulated_opacity")
 _WANT = dict(zip(GAUSSIAN_TERMS, (REG_OPACITY, REG_OPACITY_RADII, REG_ERANK)))
-
-
-def _on_device(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"regularizers {what}: tensors live on '{t.device.type}'; the regularisers run on the GPU only, there is "
-                           "no CPU fallback")
-
+_on_device = functools.partial(on_device, "regularizers", "the regularisers run")
 
 # The calls sit at the launch floor (the kernels take 10-20 microseconds at a million rows), so the path through this file is
-# kept short, as in flow.py: entry points resolved once, raw pointers, the current stream's handle without a Stream object,
+# kept short: `_host.call` (entry points resolved once, raw pointers, the current stream's handle without a Stream object)
 # and ONE allocation per forward: the five output floats, then the reduction workspace (one size for every shape).
 _OUT_BYTES = 32
-_buf = {}
 
 
 def _buffer(dev):
     """(float32 tensor, workspace bytes): out[5] at its start, the workspace from byte _OUT_BYTES on."""
-    if "n" not in _buf:
-        n = ctypes.c_size_t()
-        abi = _lib.get()
-        abi.check(abi.reg_gauss_bytes(1, ctypes.byref(n)))
-        _buf["n"] = int(n.value)
-    return torch.empty(((_OUT_BYTES + _buf["n"] + 3) // 4,), dtype=torch.float32, device=dev), _buf["n"]
+    n = nbytes(_lib.get(), "reg_gauss_bytes", 1)
+    return torch.empty(((_OUT_BYTES + n + 3) // 4,), dtype=torch.float32, device=dev), n
 
 
 def _grad_ptr(g, k):
@@ -113,8 +102,8 @@ class _GaussianReg(torch.autograd.Function):
         P = o.shape[0]
         buf, ws_bytes = _buffer(o.device)
         p = buf.data_ptr()
-        _call("eogs_reg_gauss_forward", o.device, P, want, o.data_ptr(), None if s is None else s.data_ptr(),
-              None if radii is None else radii.data_ptr(), n_init, weights.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
+        call("eogs_reg_gauss_forward", o.device, P, want, o.data_ptr(), None if s is None else s.data_ptr(),
+             None if radii is None else radii.data_ptr(), n_init, weights.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
         ctx.cfg = (P, want, n_init)
         ctx.save_for_backward(o, s, radii, weights, buf)
         ctx.set_materialize_grads(False)
@@ -129,9 +118,9 @@ class _GaussianReg(torch.autograd.Function):
         gt, gk = _grad_ptr(g_total, 1), _grad_ptr(g_terms, 3)
         g_o = torch.empty_like(o)
         g_s = torch.empty_like(s) if want & REG_ERANK else None
-        _call("eogs_reg_gauss_backward", o.device, P, want, o.data_ptr(), None if s is None else s.data_ptr(),
-              None if radii is None else radii.data_ptr(), n_init, weights.data_ptr(), buf.data_ptr(), gt and gt[0], gk and gk[0],
-              g_o.data_ptr(), None if g_s is None else g_s.data_ptr())
+        call("eogs_reg_gauss_backward", o.device, P, want, o.data_ptr(), None if s is None else s.data_ptr(),
+             None if radii is None else radii.data_ptr(), n_init, weights.data_ptr(), buf.data_ptr(), gt and gt[0], gk and gk[0],
+             g_o.data_ptr(), None if g_s is None else g_s.data_ptr())
         return g_o, g_s, None, None, None, None
 
 
@@ -202,8 +191,8 @@ class _RenderReg(torch.autograd.Function):
         dev = weights.device
         buf, ws_bytes = _buffer(dev)
         p = buf.data_ptr()
-        _call("eogs_reg_image_forward", dev, H, W, None if a is None else a.data_ptr(), None if c is None else c.data_ptr(),
-              weights.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
+        call("eogs_reg_image_forward", dev, H, W, None if a is None else a.data_ptr(), None if c is None else c.data_ptr(),
+             weights.data_ptr(), p, p + _OUT_BYTES, ws_bytes)
         ctx.cfg = (H, W)
         ctx.save_for_backward(a, c, weights)
         ctx.set_materialize_grads(False)
@@ -218,9 +207,9 @@ class _RenderReg(torch.autograd.Function):
         gt, gk = _grad_ptr(g_total, 1), _grad_ptr(g_terms, 2)
         g_a = torch.empty_like(a) if a is not None else None
         g_c = torch.empty_like(c) if c is not None else None
-        _call("eogs_reg_image_backward", weights.device, H, W, None if a is None else a.data_ptr(), None if c is None else c.data_ptr(),
-              weights.data_ptr(), gt and gt[0], gk and gk[0], None if g_a is None else g_a.data_ptr(),
-              None if g_c is None else g_c.data_ptr())
+        call("eogs_reg_image_backward", weights.device, H, W, None if a is None else a.data_ptr(), None if c is None else c.data_ptr(),
+             weights.data_ptr(), gt and gt[0], gk and gk[0], None if g_a is None else g_a.data_ptr(),
+             None if g_c is None else g_c.data_ptr())
         return g_a, g_c, None, None, None
 
 

@@ -28,7 +28,7 @@ from . import _lib
 from ._abi import (REPORT_CC_AVERAGE, REPORT_CC_REF, REPORT_FLOAT_HWC, REPORT_KINDS, REPORT_MAX_CAMERAS, REPORT_MAX_CC_ELEMS,
                    REPORT_MAX_CHANNELS, REPORT_MAX_ITEMS, REPORT_PACK_MAX_CHANNELS, REPORT_PREMAP, REPORT_REPLICATE, REPORT_REVERSE,
                    REPORT_U8_ROUND, REPORT_U8_TRUNC, ReportCamera, ReportItem, ReportTable)
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, nbytes, ptr
 
 MODES = {"float": REPORT_FLOAT_HWC, "u8_round": REPORT_U8_ROUND, "u8_trunc": REPORT_U8_TRUNC}
 KINDS = REPORT_KINDS
@@ -138,9 +138,9 @@ def normalize_colors_(f_dc, ref_weight, ref_bias, cc_weights, cc_biases):
     abi = _lib.get()
     pairs = [(w.detach(), b.detach()) for w, b in zip(cc_weights, cc_biases)]
     arr = _camera_table(pairs)
-    with _Ctx(abi, dev) as cx, torch.no_grad():
-        abi.check(abi.report_normalize_rows(P, _ptr(f_dc.detach()), _ptr(ref_weight.detach()), _ptr(ref_bias.detach()), cx.stream))
-        abi.check(abi.report_recompose(len(pairs), ctypes.cast(arr, ctypes.c_void_p), _ptr(ref_weight.detach()), _ptr(ref_bias.detach()),
+    with Ctx(abi, dev) as cx, torch.no_grad():
+        abi.check(abi.report_normalize_rows(P, ptr(f_dc.detach()), ptr(ref_weight.detach()), ptr(ref_bias.detach()), cx.stream))
+        abi.check(abi.report_recompose(len(pairs), ctypes.cast(arr, ctypes.c_void_p), ptr(ref_weight.detach()), ptr(ref_bias.detach()),
                                        cx.stream))
     return f_dc
 
@@ -202,7 +202,7 @@ def _cc_to_test(mode, train, test):
     abi = _lib.get()
     a = _camera_table([(w.detach(), b.detach()) for w, b in train])
     b = _camera_table([(w.detach(), b.detach()) for w, b in test])
-    with _Ctx(abi, dev) as cx, torch.no_grad():
+    with Ctx(abi, dev) as cx, torch.no_grad():
         abi.check(abi.report_cc_to_test(mode, len(train), ctypes.cast(a, ctypes.c_void_p), len(test), ctypes.cast(b, ctypes.c_void_p), nw, nb,
                                         cx.stream))
 
@@ -306,16 +306,14 @@ class ReportAccumulator:
             device = torch.device("cuda", torch.cuda.current_device())
         self.device = device
         abi = _lib.get()
-        n = ctypes.c_size_t()
-        abi.check(abi.report_metrics_bytes(ctypes.byref(n)))
         assert ctypes.sizeof(ReportTable) == 64
         self.table = torch.zeros((8,), dtype=torch.float64, device=device)  # eogs_report_table
-        self._ws = torch.empty((n.value,), dtype=torch.uint8, device=device)
+        self._ws = torch.empty((nbytes(abi, "report_metrics_bytes"),), dtype=torch.uint8, device=device)
 
     def reset(self):
         abi = _lib.get()
-        with _Ctx(abi, self.device) as cx:
-            abi.check(abi.report_metrics_reset(_ptr(self.table), cx.stream))
+        with Ctx(abi, self.device) as cx:
+            abi.check(abi.report_metrics_reset(ptr(self.table), cx.stream))
 
     def accumulate(self, image, gt, kind, gate=None):
         k, C, H, W = check_accumulate(image, gt, kind)
@@ -324,9 +322,9 @@ class ReportAccumulator:
         _check_gate(gate, self.device, what)
         _no_overlap(what, [("the table", self.table), ("the workspace", self._ws)], [("image", image), ("gt", gt)])
         abi = _lib.get()
-        with _Ctx(abi, self.device) as cx:
-            abi.check(abi.report_metrics_accumulate(C, H, W, _ptr(image.detach()), _ptr(gt.detach()), k, _ptr(self.table), _ptr(gate),
-                                                    _ptr(self._ws), self._ws.numel(), cx.stream))
+        with Ctx(abi, self.device) as cx:
+            abi.check(abi.report_metrics_accumulate(C, H, W, ptr(image.detach()), ptr(gt.detach()), k, ptr(self.table), ptr(gate),
+                                                    ptr(self._ws), self._ws.numel(), cx.stream))
 
     def read(self):
         """The table as it stands (one copy, one wait): {"l1": [pan, msi], "psnr": [...], "views": [...], "last": (L1, PSNR)}."""
@@ -466,8 +464,8 @@ def pack_products(items, out=None):
         a.lo, a.d = (np.float32(it.premap[0]), np.float32(it.premap[1] - it.premap[0])) if it.premap else (0.0, 1.0)
         layout.append((it.offset, it.pitch, (H, W, Co), np.float32 if eb == 4 else np.uint8))
     abi = _lib.get()
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.report_pack(len(items), ctypes.cast(arr, ctypes.c_void_p), _ptr(out), out.numel(), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.report_pack(len(items), ctypes.cast(arr, ctypes.c_void_p), ptr(out), out.numel(), cx.stream))
     return out, layout
 
 

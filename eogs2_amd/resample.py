@@ -10,18 +10,15 @@
 Gradients flow to `virtual_render` and `rendered_uva` (hence to the true camera's altitude render); `cam2virt` is
 treated as a constant, as in the reference where it is built from fixed camera matrices. No CPU / eager fallback.
 """
-import ctypes
+import functools
 
 import torch
 
 from . import _lib
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, f32c, nbytes, ptr
 
 
-def _f32c(t, dev):
-    if t.device != dev:
-        raise RuntimeError(f"resample input on {t.device}, expected {dev}")
-    return t.detach().to(torch.float32).contiguous()
+_f32c = functools.partial(f32c, label="resample input")
 
 
 class _Resample(torch.autograd.Function):
@@ -36,11 +33,11 @@ class _Resample(torch.autograd.Function):
         H, W = rendered_uva.shape[:2]
         dev = virtual_render.device
         vr, uva, M = _f32c(virtual_render, dev), _f32c(rendered_uva, dev), _f32c(cam2virt, dev)
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             sample = torch.empty((n_out, H, W), dtype=torch.float32, device=dev)
             uv = torch.empty((H, W, 2), dtype=torch.float32, device=dev)
-            abi.check(abi.resample_forward(C, Hv, Wv, H, W, n_out, _ptr(vr), _ptr(uva), _ptr(M), fill_channel,
-                                           float(fill_value), _ptr(sample), _ptr(uv), cx.stream))
+            abi.check(abi.resample_forward(C, Hv, Wv, H, W, n_out, ptr(vr), ptr(uva), ptr(M), fill_channel,
+                                           float(fill_value), ptr(sample), ptr(uv), cx.stream))
         ctx.cfg = (C, Hv, Wv, H, W, n_out, fill_channel)
         ctx.save_for_backward(vr, uva, M)
         ctx.set_materialize_grads(False)
@@ -54,16 +51,14 @@ class _Resample(torch.autograd.Function):
         C, Hv, Wv, H, W, n_out, fill_channel = ctx.cfg
         vr, uva, M = ctx.saved_tensors
         dev = vr.device
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             gs = _f32c(g_sample, dev) if g_sample is not None else torch.zeros((n_out, H, W), dtype=torch.float32, device=dev)
             guv = _f32c(g_uv, dev) if g_uv is not None else None
             g_vr = torch.empty((C, Hv, Wv), dtype=torch.float32, device=dev)
             g_uva = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-            n = ctypes.c_size_t()
-            abi.check(abi.resample_bytes(H, W, ctypes.byref(n)))
-            ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
-            abi.check(abi.resample_backward(C, Hv, Wv, H, W, n_out, _ptr(vr), _ptr(uva), _ptr(M), fill_channel, _ptr(gs),
-                                            _ptr(guv), _ptr(g_vr), _ptr(g_uva), _ptr(ws), ws.numel(), cx.stream))
+            ws = torch.empty((nbytes(abi, "resample_bytes", H, W),), dtype=torch.uint8, device=dev)
+            abi.check(abi.resample_backward(C, Hv, Wv, H, W, n_out, ptr(vr), ptr(uva), ptr(M), fill_channel, ptr(gs),
+                                            ptr(guv), ptr(g_vr), ptr(g_uva), ptr(ws), ws.numel(), cx.stream))
         return g_vr, g_uva, None, None, None, None
 
 

@@ -13,23 +13,14 @@ is not imported); float -> uint8 is x * 255 clamped to [0, 255] and truncated, a
 is undefined outside that range). `CLAHE_rescaler` raises NotImplementedError: kornia stays the caller's. CPU tensors
 raise (no CPU fallback).
 """
-import ctypes
-
 import torch
 
 from . import _lib
-from .flow import _call
-
-_ws_bytes = {}
+from ._host import call, nbytes, on_device
 
 
 def _workspace(dev, C):
-    n = _ws_bytes.get(C)
-    if n is None:
-        size = ctypes.c_size_t()
-        abi = _lib.get()
-        abi.check(abi.gtprep_bytes(C, ctypes.byref(size)))
-        n = _ws_bytes[C] = int(size.value)
+    n = nbytes(_lib.get(), "gtprep_bytes", C)
     return torch.empty((n,), dtype=torch.uint8, device=dev), n
 
 
@@ -40,9 +31,7 @@ def _image(x, what, dims=(3,)):
         raise TypeError(f"rescaler {what}: the image is float32, not {x.dtype}")
     if (dims and x.ndim not in dims) or x.numel() == 0:
         raise ValueError(f"rescaler {what}: a non-empty (C, H, W) image, got {tuple(x.shape)}")
-    if x.device.type != "cuda":
-        raise RuntimeError(f"rescaler {what}: tensors live on '{x.device.type}'; ground-truth preparation runs on the GPU only, "
-                           "there is no CPU fallback")
+    on_device("rescaler", "ground-truth preparation runs", x, what)
     return x.detach().contiguous()
 
 
@@ -52,7 +41,7 @@ def channel_minmax(image):
     C = x.shape[0]
     mm = torch.empty((C, 2), dtype=torch.float32, device=x.device)
     ws, n = _workspace(x.device, C)
-    _call("eogs_gtprep_minmax", x.device, C, x.numel() // C, x.data_ptr(), mm.data_ptr(), ws.data_ptr(), n)
+    call("eogs_gtprep_minmax", x.device, C, x.numel() // C, x.data_ptr(), mm.data_ptr(), ws.data_ptr(), n)
     return mm
 
 
@@ -70,7 +59,7 @@ def _rescale(x, mm, what):
     if tuple(mm.shape) != (C, 2) or mm.device != x.device:
         raise ValueError(f"rescaler {what}: the extrema are those of {mm.shape[0]} channels, the image has {C}")
     out = torch.empty_like(x)
-    _call("eogs_gtprep_rescale", x.device, C, x.numel() // C, x.data_ptr(), mm.data_ptr(), out.data_ptr())
+    call("eogs_gtprep_rescale", x.device, C, x.numel() // C, x.data_ptr(), mm.data_ptr(), out.data_ptr())
     return out
 
 
@@ -93,7 +82,7 @@ class clamper(base_rescaler):
     def forward(self, x):
         x = _image(x, "clamper", dims=())
         out = torch.empty_like(x)
-        _call("eogs_gtprep_clamp", x.device, x.numel(), x.data_ptr(), float(self.min_val), float(self.max_val), out.data_ptr())
+        call("eogs_gtprep_clamp", x.device, x.numel(), x.data_ptr(), float(self.min_val), float(self.max_val), out.data_ptr())
         return out
 
 
@@ -130,7 +119,7 @@ class histogram_equalizer(base_rescaler):
         C = x.shape[0]
         out = torch.empty_like(x)
         ws, n = _workspace(x.device, C)
-        _call("eogs_gtprep_equalize", x.device, C, x.numel() // C, x.data_ptr(), out.data_ptr(), ws.data_ptr(), n)
+        call("eogs_gtprep_equalize", x.device, C, x.numel() // C, x.data_ptr(), out.data_ptr(), ws.data_ptr(), n)
         return out
 
 

@@ -27,8 +27,8 @@ import torch
 
 from . import _lib
 from ._abi import RESET_MAX_TENSORS, RESET_MAX_VIEWS, ResetTensor, ResetView
+from ._host import Ctx, ptr
 from .optim import RETIRED_LOGIT
-from .rasterizer import _Ctx, _ptr
 
 C0 = 0.28209479177387814  # utils/sh_utils.py
 RETIRED_BELOW = 0.5 * RETIRED_LOGIT  # what eogs2_amd.optim.alive_rows tests
@@ -122,7 +122,7 @@ def shadow_reset_flags(xyz, views, *, opacity=None, out=None):
         _same_device(dev, out, "out")
     _need_gpu(dev, "shadow_reset_flags")
     abi = _lib.get()
-    with _Ctx(abi, dev) as cx, torch.no_grad():
+    with Ctx(abi, dev) as cx, torch.no_grad():
         flags = out if out is not None else torch.empty((P,), dtype=torch.uint8, device=dev)
         if not views:
             flags.zero_()
@@ -137,10 +137,10 @@ def shadow_reset_flags(xyz, views, *, opacity=None, out=None):
                 H, W = s.shape
                 eroded = ws[at:at + H * W]
                 at += pad(H * W)
-                abi.check(abi.reset_erode(H, W, _ptr(s), _ptr(eroded), cx.stream))
+                abi.check(abi.reset_erode(H, W, ptr(s), ptr(eroded), cx.stream))
                 a.eroded, a.affine, a.H, a.W = eroded.data_ptr(), affine.data_ptr(), H, W
-            abi.check(abi.reset_flags(P, _ptr(xyz), _ptr(opacity), RETIRED_BELOW, len(chunk), ctypes.cast(arr, ctypes.c_void_p),
-                                      int(k0 > 0), _ptr(flags), cx.stream))
+            abi.check(abi.reset_flags(P, ptr(xyz), ptr(opacity), RETIRED_BELOW, len(chunk), ctypes.cast(arr, ctypes.c_void_p),
+                                      int(k0 > 0), ptr(flags), cx.stream))
     return flags
 
 
@@ -199,8 +199,8 @@ def color_reset_(optimizer, flags):
     arr = (ResetTensor * len(plan))()
     for a, (t, value) in zip(arr, plan):
         a.data, a.row_elems, a.value = t.data_ptr(), t.numel() // P, value
-    with _Ctx(abi, dev) as cx, torch.no_grad():
-        abi.check(abi.reset_rows(P, _ptr(flags), len(plan), ctypes.cast(arr, ctypes.c_void_p), cx.stream))
+    with Ctx(abi, dev) as cx, torch.no_grad():
+        abi.check(abi.reset_rows(P, ptr(flags), len(plan), ctypes.cast(arr, ctypes.c_void_p), cx.stream))
 
 
 def reset_opacity_(optimizer, name="opacity", cap=0.01):
@@ -215,8 +215,8 @@ def reset_opacity_(optimizer, name="opacity", cap=0.01):
     _need_gpu(p.device, "reset_opacity_")
     abi = _lib.get()
     m1, m2 = moments if moments else (None, None)
-    with _Ctx(abi, p.device) as cx, torch.no_grad():
-        abi.check(abi.reset_opacity_cap(p.numel(), _ptr(p), _ptr(m1), _ptr(m2), cap_logit(cap), RETIRED_BELOW, cx.stream))
+    with Ctx(abi, p.device) as cx, torch.no_grad():
+        abi.check(abi.reset_opacity_cap(p.numel(), ptr(p), ptr(m1), ptr(m2), cap_logit(cap), RETIRED_BELOW, cx.stream))
 
 
 @torch.no_grad()

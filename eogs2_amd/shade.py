@@ -14,25 +14,20 @@ Same names, arguments and return values as the reference (paths under src/gaussi
 Each is one forward and one backward kernel (plus a tiny fixed-order reduction) where the reference runs 6-15 elementwise
 PyTorch kernels and autograd replays them. PyTorch is plumbing; there is no CPU or eager fallback.
 """
-import ctypes
+import functools
 
 import torch
 
 from . import _lib
 from ._abi import MLOSS_RANDOM, MLOSS_SUN
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, f32c, nbytes, ptr
 
 
-def _f32c(t, dev):
-    if t.device != dev:
-        raise RuntimeError(f"shade input on {t.device}, expected {dev}")
-    return t.detach().to(torch.float32).contiguous()
+_f32c = functools.partial(f32c, label="shade input")
 
 
 def _ws(abi, H, W, dev):
-    n = ctypes.c_size_t()
-    abi.check(abi.shade_bytes(H, W, ctypes.byref(n)))
-    return torch.empty((n.value,), dtype=torch.uint8, device=dev)
+    return torch.empty((nbytes(abi, "shade_bytes", H, W),), dtype=torch.uint8, device=dev)
 
 
 class _Shade(torch.autograd.Function):
@@ -50,11 +45,11 @@ class _Shade(torch.autograd.Function):
         x, m = _f32c(raw, dev), _f32c(M, dev).reshape(3, 4)
         d = _f32c(alt_diff, dev) if alt_diff is not None else None
         ins = _f32c(inshadow, dev).reshape(3) if alt_diff is not None else None
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             cc = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             shaded = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             shadow = torch.empty((H, W), dtype=torch.float32, device=dev) if d is not None else None
-            abi.check(abi.shade_forward(H, W, _ptr(x), _ptr(d), _ptr(m), _ptr(ins), _ptr(cc), _ptr(shaded), _ptr(shadow),
+            abi.check(abi.shade_forward(H, W, ptr(x), ptr(d), ptr(m), ptr(ins), ptr(cc), ptr(shaded), ptr(shadow),
                                         cx.stream))
         ctx.cfg = (H, W, d is not None, M.shape, inshadow.shape if inshadow is not None else None)
         ctx.save_for_backward(x, d, m, ins)
@@ -69,7 +64,7 @@ class _Shade(torch.autograd.Function):
         H, W, has_shadow, m_shape, ins_shape = ctx.cfg
         x, d, m, ins = ctx.saved_tensors
         dev = x.device
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             gs = _f32c(g_shaded, dev) if g_shaded is not None else torch.zeros((3, H, W), dtype=torch.float32, device=dev)
             gc = _f32c(g_cc, dev) if g_cc is not None else None
             gsh = _f32c(g_shadow, dev) if (g_shadow is not None and has_shadow) else None
@@ -77,8 +72,8 @@ class _Shade(torch.autograd.Function):
             g_alt = torch.empty((H, W), dtype=torch.float32, device=dev) if has_shadow else None
             g_par = torch.empty((15,), dtype=torch.float32, device=dev)
             ws = _ws(abi, H, W, dev)
-            abi.check(abi.shade_backward(H, W, _ptr(x), _ptr(d), _ptr(m), _ptr(ins), _ptr(gs), _ptr(gc), _ptr(gsh),
-                                         _ptr(g_raw), _ptr(g_alt), _ptr(g_par), _ptr(ws), ws.numel(), cx.stream))
+            abi.check(abi.shade_backward(H, W, ptr(x), ptr(d), ptr(m), ptr(ins), ptr(gs), ptr(gc), ptr(gsh),
+                                         ptr(g_raw), ptr(g_alt), ptr(g_par), ptr(ws), ws.numel(), cx.stream))
         g_M = g_par[:12].view(3, 4).reshape(m_shape)
         g_ins = g_par[12:].reshape(ins_shape) if has_shadow else None
         return g_raw, g_alt, g_M, g_ins
@@ -120,10 +115,10 @@ class _MaskedLoss(torch.autograd.Function):
             raise RuntimeError("masked resample loss: expected rgb (3, H, W) twice and uv (H, W, 2)")
         dev = alt_diff.device
         d, a, b, u = _f32c(alt_diff, dev), _f32c(rgb_a, dev), _f32c(rgb_b, dev), _f32c(uv, dev)
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             out = torch.empty((3,), dtype=torch.float32, device=dev)
             ws = _ws(abi, H, W, dev)
-            abi.check(abi.mloss_forward(H, W, mode, _ptr(d), _ptr(a), _ptr(b), _ptr(u), _ptr(out), _ptr(ws), ws.numel(),
+            abi.check(abi.mloss_forward(H, W, mode, ptr(d), ptr(a), ptr(b), ptr(u), ptr(out), ptr(ws), ws.numel(),
                                         cx.stream))
         ctx.cfg = (H, W, mode)
         ctx.save_for_backward(d, a, b, u, out)
@@ -138,13 +133,13 @@ class _MaskedLoss(torch.autograd.Function):
         H, W, mode = ctx.cfg
         d, a, b, u, out = ctx.saved_tensors
         dev = d.device
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             up = _f32c(g_out, dev)[:2].contiguous()
             g_alt = torch.empty((H, W), dtype=torch.float32, device=dev)
             g_a = torch.empty((3, H, W), dtype=torch.float32, device=dev)
             g_b = torch.empty((3, H, W), dtype=torch.float32, device=dev) if ctx.needs_input_grad[2] else None
-            abi.check(abi.mloss_backward(H, W, mode, _ptr(d), _ptr(a), _ptr(b), _ptr(u), _ptr(out), _ptr(up), _ptr(g_alt),
-                                         _ptr(g_a), _ptr(g_b), cx.stream))
+            abi.check(abi.mloss_backward(H, W, mode, ptr(d), ptr(a), ptr(b), ptr(u), ptr(out), ptr(up), ptr(g_alt),
+                                         ptr(g_a), ptr(g_b), cx.stream))
         return g_alt, g_a, g_b, None, None
 
 
@@ -171,10 +166,10 @@ class _TShadow(torch.autograd.Function):
         n = a.numel()
         if n == 0:
             raise RuntimeError("translucentshadows_l: empty shadow map")
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             out = torch.empty((1,), dtype=torch.float32, device=dev)
             ws = _ws(abi, 1, 1, dev)
-            abi.check(abi.tshadow_forward(n, _ptr(a), _ptr(out), _ptr(ws), ws.numel(), cx.stream))
+            abi.check(abi.tshadow_forward(n, ptr(a), ptr(out), ptr(ws), ws.numel(), cx.stream))
         ctx.save_for_backward(a)
         ctx.shape, ctx.dtype = shadowmap.shape, shadowmap.dtype
         return out[0]
@@ -184,10 +179,10 @@ class _TShadow(torch.autograd.Function):
         abi = _lib.get()
         (a,) = ctx.saved_tensors
         dev = a.device
-        with _Ctx(abi, dev) as cx:
+        with Ctx(abi, dev) as cx:
             up = _f32c(g, dev).reshape(1)
             g_a = torch.empty_like(a)
-            abi.check(abi.tshadow_backward(a.numel(), _ptr(a), _ptr(up), _ptr(g_a), cx.stream))
+            abi.check(abi.tshadow_backward(a.numel(), ptr(a), ptr(up), ptr(g_a), cx.stream))
         return g_a.view(ctx.shape).to(ctx.dtype)
 
 

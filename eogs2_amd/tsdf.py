@@ -16,14 +16,14 @@ The stages around integrate are HIP as well:
   TSDFVolume.extract_mesh(path)      tsdf.py:522-528 without mcubes: marching cubes on the device (eogs2_amd.mesh)
 No CPU / eager fallback: CPU tensors raise.
 """
-import ctypes
+import functools
 
 import numpy as np
 import torch
 import torch.nn.functional as F
 
 from . import _lib, dsm_raster, mesh
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, on_device, ptr, query_bytes
 
 
 def volume_axes(vol_bounds, vox_size, device):
@@ -135,10 +135,7 @@ def view_direction(coef):
     return F.normalize(v, dim=0, eps=1e-6)
 
 
-def _on_device(t, what):
-    if t.device.type != "cuda":
-        raise RuntimeError(f"tsdf {what}: tensors live on '{t.device.type}'; the TSDF stages run on the GPU only, there is no "
-                           "CPU fallback")
+_on_device = functools.partial(on_device, "tsdf", "the TSDF stages run")
 
 
 def normals(altitude_img, coef, intercept, view_dir=None, with_normals=True, with_weights=True):
@@ -157,8 +154,8 @@ def normals(altitude_img, coef, intercept, view_dir=None, with_normals=True, wit
     n = torch.empty((1, 3, H, W), device=dev, dtype=torch.float32) if with_normals else None
     angle = torch.empty((1, 1, H, W), device=dev, dtype=torch.float32)
     wgt = torch.empty((1, 1, H, W), device=dev, dtype=torch.float32) if with_weights else None
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.tsdf_normals(H, W, _ptr(alt), _ptr(affine), _ptr(vd), _ptr(n), _ptr(angle), _ptr(wgt), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_normals(H, W, ptr(alt), ptr(affine), ptr(vd), ptr(n), ptr(angle), ptr(wgt), cx.stream))
     return n, angle, wgt
 
 
@@ -176,11 +173,10 @@ def apply_prior(tsdf_vol, weight_vol):
     if tsdf_vol.shape != weight_vol.shape or tsdf_vol.device != weight_vol.device:
         raise RuntimeError("tsdf apply_prior: the volumes differ in shape or device")
     nx, ny, nz = tsdf_vol.shape
-    n = ctypes.c_size_t()
-    abi.check(abi.tsdf_prior_bytes(nx, ny, nz, ctypes.byref(n)))
-    ws = torch.empty(max(n.value, 1), dtype=torch.uint8, device=tsdf_vol.device)
-    with _Ctx(abi, tsdf_vol.device) as cx:
-        abi.check(abi.tsdf_prior(nx, ny, nz, _ptr(tsdf_vol), _ptr(weight_vol), _ptr(ws), n.value, cx.stream))
+    n = query_bytes(abi, "tsdf_prior_bytes", nx, ny, nz)
+    ws = torch.empty(max(n, 1), dtype=torch.uint8, device=tsdf_vol.device)
+    with Ctx(abi, tsdf_vol.device) as cx:
+        abi.check(abi.tsdf_prior(nx, ny, nz, ptr(tsdf_vol), ptr(weight_vol), ptr(ws), n, cx.stream))
 
 
 def surface(tsdf_vol, z_axis):
@@ -194,8 +190,8 @@ def surface(tsdf_vol, z_axis):
         raise RuntimeError("tsdf surface: the z axis does not match the volume")
     index = torch.empty((nx, ny), dtype=torch.int64, device=tsdf_vol.device)
     height = torch.empty((nx, ny), dtype=torch.float32, device=tsdf_vol.device)
-    with _Ctx(abi, tsdf_vol.device) as cx:
-        abi.check(abi.tsdf_surface(nx, ny, nz, _ptr(tsdf_vol), _ptr(az), _ptr(index), _ptr(height), cx.stream))
+    with Ctx(abi, tsdf_vol.device) as cx:
+        abi.check(abi.tsdf_surface(nx, ny, nz, ptr(tsdf_vol), ptr(az), ptr(index), ptr(height), cx.stream))
     return index, height
 
 
@@ -218,9 +214,9 @@ def integrate(tsdf_vol, weight_vol, axes, coef, intercept, model_scale, trunc_ma
     H, W = alt.shape[-2:]
     if alt.numel() != H * W or wgt.numel() != H * W:
         raise RuntimeError("tsdf integrate: altitude and weight images must be single-channel H x W")
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.tsdf_integrate(nx, ny, nz, _ptr(ax), _ptr(ay), _ptr(az), _ptr(affine), model_scale, trunc_margin,
-                                     H, W, _ptr(alt), _ptr(wgt), _ptr(tsdf_vol), _ptr(weight_vol), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_integrate(nx, ny, nz, ptr(ax), ptr(ay), ptr(az), ptr(affine), model_scale, trunc_margin,
+                                     H, W, ptr(alt), ptr(wgt), ptr(tsdf_vol), ptr(weight_vol), cx.stream))
 
 
 __all__ = ["RangeImage", "RangeImageEOGS", "TSDFVolume", "apply_prior", "integrate", "normals", "surface", "view_direction",

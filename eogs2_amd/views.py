@@ -37,7 +37,7 @@ import torch
 
 from . import _lib
 from ._abi import VIEWS_LOAD, VIEWS_MAX_SLOTS, VIEWS_STORE, ViewsSchedule, ViewsSlot
-from .rasterizer import _Ctx, _ptr
+from ._host import Ctx, ptr
 
 
 def reference_order(n_views, iterations, rng=random):
@@ -109,8 +109,8 @@ class ViewSchedule:
         """cursor += 1 on the device, unless `gate` (eogs2_amd.rasterizer.captured_gate()) is closed."""
         _check_gate(gate, self.device, "ViewSchedule.advance")
         abi = _lib.get()
-        with _Ctx(abi, self.device) as cx:
-            abi.check(abi.views_advance(ctypes.byref(self._struct), _ptr(gate), cx.stream))
+        with Ctx(abi, self.device) as cx:
+            abi.check(abi.views_advance(ctypes.byref(self._struct), ptr(gate), cx.stream))
 
     def state_dict(self):
         return {"order": self.order.cpu(), "cursor": self.position(), "n_views": self.n_views}
@@ -282,7 +282,7 @@ class ViewBank:
     def load(self):
         """The current view's rows into the working tensors (and `schedule.current`): one launch per 32 slots."""
         abi = _lib.get()
-        with _Ctx(abi, self.device) as cx:
+        with Ctx(abi, self.device) as cx:
             for n, arr, _ in self._descriptors():
                 abi.check(abi.views_load(n, arr, ctypes.byref(self.schedule._struct), cx.stream))
 
@@ -290,9 +290,9 @@ class ViewBank:
         """The state slots' working tensors into the rows of the view the last `load()` brought in, unless `gate` is closed."""
         _check_gate(gate, self.device, "ViewBank.store")
         abi = _lib.get()
-        with _Ctx(abi, self.device) as cx:
+        with Ctx(abi, self.device) as cx:
             for n, arr, _ in self._descriptors():
-                abi.check(abi.views_store(n, arr, ctypes.byref(self.schedule._struct), _ptr(gate), cx.stream))
+                abi.check(abi.views_store(n, arr, ctypes.byref(self.schedule._struct), ptr(gate), cx.stream))
 
     def state_dict(self):
         """{slot name: its rows as one [V, ...] tensor on the CPU}. The working tensors are not part of it: after `store()`

@@ -7,22 +7,43 @@ import re
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def header_symbols(headers=("eogs_rast.h", "eogs_loss.h", "eogs_optim.h", "eogs_resample.h", "eogs_knn.h", "eogs_shade.h", "eogs_tsdf.h")):
-    out = set()
-    for h in headers:
-        src = open(os.path.join(ROOT, "include", h)).read()
-        src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-        out |= set(re.findall(r"\b(eogs_(?:rast|loss|adam|sum|pack|compact|resample|knn|shade|mloss|tshadow|tsdf)_[a-z_0-9]+)\s*\(", src))
-    return sorted(out)
+    return sorted(sym for h in headers for sym in AC.declared(h))
 
 
-def test_header_and_binding_agree():
-    from eogs2_amd._abi import SIGNATURES
+def test_the_table_names_every_header():
+    from eogs2_amd._abi import HEADERS, HIP_ONLY, SIGNATURES
 
-    assert header_symbols() == sorted(SIGNATURES)
+    assert set(os.listdir(AC.INCLUDE)) == set(HEADERS)
+    names = [sym for table in HEADERS.values() for sym in table]
+    assert len(names) == len(set(names)) and set(names) == set(SIGNATURES)  # no name under two headers
+    assert set(HIP_ONLY) == set(names) - set(HEADERS["eogs_rast.h"])
+    # `abi.x` is eogs_x if the table holds it, else eogs_rast_x: no X may be both
+    assert not {n[len("eogs_rast_"):] for n in HEADERS["eogs_rast.h"]} & {n[len("eogs_"):] for n in HIP_ONLY}
+
+
+@pytest.mark.parametrize("h", sorted(os.listdir(AC.INCLUDE)))
+def test_header_and_binding_agree(h, hip_lib):
+    from eogs2_amd._abi import HEADERS, SIGNATURES
+
+    assert set(os.listdir(AC.INCLUDE)) == set(HEADERS)
+    decl = AC.declared(h)
+    assert sorted(decl) == sorted(HEADERS[h])
+    assert not set(decl) & AC.elsewhere(h)  # no name under two headers
+    for name, (res, args) in HEADERS[h].items():
+        assert decl[name] == len(args), name
+        x = name[len("eogs_rast_"):] if name.startswith("eogs_rast_") else name[len("eogs_"):]
+        assert ("eogs_" + x in SIGNATURES) + ("eogs_rast_" + x in SIGNATURES) == 1, name  # the short-name lookup rests on this
+        fn = getattr(hip_lib.cdll, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name  # bound on load
+        short = name[len("eogs_rast_"):] if name.startswith("eogs_rast_") else name[len("eogs_"):]
+        if short not in ("backend", "path_info", "backward_info"):  # (RastABI's own attributes of these names come first)
+            assert getattr(hip_lib, short) is fn and vars(hip_lib)[short] is fn  # the short name resolves, once
 
 
 @pytest.fixture(scope="module")

@@ -8,6 +8,8 @@ import re
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("stats_update", "bytes", "decide", "split_rows", "build")
 
@@ -29,18 +31,18 @@ def _header():
 def test_library_exports_the_entry_points(hip_lib):
     from eogs2_amd import _abi
 
-    src = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
+    src = AC.header_text("eogs_density.h")
     declared = sorted(set(re.findall(r"\b(eogs_density_[a-z_0-9]+)\s*\(", src)))
-    assert declared == sorted(_abi.DENSITY_SIGNATURES) == sorted("eogs_density_" + n for n in NAMES)
+    assert declared == sorted(_abi.HEADERS["eogs_density.h"]) == sorted("eogs_density_" + n for n in NAMES)
     for n in declared:
         assert hasattr(hip_lib.cdll, n), n
-        assert n in _abi.HIP_ONLY and n not in _abi.SIGNATURES
-        assert getattr(hip_lib.cdll, n).argtypes == _abi.DENSITY_SIGNATURES[n][1]  # bound on load
+        assert n in _abi.HIP_ONLY and n not in AC.elsewhere("eogs_density.h")
+        assert getattr(hip_lib.cdll, n).argtypes == _abi.HEADERS["eogs_density.h"][n][1]  # bound on load
         # one ctypes argument per parameter of the declaration
         params = re.search(rf"\b{n}\s*\(([^)]*)\)", src).group(1)
-        assert len([p for p in params.split(",") if p.strip()]) == len(_abi.DENSITY_SIGNATURES[n][1]), n
+        assert len([p for p in params.split(",") if p.strip()]) == len(_abi.HEADERS["eogs_density.h"][n][1]), n
     assert hip_lib.cdll.eogs_rast_abi_version() == _abi.ABI_VERSION == 8  # additions only
-    assert hip_lib.density_bytes.argtypes == _abi.DENSITY_SIGNATURES["eogs_density_bytes"][1]  # the short prefix resolves
+    assert hip_lib.density_bytes.argtypes == _abi.HEADERS["eogs_density.h"]["eogs_density_bytes"][1]  # the short prefix resolves
 
 
 def test_constants_agree_with_the_header_and_the_optimizer():

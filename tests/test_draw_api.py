@@ -11,6 +11,7 @@ import types
 import pytest
 import torch
 
+import abi_cases as AC
 import draw_cases as DC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,17 +28,17 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_draw.h")).read(), flags=re.S)
+    return AC.header_text("eogs_draw.h")
 
 
 def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_draw_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.DRAW_SIGNATURES) == ["eogs_draw_advance", "eogs_draw_iteration"]
+    assert names == sorted(_abi.HEADERS["eogs_draw.h"]) == ["eogs_draw_advance", "eogs_draw_iteration"]
     assert set(names) <= set(_abi.HIP_ONLY)
-    assert not set(names) & set(_abi.SIGNATURES)  # tests/test_abi.py pins that table to seven other headers
-    for name, (res, args) in _abi.DRAW_SIGNATURES.items():
+    assert not set(names) & AC.elsewhere("eogs_draw.h")  # under this header alone
+    for name, (res, args) in _abi.HEADERS["eogs_draw.h"].items():
         assert res is ctypes.c_int, name
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         assert len(decl.split(",")) == len(args), name
@@ -54,9 +55,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import DRAW_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in DRAW_SIGNATURES:
+    for n in HEADERS["eogs_draw.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8  # additions only
     assert hip_lib.draw_iteration is not None and hip_lib.draw_advance is not None  # the short names resolve

@@ -302,17 +302,17 @@ def test_flow_case_against_the_float64_statement(dev, name):
 def test_field_backward_overwrites_every_element_of_its_output(dev):
     """eogs_resample_flow_backward straight through the C-ABI into a buffer full of NaN, five planes at 64x32 tiles (a four-plane
     and a one-plane pass): every element written, cells no tap reaches with exact zeros, the bits of the autograd path."""
-    from eogs2_amd import _lib
+    from eogs2_amd import _host, _lib
     from eogs2_amd import flow as F
 
     c = RC.flow_case("flow_big5")
     C, H, W = c["img"].shape
     up, flow = c["up"].to(dev), c["flow"].to(dev)
     g_img = torch.full((C, H, W), float("nan"), device=dev)
-    nbytes = F._bytes(_lib.get().resample_flow_bytes, H, W)
+    nbytes = _host.nbytes(_lib.get(), "resample_flow_bytes", H, W)
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    F._call("eogs_resample_flow_backward", up.device, C, H, W, flow.data_ptr(), *flow.stride()[1:], None, up.data_ptr(), g_img.data_ptr(),
-            ws.data_ptr(), nbytes)
+    _host.call("eogs_resample_flow_backward", up.device, C, H, W, flow.data_ptr(), *flow.stride()[1:], None, up.data_ptr(), g_img.data_ptr(),
+               ws.data_ptr(), nbytes)
     torch.cuda.synchronize()
     assert not torch.isnan(g_img).any()
     reached = torch.from_numpy(RC.reached_cells(*RC.flow_tap_cells(c["flow"]), H, W, dilate=1))

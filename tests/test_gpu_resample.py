@@ -221,19 +221,19 @@ def _abi_backward(dev, c, g_vr, g_uva):
     import ctypes
 
     from eogs2_amd import _lib
-    from eogs2_amd.rasterizer import _Ctx, _ptr
+    from eogs2_amd._host import Ctx, ptr
 
     abi = _lib.get()
     (C, Hv, Wv), (H, W) = c["vr"].shape, c["alt"].shape
     vr, M = c["vr"].to(dev), c["M"].to(dev)
     uva = torch.stack((c["U"], c["V"], c["alt"]), dim=-1).to(dev)
     gs, guv = c["w_s"].to(dev), c["w_uv"].to(dev)
-    with _Ctx(abi, dev) as cx:
+    with Ctx(abi, dev) as cx:
         n = ctypes.c_size_t()
         abi.check(abi.resample_bytes(H, W, ctypes.byref(n)))
         ws = torch.empty((n.value,), dtype=torch.uint8, device=dev)
-        abi.check(abi.resample_backward(C, Hv, Wv, H, W, c["n_out"], _ptr(vr), _ptr(uva), _ptr(M), c["fill_channel"], _ptr(gs), _ptr(guv),
-                                        _ptr(g_vr), _ptr(g_uva), _ptr(ws), ws.numel(), cx.stream))
+        abi.check(abi.resample_backward(C, Hv, Wv, H, W, c["n_out"], ptr(vr), ptr(uva), ptr(M), c["fill_channel"], ptr(gs), ptr(guv),
+                                        ptr(g_vr), ptr(g_uva), ptr(ws), ws.numel(), cx.stream))
     torch.cuda.synchronize()
 
 

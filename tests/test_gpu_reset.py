@@ -24,13 +24,13 @@ def dev():
 def erode_on_device(s, dev):
     """eogs_reset_erode alone (shadow_reset_flags keeps its eroded maps in a workspace of its own)."""
     from eogs2_amd import _lib
-    from eogs2_amd.rasterizer import _Ctx, _ptr
+    from eogs2_amd._host import Ctx, ptr
 
     abi = _lib.get()
     src = s.to(dev)
     out = torch.full_like(src, -7.0)
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.reset_erode(src.shape[0], src.shape[1], _ptr(src), _ptr(out), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.reset_erode(src.shape[0], src.shape[1], ptr(src), ptr(out), cx.stream))
     return out.cpu()
 
 

@@ -179,7 +179,7 @@ def test_integrate_nan_in_coef_updates_nothing(dev, row, col):
     a NaN in a row of u or v fails the view test; a NaN in the altitude row leaves u and v valid and is stopped by the NaN sdf
     that the NaN inverse gives, which fails `sdf >= -trunc`."""
     from eogs2_amd import _lib
-    from eogs2_amd.rasterizer import _Ctx, _ptr
+    from eogs2_amd._host import Ctx, ptr
     from eogs2_amd.tsdf import _affine24
 
     axes, views, t0, w0 = tc.lattice_case(1.0)
@@ -193,15 +193,15 @@ def test_integrate_nan_in_coef_updates_nothing(dev, row, col):
     ax = [a.to(dev).contiguous() for a in axes]
     a_img, w_img = alt.to(dev).contiguous(), wgt.to(dev).contiguous()
     abi = _lib.get()
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.tsdf_integrate(*t.shape, _ptr(ax[0]), _ptr(ax[1]), _ptr(ax[2]), _ptr(affine), 1.0, tc.LATTICE_TRUNC, 9, 9,
-                                     _ptr(a_img), _ptr(w_img), _ptr(t), _ptr(w), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_integrate(*t.shape, ptr(ax[0]), ptr(ax[1]), ptr(ax[2]), ptr(affine), 1.0, tc.LATTICE_TRUNC, 9, 9,
+                                     ptr(a_img), ptr(w_img), ptr(t), ptr(w), cx.stream))
     torch.cuda.synchronize()
     assert torch.equal(tc.bits(t), tc.bits(t0)) and torch.equal(tc.bits(w), tc.bits(w0))
     # the same call with the clean matrix does update: the block above reached the kernel's decision, not an early return
     affine = _affine24(coef, intercept, torch.device("cpu")).to(dev)
-    with _Ctx(abi, dev) as cx:
-        abi.check(abi.tsdf_integrate(*t.shape, _ptr(ax[0]), _ptr(ax[1]), _ptr(ax[2]), _ptr(affine), 1.0, tc.LATTICE_TRUNC, 9, 9,
-                                     _ptr(a_img), _ptr(w_img), _ptr(t), _ptr(w), cx.stream))
+    with Ctx(abi, dev) as cx:
+        abi.check(abi.tsdf_integrate(*t.shape, ptr(ax[0]), ptr(ax[1]), ptr(ax[2]), ptr(affine), 1.0, tc.LATTICE_TRUNC, 9, 9,
+                                     ptr(a_img), ptr(w_img), ptr(t), ptr(w), cx.stream))
     ref = tc.reference(axes, views[:1], 1.0, tc.LATTICE_TRUNC, t0, w0)
     assert torch.equal(tc.bits(t), tc.bits(ref["t64"].float())) and torch.equal(tc.bits(w), tc.bits(ref["w64"].float()))

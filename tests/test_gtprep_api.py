@@ -9,6 +9,8 @@ import types
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -23,17 +25,17 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_gtprep.h")).read(), flags=re.S)
+    return AC.header_text("eogs_gtprep.h")
 
 
 def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_gtprep_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.GTPREP_SIGNATURES) and len(names) == 12
+    assert names == sorted(_abi.HEADERS["eogs_gtprep.h"]) and len(names) == 12
     assert set(names) <= set(_abi.HIP_ONLY)
-    assert not set(names) & set(_abi.SIGNATURES)  # tests/test_abi.py pins that table to seven other headers
-    for name, (res, args) in _abi.GTPREP_SIGNATURES.items():
+    assert not set(names) & AC.elsewhere("eogs_gtprep.h")  # under this header alone
+    for name, (res, args) in _abi.HEADERS["eogs_gtprep.h"].items():
         assert res is ctypes.c_int, name  # every entry returns a status
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         params = [p.strip() for p in decl.split(",")]
@@ -53,9 +55,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import GTPREP_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in GTPREP_SIGNATURES:
+    for n in HEADERS["eogs_gtprep.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8
     assert hip_lib.gtprep_pansharp is not None and hip_lib.gtprep_equalize is not None  # the short names resolve

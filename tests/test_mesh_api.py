@@ -9,6 +9,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -23,20 +25,20 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_mesh.h")).read(), flags=re.S)
+    return AC.header_text("eogs_mesh.h")
 
 
 def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_mesh_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.MESH_SIGNATURES) and len(names) == 4
+    assert names == sorted(_abi.HEADERS["eogs_mesh.h"]) and len(names) == 4
     assert set(names) <= set(_abi.HIP_ONLY)
-    assert not set(names) & set(_abi.SIGNATURES)  # tests/test_abi.py pins that table to seven other headers
-    for name, (res, args) in _abi.MESH_SIGNATURES.items():
+    assert not set(names) & AC.elsewhere("eogs_mesh.h")  # under this header alone
+    for name, (res, args) in _abi.HEADERS["eogs_mesh.h"].items():
         assert res is ctypes.c_int, name  # every entry returns a status
     # the argument counts of the declarations
-    for name, (_, args) in _abi.MESH_SIGNATURES.items():
+    for name, (_, args) in _abi.HEADERS["eogs_mesh.h"].items():
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         assert len(decl.split(",")) == len(args), name
     defines = dict(re.findall(r"#define\s+(EOGS_MESH_[A-Z_]+)\s+(\S+)", header()))
@@ -45,9 +47,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import MESH_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in MESH_SIGNATURES:
+    for n in HEADERS["eogs_mesh.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8  # additions only
     assert hip_lib.mesh_count is not None and hip_lib.mesh_bytes is not None  # the short names resolve

@@ -13,6 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden", "model")
 TRAIN_ARGS = types.SimpleNamespace(position_lr_init=1.6e-4, feature_lr=2.5e-3, opacity_lr=5e-2, scaling_lr=5e-3, rotation_lr=1e-3,
@@ -30,7 +32,7 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_model.h")).read(), flags=re.S)
+    return AC.header_text("eogs_model.h")
 
 
 # ---- the class against the reference's ----
@@ -94,9 +96,9 @@ def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_model_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.MODEL_SIGNATURES) and len(names) == 3
-    assert set(names) <= set(_abi.HIP_ONLY) and not set(names) & set(_abi.SIGNATURES)
-    for name, (res, args) in _abi.MODEL_SIGNATURES.items():
+    assert names == sorted(_abi.HEADERS["eogs_model.h"]) and len(names) == 3
+    assert set(names) <= set(_abi.HIP_ONLY) and not set(names) & AC.elsewhere("eogs_model.h")
+    for name, (res, args) in _abi.HEADERS["eogs_model.h"].items():
         assert res is ctypes.c_int, name
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         assert len(decl.split(",")) == len(args), name
@@ -108,9 +110,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import MODEL_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in MODEL_SIGNATURES:
+    for n in HEADERS["eogs_model.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8  # additions only
     assert hip_lib.model_init is not None and hip_lib.model_rows_unpack is not None  # the short names resolve

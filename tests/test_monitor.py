@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_cases as AC
 import monitor_cases as mc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -93,15 +94,15 @@ def hip_lib():
 def test_header_abi_and_library_declare_the_same_entry_points(hip_lib):
     from eogs2_amd import _abi
 
-    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = AC.header_text("eogs_monitor.h")
     declared = sorted(set(re.findall(r"\b(eogs_monitor_[a-z_0-9]+)\s*\(", src)))
-    assert declared == sorted(_abi.MONITOR_SIGNATURES) == sorted("eogs_monitor_" + n for n in NAMES)
+    assert declared == sorted(_abi.HEADERS["eogs_monitor.h"]) == sorted("eogs_monitor_" + n for n in NAMES)
     for n in NAMES:
         fn = getattr(hip_lib.cdll, "eogs_monitor_" + n)
         assert "eogs_monitor_" + n in _abi.HIP_ONLY
-        assert fn.argtypes == _abi.MONITOR_SIGNATURES["eogs_monitor_" + n][1]  # bound on load
+        assert fn.argtypes == _abi.HEADERS["eogs_monitor.h"]["eogs_monitor_" + n][1]  # bound on load
     # argument counts of the prototypes
-    for name, (_, args) in _abi.MONITOR_SIGNATURES.items():
+    for name, (_, args) in _abi.HEADERS["eogs_monitor.h"].items():
         proto = re.search(rf"\b{name}\s*\(([^;]*?)\)\s*;", src, flags=re.S).group(1)
         assert len([a for a in proto.split(",") if a.strip()]) == len(args), name
     assert hip_lib.cdll.eogs_rast_abi_version() == 8  # additions only

@@ -8,21 +8,21 @@ import types
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def header_symbols():
-    src = open(os.path.join(ROOT, "include", "eogs_pan.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(eogs_pan_[a-z_0-9]+)\s*\(", src)))
+    return sorted(set(re.findall(r"\b(eogs_pan_[a-z_0-9]+)\s*\(", AC.header_text("eogs_pan.h"))))
 
 
 def test_header_and_binding_agree():
-    from eogs2_amd._abi import HIP_ONLY, PAN_SIGNATURES, SIGNATURES
+    from eogs2_amd._abi import HEADERS, HIP_ONLY
 
-    assert header_symbols() == sorted(PAN_SIGNATURES) == ["eogs_pan_backward", "eogs_pan_bytes", "eogs_pan_forward"]
-    assert not set(PAN_SIGNATURES) & set(SIGNATURES)
-    assert set(PAN_SIGNATURES) <= set(HIP_ONLY)
+    assert header_symbols() == sorted(HEADERS["eogs_pan.h"]) == ["eogs_pan_backward", "eogs_pan_bytes", "eogs_pan_forward"]
+    assert not set(HEADERS["eogs_pan.h"]) & AC.elsewhere("eogs_pan.h")
+    assert set(HEADERS["eogs_pan.h"]) <= set(HIP_ONLY)
 
 
 def test_header_constants_match_python():

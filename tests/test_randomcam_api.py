@@ -9,6 +9,8 @@ import types
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -23,18 +25,18 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_randomcam.h")).read(), flags=re.S)
+    return AC.header_text("eogs_randomcam.h")
 
 
 def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.RANDOMCAM_SIGNATURES) == ["eogs_cmloss_backward", "eogs_cmloss_bytes", "eogs_cmloss_forward",
+    assert names == sorted(_abi.HEADERS["eogs_randomcam.h"]) == ["eogs_cmloss_backward", "eogs_cmloss_bytes", "eogs_cmloss_forward",
                                                          "eogs_randomcam_compose"]
     assert set(names) <= set(_abi.HIP_ONLY)
-    assert not set(names) & set(_abi.SIGNATURES)  # tests/test_abi.py pins that table to seven other headers
-    for name, (res, args) in _abi.RANDOMCAM_SIGNATURES.items():
+    assert not set(names) & AC.elsewhere("eogs_randomcam.h")  # under this header alone
+    for name, (res, args) in _abi.HEADERS["eogs_randomcam.h"].items():
         assert res is ctypes.c_int, name
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         assert len(decl.split(",")) == len(args), name
@@ -49,9 +51,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import RANDOMCAM_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in RANDOMCAM_SIGNATURES:
+    for n in HEADERS["eogs_randomcam.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8
     assert hip_lib.randomcam_compose is not None and hip_lib.cmloss_forward is not None  # the short names resolve

@@ -9,6 +9,8 @@ import types
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("gauss_bytes", "gauss_forward", "gauss_backward", "image_bytes", "image_forward", "image_backward")
 
@@ -24,14 +26,14 @@ def hip_lib():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import HIP_ONLY, REG_SIGNATURES
+    from eogs2_amd._abi import HEADERS, HIP_ONLY
 
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_reg.h")).read(), flags=re.S)
-    assert sorted(set(re.findall(r"\b(eogs_reg_[a-z_0-9]+)\s*\(", src))) == sorted(REG_SIGNATURES) == sorted("eogs_reg_" + n for n in NAMES)
+    src = AC.header_text("eogs_reg.h")
+    assert sorted(set(re.findall(r"\b(eogs_reg_[a-z_0-9]+)\s*\(", src))) == sorted(HEADERS["eogs_reg.h"]) == sorted("eogs_reg_" + n for n in NAMES)
     for n in NAMES:
         assert hasattr(hip_lib.cdll, "eogs_reg_" + n), n
         assert "eogs_reg_" + n in HIP_ONLY
-        assert getattr(hip_lib.cdll, "eogs_reg_" + n).argtypes == REG_SIGNATURES["eogs_reg_" + n][1]  # bound on load
+        assert getattr(hip_lib.cdll, "eogs_reg_" + n).argtypes == HEADERS["eogs_reg.h"]["eogs_reg_" + n][1]  # bound on load
     assert hip_lib.cdll.eogs_rast_abi_version() == 8  # additions only
     slots = hip_lib.profile_slot_names()
     assert {"reg_fwd", "reg_bwd"} <= set(slots) and len(slots) <= 32  # (the mask of eogs_rast_profile_select has 32 bits)

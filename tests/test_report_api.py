@@ -10,6 +10,8 @@ import types
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -24,19 +26,19 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_report.h")).read(), flags=re.S)
+    return AC.header_text("eogs_report.h")
 
 
 def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_report_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.REPORT_SIGNATURES) == ["eogs_report_cc_to_test", "eogs_report_metrics_accumulate", "eogs_report_metrics_bytes",
+    assert names == sorted(_abi.HEADERS["eogs_report.h"]) == ["eogs_report_cc_to_test", "eogs_report_metrics_accumulate", "eogs_report_metrics_bytes",
                                                       "eogs_report_metrics_reset", "eogs_report_normalize_rows", "eogs_report_pack",
                                                       "eogs_report_recompose"]
     assert set(names) <= set(_abi.HIP_ONLY)
-    assert not set(names) & set(_abi.SIGNATURES)  # tests/test_abi.py pins that table to seven other headers
-    for name, (res, args) in _abi.REPORT_SIGNATURES.items():
+    assert not set(names) & AC.elsewhere("eogs_report.h")  # under this header alone
+    for name, (res, args) in _abi.HEADERS["eogs_report.h"].items():
         assert res is ctypes.c_int, name
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         assert len(decl.split(",")) == len(args), name
@@ -59,9 +61,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import REPORT_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in REPORT_SIGNATURES:
+    for n in HEADERS["eogs_report.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8
     assert hip_lib.report_pack is not None and hip_lib.report_metrics_accumulate is not None  # the short names resolve

@@ -9,6 +9,7 @@ import re
 import pytest
 import torch
 
+import abi_cases as AC
 import reset_cases as RC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,17 +26,17 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_reset.h")).read(), flags=re.S)
+    return AC.header_text("eogs_reset.h")
 
 
 def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_reset_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.RESET_SIGNATURES) and len(names) == 4
+    assert names == sorted(_abi.HEADERS["eogs_reset.h"]) and len(names) == 4
     assert set(names) <= set(_abi.HIP_ONLY)
-    assert not set(names) & set(_abi.SIGNATURES)  # tests/test_abi.py pins that table to seven other headers
-    for name, (res, args) in _abi.RESET_SIGNATURES.items():
+    assert not set(names) & AC.elsewhere("eogs_reset.h")  # under this header alone
+    for name, (res, args) in _abi.HEADERS["eogs_reset.h"].items():
         assert res is ctypes.c_int, name  # every entry returns a status
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         assert len(decl.split(",")) == len(args), name
@@ -52,9 +53,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import RESET_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in RESET_SIGNATURES:
+    for n in HEADERS["eogs_reset.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8  # additions only
     assert hip_lib.reset_erode is not None and hip_lib.reset_opacity_cap is not None  # the short names resolve

@@ -8,13 +8,14 @@ import re
 import pytest
 import torch
 
+import abi_cases as AC
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _declarations():
     """{symbol: number of parameters} of the functions include/eogs_step.h declares."""
-    src = open(os.path.join(ROOT, "include", "eogs_step.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = AC.header_text("eogs_step.h")
     return {name: len([a for a in args.split(",") if a.strip() and a.strip() != "void"])
             for name, args in re.findall(r"\bint\s+(eogs_step_[a-z_0-9]+)\s*\(([^)]*)\)", src)}
 
@@ -23,12 +24,11 @@ def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     decl = _declarations()
-    assert sorted(decl) == sorted(_abi.STEP_SIGNATURES) and len(decl) == 3
-    for name, (res, args) in _abi.STEP_SIGNATURES.items():
+    assert sorted(decl) == sorted(_abi.HEADERS["eogs_step.h"]) and len(decl) == 3
+    for name, (res, args) in _abi.HEADERS["eogs_step.h"].items():
         assert res is ctypes.c_int and len(args) == decl[name], name
         assert name in _abi.HIP_ONLY, name
-    for other in (_abi.SIGNATURES, _abi.REG_SIGNATURES, _abi.PAN_SIGNATURES, _abi.DENSITY_SIGNATURES):
-        assert not set(other) & set(_abi.STEP_SIGNATURES)
+    assert not set(_abi.HEADERS["eogs_step.h"]) & AC.elsewhere("eogs_step.h")
     # the structs are those of the header, field for field
     assert [f[0] for f in _abi.StepForward._fields_] == ["geom", "geom_bytes", "P", "capacity"]
     assert [f[0] for f in _abi.StepAdamTensor._fields_] == ["param", "grad", "exp_avg", "exp_avg_sq", "numel", "lr", "step", "retire_below"]
@@ -47,11 +47,11 @@ def hip_lib():
 
 
 def test_library_exports_and_binds_the_symbols(hip_lib):
-    from eogs2_amd._abi import STEP_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
     assert hip_lib.backend == "hip-gfx950"
     assert hip_lib.cdll.eogs_rast_abi_version() == 8
-    for name, (res, args) in STEP_SIGNATURES.items():
+    for name, (res, args) in HEADERS["eogs_step.h"].items():
         fn = getattr(hip_lib.cdll, name)
         assert fn.restype is res and list(fn.argtypes) == list(args), name
     assert hip_lib.step_adam is hip_lib.cdll.eogs_step_adam or hip_lib.step_adam.argtypes == hip_lib.cdll.eogs_step_adam.argtypes

@@ -13,6 +13,7 @@ import types
 import pytest
 import torch
 
+import abi_cases as AC
 import views_cases as VC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,17 +30,17 @@ def hip_lib():
 
 
 def header():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "eogs_views.h")).read(), flags=re.S)
+    return AC.header_text("eogs_views.h")
 
 
 def test_header_and_binding_agree():
     from eogs2_amd import _abi
 
     names = sorted(set(re.findall(r"\b(eogs_views_[a-z_0-9]+)\s*\(", header())))
-    assert names == sorted(_abi.VIEWS_SIGNATURES) and len(names) == 4
+    assert names == sorted(_abi.HEADERS["eogs_views.h"]) and len(names) == 4
     assert set(names) <= set(_abi.HIP_ONLY)
-    assert not set(names) & set(_abi.SIGNATURES)  # tests/test_abi.py pins that table to seven other headers
-    for name, (res, args) in _abi.VIEWS_SIGNATURES.items():
+    assert not set(names) & AC.elsewhere("eogs_views.h")  # under this header alone
+    for name, (res, args) in _abi.HEADERS["eogs_views.h"].items():
         assert res is ctypes.c_int, name  # every entry returns a status
         decl = re.search(name + r"\s*\(([^)]*)\)", header()).group(1)
         assert len(decl.split(",")) == len(args), name
@@ -57,9 +58,9 @@ def test_header_and_binding_agree():
 
 
 def test_library_exports_the_entry_points(hip_lib):
-    from eogs2_amd._abi import VIEWS_SIGNATURES
+    from eogs2_amd._abi import HEADERS
 
-    for n in VIEWS_SIGNATURES:
+    for n in HEADERS["eogs_views.h"]:
         assert hasattr(hip_lib.cdll, n), n
     assert hip_lib.cdll.eogs_rast_abi_version() == 8  # additions only
     assert hip_lib.views_load is not None and hip_lib.views_advance is not None  # the short names resolve
