@@ -78,6 +78,7 @@ STEP_MAX_FORWARDS = STEP_MAX_TENSORS = 16  # EOGS_STEP_MAX_*
 DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP = 1, 2, 4, 8  # EOGS_DENSITY_*: the flag byte
 DENSITY_COPY, DENSITY_ZERO, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2, 3  # the tensor kinds of eogs_density_build
 DENSITY_MAX_N = 8
+NLL_MASK, NLL_FULL, NLL_SUM = 1, 2, 4  # include/eogs_nll.h EOGS_NLL_*: the mode bits
 
 _p = C.c_void_p
 _i = C.c_int
@@ -295,6 +296,11 @@ HEADERS = {
         "eogs_report_metrics_reset": (_i, [_p, _p]),
         "eogs_report_metrics_accumulate": (_i, [_i, _i, _i, _p, _p, _i, _p, _p, _p, _z, _p]),
         "eogs_report_pack": (_i, [_i, _p, _p, _z, _p]),
+    },
+    "eogs_nll.h": {
+        "eogs_nll_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_nll_forward": (_i, [_i, _i, _i, _u, _p, _p, _p, _i, _f, _f, _p, _p, _p, _z, _p]),
+        "eogs_nll_backward": (_i, [_i, _i, _i, _u, _p, _p, _p, _i, _f, _f] + [_p] * 5 + [_p]),
     },
 }
 # name -> (restype, argtypes) of every header

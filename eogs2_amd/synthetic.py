@@ -139,6 +139,17 @@ def _finish_scene(P, H, W, seed, g, device, xyz, scales, q, op):
     return {k: v.to(device=device, dtype=torch.float32).contiguous() for k, v in out.items()}
 
 
+def paint_transient(gt, value=1.0, box=None):
+    """Paints a bright rectangle — a transient object, present in this one view only — into the ground truth `gt` [..., H, W] in
+    place and returns its box (y0, y1, x0, x1): by default a quarter of the height by a quarter of the width, right of the centre."""
+    H, W = gt.shape[-2:]
+    y0, y1, x0, x1 = box if box is not None else (H // 4, H // 4 + max(1, H // 4), W // 2, W // 2 + max(1, W // 4))
+    if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W):
+        raise ValueError(f"paint_transient: the box {(y0, y1, x0, x1)} does not lie inside {H} x {W}")
+    gt[..., y0:y1, x0:x1] = value
+    return (y0, y1, x0, x1)
+
+
 def settings_for(scene, H, W, antialiasing=False, debug=False):
     from .rasterizer import GaussianRasterizationSettings
 

@@ -52,6 +52,15 @@ and render pipeline and their L1 and PSNR summed on the device (`evaluate_views`
 `--normalize-colors` is the reference's `normalize_before_saving` before the final save (train_pan.py:614-620) in place, and
 `--render-set DIR` writes `render_set`'s products of every view (render_pan.py) as DIR/<product>/<view>.npy — one packing launch and
 one copy per view (`view_products`, `fetch_products`) — and render_video.py's frame `[final | elevation]` as DIR/frames/<view>.npy.
+`--transient-nll W` adds the reference's transient-uncertainty term `w_L_nll * L_nll` (train_pan.py:433-449, `use_transient`) through
+`eogs2_amd.uncertainty.transient_nll`: the camera owns an H x W trainable transient mask (`--transient-init V`, affine_cameras.py:282-289)
+that sits in the camera optimizer — with `--views V` as a `ViewBank` state slot "transient_mask" per view, its Adam moments and step count
+beside it — and the Gaussian negative log-likelihood of the shaded image under the variance (clip(mask, 0, 1) + 1e-3)^2 joins the loss.
+The weight lives in a device tensor that is 0 until `--transient-from ITER` has passed (`iteration > iterstart_L_nll`) and W afterwards: a
+write between two replays, so a recorded step keeps replaying across the switch. (Until then the mask receives exact zeros where the
+reference's receives no gradient at all: its Adam step count runs from iteration 1 here.) A bright rectangle is painted into ONE view's
+ground truth (`eogs2_amd.synthetic.paint_transient`: view 1 with `--views`, else the view) and the run prints that view's final mean mask
+inside and outside of it.
 """
 import argparse
 import math
@@ -83,7 +92,8 @@ from eogs2_amd.model import GaussianModel, parse_ply_header  # noqa: E402
 from eogs2_amd.monitor import MONITOR_METRICS, TrainingMonitor  # noqa: E402
 from eogs2_amd.pansharp import METHODS as PANSHARP_METHODS, Pansharploss  # noqa: E402
 from eogs2_amd.pan import FIXED_PARAMS, KINDS as PAN_KINDS, PanMap, render_pipeline as pan_render_pipeline  # noqa: E402
-from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene  # noqa: E402
+from eogs2_amd.synthetic import ALT_SCALE, make_camera, make_scene, paint_transient  # noqa: E402
+from eogs2_amd.uncertainty import transient_nll, transient_parameters  # noqa: E402
 from eogs2_amd.views import ViewBank, ViewSchedule, reference_order  # noqa: E402
 from eogs2_amd.draw import DrawStream, IterationDraws  # noqa: E402
 from eogs2_amd.randomcam import RENDER_TYPES, RandomcamRendering_Loss  # noqa: E402
@@ -330,7 +340,22 @@ def main(argv=None):
                          "for every train and test view as DIR/<product>/<view>.npy in file layout, and render_video.py's frame "
                          "[final | normalised elevation] (8-bit BGR) as DIR/frames/<view>.npy: eogs2_amd.report.view_products, "
                          "fetch_products (one packing launch and one copy per view) and video_frame")
+    ap.add_argument("--transient-nll", type=float, default=0.0, metavar="W",
+                    help="adds W x the transient-uncertainty term (train_pan.py:433-449: gaussian_nll_loss of the shaded image under the "
+                         "variance (clip(transient_mask, 0, 1) + 1e-3)^2) through eogs2_amd.uncertainty.transient_nll: one forward launch "
+                         "group and one backward launch, no wait. The H x W mask is a parameter of the camera optimizer, with --views a "
+                         "ViewBank state slot per view; a bright rectangle is painted into one view's ground truth and the final mean mask "
+                         "inside and outside of it is printed (main.last_transient). 0 = absent")
+    ap.add_argument("--transient-init", type=float, default=0.01, metavar="V",
+                    help="with --transient-nll: transient_params.init_value, what every camera's mask starts at (the reference's default)")
+    ap.add_argument("--transient-from", type=int, default=0, metavar="ITER",
+                    help="with --transient-nll: opt.iterstart_L_nll. The term's weight is a device tensor that holds 0 up to and including "
+                         "iteration ITER and W after it: the switch is a write into that tensor, a recorded step is not recorded again")
     a = ap.parse_args(argv)
+    if a.transient_nll < 0 or a.transient_from < 0:
+        ap.error("--transient-nll and --transient-from are not negative")
+    if (a.transient_from or a.transient_init != 0.01) and not a.transient_nll:
+        ap.error("--transient-init and --transient-from belong to --transient-nll W")
     if a.test_views < 0 or a.report_every < 0:
         ap.error("--test-views and --report-every are not negative")
     if a.report_every and not a.test_views:
@@ -492,6 +517,7 @@ def main(argv=None):
     with torch.no_grad():
         target_view = view(target_model, colour_camera(0.0))
         gt = target_view[5]["final"].clone()
+        transient_box = paint_transient(gt) if a.transient_nll and a.views == 1 else None
         gt_altitude = target_view[0]["render"][3].clone() if a.dsm_mae_every else None
         del target_view
     dsm_cam = dsm_scene = dsm_geometry = gt_dsm = None
@@ -522,10 +548,18 @@ def main(argv=None):
         flow_opt = types.SimpleNamespace(flowmatching=types.SimpleNamespace(max_value_flow=3.0))
     cc_cam = colour_camera(0.15)
     camera_parameters = [*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction, *getattr(cc_cam, "map_parameters", ())]
+    # --transient-nll: the camera's transient mask joins its optimizer (affine_cameras.py:282-289, train_pan.py:135-138); the weight
+    # of the term is a device tensor, 0 until --transient-from has passed
+    transient_mask = transient_weight = None
+    optimizer_parameters = list(camera_parameters)
+    if a.transient_nll:
+        transient_mask = transient_parameters(H, W, a.transient_init, dev)
+        transient_weight = torch.zeros(1, device=dev)
+        optimizer_parameters.append(transient_mask)
     if a.optimizer_in_graph or a.views > 1:  # one prologue + one element launch for the handful of 3-12 element tensors
-        camera_optimizer = FusedAdam(camera_parameters, lr=2e-3, capturable=True)  # (--views: the bank carries device step counts)
+        camera_optimizer = FusedAdam(optimizer_parameters, lr=2e-3, capturable=True)  # (--views: the bank carries device step counts)
     else:
-        camera_optimizer = torch.optim.Adam(camera_parameters, lr=2e-3)
+        camera_optimizer = torch.optim.Adam(optimizer_parameters, lr=2e-3)
 
     view_bank = view_schedule = None
     if a.views > 1:
@@ -547,6 +581,8 @@ def main(argv=None):
                 t.copy_(r)
             with torch.no_grad():
                 gt_v = view(target_model, identity_camera)[5]["final"].clone()
+            if a.transient_nll and v == 1:  # the transient object: in this one view's ground truth only
+                transient_box = paint_transient(gt_v)
             for k, r in zip(rows, (vm, sun_vm, c2s, c2r, bg_v, gt_v)):
                 rows[k].append(r)
         cc_rows = [[p.detach().clone() for p in camera_parameters]]
@@ -559,7 +595,9 @@ def main(argv=None):
             view_bank.add_input(k, t, rows[k])
         for i, p in enumerate(camera_parameters):
             view_bank.add_state(f"camera.{i}", p, [cc_rows[v][i] for v in range(n_views)])
-        for p in camera_parameters:  # one eager step creates the optimizer's state; zero gradients move no parameter
+        if transient_mask is not None:  # every view's mask starts at --transient-init: the rows are copies of the working tensor
+            view_bank.add_state("transient_mask", transient_mask)
+        for p in optimizer_parameters:  # one eager step creates the optimizer's state; zero gradients move no parameter
             p.grad = torch.zeros_like(p)
         camera_optimizer.step()
         view_bank.attach_optimizer(camera_optimizer)  # every view starts at step 0 with zero moments, as torch's lazy state does
@@ -712,6 +750,9 @@ def main(argv=None):
                 kept["random_camera"] = (L_new_alt.detach(), L_new_rgb.detach())
         if reg_want:  # train_pan.py:450-465: w_L_opacity * L_opacity (+ w_L_erank * L_erank), summed in the kernel
             loss = loss + gaussian_regularizers(model._opacity, model._scaling, n_init=P, weights=reg_weights, want=reg_want)[0]
+        if transient_mask is not None:  # w_L_nll * L_nll (train_pan.py:433-440,461): the weight is read on the device
+            nll_total, _, kept["transient"] = transient_nll(final, gt, transient_mask, weight=transient_weight)
+            loss = loss + nll_total
         if pansharp_term is not None:  # w_L_pansharp * L_pansharp: one forward and one backward kernel, no full-size temporaries
             kept["pansharp"] = pansharp_term(lift(final), *pansharp_args)
             loss = loss + pansharp_term.lambda_L_pansharp * kept["pansharp"]
@@ -767,6 +808,8 @@ def main(argv=None):
         if it == a.iters - timed + 1:
             torch.cuda.synchronize()
             t_steady = time.perf_counter()
+        if transient_weight is not None and it == a.transient_from + 1:  # iteration > iterstart_L_nll: a device write, no recording
+            transient_weight.fill_(a.transient_nll)
         t_in = time.perf_counter()
         if steps_inside and it == 1:
             # the first iteration runs eagerly: it creates the optimizers' state and uploads the learning rates, which a
@@ -935,6 +978,20 @@ def main(argv=None):
     if not a.quiet:
         print(f"{a.iters} iterations in {dt:.2f} s ({dt / a.iters * 1e3:.2f} ms/iter over all, {main.last_ms_per_iter:.2f} ms/iter over the "
               f"last {timed}; {3 if a.random_camera else 2} renders + resample + render pipeline + losses + Adam each)")
+    main.last_transient = None
+    if transient_mask is not None:  # the painted view's mask inside and outside the rectangle: printed, not judged
+        painted = view_bank.row("transient_mask", 1) if view_bank is not None else transient_mask.detach()
+        y0, y1, x0, x1 = transient_box
+        inside = painted[y0:y1, x0:x1]
+        n_in = inside.numel()
+        main.last_transient = dict(weight=float(transient_weight), init=a.transient_init, box=transient_box, inside=float(inside.mean()),
+                                   outside=float((painted.sum() - inside.sum()) / (painted.numel() - n_in)),
+                                   stats=[float(x) for x in kept["transient"]])
+        if not a.quiet:
+            t = main.last_transient
+            print(f"transient mask of the painted view: mean {t['inside']:.6g} inside the rectangle {transient_box}, {t['outside']:.6g} outside "
+                  f"(started at {a.transient_init:g}; weight {t['weight']:g} after iteration {a.transient_from}); last iteration's mask mean "
+                  f"{t['stats'][0]:.6g} std {t['stats'][1]:.6g}, {int(t['stats'][3])} pixels outside [0, 1]")
     main.last_random_camera = tuple(float(v) for v in kept["random_camera"]) if "random_camera" in kept else None
     if rc_loss is not None and not a.quiet:
         print(f"random camera: {a.random_camera_type}, target {'ground truth' if a.random_camera_gt else 'the view itself'}, sun render "
