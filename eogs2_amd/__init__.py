@@ -26,6 +26,7 @@ from . import views  # noqa: F401,E402  (several views in one recorded step: dev
 from . import draw  # noqa: F401,E402  (per-iteration random background and virtual camera on the device: train_pan.py:272-277,375-378)
 from . import randomcam  # noqa: F401,E402  (RandomcamRendering_Loss in full: shadow-mapped render type, GT target: loss/main_loss.py:56-221)
 from . import report  # noqa: F401,E402  (training_report's metrics, colour alignment before save_ply, cc train -> test, product packing: train_pan.py:838-1025, utils/save_utils.py)
+from . import raft  # noqa: F401,E402  (the flow network, RAFT, with on-demand correlation lookup: flowmatching/flow_matching.py:76-86)
 from . import uncertainty  # noqa: F401,E402  (transient-mask Gaussian NLL term and its statistics: train_pan.py:433-449)
 
 __version__ = "0.1.0"

@@ -79,6 +79,10 @@ DENSITY_CLONE, DENSITY_SPLIT, DENSITY_PRUNE_SELF, DENSITY_PRUNE_SAMP = 1, 2, 4, 
 DENSITY_COPY, DENSITY_ZERO, DENSITY_XYZ, DENSITY_SCALING = 0, 1, 2, 3  # the tensor kinds of eogs_density_build
 DENSITY_MAX_N = 8
 NLL_MASK, NLL_FULL, NLL_SUM = 1, 2, 4  # include/eogs_nll.h EOGS_NLL_*: the mode bits
+RAFT_MAX_LEVELS, RAFT_MAX_RADIUS = 4, 4  # include/eogs_resample.h EOGS_RAFT_MAX_*
+RAFT_NO_STAGE = 1  # EOGS_RAFT_NO_STAGE: the lookup's flag
+RAFT_UP_CONVEX, RAFT_UP_BILINEAR = 0, 1  # EOGS_RAFT_UP_*: the upsampling modes
+RAFT_MASK_CHANNELS = 576  # EOGS_RAFT_MASK_CHANNELS
 
 _p = C.c_void_p
 _i = C.c_int
@@ -170,6 +174,13 @@ HEADERS = {
         "eogs_resample_flow_backward": (_i, [_i, _i, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _z, _p]),
         "eogs_resample_flow_stats_bytes": (_i, [_i, _i, C.POINTER(_z)]),
         "eogs_resample_flow_stats": (_i, [_i, _i, _p, _i64, _i64, _i64, _p, _p, _z, _p]),
+        # the flow network (RAFT): feature pyramid, on-demand correlation lookup, flow upsampling
+        "eogs_raft_bytes": (_i, [_i, _i, _i, _i, _i, C.POINTER(_z)]),
+        "eogs_raft_level_offset": (_i, [_i, _i, _i, _i, _i, C.POINTER(_z)]),
+        "eogs_raft_pyramid": (_i, [_i, _i, _i, _i, _i, _p, _p, _z, _p]),
+        "eogs_raft_lookup": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _u, _p]),
+        "eogs_raft_stage_info": (_i, [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+        "eogs_raft_upsample": (_i, [_i, _i, _i, _i, _p, _p, _p, _p]),
     },
     "eogs_knn.h": {
         "eogs_knn_bytes": (_i, [_i, C.POINTER(_z)]),

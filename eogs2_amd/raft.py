@@ -1,0 +1,480 @@
+"""The optical-flow network of the flow-matching step, RAFT (the reference takes it from torchvision:
+flowmatching/flow_matching.py:76-86), with its correlation looked up ON DEMAND over the eogs_raft_* entries of include/eogs_resample.h.
+
+  corr_pyramid(fmap, levels)                        channel-last feature pyramid in one workspace      one launch per level
+  corr_lookup(fmap1_cl, pyramid, coords, radius)    [N, levels (2r+1)^2, h, w] correlation features    one launch
+  upsample_flow(flow, mask=None)                    convex (mask) or bilinear x 8 upsampling           one launch
+  RAFT, raft_small(), raft_large()                  the two published configurations as nn.Modules
+  RAFT.load_weights(path_or_state_dict)             a torchvision checkpoint, strict
+
+RAFT as published materialises the all-pairs correlation volume, n x n floats for n = HW / 64 feature positions plus three
+pooled levels, and reads it through grid_sample at every update. Average-pooling the correlation over the second image's
+positions equals correlating with the pooled features, and all (2r+1)^2 taps of a pixel at a level share one fractional
+offset: the on-demand lookup computes (2r+2)^2 dot products per pixel and level against a small feature pyramid and blends
+them 2 x 2. Memory is linear in n. `corr="volume"` keeps the materialised form in plain torch (matmul, avg_pool2d,
+grid_sample): it is the CPU path and works in any dtype, so a float64 run of the whole network arbitrates the tests.
+
+The convolutions, norms and GRUs are torch modules. Everything here is forward only (the reference runs the network under
+inference_mode); the three operators are float32 and refuse CPU tensors (no CPU fallback).
+
+The module tree mirrors torchvision.models.optical_flow.raft name for name, so a torchvision state dict loads with
+strict=True. torchvision is not a dependency and its checkpoints were not at hand when this was written: `TORCHVISION_NAMES`
+is the one table of names, and a wrong name fails loudly at load_weights instead of leaving random weights in place.
+Nothing is ever downloaded.
+"""
+import ctypes
+import functools
+import math
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+from ._abi import RAFT_MASK_CHANNELS, RAFT_MAX_LEVELS, RAFT_MAX_RADIUS, RAFT_NO_STAGE, RAFT_UP_BILINEAR, RAFT_UP_CONVEX
+from ._host import Workspaces, call, nbytes, on_device
+
+_on_device = functools.partial(on_device, "raft", "the correlation lookup runs")
+
+
+def _map(t, name, what, channels=None):
+    if not torch.is_tensor(t):
+        raise TypeError(f"raft {what}: expected a tensor for {name}, got {type(t).__name__}")
+    if t.ndim != 4 or t.numel() == 0 or (channels is not None and t.shape[1] != channels):
+        want = "(N, C, h, w)" if channels is None else f"(N, {channels}, h, w)"
+        raise ValueError(f"raft {what}: {name} is a non-empty {want} tensor, got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"raft {what}: {name} is float32, not {t.dtype}")
+    return tuple(int(s) for s in t.shape)
+
+
+def _levels(levels, h, w, what):
+    levels = int(levels)
+    if not 1 <= levels <= RAFT_MAX_LEVELS:
+        raise ValueError(f"raft {what}: levels must be 1 to {RAFT_MAX_LEVELS}, got {levels}")
+    if (h >> (levels - 1)) < 1 or (w >> (levels - 1)) < 1:
+        raise ValueError(f"raft {what}: a ({h}, {w}) map is too small for {levels} levels (the last one would be empty)")
+    return levels
+
+
+class CorrPyramid:
+    """The workspace `corr_pyramid` filled: `buffer` (uint8) holds level after level, channel-last. `level(l)` is a float32
+    view [N, h_l, w_l, C] of one of them."""
+
+    def __init__(self, buffer, N, C, h, w, levels):
+        self.buffer, self.N, self.C, self.h, self.w, self.levels = buffer, N, C, h, w, levels
+
+    def level(self, l):  # noqa: E741
+        if not 0 <= l < self.levels:
+            raise IndexError(f"raft CorrPyramid: level {l} of {self.levels}")
+        off = nbytes(_lib.get(), "raft_level_offset", self.N, self.C, self.h, self.w, l)
+        base = (-self.buffer.data_ptr()) % 256  # the library rounds the pointer up to 256 bytes
+        hl, wl = self.h >> l, self.w >> l
+        n = self.N * hl * wl * self.C
+        return self.buffer[base + off: base + off + 4 * n].view(torch.float32).view(self.N, hl, wl, self.C)
+
+
+def corr_pyramid(fmap, levels=4, out=None):
+    """The feature pyramid of `fmap` [N, C, h, w] (NCHW, as a convolution leaves it): level l is avg_pool2d(., 2, 2) applied
+    l times (floor sizes), every level channel-last. levels=1 is the channel-last copy `corr_lookup` wants of the first
+    map. `out`: a CorrPyramid of the same shape to fill again instead of a new one."""
+    what = "corr_pyramid"
+    N, C, h, w = _map(fmap, "the feature map", what)
+    if C % 4:
+        raise ValueError(f"raft {what}: C must be a multiple of 4, got {C}")
+    levels = _levels(levels, h, w, what)
+    _on_device(fmap, what)
+    x = fmap.detach()
+    x = x if x.is_contiguous() else x.contiguous()
+    size = nbytes(_lib.get(), "raft_bytes", N, C, h, w, levels)
+    if out is None:
+        out = CorrPyramid(Workspaces.bytes(x.device, size), N, C, h, w, levels)
+    elif (out.N, out.C, out.h, out.w, out.levels) != (N, C, h, w, levels) or out.buffer.device != x.device:
+        raise ValueError(f"raft {what}: `out` was made for another shape or device")
+    call("eogs_raft_pyramid", x.device, N, C, h, w, levels, x.data_ptr(), out.buffer.data_ptr(), out.buffer.numel())
+    return out
+
+
+def corr_lookup(fmap1_cl, pyramid, coords, radius, no_stage=False):
+    """Correlation features [N, levels (2r+1)^2, h, w] of `coords` [N, 2, h, w] (plane 0 x, plane 1 y, level-0 pixels):
+    for each level the (2r+1)^2 bilinear samples, x offset slow, of <fmap1(p), fmap2_l(.)> / sqrt(C) around coords / 2^l,
+    zero outside the level (include/eogs_resample.h has the statement). `fmap1_cl`: corr_pyramid(fmap1, 1); `pyramid`:
+    corr_pyramid(fmap2, levels). A pixel whose coordinate is NaN or infinite gets zeros. `no_stage` forces the path that
+    gathers straight from the pyramid: the same bits."""
+    what = "corr_lookup"
+    if not isinstance(fmap1_cl, CorrPyramid) or not isinstance(pyramid, CorrPyramid):
+        raise TypeError(f"raft {what}: fmap1_cl and pyramid are what corr_pyramid returns")
+    N, C, h, w = pyramid.N, pyramid.C, pyramid.h, pyramid.w
+    if (fmap1_cl.N, fmap1_cl.C, fmap1_cl.h, fmap1_cl.w) != (N, C, h, w):
+        raise ValueError(f"raft {what}: the two maps differ in shape, {(fmap1_cl.N, fmap1_cl.C, fmap1_cl.h, fmap1_cl.w)} and {(N, C, h, w)}")
+    radius = int(radius)
+    if not 1 <= radius <= RAFT_MAX_RADIUS:
+        raise ValueError(f"raft {what}: radius must be 1 to {RAFT_MAX_RADIUS}, got {radius}")
+    if _map(coords, "coords", what, 2) != (N, 2, h, w):
+        raise ValueError(f"raft {what}: coords is {tuple(coords.shape)}, the maps ask for {(N, 2, h, w)}")
+    _on_device(coords, what)
+    dev = coords.device
+    if fmap1_cl.buffer.device != dev or pyramid.buffer.device != dev:
+        raise RuntimeError(f"raft {what}: the maps and coords live on different devices")
+    c = coords.detach()
+    c = c if c.is_contiguous() else c.contiguous()
+    K = 2 * radius + 1
+    out = torch.empty((N, pyramid.levels * K * K, h, w), dtype=torch.float32, device=dev)
+    call("eogs_raft_lookup", dev, N, C, h, w, pyramid.levels, radius, fmap1_cl.buffer.data_ptr(), pyramid.buffer.data_ptr(),
+         c.data_ptr(), out.data_ptr(), RAFT_NO_STAGE if no_stage else 0)
+    return out
+
+
+def upsample_flow(flow, mask=None):
+    """`flow` [N, 2, h, w] at 1/8 resolution to [N, 2, 8h, 8w]. With `mask` [N, 576, h, w]: RAFT's learned convex
+    upsampling (a softmax over 9 mask channels per output pixel weighs 8 flow over the zero-padded 3 x 3 neighbourhood);
+    without: 8 * interpolate(flow, scale_factor=8, mode="bilinear", align_corners=True)."""
+    what = "upsample_flow"
+    N, _, h, w = _map(flow, "the flow", what, 2)
+    if mask is not None and _map(mask, "the mask", what, RAFT_MASK_CHANNELS) != (N, RAFT_MASK_CHANNELS, h, w):
+        raise ValueError(f"raft {what}: the mask is {tuple(mask.shape)}, the flow asks for {(N, RAFT_MASK_CHANNELS, h, w)}")
+    if h > 8192 or w > 8192:
+        raise ValueError(f"raft {what}: h and w at most 8192, got {(h, w)}")
+    _on_device(flow, what)
+    dev = flow.device
+    f = flow.detach()
+    f = f if f.is_contiguous() else f.contiguous()
+    m = None
+    if mask is not None:
+        _on_device(mask, what)
+        if mask.device != dev:
+            raise RuntimeError(f"raft {what}: flow and mask live on different devices")
+        m = mask.detach()
+        m = m if m.is_contiguous() else m.contiguous()
+    out = torch.empty((N, 2, 8 * h, 8 * w), dtype=torch.float32, device=dev)
+    call("eogs_raft_upsample", dev, N, h, w, RAFT_UP_BILINEAR if m is None else RAFT_UP_CONVEX, f.data_ptr(),
+         None if m is None else m.data_ptr(), out.data_ptr())
+    return out
+
+
+def stage_info():
+    """(tile width, tile height, staged positions) of the lookup kernel: a workgroup stages its windows' bounding box into
+    LDS when the box holds at most that many positions of the level."""
+    a, b, c = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    abi = _lib.get()
+    abi.check(abi.raft_stage_info(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+    return a.value, b.value, c.value
+
+
+# ---- the materialised form, in plain torch: any dtype, any device ----
+
+def volume_pyramid(fmap1, fmap2, levels):
+    """[N h w, 1, h_l, w_l] for l < levels: the all-pairs correlation / sqrt(C), average-pooled over the second map."""
+    N, C, h, w = fmap1.shape
+    corr = torch.matmul(fmap1.reshape(N, C, h * w).transpose(1, 2), fmap2.reshape(N, C, h * w)) / math.sqrt(C)
+    corr = corr.reshape(N * h * w, 1, h, w)
+    pyramid = [corr]
+    for _ in range(levels - 1):
+        corr = F.avg_pool2d(corr, kernel_size=2, stride=2)
+        pyramid.append(corr)
+    return pyramid
+
+
+def volume_lookup(pyramid, coords, radius):
+    """torchvision's CorrBlock.index_pyramid: grid_sample(bilinear, align_corners=True, zeros) of each level at
+    coords / 2^l + (d_i, d_j), the offsets from meshgrid(d, d, indexing="ij") stacked onto (x, y): i offsets x."""
+    N, _, h, w = coords.shape
+    K = 2 * radius + 1
+    d = torch.linspace(-radius, radius, K, dtype=coords.dtype, device=coords.device)
+    delta = torch.stack(torch.meshgrid(d, d, indexing="ij"), dim=-1).view(1, K, K, 2)
+    c = coords.permute(0, 2, 3, 1).reshape(N * h * w, 1, 1, 2)
+    out = []
+    for corr in pyramid:
+        hl, wl = corr.shape[-2:]
+        s = c + delta
+        if hl < 2 or wl < 2:
+            raise ValueError(f"raft volume_lookup: a level of {(hl, wl)} has no extent to normalise grid_sample's coordinates by")
+        grid = torch.stack([2 * s[..., 0] / (wl - 1) - 1, 2 * s[..., 1] / (hl - 1) - 1], dim=-1)
+        out.append(F.grid_sample(corr, grid, mode="bilinear", padding_mode="zeros", align_corners=True).view(N, h, w, K * K))
+        c = c / 2
+    return torch.cat(out, dim=-1).permute(0, 3, 1, 2).contiguous()
+
+
+def convex_upsample_torch(flow, mask):
+    """The unfold / softmax / permute statement of the convex upsampling, any dtype."""
+    N, _, h, w = flow.shape
+    m = torch.softmax(mask.view(N, 1, 9, 8, 8, h, w), dim=2)
+    u = F.unfold(8 * flow, kernel_size=3, padding=1).view(N, 2, 9, 1, 1, h, w)
+    return torch.sum(m * u, dim=2).permute(0, 1, 4, 2, 5, 3).reshape(N, 2, 8 * h, 8 * w)
+
+
+def _upsample_torch(flow, mask):
+    if mask is not None:
+        return convex_upsample_torch(flow, mask)
+    return 8 * F.interpolate(flow, size=(8 * flow.shape[2], 8 * flow.shape[3]), mode="bilinear", align_corners=True)
+
+
+# ---- the network: torchvision.models.optical_flow.raft, name for name ----
+
+def _cna(cin, cout, norm, kernel_size, stride=1, act=True):
+    """torchvision's Conv2dNormActivation: Sequential(conv [0], norm [1] if any, ReLU), padding (k - 1) // 2, bias=True."""
+    layers = [nn.Conv2d(cin, cout, kernel_size, stride=stride, padding=(kernel_size - 1) // 2, bias=True)]
+    if norm is not None:
+        layers.append(norm(cout))
+    if act:
+        layers.append(nn.ReLU(inplace=True))
+    return nn.Sequential(*layers)
+
+
+class ResidualBlock(nn.Module):
+    def __init__(self, cin, cout, norm, stride=1):
+        super().__init__()
+        self.convnormrelu1 = _cna(cin, cout, norm, 3, stride)
+        self.convnormrelu2 = _cna(cout, cout, norm, 3)
+        self.downsample = nn.Identity() if stride == 1 else _cna(cin, cout, norm, 1, stride, act=False)
+        self.relu = nn.ReLU(inplace=True)
+
+    def forward(self, x):
+        y = self.convnormrelu2(self.convnormrelu1(x))
+        return self.relu(self.downsample(x) + y)
+
+
+class BottleneckBlock(nn.Module):
+    def __init__(self, cin, cout, norm, stride=1):
+        super().__init__()
+        self.convnormrelu1 = _cna(cin, cout // 4, norm, 1)
+        self.convnormrelu2 = _cna(cout // 4, cout // 4, norm, 3, stride)
+        self.convnormrelu3 = _cna(cout // 4, cout, norm, 1)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = nn.Identity() if stride == 1 else _cna(cin, cout, norm, 1, stride, act=False)
+
+    def forward(self, x):
+        y = self.convnormrelu3(self.convnormrelu2(self.convnormrelu1(x)))
+        return self.relu(self.downsample(x) + y)
+
+
+class FeatureEncoder(nn.Module):
+    def __init__(self, block, layers, norm):
+        super().__init__()
+        self.convnormrelu = _cna(3, layers[0], norm, 7, 2)
+        self.layer1 = nn.Sequential(block(layers[0], layers[1], norm, 1), block(layers[1], layers[1], norm, 1))
+        self.layer2 = nn.Sequential(block(layers[1], layers[2], norm, 2), block(layers[2], layers[2], norm, 1))
+        self.layer3 = nn.Sequential(block(layers[2], layers[3], norm, 2), block(layers[3], layers[3], norm, 1))
+        self.conv = nn.Conv2d(layers[3], layers[4], kernel_size=1)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, (nn.BatchNorm2d, nn.InstanceNorm2d)) and m.weight is not None:
+                nn.init.constant_(m.weight, 1)
+                nn.init.constant_(m.bias, 0)
+
+    def forward(self, x):
+        return self.conv(self.layer3(self.layer2(self.layer1(self.convnormrelu(x)))))
+
+
+class MotionEncoder(nn.Module):
+    def __init__(self, in_channels_corr, corr_layers, flow_layers, out_channels):
+        super().__init__()
+        self.convcorr1 = _cna(in_channels_corr, corr_layers[0], None, 1)
+        self.convcorr2 = _cna(corr_layers[0], corr_layers[1], None, 3) if len(corr_layers) == 2 else nn.Identity()
+        self.convflow1 = _cna(2, flow_layers[0], None, 7)
+        self.convflow2 = _cna(flow_layers[0], flow_layers[1], None, 3)
+        self.conv = _cna(corr_layers[-1] + flow_layers[-1], out_channels - 2, None, 3)  # (the flow's 2 planes are appended)
+        self.out_channels = out_channels
+
+    def forward(self, flow, corr_features):
+        corr = self.convcorr2(self.convcorr1(corr_features))
+        f = self.convflow2(self.convflow1(flow))
+        return torch.cat([self.conv(torch.cat([corr, f], dim=1)), flow], dim=1)
+
+
+class ConvGRU(nn.Module):
+    def __init__(self, input_size, hidden_size, kernel_size, padding):
+        super().__init__()
+        self.convz = nn.Conv2d(hidden_size + input_size, hidden_size, kernel_size=kernel_size, padding=padding)
+        self.convr = nn.Conv2d(hidden_size + input_size, hidden_size, kernel_size=kernel_size, padding=padding)
+        self.convq = nn.Conv2d(hidden_size + input_size, hidden_size, kernel_size=kernel_size, padding=padding)
+
+    def forward(self, h, x):
+        hx = torch.cat([h, x], dim=1)
+        z = torch.sigmoid(self.convz(hx))
+        r = torch.sigmoid(self.convr(hx))
+        q = torch.tanh(self.convq(torch.cat([r * h, x], dim=1)))
+        return (1 - z) * h + z * q
+
+
+class RecurrentBlock(nn.Module):
+    def __init__(self, input_size, hidden_size, kernel_size, padding):
+        super().__init__()
+        self.convgru1 = ConvGRU(input_size, hidden_size, kernel_size[0], padding[0])
+        self.convgru2 = ConvGRU(input_size, hidden_size, kernel_size[1], padding[1]) if len(kernel_size) == 2 else nn.Identity()
+        self.hidden_size = hidden_size
+
+    def forward(self, h, x):
+        h = self.convgru1(h, x)
+        if isinstance(self.convgru2, ConvGRU):
+            h = self.convgru2(h, x)
+        return h
+
+
+class FlowHead(nn.Module):
+    def __init__(self, in_channels, hidden_size):
+        super().__init__()
+        self.conv1 = nn.Conv2d(in_channels, hidden_size, 3, padding=1)
+        self.conv2 = nn.Conv2d(hidden_size, 2, 3, padding=1)
+        self.relu = nn.ReLU(inplace=True)
+
+    def forward(self, x):
+        return self.conv2(self.relu(self.conv1(x)))
+
+
+class UpdateBlock(nn.Module):
+    def __init__(self, motion_encoder, recurrent_block, flow_head):
+        super().__init__()
+        self.motion_encoder, self.recurrent_block, self.flow_head = motion_encoder, recurrent_block, flow_head
+        self.hidden_state_size = recurrent_block.hidden_size
+
+    def forward(self, hidden_state, context, corr_features, flow):
+        x = torch.cat([context, self.motion_encoder(flow, corr_features)], dim=1)
+        hidden_state = self.recurrent_block(hidden_state, x)
+        return hidden_state, self.flow_head(hidden_state)
+
+
+class MaskPredictor(nn.Module):
+    def __init__(self, in_channels, hidden_size, multiplier=0.25):
+        super().__init__()
+        self.convrelu = _cna(in_channels, hidden_size, None, 3)
+        self.conv = nn.Conv2d(hidden_size, RAFT_MASK_CHANNELS, 1, padding=0)
+        self.multiplier = multiplier  # (RAFT's 0.25: it balances the gradients of the mask head)
+
+    def forward(self, x):
+        return self.multiplier * self.conv(self.convrelu(x))
+
+
+# The two published configurations (torchvision's raft_small / raft_large builders).
+CONFIGS = {
+    "small": dict(block=BottleneckBlock, feature_layers=(32, 32, 64, 96, 128), feature_norm=nn.InstanceNorm2d,
+                  context_layers=(32, 32, 64, 96, 160), context_norm=None, corr_levels=4, corr_radius=3,
+                  motion_corr_layers=(96,), motion_flow_layers=(64, 32), motion_out=82, hidden=96, gru_kernels=(3,),
+                  gru_paddings=(1,), flow_head_hidden=128, mask_hidden=None),
+    "large": dict(block=ResidualBlock, feature_layers=(64, 64, 96, 128, 256), feature_norm=nn.InstanceNorm2d,
+                  context_layers=(64, 64, 96, 128, 256), context_norm=nn.BatchNorm2d, corr_levels=4, corr_radius=4,
+                  motion_corr_layers=(256, 192), motion_flow_layers=(128, 64), motion_out=128, hidden=128,
+                  gru_kernels=((1, 5), (5, 1)), gru_paddings=((0, 2), (2, 0)), flow_head_hidden=256, mask_hidden=256),
+}
+
+# THE table of parameter names: this module's top-level blocks -> the prefixes of a torchvision RAFT state dict. Below a
+# prefix the names are the module tree's (convnormrelu1.0.weight, layer2.1.downsample.0.bias, recurrent_block.convgru1.convz
+# .weight, ...), which mirrors torchvision's. Not verified against a torchvision checkpoint; load_weights is strict.
+TORCHVISION_NAMES = {
+    "feature_encoder": "feature_encoder",
+    "context_encoder": "context_encoder",
+    "update_block": "update_block",
+    "mask_predictor": "mask_predictor",
+}
+
+
+class RAFT(nn.Module):
+    """RAFT with torchvision's call shape: `model(image1, image2, num_flow_updates=12) -> list of flows`, images [N, 3, H, W]
+    in [-1, 1], H and W multiples of 8 and at least 128. The last entry is the final [N, 2, H, W] flow; with
+    return_all=False (the default: flow_matching.py reads [-1] alone) it is the only one.
+
+    corr: "ondemand" (the HIP lookup; float32 on the GPU), "volume" (plain torch, any dtype and device) or "auto": on-demand
+    for float32 inputs on the GPU, volume otherwise."""
+
+    def __init__(self, name="small", corr="auto"):
+        super().__init__()
+        if name not in CONFIGS:
+            raise ValueError(f"raft RAFT: name is 'small' or 'large', got {name!r}")
+        if corr not in ("auto", "ondemand", "volume"):
+            raise ValueError(f"raft RAFT: corr is 'auto', 'ondemand' or 'volume', got {corr!r}")
+        cfg = CONFIGS[name]
+        self.name, self.corr = name, corr
+        self.corr_levels, self.corr_radius = cfg["corr_levels"], cfg["corr_radius"]
+        self.feature_encoder = FeatureEncoder(cfg["block"], cfg["feature_layers"], cfg["feature_norm"])
+        self.context_encoder = FeatureEncoder(cfg["block"], cfg["context_layers"], cfg["context_norm"])
+        hidden = cfg["hidden"]
+        self.context_size = cfg["context_layers"][-1] - hidden
+        motion = MotionEncoder(self.corr_levels * (2 * self.corr_radius + 1) ** 2, cfg["motion_corr_layers"],
+                               cfg["motion_flow_layers"], cfg["motion_out"])
+        recurrent = RecurrentBlock(motion.out_channels + self.context_size, hidden, cfg["gru_kernels"], cfg["gru_paddings"])
+        self.update_block = UpdateBlock(motion, recurrent, FlowHead(hidden, cfg["flow_head_hidden"]))
+        self.mask_predictor = None if cfg["mask_hidden"] is None else MaskPredictor(hidden, cfg["mask_hidden"])
+
+    def _ondemand(self, x):
+        if self.corr == "volume":
+            return False
+        ok = x.device.type == "cuda" and x.dtype == torch.float32
+        if self.corr == "ondemand" and not ok:
+            raise RuntimeError(f"raft RAFT: corr='ondemand' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
+                               "there is no CPU fallback, corr='volume' is the plain torch form")
+        return ok
+
+    def forward(self, image1, image2, num_flow_updates=12, return_all=False):
+        N, _, H, W = image1.shape
+        if image1.shape != image2.shape:
+            raise ValueError("input images should have the same shape, instead got "
+                             f"({H}, {W}) != ({image2.shape[-2]}, {image2.shape[-1]})")
+        if H % 8 or W % 8:
+            raise ValueError(f"input image H and W should be divisible by 8, instead got {H} (h) and {W} (w)")
+        h, w = H // 8, W // 8
+        if h < 16 or w < 16:
+            raise ValueError(f"input image H and W should be at least 128, instead got {H} (h) and {W} (w): the feature "
+                             "encoder downsamples by 8 and the correlation pyramid by another 8")
+        ondemand = self._ondemand(image1)
+        fmaps = self.feature_encoder(torch.cat([image1, image2], dim=0))
+        fmap1, fmap2 = torch.chunk(fmaps, chunks=2, dim=0)
+        if ondemand:
+            f1cl = corr_pyramid(fmap1, 1)
+            pyramid = corr_pyramid(fmap2, self.corr_levels)
+        else:
+            pyramid = volume_pyramid(fmap1, fmap2, self.corr_levels)
+        context_out = self.context_encoder(image1)
+        hidden_state, context = torch.split(context_out, [self.update_block.hidden_state_size, self.context_size], dim=1)
+        hidden_state, context = torch.tanh(hidden_state), F.relu(context)
+        ys, xs = torch.meshgrid(torch.arange(h, dtype=image1.dtype, device=image1.device),
+                                torch.arange(w, dtype=image1.dtype, device=image1.device), indexing="ij")
+        coords0 = torch.stack([xs, ys], dim=0)[None].repeat(N, 1, 1, 1)
+        coords1 = coords0.clone()
+        flows = []
+        for it in range(num_flow_updates):
+            coords1 = coords1.detach()
+            if ondemand:
+                corr_features = corr_lookup(f1cl, pyramid, coords1, self.corr_radius)
+            else:
+                corr_features = volume_lookup(pyramid, coords1, self.corr_radius)
+            hidden_state, delta = self.update_block(hidden_state, context, corr_features, coords1 - coords0)
+            coords1 = coords1 + delta
+            if return_all or it == num_flow_updates - 1:
+                mask = None if self.mask_predictor is None else self.mask_predictor(hidden_state)
+                flow = coords1 - coords0
+                flows.append(upsample_flow(flow, mask) if ondemand else _upsample_torch(flow, mask))
+        return flows
+
+    def torchvision_state_dict(self):
+        """This module's state dict under torchvision's names (TORCHVISION_NAMES)."""
+        return {_rename(k, TORCHVISION_NAMES): v for k, v in self.state_dict().items()}
+
+    def load_weights(self, path_or_state_dict):
+        """Loads a torchvision RAFT checkpoint (raft_small / raft_large weights: a path for torch.load, or the state dict),
+        strict: a missing or an unexpected name raises. Returns self, in eval mode. Nothing is downloaded."""
+        sd = path_or_state_dict
+        if not isinstance(sd, dict):
+            sd = torch.load(sd, map_location="cpu", weights_only=True)
+        back = {v: k for k, v in TORCHVISION_NAMES.items()}
+        self.load_state_dict({_rename(k, back): v for k, v in sd.items()}, strict=True)
+        return self.eval()
+
+
+def _rename(key, table):
+    head, _, tail = key.partition(".")
+    return f"{table.get(head, head)}.{tail}" if tail else table.get(head, head)
+
+
+def raft_small(corr="auto"):
+    """RAFT-small: bottleneck encoders (128 feature channels), 4 levels at radius 3, one 3 x 3 GRU, bilinear upsampling."""
+    return RAFT("small", corr)
+
+
+def raft_large(corr="auto"):
+    """RAFT-large: residual encoders (256 feature channels), 4 levels at radius 4, 1 x 5 + 5 x 1 GRUs, convex upsampling."""
+    return RAFT("large", corr)
+
+
+__all__ = ["CONFIGS", "CorrPyramid", "RAFT", "TORCHVISION_NAMES", "convex_upsample_torch", "corr_lookup", "corr_pyramid", "raft_large",
+           "raft_small", "stage_info", "upsample_flow", "volume_lookup", "volume_pyramid"]

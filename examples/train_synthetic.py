@@ -227,6 +227,16 @@ def main(argv=None):
                          "the photometric loss (eogs2_amd.flow.perform_flow_matching, on_device=True, perform_cst_displacement=True: the "
                          "max_value_flow decision stays on the device, so --graph records it). The flow network is a stand-in that "
                          "answers that displacement as a field: RAFT, which the reference loads from torchvision, is the caller's")
+    ap.add_argument("--flow-network", choices=["small", "large"], default=None, metavar="NAME",
+                    help="with --flow-matching: eogs2_amd.raft.raft_small() or raft_large() (RAFT with the on-demand correlation "
+                         "lookup of include/eogs_resample.h) takes the stand-in's place behind the same performOpticalmatching, 12 updates "
+                         "per iteration. Without --flow-weights the network's weights are random: that demonstrates the plumbing "
+                         "only, the max_value_flow criterion will reject the random flows and the image passes unwarped. Needs "
+                         "--size of at least 121 (the network sees the size rounded up to a multiple of 8, at least 128); not "
+                         "with --graph")
+    ap.add_argument("--flow-weights", default=None, metavar="PATH",
+                    help="with --flow-network: a torchvision RAFT checkpoint of that configuration (raft_small / raft_large state "
+                         "dict), loaded strictly by eogs2_amd.raft.RAFT.load_weights; nothing is downloaded")
     ap.add_argument("--opacity-loss", type=float, default=0.0, metavar="W",
                     help="adds W x OpacityLoss (loss/opacity.py:14-17: the sum of the opacities over the initial number of Gaussians) "
                          "through eogs2_amd.regularizers.gaussian_regularizers; the reference's shipped configuration runs it on "
@@ -387,6 +397,13 @@ def main(argv=None):
         ap.error("--dsm-resolution needs --dsm-mae-every")
     if a.pan_first and not a.pan_map:
         ap.error("--pan-first needs --pan-map")
+    if (a.flow_network or a.flow_weights) and not a.flow_matching:
+        ap.error("--flow-network and --flow-weights belong to --flow-matching")
+    if a.flow_weights and not a.flow_network:
+        ap.error("--flow-weights needs --flow-network small|large")
+    if a.flow_network and (a.size < 121 or a.graph):
+        ap.error("--flow-network: RAFT needs images of at least 128 px after rounding up to a multiple of 8 (--size >= 121), and is "
+                 "not recorded into a graph here (not with --graph)")
     if a.pan_map and a.flow_matching:
         ap.error("--flow-matching runs on the three-plane pipeline here: not with --pan-map")
     if a.load_ply:  # the scene, the noise and the statistics are sized by --gaussians: the file must hold as many rows
@@ -543,8 +560,15 @@ def main(argv=None):
             gt = apply_flow(gt, shift).clone()  # gt(x) <- gt(x + shift): what a flow of `shift` applied to the render undoes
         hp, wp = -(-H // 8) * 8, -(-W // 8) * 8  # the size the network is called with (mode "upscale")
         field = torch.tensor(FLOW_SHIFT, device=dev).view(1, 2, 1, 1).repeat(1, 1, hp, wp)
-        warper = performOpticalmatching(True, mode="upscale", device=dev, model_name="small", criteria="max_value_flow",
-                                        model=lambda gt_n, img_n, num_flow_updates=12: [field])
+        flow_model = lambda gt_n, img_n, num_flow_updates=12: [field]  # noqa: E731  (the stand-in)
+        if a.flow_network:
+            from eogs2_amd import raft
+
+            flow_model = raft.RAFT(a.flow_network).eval().to(dev)
+            if a.flow_weights:
+                flow_model.load_weights(a.flow_weights)
+        warper = performOpticalmatching(True, mode="upscale", device=dev, model_name=a.flow_network or "small", criteria="max_value_flow",
+                                        model=flow_model)
         flow_opt = types.SimpleNamespace(flowmatching=types.SimpleNamespace(max_value_flow=3.0))
     cc_cam = colour_camera(0.15)
     camera_parameters = [*cc_cam.color_correction.parameters(), cc_cam.inshadow_color_correction, *getattr(cc_cam, "map_parameters", ())]

@@ -79,6 +79,75 @@ int eogs_resample_flow_stats_bytes(int H, int W, size_t* bytes);
 int eogs_resample_flow_stats(int H, int W, const float* flow, int64_t plane_stride, int64_t row_stride, int64_t col_stride,
                              float* stats, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- The flow network of the flow-matching step (RAFT; the reference takes it from torchvision, flowmatching/
+ * flow_matching.py:76-86): the three operators it needs beside convolutions — the correlation between the two feature maps
+ * looked up ON DEMAND, and the two ways RAFT brings its 1/8-resolution flow to the image's size. They live in this header,
+ * beside the warp and the statistics of the same step.
+ *
+ * RAFT as published materialises the all-pairs correlation volume (n x n floats for n = h w feature positions, plus three
+ * pooled levels) and reads it through grid_sample at every update. Here nothing quadratic is built: average-pooling the
+ * correlation over the second image's positions equals correlating with the pooled features, and all (2r+1)^2 taps of a
+ * pixel at a level share one fractional offset, so a lookup is (2r+2)^2 dot products per pixel and level against a small
+ * feature pyramid, then one 2 x 2 blend per tap. Memory is linear in n. Everything is float32 and forward only. The library
+ * never allocates and never waits for the device, arguments are checked before anything touches a device. No atomics and a
+ * fixed order of every sum: results are bitwise reproducible. Device pointers must be 16-byte aligned. ---- */
+
+#define EOGS_RAFT_MAX_LEVELS 4
+#define EOGS_RAFT_MAX_RADIUS 4
+
+/* eogs_raft_lookup flags: NO_STAGE forces the path that gathers straight from the pyramid (same bits, for tests and probes) */
+#define EOGS_RAFT_NO_STAGE 1u
+
+/* eogs_raft_upsample modes */
+#define EOGS_RAFT_UP_CONVEX 0
+#define EOGS_RAFT_UP_BILINEAR 1
+#define EOGS_RAFT_MASK_CHANNELS 576
+
+/* The feature pyramid of a map f32[N][C][h][w]: level l is avg_pool2d(., 2, 2) applied l times, h_l = h >> l, w_l = w >> l (a
+ * trailing odd row or column is dropped), every level CHANNEL-LAST f32[N][h_l][w_l][C], level after level in one workspace,
+ * each level's start rounded up to 256 bytes. Level 0 is the map itself, so levels = 1 is the channel-last copy the lookup
+ * wants of the first map. eogs_raft_bytes gives the workspace's size; eogs_raft_level_offset the byte offset of a level.
+ * Each level is pooled from the one above as ((a + b) + (c + d)) * 0.25 over (2y, 2x), (2y, 2x+1), (2y+1, 2x), (2y+1, 2x+1).
+ *
+ * Refused: N, C, h or w below 1; C not a multiple of 4; levels outside [1, 4]; a level that would be empty (h >> (levels - 1)
+ * or w >> (levels - 1) is 0); N above 65535; more than 2^31 - 1 elements in a map; a workspace too small; NULL. */
+int eogs_raft_bytes(int N, int C, int h, int w, int levels, size_t* bytes);
+int eogs_raft_level_offset(int N, int C, int h, int w, int level, size_t* offset);
+int eogs_raft_pyramid(int N, int C, int h, int w, int levels, const float* fmap, void* pyramid, size_t pyramid_bytes,
+                      void* stream);
+
+/* The correlation lookup. fmap1_cl: eogs_raft_pyramid(levels = 1) of the first map; pyramid: eogs_raft_pyramid(levels) of the
+ * second; coords f32[N][2][h][w], plane 0 x and plane 1 y, in pixels of level 0; out f32[N][levels K^2][h][w], K = 2 radius + 1,
+ * fully overwritten. For pixel p and level l, per axis
+ *
+ *   s = coords * 2^-l,  f = floor(s),  w = s - f
+ *   D[a][b] = <fmap1(p), fmap2_l(f_x - r + a, f_y - r + b)> / sqrt(C)   for a, b in [0, 2r + 1]; exactly 0 where the position
+ *                                                                        lies outside [0, w_l) x [0, h_l)
+ *   out[l K^2 + a K + b] = (1-w_x)(1-w_y) D[a][b] + w_x (1-w_y) D[a+1][b] + (1-w_x) w_y D[a][b+1] + w_x w_y D[a+1][b+1]
+ *
+ * The x offset a is the slow index. A coordinate whose floor is not within [-(r + 2), n_l + r + 1] (NaN, +-inf, +-1e30 among
+ * them) has every tap outside and weight 0: its outputs at that level are exactly 0. The dot product runs over the channels
+ * in ascending order, one fused multiply-add per channel, on both paths: a workgroup stages the bounding box of its tile's
+ * windows into LDS when it fits (eogs_raft_stage_info) and gathers from the pyramid otherwise, bit for bit the same.
+ *
+ * Refused: what eogs_raft_bytes refuses; radius outside [1, 4]; unknown flags; NULL; a pointer not 16-byte aligned. */
+int eogs_raft_lookup(int N, int C, int h, int w, int levels, int radius, const float* fmap1_cl, const void* pyramid,
+                     const float* coords, float* out, unsigned flags, void* stream);
+
+/* The lookup's tiling, for tests and probes: a workgroup owns tile_w x tile_h pixels at one level and stages its windows'
+ * bounding box when that holds at most max_positions positions of the level. */
+int eogs_raft_stage_info(int* tile_w, int* tile_h, int* max_positions);
+
+/* Flow f32[N][2][h][w] at 1/8 resolution to out f32[N][2][8h][8w].
+ *   EOGS_RAFT_UP_CONVEX    mask f32[N][576][h][w]: for output (8y + i, 8x + j) a softmax over the 9 mask channels
+ *                          k 64 + i 8 + j of pixel (y, x) weighs 8 flow over the zero-padded 3 x 3 neighbourhood
+ *                          (y + k / 3 - 1, x + k % 3 - 1)
+ *   EOGS_RAFT_UP_BILINEAR  8 * interpolate(flow, scale_factor = 8, bilinear, align_corners = True); mask must be NULL. The
+ *                          source position Y (h - 1) / (8h - 1) is split into integer and fraction in integer arithmetic.
+ * Refused: N, h or w below 1; h or w above 8192; N above 65535; an unknown mode; a mask that does not fit the mode; NULL; a
+ * pointer not 16-byte aligned. */
+int eogs_raft_upsample(int N, int h, int w, int mode, const float* flow, const float* mask, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
