@@ -25,6 +25,13 @@ int check_launch(hipStream_t s, bool debug, const char* what);
     if (rc_ != EOGS_OK) return rc_;           \
   } while (0)
 
+// the grid of a grid-stride launch: one thread per item (an element, or a unit of four where the kernel counts in those),
+// at least one workgroup and at most `cap`
+inline int capped_blocks(int64_t items, int threads, int cap) {
+  const int64_t b = (items + threads - 1) / threads;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
 // ---- optional per-kernel-group timing with hipEvents on the launch stream ----
 // (the order is the ABI of eogs_rast_profile_get: slots are read by index; their names are api.hip's kSlotNames)
 enum { PS_PREPROCESS, PS_DEPTH_SORT, PS_BINNING, PS_RENDER_FWD, PS_RENDER_BWD, PS_GAUSS_BWD, PS_LOSS_FWD, PS_LOSS_BWD, PS_ADAM,

@@ -201,7 +201,6 @@ constexpr int ST_MAX_GRID = 256;
 constexpr int ST_N = 5;  // sum x', sum y', sum |x| + |y|, sum x'^2, sum y'^2
 
 __global__ __launch_bounds__(BLK) void flow_stats_partial_kernel(int H, int W, const FlowField fl, double* __restrict__ part) {
-  __shared__ double s_red[BLK / 64][ST_N];
   const float2 piv = fl.at(0, 0);
   const int HW = H * W;
   double a[ST_N] = {0., 0., 0., 0., 0.};
@@ -211,18 +210,7 @@ __global__ __launch_bounds__(BLK) void flow_stats_partial_kernel(int H, int W, c
     const double ux = (double)f.x - (double)piv.x, uy = (double)f.y - (double)piv.y;
     a[0] += ux; a[1] += uy; a[2] += (double)fabsf(f.x) + (double)fabsf(f.y); a[3] += ux * ux; a[4] += uy * uy;
   }
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < ST_N; k++) {
-    a[k] = wave_sum(a[k]);
-    if (lane == 0) s_red[wv][k] = a[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < ST_N) {
-    double v = s_red[0][threadIdx.x];
-    for (int w = 1; w < BLK / 64; w++) v += s_red[w][threadIdx.x];
-    part[(size_t)blockIdx.x * ST_N + threadIdx.x] = v;
-  }
+  wg_partials<BLK>(a, part + (size_t)blockIdx.x * ST_N);
 }
 
 __global__ __launch_bounds__(64) void flow_stats_final_kernel(int H, int W, const FlowField fl, const double* __restrict__ part,
@@ -242,14 +230,9 @@ __global__ __launch_bounds__(64) void flow_stats_final_kernel(int H, int W, cons
   stats[4] = (float)sqrt(vy);
 }
 
-inline int stats_grid(int H, int W) {
-  const int64_t nb = ((int64_t)H * W + BLK - 1) / BLK;
-  return (int)(nb < ST_MAX_GRID ? nb : ST_MAX_GRID);
-}
-
 }  // namespace
 
-static size_t flow_stats_ws_bytes(int H, int W) { return (size_t)stats_grid(H, W) * ST_N * sizeof(double) + 256; }
+static size_t flow_stats_ws_bytes(int H, int W) { return (size_t)capped_blocks((int64_t)H * W, BLK, ST_MAX_GRID) * ST_N * sizeof(double) + 256; }
 
 // the field backward's workspace: one box per 16 x 16 output tile (a constant displacement needs none)
 static size_t flow_bwd_ws_bytes(int H, int W) {
@@ -344,7 +327,7 @@ int eogs_resample_flow_stats(int H, int W, const float* flow, int64_t plane_stri
   hipStream_t s = (hipStream_t)stream;
   const FlowField fl{flow, plane_stride, row_stride, col_stride};
   double* part = reinterpret_cast<double*>(ws_base(ws));
-  const int nb = stats_grid(H, W);
+  const int nb = capped_blocks((int64_t)H * W, BLK, ST_MAX_GRID);
   {
     ProfScope ps(PS_FLOW_STATS, s);
     hipLaunchKernelGGL(flow_stats_partial_kernel, dim3(nb), dim3(BLK), 0, s, H, W, fl, part);

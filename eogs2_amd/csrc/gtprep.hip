@@ -4,9 +4,9 @@
 //
 // One lane per output pixel in a grid-stride loop: the upsampling taps and weights are computed once per pixel and shared
 // by the channels, the small MSI image is read through the caches, PAN / synthesised image are read once and the result
-// (or the gradient) is written once with plain stores; the loss never stores the pansharpened image. Sums as in reg.hip:
-// float64 per lane, wave, workgroup, then one workgroup combines the partials in a fixed order — no float atomics, a grid
-// that depends on the shape alone, bitwise reproducible. The histogram counts with integer atomics (exact in any order).
+// (or the gradient) is written once with plain stores; the loss never stores the pansharpened image. Sums through
+// reduce.h's two stages in float64 — no float atomics, a grid that depends on the shape alone, bitwise reproducible. The
+// histogram counts with integer atomics (exact in any order).
 #include "api_util.h"
 #include "eogs_gtprep.h"
 #include "reduce.h"
@@ -18,11 +18,6 @@ constexpr int GMAXBLK = 1024;    // workgroups per reduction launch: one float64
 constexpr int GCBLK = 256;       // workgroups per channel of the min/max and histogram passes
 constexpr int MAXC = EOGS_GTPREP_MAX_CHANNELS;
 constexpr int M_TARGET = 3;      // "method" of the kernels below when the target is given (Lpan)
-
-inline int gt_blocks(int64_t n, int cap = GMAXBLK) {
-  const int64_t b = (n + GT - 1) / GT;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
 
 // ---- upsampling taps -------------------------------------------------------------------------------------------------
 // torch's area_pixel_compute_source_index, align_corners = False. One rounding: the reference's builds contract the product
@@ -131,7 +126,7 @@ __global__ __launch_bounds__(GT) void fuse_kernel(Shape s, const float* __restri
   const int64_t n = (int64_t)s.H * s.W;
   float coef = 0.f;
   if (MODE == MODE_GRAD) coef = (2.f / (float)((double)n * (double)s.C)) * (upstream ? upstream[0] : 1.f);
-  double acc = 0.;
+  double acc[1] = {0.};
   for (int64_t p = (int64_t)blockIdx.x * GT + threadIdx.x; p < n; p += (int64_t)gridDim.x * GT) {
     float t[MAXC];
     if (METHOD == M_TARGET) {
@@ -148,16 +143,12 @@ __global__ __launch_bounds__(GT) void fuse_kernel(Shape s, const float* __restri
         dst[q] = t[c];
       } else {
         const float d = syn[q] - t[c];
-        if (MODE == MODE_LOSS) acc += (double)d * (double)d;
+        if (MODE == MODE_LOSS) acc[0] += (double)d * (double)d;
         else dst[q] = d * coef;
       }
     }
   }
-  if (MODE == MODE_LOSS) {
-    __shared__ double s_red[GT / 64];
-    const double tot = wg_sum(acc, s_red);
-    if (threadIdx.x == 0) partial[blockIdx.x] = tot;
-  }
+  if (MODE == MODE_LOSS) wg_partials<GT>(acc, partial + blockIdx.x);
 }
 
 // K columns of partials [nblk][K], summed by one workgroup in a fixed order; out = sum_k column_k / count
@@ -166,11 +157,7 @@ __global__ __launch_bounds__(GT) void mean_final_kernel(const double* __restrict
                                                         float* __restrict__ out) {
   __shared__ double s_red[GT / 64];
   double res = 0.;
-  for (int k = 0; k < K; k++) {
-    double a = 0.;
-    for (int b = threadIdx.x; b < nblk; b += GT) a += partial[(size_t)b * K + k];
-    res += wg_sum(a, s_red) / count;
-  }
+  for (int k = 0; k < K; k++) res += column_sum<GT>(partial + k, nblk, K, s_red) / count;
   if (threadIdx.x == 0) out[0] = (float)res;
 }
 
@@ -210,7 +197,7 @@ __global__ __launch_bounds__(GT) void grad_l2_kernel(int64_t B, int H, int W, co
   const int64_t hw = (int64_t)H * W, n = B * hw;
   float coef = 0.f;
   if (BACKWARD) coef = (2.f / (float)(double)n) * (upstream ? upstream[0] : 1.f);
-  double ay = 0., ax = 0.;
+  double a[2] = {0., 0.};  // sums of the squared vertical and horizontal gradients
   for (int64_t p = (int64_t)blockIdx.x * GT + threadIdx.x; p < n; p += (int64_t)gridDim.x * GT) {
     const int64_t b = p / hw;
     const int64_t r = p - b * hw;
@@ -221,18 +208,11 @@ __global__ __launch_bounds__(GT) void grad_l2_kernel(int64_t B, int H, int W, co
       g_pan[p] = (grad_transposed(pan, gt, col0, (size_t)W, y, H) + grad_transposed(pan, gt, row0, 1, x, W)) * coef;
     } else {
       const float gy = grad_at(pan, gt, col0, (size_t)W, y, H), gx = grad_at(pan, gt, row0, 1, x, W);
-      ay += (double)gy * (double)gy;
-      ax += (double)gx * (double)gx;
+      a[0] += (double)gy * (double)gy;
+      a[1] += (double)gx * (double)gx;
     }
   }
-  if (!BACKWARD) {
-    __shared__ double s_red[GT / 64];
-    const double ty = wg_sum(ay, s_red), tx = wg_sum(ax, s_red);
-    if (threadIdx.x == 0) {
-      partial[(size_t)blockIdx.x * 2] = ty;
-      partial[(size_t)blockIdx.x * 2 + 1] = tx;
-    }
-  }
+  if (!BACKWARD) wg_partials<GT>(a, partial + (size_t)blockIdx.x * 2);
 }
 
 // ---- rescalers ---------------------------------------------------------------------------------------------------------
@@ -444,7 +424,7 @@ int eogs_gtprep_pansharp(int method, int C, int h, int w, int H, int W, const fl
   if (rc != EOGS_OK) return rc;
   if (!msi || !pan || !out) return fail(EOGS_ERR_INVALID_ARG, "gtprep_pansharp: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  launch_fuse<MODE_WRITE>(method, gt_blocks((int64_t)H * W, 1 << 20), s, make_shape(C, h, w, H, W, weight), msi, pan, nullptr, nullptr,
+  launch_fuse<MODE_WRITE>(method, capped_blocks((int64_t)H * W, GT, 1 << 20), s, make_shape(C, h, w, H, W, weight), msi, pan, nullptr, nullptr,
                           out, nullptr);
   LAUNCH_TRY(s, false, "gtprep_pansharp");
   return EOGS_OK;
@@ -459,7 +439,7 @@ int eogs_gtprep_pansharp_l2_forward(int method, int C, int h, int w, int H, int 
   if (ws_bytes < gtprep_ws_bytes(C)) return fail(EOGS_ERR_WORKSPACE, "gtprep_pansharp_l2_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
-  const int nb = gt_blocks((int64_t)H * W);
+  const int nb = capped_blocks((int64_t)H * W, GT, GMAXBLK);
   launch_fuse<MODE_LOSS>(method, nb, s, make_shape(C, h, w, H, W, weight), msi, pan, syn, nullptr, nullptr, partial);
   hipLaunchKernelGGL(mean_final_kernel<1>, dim3(1), dim3(GT), 0, s, (const double*)partial, nb, (double)C * (double)H * (double)W, out);
   LAUNCH_TRY(s, false, "gtprep_pansharp_l2_fwd");
@@ -473,7 +453,7 @@ int eogs_gtprep_pansharp_l2_backward(int method, int C, int h, int w, int H, int
   if (rc != EOGS_OK) return rc;
   if (!syn || !msi || !pan || !g_syn) return fail(EOGS_ERR_INVALID_ARG, "gtprep_pansharp_l2_backward: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  launch_fuse<MODE_GRAD>(method, gt_blocks((int64_t)H * W, 1 << 20), s, make_shape(C, h, w, H, W, weight), msi, pan, syn, upstream,
+  launch_fuse<MODE_GRAD>(method, capped_blocks((int64_t)H * W, GT, 1 << 20), s, make_shape(C, h, w, H, W, weight), msi, pan, syn, upstream,
                          g_syn, nullptr);
   LAUNCH_TRY(s, false, "gtprep_pansharp_l2_bwd");
   return EOGS_OK;
@@ -488,7 +468,7 @@ int eogs_gtprep_l2_forward(int64_t n, const float* image, const float* target, f
   if (ws_bytes < gtprep_ws_bytes(1)) return fail(EOGS_ERR_WORKSPACE, "gtprep_l2_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
-  const int nb = gt_blocks(n);
+  const int nb = capped_blocks(n, GT, GMAXBLK);
   launch_fuse<MODE_LOSS>(M_TARGET, nb, s, sh, nullptr, target, image, nullptr, nullptr, partial);
   hipLaunchKernelGGL(mean_final_kernel<1>, dim3(1), dim3(GT), 0, s, (const double*)partial, nb, (double)n, out);
   LAUNCH_TRY(s, false, "gtprep_l2_fwd");
@@ -502,7 +482,7 @@ int eogs_gtprep_l2_backward(int64_t n, const float* image, const float* target, 
   if (!flat_shape(n, sh)) return fail(EOGS_ERR_INVALID_ARG, "gtprep_l2_backward: bad size");
   if (!image || !target || !g_image) return fail(EOGS_ERR_INVALID_ARG, "gtprep_l2_backward: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  launch_fuse<MODE_GRAD>(M_TARGET, gt_blocks(n, 1 << 20), s, sh, nullptr, target, image, upstream, g_image, nullptr);
+  launch_fuse<MODE_GRAD>(M_TARGET, capped_blocks(n, GT, 1 << 20), s, sh, nullptr, target, image, upstream, g_image, nullptr);
   LAUNCH_TRY(s, false, "gtprep_l2_bwd");
   return EOGS_OK;
 }
@@ -516,7 +496,7 @@ int eogs_gtprep_grad_l2_forward(int64_t B, int H, int W, const float* pan, const
   hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
   const int64_t n = B * (int64_t)H * W;
-  const int nb = gt_blocks(n);
+  const int nb = capped_blocks(n, GT, GMAXBLK);
   hipLaunchKernelGGL(grad_l2_kernel<false>, dim3(nb), dim3(GT), 0, s, B, H, W, pan, gt, (const float*)nullptr, (float*)nullptr, partial);
   hipLaunchKernelGGL(mean_final_kernel<2>, dim3(1), dim3(GT), 0, s, (const double*)partial, nb, (double)n, out);
   LAUNCH_TRY(s, false, "gtprep_grad_l2_fwd");
@@ -529,7 +509,7 @@ int eogs_gtprep_grad_l2_backward(int64_t B, int H, int W, const float* pan, cons
   if (B < 1 || H < 2 || W < 2) return fail(EOGS_ERR_INVALID_ARG, "gtprep_grad_l2_backward: bad sizes (H and W must be at least 2)");
   if (!pan || !gt || !g_pan) return fail(EOGS_ERR_INVALID_ARG, "gtprep_grad_l2_backward: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(grad_l2_kernel<true>, dim3(gt_blocks(B * (int64_t)H * W, 1 << 20)), dim3(GT), 0, s, B, H, W, pan, gt, upstream, g_pan,
+  hipLaunchKernelGGL(grad_l2_kernel<true>, dim3(capped_blocks(B * (int64_t)H * W, GT, 1 << 20)), dim3(GT), 0, s, B, H, W, pan, gt, upstream, g_pan,
                      (double*)nullptr);
   LAUNCH_TRY(s, false, "gtprep_grad_l2_bwd");
   return EOGS_OK;
@@ -542,7 +522,7 @@ int eogs_gtprep_minmax(int C, int64_t n, const float* x, float* mm, void* ws, si
   if (ws_bytes < gtprep_ws_bytes(C)) return fail(EOGS_ERR_WORKSPACE, "gtprep_minmax: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   float* partial = reinterpret_cast<float*>(ws_base(ws));
-  const int nb = gt_blocks(n, GCBLK);
+  const int nb = capped_blocks(n, GT, GCBLK);
   hipLaunchKernelGGL(minmax_kernel, dim3(nb, C), dim3(GT), 0, s, n, x, partial);
   hipLaunchKernelGGL(minmax_final_kernel, dim3(C), dim3(GT), 0, s, nb, (const float*)partial, mm);
   LAUNCH_TRY(s, false, "gtprep_minmax");
@@ -554,7 +534,7 @@ int eogs_gtprep_rescale(int C, int64_t n, const float* x, const float* mm, float
   if (C < 1 || C > 65535 || n < 1) return fail(EOGS_ERR_INVALID_ARG, "gtprep_rescale: bad sizes");
   if (!x || !mm || !out) return fail(EOGS_ERR_INVALID_ARG, "gtprep_rescale: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(rescale_kernel, dim3(gt_blocks(n, 1 << 16), C), dim3(GT), 0, s, n, x, mm, out);
+  hipLaunchKernelGGL(rescale_kernel, dim3(capped_blocks(n, GT, 1 << 16), C), dim3(GT), 0, s, n, x, mm, out);
   LAUNCH_TRY(s, false, "gtprep_rescale");
   return EOGS_OK;
 }
@@ -565,7 +545,7 @@ int eogs_gtprep_clamp(int64_t n, const float* x, float lo, float hi, float* out,
   if (!x || !out) return fail(EOGS_ERR_INVALID_ARG, "gtprep_clamp: NULL argument");
   if (lo != lo || hi != hi) return fail(EOGS_ERR_INVALID_ARG, "gtprep_clamp: the bounds are numbers");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(clamp_kernel, dim3(gt_blocks(n, 1 << 20)), dim3(GT), 0, s, n, x, lo, hi, out);
+  hipLaunchKernelGGL(clamp_kernel, dim3(capped_blocks(n, GT, 1 << 20)), dim3(GT), 0, s, n, x, lo, hi, out);
   LAUNCH_TRY(s, false, "gtprep_clamp");
   return EOGS_OK;
 }
@@ -579,11 +559,11 @@ int eogs_gtprep_equalize(int C, int64_t n, const float* x, float* out, void* ws,
   hipStream_t s = (hipStream_t)stream;
   unsigned* hist = reinterpret_cast<unsigned*>(ws_base(ws));
   int* lut = reinterpret_cast<int*>(hist + (size_t)C * 256);
-  const int nb = gt_blocks(n, GCBLK);
+  const int nb = capped_blocks(n, GT, GCBLK);
   hipLaunchKernelGGL(hist_zero_kernel, dim3(C), dim3(GT), 0, s, C * 256, hist);
   hipLaunchKernelGGL(hist_kernel, dim3(nb, C), dim3(GT), 0, s, n, x, hist);
   hipLaunchKernelGGL(hist_lut_kernel, dim3(C), dim3(GT), 0, s, (const unsigned*)hist, lut);
-  hipLaunchKernelGGL(hist_apply_kernel, dim3(gt_blocks(n, 1 << 16), C), dim3(GT), 0, s, n, x, (const int*)lut, out);
+  hipLaunchKernelGGL(hist_apply_kernel, dim3(capped_blocks(n, GT, 1 << 16), C), dim3(GT), 0, s, n, x, (const int*)lut, out);
   LAUNCH_TRY(s, false, "gtprep_equalize");
   return EOGS_OK;
 }

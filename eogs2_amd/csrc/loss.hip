@@ -187,16 +187,11 @@ __global__ __launch_bounds__(LTHREADS) void loss_plane_reduce_kernel(const float
                                                                      float* __restrict__ plane_tmp) {
   __shared__ float s_red[4];
   const int plane = blockIdx.x;
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < tiles; i += LTHREADS) {
-    a += partial[2 * ((size_t)plane * tiles + i)];
-    b += partial[2 * ((size_t)plane * tiles + i) + 1];
-  }
-  a = wg_sum(a, s_red);
-  b = wg_sum(b, s_red);
+  float tot[2];
+  column_sums<LTHREADS>(partial + 2 * (size_t)plane * tiles, tiles, 2, tot, s_red);  // [tile][2]
   if (threadIdx.x == 0) {
-    plane_tmp[2 * plane] = a;
-    plane_tmp[2 * plane + 1] = b;
+    plane_tmp[2 * plane] = tot[0];
+    plane_tmp[2 * plane + 1] = tot[1];
   }
 }
 

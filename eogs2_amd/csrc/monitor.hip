@@ -3,7 +3,7 @@
 // sum of squared differences of the PSNR (L1 and SSIM come from the loss the iteration has already run); everything else
 // is a few scalars.
 //
-// Latency-bound work: what counts is the number of launches and the order of the sums. Two-stage reductions, as reg.hip's:
+// Latency-bound work: what counts is the number of launches and the order of the sums. reduce.h's two-stage reductions:
 // a grid that depends on the shape alone leaves float64 per-workgroup partials with plain stores, one workgroup adds them
 // in a fixed order and updates the state in the same launch. No atomics: the same bits on every run and stream. An element
 // is assigned to a lane by its INDEX in the plane (groups of four consecutive elements), so a base that is not 16-byte
@@ -23,22 +23,11 @@ constexpr int MMODEL_MAXBLK = 1024;  // workgroups of the model pass
 
 __device__ inline bool gate_closed(const uint32_t* gate) { return gate != nullptr && gate[0] == 0u; }
 
-inline int sq_blocks(int64_t n) {
-  const int64_t groups = (n + 3) / 4, b = (groups + MT - 1) / MT;
-  return (int)(b < 1 ? 1 : (b > MSQ_MAXBLK ? MSQ_MAXBLK : b));
-}
-
-inline int model_blocks(int64_t P) {
-  const int64_t groups = (P + 3) / 4, b = (groups + MT - 1) / MT;
-  return (int)(b < 1 ? 1 : (b > MMODEL_MAXBLK ? MMODEL_MAXBLK : b));
-}
-
 // ---- per-plane sum of (x - y)^2 ------------------------------------------------------------------------------------
 // grid (blocks per plane, planes). A lane walks groups of four consecutive elements, d and d*d in fp32 as the reference
 // forms them (image_utils.py:20), added into one fp32 accumulator in element order; wave and workgroup sums in double.
 __global__ __launch_bounds__(MT) void monitor_sq_kernel(int64_t n, const float* __restrict__ img, const float* __restrict__ gt,
                                                         double* __restrict__ partial) {
-  __shared__ double s_red[MT / 64];
   const float* __restrict__ x = img + (size_t)blockIdx.y * n;
   const float* __restrict__ y = gt + (size_t)blockIdx.y * n;
   const bool vec = ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15u) == 0;  // uniform over the workgroup
@@ -66,8 +55,8 @@ __global__ __launch_bounds__(MT) void monitor_sq_kernel(int64_t n, const float* 
       }
     }
   }
-  const double s = wg_sum((double)acc, s_red);
-  if (threadIdx.x == 0) partial[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = s;
+  double s[1] = {(double)acc};
+  wg_partials<MT>(s, partial + (size_t)blockIdx.y * gridDim.x + blockIdx.x);
 }
 
 // One workgroup: per plane the partials in a fixed order, the plane's PSNR in fp32 (image_utils.py:20-21), their mean;
@@ -81,9 +70,7 @@ __global__ __launch_bounds__(MT) void monitor_observe_kernel(int planes, int nbl
   if (gate_closed(gate)) return;  // uniform: before any barrier
   double psnr_sum = 0.;  // thread 0's
   for (int p = 0; p < planes; p++) {
-    double a = 0.;
-    for (int b = threadIdx.x; b < nblk; b += MT) a += partial[(size_t)p * nblk + b];
-    const double tot = wg_sum(a, s_red);
+    const double tot = column_sum<MT>(partial + (size_t)p * nblk, nblk, 1, s_red);
     if (threadIdx.x == 0) {
       const float mse = (float)(tot / (double)n);
       psnr_sum += (double)(20.f * log10f(1.f / sqrtf(mse)));  // mse 0: +inf, as the reference's
@@ -116,10 +103,9 @@ __global__ __launch_bounds__(MT) void monitor_observe_kernel(int planes, int nbl
 // ---- the model: mean opacity over the rows that are not retired, and their number ----------------------------------
 __global__ __launch_bounds__(MT) void monitor_model_kernel(int64_t P, const float* __restrict__ opacity,
                                                            double* __restrict__ partial) {
-  __shared__ double s_red[MT / 64];
   const bool vec = (reinterpret_cast<uintptr_t>(opacity) & 15u) == 0;
   const int64_t full = P >> 2, groups = (P + 3) >> 2;
-  double sum = 0., rows = 0.;
+  double a[2] = {0., 0.};  // sum of sigmoid(opacity), rows
   for (int64_t g = (int64_t)blockIdx.x * MT + threadIdx.x; g < groups; g += (int64_t)gridDim.x * MT) {
     float o[4];
     int k = 4;
@@ -134,16 +120,11 @@ __global__ __launch_bounds__(MT) void monitor_model_kernel(int64_t P, const floa
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       if (o[j] <= EOGS_REG_RETIRED_BELOW) continue;  // eogs_reg.h's rule (a NaN logit is a row, as there)
-      sum += (double)sigmoidf_(o[j]);
-      rows += 1.;
+      a[0] += (double)sigmoidf_(o[j]);
+      a[1] += 1.;
     }
   }
-  const double s = wg_sum(sum, s_red);
-  const double r = wg_sum(rows, s_red);
-  if (threadIdx.x == 0) {
-    partial[2 * (size_t)blockIdx.x] = s;
-    partial[2 * (size_t)blockIdx.x + 1] = r;
-  }
+  wg_partials<MT>(a, partial + 2 * (size_t)blockIdx.x);
 }
 
 __global__ __launch_bounds__(MT) void monitor_model_final_kernel(int nblk, const double* __restrict__ partial,
@@ -151,13 +132,9 @@ __global__ __launch_bounds__(MT) void monitor_model_final_kernel(int nblk, const
                                                                  eogs_monitor_state* __restrict__ st) {
   __shared__ double s_red[MT / 64];
   if (gate_closed(gate)) return;
-  double a = 0., r = 0.;
-  for (int b = threadIdx.x; b < nblk; b += MT) {
-    a += partial[2 * (size_t)b];
-    r += partial[2 * (size_t)b + 1];
-  }
-  const double sum = wg_sum(a, s_red);
-  const double rows = wg_sum(r, s_red);
+  double tot[2];
+  column_sums<MT>(partial, nblk, 2, tot, s_red);
+  const double sum = tot[0], rows = tot[1];
   if (threadIdx.x != 0) return;
   st->mean_opacity = rows > 0. ? (float)(sum / rows) : 0.f;
   st->rows = (int64_t)rows;
@@ -222,10 +199,10 @@ __global__ void monitor_close_kernel(int metric, int op, int64_t patience, const
 }  // namespace
 
 static size_t monitor_sq_bytes(int planes, int H, int W) {  // the per-plane partials of observe, a multiple of 256
-  return (((size_t)planes * sq_blocks((int64_t)H * W) * sizeof(double)) + 255) & ~(size_t)255;
+  return (((size_t)planes * capped_blocks(((int64_t)H * W + 3) / 4, MT, MSQ_MAXBLK) * sizeof(double)) + 255) & ~(size_t)255;
 }
 
-static size_t monitor_model_ws_bytes(int64_t P) { return (size_t)model_blocks(P) * 2 * sizeof(double) + 256; }
+static size_t monitor_model_ws_bytes(int64_t P) { return (size_t)capped_blocks((P + 3) / 4, MT, MMODEL_MAXBLK) * 2 * sizeof(double) + 256; }
 
 static int monitor_state_check(const char* who, const void* state) {
   if (!state) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL state", who);
@@ -299,7 +276,7 @@ int eogs_monitor_observe(int planes, int H, int W, const float* image, const flo
     loss_out = out;
   }
   const int64_t n = (int64_t)H * W;
-  const int nb = sq_blocks(n);
+  const int nb = capped_blocks((n + 3) / 4, MT, MSQ_MAXBLK);
   double* partial = reinterpret_cast<double*>(base);
   hipLaunchKernelGGL(monitor_sq_kernel, dim3(nb, planes), dim3(MT), 0, s, n, image, gt, partial);
   hipLaunchKernelGGL(monitor_observe_kernel, dim3(1), dim3(MT), 0, s, planes, nb, n, (const double*)partial, loss_out, oml, lam, kind,
@@ -324,7 +301,7 @@ int eogs_monitor_observe_model(int64_t P, const float* opacity, const uint32_t* 
   if (ws_bytes < monitor_model_ws_bytes(P)) return fail(EOGS_ERR_WORKSPACE, "monitor_observe_model: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
-  const int nb = model_blocks(P);
+  const int nb = capped_blocks((P + 3) / 4, MT, MMODEL_MAXBLK);
   hipLaunchKernelGGL(monitor_model_kernel, dim3(nb), dim3(MT), 0, s, P, opacity, partial);
   hipLaunchKernelGGL(monitor_model_final_kernel, dim3(1), dim3(MT), 0, s, nb, (const double*)partial, gate,
                      (eogs_monitor_state*)state);

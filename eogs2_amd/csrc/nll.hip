@@ -23,7 +23,7 @@ namespace {
 
 constexpr int NT = 256;         // threads per workgroup
 constexpr int NMAXBLK = 1024;   // workgroups of the forward (4 per CU); partials live in the caller's workspace
-constexpr int NK = 6;           // doubles per workgroup partial: loss sum, n, mean, M2, negatives, outside [0, 1]
+constexpr int NK = 6;           // doubles per workgroup partial: loss sum, negatives, outside [0, 1], then n, mean, M2
 constexpr int UNIT = 4;         // pixels per lane and trip
 
 struct Moments {
@@ -155,33 +155,37 @@ __global__ __launch_bounds__(NT) void nll_fwd_kernel(int planes, int64_t HW, boo
       }
     }
   }
+  // Three wg_sum calls, not wg_partials. The forward launch group (this kernel and nll_final_kernel) against the parent
+  // build, alternating processes, three turns each, median [min, max] in microseconds at 3 x 1024^2, 3 x 2048^2 and
+  // 1 x 4096^2. With wg_partials here and a pass per column in nll_final_kernel: 16.8 [16.7, 17.0] -> 18.4 [18.3, 18.5],
+  // 31.0 [31.0, 31.8] -> 33.3 [33.2, 33.5], 64.6 [64.3, 64.9] -> 70.9 [70.8, 71.8]: the final kernel's grid is 1024 rows
+  // at all three sizes, so what grows with the size is this kernel's (registers and occupancy were the same). As it
+  // stands, five turns each: 16.4 [16.2, 16.7] -> 16.3 [16.2, 16.6], 30.4 [30.2, 30.6] -> 30.3 [30.2, 30.6],
+  // 66.0 [65.4, 67.7] -> 67.0 [66.3, 67.7].
   loss = wg_sum(loss, s_red);
   neg = wg_sum(neg, s_red);
   outside = wg_sum(outside, s_red);
   mom = wg_moments(mom, s_mom);
   if (threadIdx.x == 0) {
     double* row = partial + (size_t)blockIdx.x * NK;
-    row[0] = loss, row[1] = mom.n, row[2] = mom.mean, row[3] = mom.m2, row[4] = neg, row[5] = outside;
+    row[0] = loss, row[1] = neg, row[2] = outside, row[3] = mom.n, row[4] = mom.mean, row[5] = mom.m2;
   }
 }
 
-// one workgroup: lane t takes the partials of workgroups t, t + NT, ... in that order, then the workgroup reductions
+// one workgroup: the three plain sums column by column; for the moments lane t merges the partials of workgroups t,
+// t + NT, ... in that order, then the workgroup's tree
 __global__ __launch_bounds__(NT) void nll_final_kernel(const double* __restrict__ partial, int nblk, double N, bool full,
                                                        bool sum, const float* __restrict__ weight, float* __restrict__ out) {
   __shared__ Moments s_mom[NT / 64];
   __shared__ double s_red[NT / 64];
-  double loss = 0., neg = 0., outside = 0.;
+  double tot[3];
+  column_sums<NT>(partial, nblk, NK, tot, s_red);
+  const double loss = tot[0], neg = tot[1], outside = tot[2];
   Moments mom = {0., 0., 0.};
   for (int b = threadIdx.x; b < nblk; b += NT) {
     const double* row = partial + (size_t)b * NK;
-    loss += row[0];
-    mom = chan(mom, Moments{row[1], row[2], row[3]});
-    neg += row[4];
-    outside += row[5];
+    mom = chan(mom, Moments{row[3], row[4], row[5]});
   }
-  loss = wg_sum(loss, s_red);
-  neg = wg_sum(neg, s_red);
-  outside = wg_sum(outside, s_red);
   mom = wg_moments(mom, s_mom);
   if (threadIdx.x != 0) return;
   const double half_log_2pi = 0.91893853320467274178;
@@ -248,11 +252,6 @@ __global__ __launch_bounds__(NT) void nll_bwd_kernel(int planes, int64_t HW, boo
   }
 }
 
-inline int nll_fwd_blocks(int64_t HW) {
-  const int64_t b = ((HW + UNIT - 1) / UNIT + NT - 1) / NT;
-  return (int)(b > NMAXBLK ? NMAXBLK : b);
-}
-
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -292,7 +291,7 @@ int eogs_nll_forward(int planes, int H, int W, unsigned mode, const float* input
   double* partial = reinterpret_cast<double*>(ws_base(ws));
   const int64_t HW = (int64_t)H * W;
   const bool vec = HW % UNIT == 0 && aligned16(input) && aligned16(target) && aligned16(var_or_mask);
-  const int nb = nll_fwd_blocks(HW);
+  const int nb = capped_blocks((HW + UNIT - 1) / UNIT, NT, NMAXBLK);
   hipLaunchKernelGGL(nll_fwd_kernel, dim3(nb), dim3(NT), 0, s, planes, HW, (mode & EOGS_NLL_MASK) != 0u, var_planes, vec, input,
                      target, var_or_mask, floor_, eps, partial);
   hipLaunchKernelGGL(nll_final_kernel, dim3(1), dim3(NT), 0, s, (const double*)partial, nb, (double)planes * (double)HW,
@@ -312,8 +311,7 @@ int eogs_nll_backward(int planes, int H, int W, unsigned mode, const float* inpu
   const int64_t HW = (int64_t)H * W;
   const bool vec = HW % UNIT == 0 && aligned16(input) && aligned16(target) && aligned16(var_or_mask) && aligned16(g_input) &&
                    aligned16(g_var_or_mask);
-  const int64_t blocks = ((HW + UNIT - 1) / UNIT + NT - 1) / NT;  // (H, W are ints: at most 2^62 / 1024 pixels, the loop strides)
-  const int nb = (int)(blocks > (int64_t)1 << 20 ? (int64_t)1 << 20 : blocks);
+  const int nb = capped_blocks((HW + UNIT - 1) / UNIT, NT, 1 << 20);  // (the loop strides)
   hipLaunchKernelGGL(nll_bwd_kernel, dim3(nb), dim3(NT), 0, s, planes, HW, (mode & EOGS_NLL_MASK) != 0u, var_planes, vec,
                      (mode & EOGS_NLL_SUM) != 0u, input, target, var_or_mask, floor_, eps, weight, g_loss, g_total, g_input,
                      g_var_or_mask);

@@ -6,10 +6,9 @@
 // pixels (one 16-byte access per plane) per lane and trip where H*W and the pointers allow it, V = 1 otherwise. The
 // order of the pipeline, the map and the presence of the shadow term are launch-uniform and therefore template
 // parameters: the pixel loop carries no branch on them. Nothing is saved between forward and backward. The parameter
-// sums are reduced per wave (shuffles), per workgroup (LDS, fixed order) and then column by column over the workgroups'
-// partials by a second kernel, again in a fixed order — no atomics, bitwise reproducible.
+// sums go through reduce.h's two stages (one workgroup of the second kernel per column) — no atomics, bitwise reproducible.
 #include "api_util.h"
-#include "reduce.h"  // shadow_clip: the same clamp as shade.hip
+#include "reduce.h"
 
 namespace {
 
@@ -17,11 +16,6 @@ constexpr int PT = 256;               // threads per workgroup
 constexpr int PMAXBLK = 1024;         // workgroups per launch (4 per CU); partial sums live in the caller's workspace
 constexpr int PK = EOGS_PAN_NPARAMS;  // floats per workgroup partial: dM[12], dinshadow[3], dmap_params[5]
 constexpr int A_INS = 12, A_MAP = 15;
-
-inline int pan_blocks(int64_t n) {
-  const int64_t b = (n + PT - 1) / PT;
-  return (int)(b < 1 ? 1 : (b > PMAXBLK ? PMAXBLK : b));
-}
 
 __host__ __device__ constexpr int map_nparams(int kind) {
   return kind == EOGS_PAN_FIXED ? 5
@@ -179,7 +173,6 @@ __global__ __launch_bounds__(PT) void pan_bwd_kernel(int64_t n, const float* __r
                                                      float* __restrict__ partial) {
   constexpr bool A = ORDER == EOGS_PAN_ORDER_CC_FIRST;
   constexpr int NCC = A ? 3 : 1;
-  __shared__ float s_red[PT / 64][PK];
   float M[12], ins[3], mp[8];
   load_params<ORDER, KIND>(Mp, insp, mpp, SH, M, ins, mp);
   float acc[PK];
@@ -270,31 +263,14 @@ __global__ __launch_bounds__(PT) void pan_bwd_kernel(int64_t n, const float* __r
     for (int k = 0; k < 3; k++) stv<V>(g_raw + k * n + p, og[k]);
     if constexpr (SH) stv<V>(g_alt + p, oa);
   }
-  // wave sums by shuffles, then the four waves' sums in a fixed order
-#pragma unroll
-  for (int i = 0; i < PK; i++) {
-    float v = acc[i];
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6][i] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < PK)
-    partial[(size_t)blockIdx.x * PK + threadIdx.x] =
-        s_red[0][threadIdx.x] + s_red[1][threadIdx.x] + s_red[2][threadIdx.x] + s_red[3][threadIdx.x];
+  wg_partials<PT>(acc, partial + (size_t)blockIdx.x * PK);
 }
 
 // out[k] = sum_b partial[b][k]: workgroup k sums column k of the [nblk][PK] partials in a fixed order
 __global__ __launch_bounds__(PT) void pan_reduce_kernel(const float* __restrict__ partial, int nblk, float* __restrict__ out) {
   __shared__ float s_red[PT / 64];
-  const int k = blockIdx.x;
-  float a = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += PT) a += partial[(size_t)i * PK + k];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += __shfl_xor(a, o, 64);
-  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) out[k] = s_red[0] + s_red[1] + s_red[2] + s_red[3];
+  const float tot = column_sum<PT>(partial + blockIdx.x, nblk, PK, s_red);
+  if (threadIdx.x == 0) out[blockIdx.x] = tot;
 }
 
 struct PanArgs {
@@ -347,7 +323,7 @@ void pan_dispatch(int order, int kind, PanArgs& a) {
   a.vec = (a.n % 4 == 0) && aligned16(a.raw) && aligned16(a.alt_diff) && aligned16(a.g_shaded) && aligned16(a.g_cc) &&
           aligned16(a.g_shadow) && aligned16(a.cc) && aligned16(a.shaded) && aligned16(a.shadow) && aligned16(a.g_raw) &&
           aligned16(a.g_alt);
-  a.nb = pan_blocks(a.vec ? a.n / 4 : a.n);
+  a.nb = capped_blocks(a.vec ? a.n / 4 : a.n, PT, PMAXBLK);
   if (order == EOGS_PAN_ORDER_CC_FIRST) pan_launch_order<EOGS_PAN_ORDER_CC_FIRST>(kind, a);
   else pan_launch_order<EOGS_PAN_ORDER_MAP_FIRST>(kind, a);
 }

@@ -2,6 +2,15 @@
 // The library is built without fast-math and with -ffp-contract=off: each of these is ONE expression tree, so every kernel
 // that sums through it rounds in the same order — what the modules' "same bits on every run" (and monitor.hip's "same
 // bits as reg.hip") rest on.
+//
+// The two-stage sum every side module's scalars go through, in words (tests/reduce_cases.py restates it from here):
+//   Stage 1. Workgroups of 256 threads, the grid capped (api_util.h: capped_blocks). Thread t of workgroup g adds its
+//            elements g * 256 + t, + grid * 256, ... in that order into its own accumulator. The 64 lanes of a wave
+//            combine by the xor butterfly (offsets 32, 16, ..., 1: v += v of lane ^ offset), the workgroup adds its four
+//            wave sums left to right, ((w0 + w1) + w2) + w3, and stores one row of partials (wg_partials).
+//   Stage 2. One workgroup of 256 threads per column of the partials: thread t adds rows t, t + 256, ... in that order,
+//            then the same butterfly and the same four waves (column_sum, column_sums). What follows the sum — a
+//            division, a weight, a table update — is the kernel's own epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -36,6 +45,51 @@ __device__ inline T wg_sum(T v, T* s_red) {
   if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
   __syncthreads();
   return ((s_red[0] + s_red[1]) + s_red[2]) + s_red[3];
+}
+
+// Stage 1's end: the workgroup's sum of each of K per-lane accumulators (float or double), stored by its first K threads
+// to row[k] — the caller passes its own row, partial + blockIdx.x * pitch. One barrier; the bits of K wg_sum calls and a
+// store. Its LDS has no leading barrier: one call per kernel. THREADS is the caller's workgroup size: four waves.
+template <int THREADS, int K, typename T>
+__device__ inline void wg_partials(const T (&a)[K], T* __restrict__ row) {
+  static_assert(THREADS == 4 * 64 && K <= 64, "four waves of 64 lanes; the first wave stores");
+  __shared__ T s_part[4][K];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    T v = a[k];  // wave_sum's butterfly written out: as a call it is unrolled before it is inlined and the K chains are
+                 // scheduled together, which cost pan_bwd_kernel 39 VGPRs and three waves of occupancy
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    if (lane == 0) s_part[wv][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < K) row[threadIdx.x] = ((s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + s_part[2][threadIdx.x]) + s_part[3][threadIdx.x];
+}
+
+// Stage 2: K neighbouring columns of `nblk` rows of partials, tot[k] = the sum over b of rows[b * stride + k], formed by one
+// workgroup and returned on every thread: thread t takes b = t, t + THREADS, ... in that order, then wg_sum per column.
+// One trip over the rows serves the K columns (a pass of dependent loads per column is what a final kernel's time is).
+// `s_red` as for wg_sum.
+template <int THREADS, int K, typename T>
+__device__ inline void column_sums(const T* __restrict__ rows, int nblk, size_t stride, T (&tot)[K], T* s_red) {
+  static_assert(THREADS == 4 * 64, "four waves of 64 lanes");
+  T a[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) a[k] = 0;
+  for (int b = threadIdx.x; b < nblk; b += THREADS) {
+#pragma unroll
+    for (int k = 0; k < K; k++) a[k] += rows[(size_t)b * stride + k];
+  }
+#pragma unroll
+  for (int k = 0; k < K; k++) tot[k] = wg_sum(a[k], s_red);
+}
+// ... one column: element b at col[b * stride]
+template <int THREADS, typename T>
+__device__ inline T column_sum(const T* __restrict__ col, int nblk, size_t stride, T* s_red) {
+  T tot[1];
+  column_sums<THREADS>(col, nblk, stride, tot, s_red);
+  return tot[0];
 }
 
 // the float sum on the DPP path: four rotations inside each row of 16 lanes, the row totals handed on by row_bcast15 /

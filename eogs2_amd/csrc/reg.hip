@@ -17,37 +17,6 @@ constexpr int RT = 256;         // threads per workgroup
 constexpr int RMAXBLK = 1024;   // workgroups per launch (4 per CU); partial sums live in the caller's workspace
 constexpr int RK = 4;           // doubles per workgroup partial
 
-inline int reg_blocks(int64_t n) {
-  const int64_t b = (n + RT - 1) / RT;
-  return (int)(b < 1 ? 1 : (b > RMAXBLK ? RMAXBLK : b));
-}
-
-// the workgroup's sum of each of K per-lane accumulators, written by its first K lanes to partial[block][k]
-template <int K>
-__device__ inline void wg_partials(double (&a)[K], double* __restrict__ partial) {
-  __shared__ double s_red[RT / 64][K];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    a[k] = wave_sum(a[k]);
-    if (lane == 0) s_red[wv][k] = a[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < K) {
-    double v = s_red[0][threadIdx.x];
-    for (int w = 1; w < RT / 64; w++) v += s_red[w][threadIdx.x];
-    partial[(size_t)blockIdx.x * RK + threadIdx.x] = v;
-  }
-}
-
-// column k of the partials, summed by one workgroup in a fixed order: lane t takes blocks t, t + RT, ..., then the
-// butterfly over the wave and the four waves in index order. Every lane returns the same value.
-__device__ inline double column_sum(const double* __restrict__ partial, int nblk, int k, double* s_red) {
-  double a = 0.;
-  for (int b = threadIdx.x; b < nblk; b += RT) a += partial[(size_t)b * RK + k];
-  return wg_sum(a, s_red);
-}
-
 // ---- Gaussian-space terms ------------------------------------------------------------------------------------------
 // main_loss.py:27-32 for one row; everything backward needs again
 struct ErankRow {
@@ -94,7 +63,7 @@ __global__ __launch_bounds__(RT) void reg_gauss_fwd_kernel(int64_t P, unsigned w
       a[2] += (double)(fmaxf(r.t, 0.f) + sqrtf(r.m));
     }
   }
-  wg_partials<4>(a, partial);
+  wg_partials<RT>(a, partial + (size_t)blockIdx.x * RK);
 }
 
 __global__ __launch_bounds__(RT) void reg_gauss_final_kernel(const double* __restrict__ partial, int nblk, unsigned want,
@@ -102,7 +71,7 @@ __global__ __launch_bounds__(RT) void reg_gauss_final_kernel(const double* __res
                                                              float* __restrict__ out) {
   __shared__ double s_red[RT / 64];
   double tot[4];
-  for (int k = 0; k < 4; k++) tot[k] = column_sum(partial, nblk, k, s_red);
+  for (int k = 0; k < 4; k++) tot[k] = column_sum<RT>(partial + k, nblk, RK, s_red);
   if (threadIdx.x != 0) return;
   const float t0 = (want & EOGS_REG_OPACITY) ? (float)(tot[0] / (double)n_init) : 0.f;
   const float t1 = (want & EOGS_REG_OPACITY_RADII) ? (float)(tot[1] / (double)n_init) : 0.f;
@@ -198,7 +167,7 @@ __global__ __launch_bounds__(RT) void reg_image_fwd_kernel(int H, int W, const f
     }
     if (acc) a[2] += (double)(1.f - acc[p]);
   }
-  wg_partials<3>(a, partial);
+  wg_partials<RT>(a, partial + (size_t)blockIdx.x * RK);
 }
 
 __global__ __launch_bounds__(RT) void reg_image_final_kernel(const double* __restrict__ partial, int nblk, int H, int W,
@@ -206,7 +175,7 @@ __global__ __launch_bounds__(RT) void reg_image_final_kernel(const double* __res
                                                              float* __restrict__ out) {
   __shared__ double s_red[RT / 64];
   double tot[3];
-  for (int k = 0; k < 3; k++) tot[k] = column_sum(partial, nblk, k, s_red);
+  for (int k = 0; k < 3; k++) tot[k] = column_sum<RT>(partial + k, nblk, RK, s_red);
   if (threadIdx.x != 0) return;
   const double nv = (double)(H - 1) * (double)W, nh = (double)H * (double)(W - 1), n = (double)H * (double)W;
   const float t0 = has_alt ? (float)(0.5 * (tot[0] / nv + tot[1] / nh)) : 0.f;
@@ -279,7 +248,7 @@ int eogs_reg_gauss_forward(int64_t P, unsigned want, const float* opacity, const
   if (ws_bytes < reg_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "reg_gauss_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
-  const int nb = reg_blocks(P);
+  const int nb = capped_blocks(P, RT, RMAXBLK);
   {
     ProfScope ps(PS_REG_FWD, s);
     hipLaunchKernelGGL(reg_gauss_fwd_kernel, dim3(nb), dim3(RT), 0, s, P, want, opacity, log_scales, radii, partial);
@@ -301,7 +270,7 @@ int eogs_reg_gauss_backward(int64_t P, unsigned want, const float* opacity, cons
   hipStream_t s = (hipStream_t)stream;
   {
     ProfScope ps(PS_REG_BWD, s);
-    hipLaunchKernelGGL(reg_gauss_bwd_kernel, dim3(reg_blocks(P)), dim3(RT), 0, s, P, want, opacity, log_scales, radii, n_init,
+    hipLaunchKernelGGL(reg_gauss_bwd_kernel, dim3(capped_blocks(P, RT, RMAXBLK)), dim3(RT), 0, s, P, want, opacity, log_scales, radii, n_init,
                        weights, out, g_total, g_terms, g_opacity, g_scaling);
   }
   LAUNCH_TRY(s, false, "reg_gauss_bwd");
@@ -323,7 +292,7 @@ int eogs_reg_image_forward(int H, int W, const float* altitude, const float* acc
   if (ws_bytes < reg_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "reg_image_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   double* partial = reinterpret_cast<double*>(ws_base(ws));
-  const int nb = reg_blocks((int64_t)H * W);
+  const int nb = capped_blocks((int64_t)H * W, RT, RMAXBLK);
   {
     ProfScope ps(PS_REG_FWD, s);
     hipLaunchKernelGGL(reg_image_fwd_kernel, dim3(nb), dim3(RT), 0, s, H, W, altitude, accumulated_opacity, partial);
@@ -345,7 +314,7 @@ int eogs_reg_image_backward(int H, int W, const float* altitude, const float* ac
   hipStream_t s = (hipStream_t)stream;
   {
     ProfScope ps(PS_REG_BWD, s);
-    hipLaunchKernelGGL(reg_image_bwd_kernel, dim3(reg_blocks((int64_t)H * W)), dim3(RT), 0, s, H, W, altitude,
+    hipLaunchKernelGGL(reg_image_bwd_kernel, dim3(capped_blocks((int64_t)H * W, RT, RMAXBLK)), dim3(RT), 0, s, H, W, altitude,
                        accumulated_opacity != nullptr, weights, g_total, g_terms, g_altitude, g_accumulated_opacity);
   }
   LAUNCH_TRY(s, false, "reg_image_bwd");

@@ -129,26 +129,18 @@ __device__ __forceinline__ float clamp01_keep_nan(float g) { return g < 0.f ? 0.
 template <int C>
 __global__ __launch_bounds__(RT) void report_metrics_partial_kernel(int64_t n, const float* __restrict__ image, const float* __restrict__ gt,
                                                                     double* __restrict__ partial) {
-  __shared__ double s_red[4];
-  double s_abs[C], s_sq[C];
+  double a[2 * C];  // sum |d| and sum d^2, channel by channel
 #pragma unroll
-  for (int k = 0; k < C; k++) s_abs[k] = s_sq[k] = 0.0;
+  for (int k = 0; k < 2 * C; k++) a[k] = 0.0;
   for (int64_t p = (int64_t)blockIdx.x * RT + threadIdx.x; p < n; p += (int64_t)gridDim.x * RT) {
 #pragma unroll
     for (int k = 0; k < C; k++) {
       const double d = (double)image[k * n + p] - (double)clamp01_keep_nan(gt[k * n + p]);  // exact in double
-      s_abs[k] += fabs(d);
-      s_sq[k] += d * d;
+      a[2 * k] += fabs(d);
+      a[2 * k + 1] += d * d;
     }
   }
-#pragma unroll
-  for (int k = 0; k < C; k++) {
-    const double a = wg_sum(s_abs[k], s_red), q = wg_sum(s_sq[k], s_red);
-    if (threadIdx.x == 0) {
-      partial[(size_t)blockIdx.x * RK + 2 * k] = a;
-      partial[(size_t)blockIdx.x * RK + 2 * k + 1] = q;
-    }
-  }
+  wg_partials<RT>(a, partial + (size_t)blockIdx.x * RK);
 }
 
 // one workgroup: the partials column by column in index order, then the view's two figures and the table
@@ -161,11 +153,7 @@ __global__ __launch_bounds__(RT) void report_metrics_final_kernel(int C, int64_t
 #pragma unroll
   for (int k = 0; k < RK; k++) {
     tot[k] = 0.0;
-    if (k < 2 * C) {  // (uniform)
-      double a = 0.0;
-      for (int i = threadIdx.x; i < nblk; i += RT) a += partial[(size_t)i * RK + k];
-      tot[k] = wg_sum(a, s_red);
-    }
+    if (k < 2 * C) tot[k] = column_sum<RT>(partial + k, nblk, RK, s_red);  // (uniform)
   }
   if (threadIdx.x != 0) return;
   double sum_abs = 0.0, sum_psnr = 0.0;
@@ -384,8 +372,7 @@ int eogs_report_metrics_accumulate(int C, int H, int W, const float* image, cons
       overlaps(ws, ws_bytes, image, ib) || overlaps(ws, ws_bytes, gt, ib) || overlaps(ws, ws_bytes, table, sizeof(eogs_report_table)))
     return fail(EOGS_ERR_INVALID_ARG, "report_metrics_accumulate: the table or the workspace overlaps an input");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t b = (n + RT - 1) / RT;
-  const int nb = (int)(b > RMAXBLK ? RMAXBLK : b);
+  const int nb = capped_blocks(n, RT, RMAXBLK);
   double* partial = reinterpret_cast<double*>(ws_base(ws));
   switch (C) {
     case 1: hipLaunchKernelGGL(report_metrics_partial_kernel<1>, dim3(nb), dim3(RT), 0, s, n, image, gt, partial); break;

@@ -9,29 +9,22 @@
 // a fixed order — no atomics, bitwise reproducible.
 #include "api_util.h"
 #include "reduce.h"
+#include "eogs_randomcam.h"
 
 namespace {
 
 constexpr int ST = 256;        // threads per workgroup
 constexpr int SMAXBLK = 1024;  // workgroups per launch (4 per CU); partial sums live in the caller's workspace
 constexpr int SK = 16;         // floats per workgroup partial (15 used by shade_bwd)
+constexpr int MK = 4;          // ... of the masked losses (3 used): what eogs_cmloss_bytes covers
 
-inline int shade_blocks(int64_t n) {
-  const int64_t b = (n + ST - 1) / ST;
-  return (int)(b < 1 ? 1 : (b > SMAXBLK ? SMAXBLK : b));
-}
-
-// sums the per-workgroup partials [nblk][SK] column by column in a fixed order: out[k] = sum_b partial[b][k], k < K
+// sums the per-workgroup partials [nblk][pitch] column by column: out[k] = sum_b partial[b][k], k < K
 template <int MODE>  // 0: plain sums (shade_bwd); 1: mloss {S_alt/N, S_rgb/N, N}; 2: tshadow -S/n
-__global__ __launch_bounds__(ST) void shade_reduce_kernel(const float* __restrict__ partial, int nblk, int K, float scale,
+__global__ __launch_bounds__(ST) void shade_reduce_kernel(const float* __restrict__ partial, int nblk, int pitch, int K, float scale,
                                                           float* __restrict__ out) {
   __shared__ float s_red[4];
   float tot[SK];
-  for (int k = 0; k < K; k++) {
-    float a = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += ST) a += partial[(size_t)i * SK + k];
-    tot[k] = wg_sum(a, s_red);
-  }
+  for (int k = 0; k < K; k++) tot[k] = column_sum<ST>(partial + k, nblk, pitch, s_red);
   if (threadIdx.x != 0) return;
   if (MODE == 0) {
     for (int k = 0; k < K; k++) out[k] = tot[k];
@@ -96,7 +89,6 @@ __global__ __launch_bounds__(ST) void shade_bwd_kernel(int64_t n, const float* _
                                                        const float* __restrict__ g_shaded, const float* __restrict__ g_cc,
                                                        const float* __restrict__ g_shadow, float* __restrict__ g_raw,
                                                        float* __restrict__ g_alt, float* __restrict__ partial) {
-  __shared__ float s_red[4];
   float M[12], ins[3] = {0.f, 0.f, 0.f};
 #pragma unroll
   for (int i = 0; i < 12; i++) M[i] = Mp[i];
@@ -143,41 +135,39 @@ __global__ __launch_bounds__(ST) void shade_bwd_kernel(int64_t n, const float* _
       acc[4 * k + 3] += gcc[k];
     }
   }
-#pragma unroll
-  for (int i = 0; i < 15; i++) {
-    const float t = wg_sum(acc[i], s_red);
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * SK + i] = t;
-  }
+  wg_partials<ST>(acc, partial + (size_t)blockIdx.x * SK);
 }
 
 // ---- masked resample losses ----------------------------------------------------------------------------------------
-__device__ inline bool mloss_mask(int mode, float d, float2 uv) {
+// One kernel pair for eogs_mloss_* (three planes, either mode) and randomcam's eogs_cmloss_* (1 .. 4 planes, mode RANDOM,
+// either side's gradient optional): the same launch shape, per-lane expression trees and reduction, so three planes in
+// mode RANDOM give the same bits through either entry.
+__device__ inline bool mloss_mask(int mode, float d, float2 uv) {  // main_loss.py:83-85, 151-153
   const bool alt_ok = mode == EOGS_MLOSS_SUN ? d > -1e-2f : fabsf(d) < 0.30f;
   return alt_ok && fabsf(uv.x) < 1.f && fabsf(uv.y) < 1.f;
 }
 
+template <int C>
 __global__ __launch_bounds__(ST) void mloss_fwd_kernel(int64_t n, int mode, const float* __restrict__ alt_diff,
                                                        const float* __restrict__ a, const float* __restrict__ b,
                                                        const float2* __restrict__ uv, float* __restrict__ partial) {
-  __shared__ float s_red[4];
-  float s_alt = 0.f, s_rgb = 0.f, cnt = 0.f;
+  float acc[3] = {0.f, 0.f, 0.f};  // S_alt, S_rgb, N
   for (int64_t p = (int64_t)blockIdx.x * ST + threadIdx.x; p < n; p += (int64_t)gridDim.x * ST) {
     const float d = alt_diff[p];
     if (mloss_mask(mode, d, uv[p])) {
-      s_alt += fabsf(d);
-      s_rgb += fabsf(a[p] - b[p]) + fabsf(a[n + p] - b[n + p]) + fabsf(a[2 * n + p] - b[2 * n + p]);
-      cnt += 1.f;  // at most 2^24 / gridDim.x per lane: exact
+      acc[0] += fabsf(d);
+      float t = fabsf(a[p] - b[p]);
+#pragma unroll
+      for (int k = 1; k < C; k++) t += fabsf(a[k * n + p] - b[k * n + p]);
+      acc[1] += t;
+      acc[2] += 1.f;  // at most 2^24 / gridDim.x per lane: exact
     }
   }
-  const float t0 = wg_sum(s_alt, s_red), t1 = wg_sum(s_rgb, s_red), t2 = wg_sum(cnt, s_red);
-  if (threadIdx.x == 0) {
-    partial[(size_t)blockIdx.x * SK] = t0;
-    partial[(size_t)blockIdx.x * SK + 1] = t1;
-    partial[(size_t)blockIdx.x * SK + 2] = t2;
-  }
+  wg_partials<ST>(acc, partial + (size_t)blockIdx.x * MK);
 }
 
-
+// g_a and g_b may each be NULL (uniform branches); eogs_mloss_backward refuses a NULL g_a at its entry
+template <int C>
 __global__ __launch_bounds__(ST) void mloss_bwd_kernel(int64_t n, int mode, const float* __restrict__ alt_diff,
                                                        const float* __restrict__ a, const float* __restrict__ b,
                                                        const float2* __restrict__ uv, const float* __restrict__ out,
@@ -188,8 +178,8 @@ __global__ __launch_bounds__(ST) void mloss_bwd_kernel(int64_t n, int mode, cons
     for (int64_t p = (int64_t)blockIdx.x * ST + threadIdx.x; p < n; p += (int64_t)gridDim.x * ST) {
       g_alt[p] = 0.f;
 #pragma unroll
-      for (int k = 0; k < 3; k++) {
-        g_a[k * n + p] = 0.f;
+      for (int k = 0; k < C; k++) {
+        if (g_a) g_a[k * n + p] = 0.f;
         if (g_b) g_b[k * n + p] = 0.f;
       }
     }
@@ -201,27 +191,52 @@ __global__ __launch_bounds__(ST) void mloss_bwd_kernel(int64_t n, int mode, cons
     // the reference's (grad * mask) * sign(x): outside the mask a zero with the sign of w sign(x) (NaN under a non-finite w)
     const float mf = mloss_mask(mode, d, uv[p]) ? 1.f : 0.f;
     g_alt[p] = (w_alt * mf) * sgn(d);
+    if (!g_a && !g_b) continue;
     const float wr = w_rgb * mf;
 #pragma unroll
-    for (int k = 0; k < 3; k++) {
+    for (int k = 0; k < C; k++) {
       const float g = wr * sgn(a[k * n + p] - b[k * n + p]);
-      g_a[k * n + p] = g;
+      if (g_a) g_a[k * n + p] = g;
       if (g_b) g_b[k * n + p] = -g;
     }
   }
 }
 
+// both entries' launches; `partial` holds SMAXBLK rows of MK floats
+void mloss_launch_fwd(int C, int64_t n, int mode, const float* alt_diff, const float* a, const float* b, const float* uv, float* out,
+                      float* partial, hipStream_t s) {
+  const int nb = capped_blocks(n, ST, SMAXBLK);
+  const float2* uv2 = reinterpret_cast<const float2*>(uv);
+  switch (C) {
+    case 1: hipLaunchKernelGGL(mloss_fwd_kernel<1>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, partial); break;
+    case 2: hipLaunchKernelGGL(mloss_fwd_kernel<2>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, partial); break;
+    case 3: hipLaunchKernelGGL(mloss_fwd_kernel<3>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, partial); break;
+    default: hipLaunchKernelGGL(mloss_fwd_kernel<4>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, partial); break;
+  }
+  hipLaunchKernelGGL(shade_reduce_kernel<1>, dim3(1), dim3(ST), 0, s, partial, nb, MK, 3, 1.f, out);
+}
+
+void mloss_launch_bwd(int C, int64_t n, int mode, const float* alt_diff, const float* a, const float* b, const float* uv,
+                      const float* out, const float* upstream, float* g_alt, float* g_a, float* g_b, hipStream_t s) {
+  const int nb = capped_blocks(n, ST, SMAXBLK);
+  const float2* uv2 = reinterpret_cast<const float2*>(uv);
+  switch (C) {
+    case 1: hipLaunchKernelGGL(mloss_bwd_kernel<1>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, out, upstream, g_alt, g_a, g_b); break;
+    case 2: hipLaunchKernelGGL(mloss_bwd_kernel<2>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, out, upstream, g_alt, g_a, g_b); break;
+    case 3: hipLaunchKernelGGL(mloss_bwd_kernel<3>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, out, upstream, g_alt, g_a, g_b); break;
+    default: hipLaunchKernelGGL(mloss_bwd_kernel<4>, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, a, b, uv2, out, upstream, g_alt, g_a, g_b); break;
+  }
+}
+
 // ---- translucent-shadow regulariser ------------------------------------------------------------------------------
 __global__ __launch_bounds__(ST) void tshadow_fwd_kernel(int64_t n, const float* __restrict__ a, float* __restrict__ partial) {
-  __shared__ float s_red[4];
-  float s = 0.f;
+  float s[1] = {0.f};
   for (int64_t p = (int64_t)blockIdx.x * ST + threadIdx.x; p < n; p += (int64_t)gridDim.x * ST) {
     const float x = a[p];
     const float b = tshadow_clip(x);
-    s += x * log2f(b) + (1.f - x) * log2f(1.f - b);
+    s[0] += x * log2f(b) + (1.f - x) * log2f(1.f - b);
   }
-  const float t = wg_sum(s, s_red);
-  if (threadIdx.x == 0) partial[(size_t)blockIdx.x * SK] = t;
+  wg_partials<ST>(s, partial + (size_t)blockIdx.x * SK);
 }
 
 __global__ __launch_bounds__(ST) void tshadow_bwd_kernel(int64_t n, const float* __restrict__ a, const float* __restrict__ upstream,
@@ -240,6 +255,7 @@ __global__ __launch_bounds__(ST) void tshadow_bwd_kernel(int64_t n, const float*
 }  // namespace
 
 static size_t shade_ws_bytes() { return (size_t)SMAXBLK * SK * sizeof(float) + 256; }
+static size_t cmloss_ws_bytes() { return (size_t)SMAXBLK * MK * sizeof(float) + 256; }
 
 extern "C" {
 
@@ -261,7 +277,7 @@ int eogs_shade_forward(int H, int W, const float* raw, const float* alt_diff, co
   const int64_t n = (int64_t)H * W;
   {
     ProfScope ps(PS_SHADE_FWD, s);
-    hipLaunchKernelGGL(shade_fwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, raw, alt_diff, M, inshadow, cc, shaded, shadow);
+    hipLaunchKernelGGL(shade_fwd_kernel, dim3(capped_blocks(n, ST, SMAXBLK)), dim3(ST), 0, s, n, raw, alt_diff, M, inshadow, cc, shaded, shadow);
   }
   LAUNCH_TRY(s, false, "shade_fwd");
   return EOGS_OK;
@@ -278,13 +294,13 @@ int eogs_shade_backward(int H, int W, const float* raw, const float* alt_diff, c
   if (ws_bytes < shade_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "shade_backward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   const int64_t n = (int64_t)H * W;
-  const int nb = shade_blocks(n);
+  const int nb = capped_blocks(n, ST, SMAXBLK);
   float* partial = reinterpret_cast<float*>(ws_base(ws));
   {
     ProfScope ps(PS_SHADE_BWD, s);
     hipLaunchKernelGGL(shade_bwd_kernel, dim3(nb), dim3(ST), 0, s, n, raw, alt_diff, M, inshadow, g_shaded, g_cc, g_shadow, g_raw,
                        g_alt_diff, partial);
-    hipLaunchKernelGGL(shade_reduce_kernel<0>, dim3(1), dim3(ST), 0, s, partial, nb, 15, 1.f, g_params);
+    hipLaunchKernelGGL(shade_reduce_kernel<0>, dim3(1), dim3(ST), 0, s, partial, nb, SK, 15, 1.f, g_params);
   }
   LAUNCH_TRY(s, false, "shade_bwd");
   return EOGS_OK;
@@ -298,14 +314,9 @@ int eogs_mloss_forward(int H, int W, int mode, const float* alt_diff, const floa
   if (!alt_diff || !rgb_a || !rgb_b || !uv || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "mloss_forward: NULL argument");
   if (ws_bytes < shade_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "mloss_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t n = (int64_t)H * W;
-  const int nb = shade_blocks(n);
-  float* partial = reinterpret_cast<float*>(ws_base(ws));
   {
     ProfScope ps(PS_MLOSS_FWD, s);
-    hipLaunchKernelGGL(mloss_fwd_kernel, dim3(nb), dim3(ST), 0, s, n, mode, alt_diff, rgb_a, rgb_b,
-                       reinterpret_cast<const float2*>(uv), partial);
-    hipLaunchKernelGGL(shade_reduce_kernel<1>, dim3(1), dim3(ST), 0, s, partial, nb, 3, 1.f, out);
+    mloss_launch_fwd(3, (int64_t)H * W, mode, alt_diff, rgb_a, rgb_b, uv, out, reinterpret_cast<float*>(ws_base(ws)), s);
   }
   LAUNCH_TRY(s, false, "mloss_fwd");
   return EOGS_OK;
@@ -320,13 +331,52 @@ int eogs_mloss_backward(int H, int W, int mode, const float* alt_diff, const flo
   if (!alt_diff || !rgb_a || !rgb_b || !uv || !out || !upstream || !g_alt_diff || !g_rgb_a)
     return fail(EOGS_ERR_INVALID_ARG, "mloss_backward: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  const int64_t n = (int64_t)H * W;
   {
     ProfScope ps(PS_MLOSS_BWD, s);
-    hipLaunchKernelGGL(mloss_bwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, mode, alt_diff, rgb_a, rgb_b,
-                       reinterpret_cast<const float2*>(uv), out, upstream, g_alt_diff, g_rgb_a, g_rgb_b);
+    mloss_launch_bwd(3, (int64_t)H * W, mode, alt_diff, rgb_a, rgb_b, uv, out, upstream, g_alt_diff, g_rgb_a, g_rgb_b, s);
   }
   LAUNCH_TRY(s, false, "mloss_bwd");
+  return EOGS_OK;
+}
+
+// randomcam's comparison (include/eogs_randomcam.h): the same kernels in mode RANDOM for 1 .. 4 planes
+int eogs_cmloss_bytes(int H, int W, size_t* bytes) {
+  clear_error();
+  if (H <= 0 || W <= 0 || !bytes) return fail(EOGS_ERR_INVALID_ARG, "cmloss_bytes: bad argument");
+  *bytes = cmloss_ws_bytes();
+  return EOGS_OK;
+}
+
+int eogs_cmloss_forward(int H, int W, int C, const float* alt_diff, const float* rgb_a, const float* rgb_b, const float* uv,
+                        float* out, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "cmloss_forward: bad sizes");
+  if (C < 1 || C > EOGS_CMLOSS_MAX_CHANNELS) return fail(EOGS_ERR_INVALID_ARG, "cmloss_forward: 1 to 4 channels");
+  if (!alt_diff || !rgb_a || !rgb_b || !uv || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "cmloss_forward: NULL argument");
+  if (ws_bytes < cmloss_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "cmloss_forward: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps(PS_MLOSS_FWD, s);
+    mloss_launch_fwd(C, (int64_t)H * W, EOGS_MLOSS_RANDOM, alt_diff, rgb_a, rgb_b, uv, out, reinterpret_cast<float*>(ws_base(ws)), s);
+  }
+  LAUNCH_TRY(s, false, "cmloss_fwd");
+  return EOGS_OK;
+}
+
+int eogs_cmloss_backward(int H, int W, int C, const float* alt_diff, const float* rgb_a, const float* rgb_b, const float* uv,
+                         const float* out, const float* upstream, float* g_alt_diff, float* g_rgb_a, float* g_rgb_b,
+                         void* stream) {
+  clear_error();
+  if (H <= 0 || W <= 0) return fail(EOGS_ERR_INVALID_ARG, "cmloss_backward: bad sizes");
+  if (C < 1 || C > EOGS_CMLOSS_MAX_CHANNELS) return fail(EOGS_ERR_INVALID_ARG, "cmloss_backward: 1 to 4 channels");
+  if (!alt_diff || !rgb_a || !rgb_b || !uv || !out || !upstream || !g_alt_diff)
+    return fail(EOGS_ERR_INVALID_ARG, "cmloss_backward: NULL argument");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    ProfScope ps(PS_MLOSS_BWD, s);
+    mloss_launch_bwd(C, (int64_t)H * W, EOGS_MLOSS_RANDOM, alt_diff, rgb_a, rgb_b, uv, out, upstream, g_alt_diff, g_rgb_a, g_rgb_b, s);
+  }
+  LAUNCH_TRY(s, false, "cmloss_bwd");
   return EOGS_OK;
 }
 
@@ -336,10 +386,10 @@ int eogs_tshadow_forward(int64_t n, const float* a, float* out, void* ws, size_t
   if (!a || !out || !ws) return fail(EOGS_ERR_INVALID_ARG, "tshadow_forward: NULL argument");
   if (ws_bytes < shade_ws_bytes()) return fail(EOGS_ERR_WORKSPACE, "tshadow_forward: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int nb = shade_blocks(n);
+  const int nb = capped_blocks(n, ST, SMAXBLK);
   float* partial = reinterpret_cast<float*>(ws_base(ws));
   hipLaunchKernelGGL(tshadow_fwd_kernel, dim3(nb), dim3(ST), 0, s, n, a, partial);
-  hipLaunchKernelGGL(shade_reduce_kernel<2>, dim3(1), dim3(ST), 0, s, partial, nb, 1, 1.f / (float)n, out);
+  hipLaunchKernelGGL(shade_reduce_kernel<2>, dim3(1), dim3(ST), 0, s, partial, nb, SK, 1, 1.f / (float)n, out);
   LAUNCH_TRY(s, false, "tshadow_fwd");
   return EOGS_OK;
 }
@@ -349,7 +399,7 @@ int eogs_tshadow_backward(int64_t n, const float* a, const float* upstream, floa
   if (n <= 0) return fail(EOGS_ERR_INVALID_ARG, "tshadow_backward: bad size");
   if (!a || !upstream || !g_a) return fail(EOGS_ERR_INVALID_ARG, "tshadow_backward: NULL argument");
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(tshadow_bwd_kernel, dim3(shade_blocks(n)), dim3(ST), 0, s, n, a, upstream, g_a);
+  hipLaunchKernelGGL(tshadow_bwd_kernel, dim3(capped_blocks(n, ST, SMAXBLK)), dim3(ST), 0, s, n, a, upstream, g_a);
   LAUNCH_TRY(s, false, "tshadow_bwd");
   return EOGS_OK;
 }
