@@ -83,6 +83,10 @@ RAFT_MAX_LEVELS, RAFT_MAX_RADIUS = 4, 4  # include/eogs_resample.h EOGS_RAFT_MAX
 RAFT_NO_STAGE = 1  # EOGS_RAFT_NO_STAGE: the lookup's flag
 RAFT_UP_CONVEX, RAFT_UP_BILINEAR = 0, 1  # EOGS_RAFT_UP_*: the upsampling modes
 RAFT_MASK_CHANNELS = 576  # EOGS_RAFT_MASK_CHANNELS
+FLOWNET_MAX_SEGMENTS, FLOWNET_MAX_KERNEL = 3, 7  # EOGS_FLOWNET_MAX_*
+FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_EPI_GATES, FLOWNET_EPI_GRU = 0, 1, 2, 3  # EOGS_FLOWNET_EPI_*: the epilogues
+FLOWNET_IN0_NCHW, FLOWNET_OUT_NCHW = 1, 8  # EOGS_FLOWNET_IN0_NCHW (<< i for segment i), _OUT_NCHW: the convolution's flags
+FLOWNET_UPDATE_PARAMS = 18  # EOGS_FLOWNET_UPDATE_PARAMS
 
 _p = C.c_void_p
 _i = C.c_int
@@ -181,6 +185,15 @@ HEADERS = {
         "eogs_raft_lookup": (_i, [_i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _u, _p]),
         "eogs_raft_stage_info": (_i, [C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
         "eogs_raft_upsample": (_i, [_i, _i, _i, _i, _p, _p, _p, _p]),
+        # the flow network's update block: the channel-last convolution and RAFT-small's step composed of it
+        "eogs_flownet_conv_info": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+        "eogs_flownet_conv_pack_bytes": (_i, [_i, _i, C.POINTER(_i), _i, C.POINTER(_z)]),
+        "eogs_flownet_conv_pack": (_i, [_i, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _p, _p, _z, _p]),
+        "eogs_flownet_conv": (_i, [_i, _i, _i, _i, _i, C.POINTER(_i), _p, _p, _p, _i, _p, _z, _p, _p, _p, _p, _i, _u, _p]),
+        "eogs_flownet_update_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_flownet_update_hidden_offset": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_flownet_update_begin": (_i, [_i, _i, _i, C.POINTER(_p), _p, _p, _p, _z, _p]),
+        "eogs_flownet_update_step": (_i, [_i, _i, _i, _p, _p, _p, _z, _p, _p]),
     },
     "eogs_knn.h": {
         "eogs_knn_bytes": (_i, [_i, C.POINTER(_z)]),

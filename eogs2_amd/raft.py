@@ -4,6 +4,8 @@ flowmatching/flow_matching.py:76-86), with its correlation looked up ON DEMAND o
   corr_pyramid(fmap, levels)                        channel-last feature pyramid in one workspace      one launch per level
   corr_lookup(fmap1_cl, pyramid, coords, radius)    [N, levels (2r+1)^2, h, w] correlation features    one launch
   upsample_flow(flow, mask=None)                    convex (mask) or bilinear x 8 upsampling           one launch
+  conv2d_cl(inputs, weight, bias, act, add)         channel-last convolution on the fp32 matrix cores  pack + one launch
+  FusedUpdate(update_block)                         RAFT-small's update block over that convolution    eight launches per update
   RAFT, raft_small(), raft_large()                  the two published configurations as nn.Modules
   RAFT.load_weights(path_or_state_dict)             a torchvision checkpoint, strict
 
@@ -14,8 +16,14 @@ offset: the on-demand lookup computes (2r+2)^2 dot products per pixel and level 
 them 2 x 2. Memory is linear in n. `corr="volume"` keeps the materialised form in plain torch (matmul, avg_pool2d,
 grid_sample): it is the CPU path and works in any dtype, so a float64 run of the whole network arbitrates the tests.
 
-The convolutions, norms and GRUs are torch modules. Everything here is forward only (the reference runs the network under
-inference_mode); the three operators are float32 and refuse CPU tensors (no CPU fallback).
+The encoders (convolutions, norms) are torch modules, and so is the update block (motion encoder, ConvGRU, flow head) under
+`update="torch"`. Under `update="fused"` RAFT-small's update block runs over the eogs_flownet_* entries of the same header:
+one channel-last convolution kernel on the exact-fp32 matrix instruction with the bias, ReLU, gate and GRU-blend epilogues in
+registers, the context's share of the three GRU convolutions computed once per forward and added as a plane, no torch.cat
+and no layout round trip; the weights stay the torch modules' parameters and are repacked at every forward. `update="auto"`
+follows the measurement of tools/raft_update_probe.py (profiles/raft_update_probe.json; README). Everything here is forward
+only (the reference runs the network under inference_mode); the HIP operators are float32 and refuse CPU tensors (no CPU
+fallback).
 
 The module tree mirrors torchvision.models.optical_flow.raft name for name, so a torchvision state dict loads with
 strict=True. torchvision is not a dependency and its checkpoints were not at hand when this was written: `TORCHVISION_NAMES`
@@ -31,8 +39,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._abi import RAFT_MASK_CHANNELS, RAFT_MAX_LEVELS, RAFT_MAX_RADIUS, RAFT_NO_STAGE, RAFT_UP_BILINEAR, RAFT_UP_CONVEX
-from ._host import Workspaces, call, nbytes, on_device
+from ._abi import (FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_MAX_KERNEL, FLOWNET_MAX_SEGMENTS, FLOWNET_UPDATE_PARAMS,
+                   RAFT_MASK_CHANNELS, RAFT_MAX_LEVELS, RAFT_MAX_RADIUS, RAFT_NO_STAGE, RAFT_UP_BILINEAR, RAFT_UP_CONVEX)
+from ._host import Workspaces, call, nbytes, on_device, query_bytes
 
 _on_device = functools.partial(on_device, "raft", "the correlation lookup runs")
 
@@ -159,6 +168,173 @@ def stage_info():
     abi = _lib.get()
     abi.check(abi.raft_stage_info(ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
     return a.value, b.value, c.value
+
+
+# ---- the update block's convolutions (eogs_flownet_*) ----
+
+def _aligned(t):
+    """`t` detached, contiguous and on a 16-byte boundary (a slice of a larger tensor may start anywhere)."""
+    t = t.detach()
+    t = t if t.is_contiguous() else t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _f32(t, name, what):
+    if not torch.is_tensor(t):
+        raise TypeError(f"raft {what}: expected a tensor for {name}, got {type(t).__name__}")
+    if t.dtype != torch.float32:
+        raise TypeError(f"raft {what}: {name} is float32, not {t.dtype}")
+
+
+def conv_info():
+    """(tile width, tile height) of the convolution kernel: the positions of one image a workgroup owns."""
+    a, b = ctypes.c_int(), ctypes.c_int()
+    abi = _lib.get()
+    abi.check(abi.flownet_conv_info(ctypes.byref(a), ctypes.byref(b)))
+    return a.value, b.value
+
+
+def conv2d_cl(inputs, weight, bias=None, act="none", add=None):
+    """conv2d(cat(inputs), weight, bias, stride 1, padding (k - 1) // 2) (+ add) (then ReLU) on CHANNEL-LAST maps: `inputs` is
+    a list of one to three [N, h, w, C_i] tensors whose concatenation along the channels is never formed, `weight` torch's
+    [Cout, sum C_i, k, k] with k in 1, 3, 5, 7, `bias` [Cout] or None, `add` [N, h, w, Cout] or None; returns [N, h, w, Cout].
+    The weight is repacked at every call (include/eogs_resample.h has the kernel's statement and the order of its sums)."""
+    what = "conv2d_cl"
+    if not isinstance(inputs, (list, tuple)):
+        raise TypeError(f"raft {what}: inputs is a list of channel-last tensors, got {type(inputs).__name__}")
+    if not 1 <= len(inputs) <= FLOWNET_MAX_SEGMENTS:
+        raise ValueError(f"raft {what}: one to {FLOWNET_MAX_SEGMENTS} inputs, got {len(inputs)}")
+    for i, t in enumerate(inputs):
+        _f32(t, f"input {i}", what)
+        if t.ndim != 4 or t.numel() == 0 or t.shape[:3] != inputs[0].shape[:3]:
+            raise ValueError(f"raft {what}: the inputs are non-empty (N, h, w, C_i) tensors of one (N, h, w), got {[tuple(x.shape) for x in inputs]}")
+    _f32(weight, "the weight", what)
+    N, h, w = (int(v) for v in inputs[0].shape[:3])
+    chans = [int(t.shape[3]) for t in inputs]
+    if weight.ndim != 4 or weight.shape[1] != sum(chans) or weight.shape[2] != weight.shape[3] or weight.shape[0] < 1:
+        raise ValueError(f"raft {what}: the weight is (Cout, {sum(chans)}, k, k), got {tuple(weight.shape)}")
+    cout, k = int(weight.shape[0]), int(weight.shape[2])
+    if k % 2 == 0 or k > FLOWNET_MAX_KERNEL:
+        raise ValueError(f"raft {what}: the kernel size is odd and at most {FLOWNET_MAX_KERNEL}, got {k}")
+    if act not in ("none", "relu"):
+        raise ValueError(f"raft {what}: act is 'none' or 'relu', got {act!r}")
+    if bias is not None:
+        _f32(bias, "the bias", what)
+        if tuple(bias.shape) != (cout,):
+            raise ValueError(f"raft {what}: the bias is ({cout},), got {tuple(bias.shape)}")
+    if add is not None:
+        _f32(add, "add", what)
+        if tuple(add.shape) != (N, h, w, cout):
+            raise ValueError(f"raft {what}: add is {(N, h, w, cout)}, got {tuple(add.shape)}")
+    every = list(inputs) + [weight] + [t for t in (bias, add) if t is not None]
+    for t in every:
+        _on_device(t, what)
+    dev = inputs[0].device
+    if any(t.device != dev for t in every):
+        raise RuntimeError(f"raft {what}: the tensors live on different devices")
+    xs = [_aligned(t) for t in inputs] + [None] * (FLOWNET_MAX_SEGMENTS - len(inputs))
+    wt, b, a = _aligned(weight), None if bias is None else _aligned(bias), None if add is None else _aligned(add)
+    seg = (ctypes.c_int * len(chans))(*chans)
+    size = query_bytes(_lib.get(), "flownet_conv_pack_bytes", k, len(chans), seg, cout)
+    packed = Workspaces.bytes(dev, size)
+    call("eogs_flownet_conv_pack", dev, k, len(chans), seg, None, sum(chans), cout, 0, cout, wt.data_ptr(), packed.data_ptr(), size)
+    out = torch.empty((N, h, w, cout), dtype=torch.float32, device=dev)
+    call("eogs_flownet_conv", dev, N, h, w, k, len(chans), seg, *(None if x is None else x.data_ptr() for x in xs), cout,
+         packed.data_ptr(), size, None if b is None else b.data_ptr(), None if a is None else a.data_ptr(), None, out.data_ptr(),
+         FLOWNET_EPI_RELU if act == "relu" else FLOWNET_EPI_BIAS, 0)
+    return out
+
+
+class FusedUpdate:
+    """RAFT-small's `UpdateBlock` over the convolution kernel, with the call order of UpdateBlock.forward split in two:
+
+        fused.begin(hidden_state, context)         once per forward: the NCHW halves of the context encoder after tanh / relu
+        delta = fused.step(corr_features, flow)    once per update: [N, 2, h, w]; the hidden state advances in the workspace
+        fused.hidden()                             the hidden state as [N, 96, h, w]
+
+    It holds the block, not a copy of its weights: `begin` repacks them at every forward, so edited or reloaded weights can
+    never go stale. It is no nn.Module and registers no parameter and no buffer. Float32 on the GPU, forward only."""
+
+    NAMES = ("motion_encoder.convcorr1.0", "motion_encoder.convflow1.0", "motion_encoder.convflow2.0", "motion_encoder.conv.0",
+             "recurrent_block.convgru1.convz", "recurrent_block.convgru1.convr", "recurrent_block.convgru1.convq",
+             "flow_head.conv1", "flow_head.conv2")
+    SHAPES = ((96, 196, 1, 1), (64, 2, 7, 7), (32, 64, 3, 3), (80, 128, 3, 3), (96, 242, 3, 3), (96, 242, 3, 3), (96, 242, 3, 3),
+              (128, 96, 3, 3), (2, 128, 3, 3))
+    HIDDEN, CONTEXT, CORR = 96, 64, 196
+
+    def __init__(self, update_block):
+        if not isinstance(update_block, UpdateBlock):
+            raise TypeError(f"raft FusedUpdate: expected an UpdateBlock, got {type(update_block).__name__}")
+        convs = [update_block.get_submodule(n) for n in self.NAMES]
+        got = tuple(tuple(c.weight.shape) for c in convs)
+        if got != self.SHAPES or not isinstance(update_block.motion_encoder.convcorr2, nn.Identity) or \
+                not isinstance(update_block.recurrent_block.convgru2, nn.Identity):
+            raise ValueError("raft FusedUpdate: the fused update is RAFT-small's (one 1 x 1 correlation convolution, one 3 x 3 GRU); "
+                             f"this block's convolutions are {got}")
+        self._convs = convs
+        self._ws = Workspaces()
+        self._state = None
+
+    def __getstate__(self):  # a copied or pickled module starts without workspaces
+        return {"_convs": self._convs}
+
+    def __setstate__(self, state):
+        self._convs, self._ws, self._state = state["_convs"], Workspaces(), None
+
+    def _params(self, dev):
+        out = []
+        for name, c in zip(self.NAMES, self._convs):
+            for p in (c.weight, c.bias):
+                if p.dtype != torch.float32 or p.device != dev:
+                    raise RuntimeError(f"raft FusedUpdate: {name} is {p.dtype} on {p.device}; the fused update runs in float32 on "
+                                       f"the inputs' device ({dev}), there is no CPU fallback")
+                out.append(_aligned(p))
+        return out
+
+    def begin(self, hidden_state, context):
+        what = "FusedUpdate.begin"
+        N, _, h, w = _map(hidden_state, "the hidden state", what, self.HIDDEN)
+        if _map(context, "the context", what, self.CONTEXT) != (N, self.CONTEXT, h, w):
+            raise ValueError(f"raft {what}: the context is {tuple(context.shape)}, the hidden state asks for {(N, self.CONTEXT, h, w)}")
+        _on_device(hidden_state, what)
+        _on_device(context, what)
+        dev = hidden_state.device
+        if context.device != dev:
+            raise RuntimeError(f"raft {what}: the hidden state and the context live on different devices")
+        params = self._params(dev)
+        assert len(params) == FLOWNET_UPDATE_PARAMS
+        size = nbytes(_lib.get(), "flownet_update_bytes", N, h, w)
+        ws = self._ws.of((N, h, w), dev, lambda: Workspaces.bytes(dev, size))
+        hid, ctx = _aligned(hidden_state), _aligned(context)
+        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
+        call("eogs_flownet_update_begin", dev, N, h, w, table, hid.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws.numel())
+        self._state = (N, h, w, ws)
+
+    def step(self, corr_features, flow):
+        what = "FusedUpdate.step"
+        if self._state is None:
+            raise RuntimeError(f"raft {what}: begin(hidden_state, context) comes first")
+        N, h, w, ws = self._state
+        if _map(corr_features, "the correlation features", what, self.CORR) != (N, self.CORR, h, w) or _map(flow, "the flow", what, 2) != (N, 2, h, w):
+            raise ValueError(f"raft {what}: begin was given {(N, h, w)}; the correlation features are {tuple(corr_features.shape)}, "
+                             f"the flow is {tuple(flow.shape)}")
+        _on_device(corr_features, what)
+        _on_device(flow, what)
+        if corr_features.device != ws.device or flow.device != ws.device:
+            raise RuntimeError(f"raft {what}: the tensors and the workspace live on different devices")
+        corr, fl = _aligned(corr_features), _aligned(flow)
+        delta = torch.empty((N, 2, h, w), dtype=torch.float32, device=ws.device)
+        call("eogs_flownet_update_step", ws.device, N, h, w, corr.data_ptr(), fl.data_ptr(), ws.data_ptr(), ws.numel(), delta.data_ptr())
+        return delta
+
+    def hidden(self):
+        if self._state is None:
+            raise RuntimeError("raft FusedUpdate.hidden: begin(hidden_state, context) comes first")
+        N, h, w, ws = self._state
+        off = nbytes(_lib.get(), "flownet_update_hidden_offset", N, h, w)
+        base = (-ws.data_ptr()) % 256  # the library rounds the pointer up to 256 bytes
+        cl = ws[base + off: base + off + 4 * N * h * w * self.HIDDEN].view(torch.float32).view(N, h, w, self.HIDDEN)
+        return cl.permute(0, 3, 1, 2).contiguous()
 
 
 # ---- the materialised form, in plain torch: any dtype, any device ----
@@ -369,22 +545,38 @@ TORCHVISION_NAMES = {
 }
 
 
+# What update="auto" runs for RAFT-small in float32 on the GPU when no gradient is recorded (inference_mode, no_grad: how the
+# flow-matching step calls it; the fused path has no backward, so with gradients enabled "auto" stays the torch modules). It
+# follows tools/raft_update_probe.py (profiles/raft_update_probe.json): the fused path only if, at 1024^2 and at 2048^2, its
+# slowest turn of the update phase plus `begin` is faster than the torch path's fastest turn of the update phase. Measured:
+# 5.85 + 0.15 ms against 6.49 ms at 1024^2, 13.79 + 0.33 ms against 17.36 ms at 2048^2.
+AUTO_UPDATE_IS_FUSED = True
+
+
 class RAFT(nn.Module):
     """RAFT with torchvision's call shape: `model(image1, image2, num_flow_updates=12) -> list of flows`, images [N, 3, H, W]
     in [-1, 1], H and W multiples of 8 and at least 128. The last entry is the final [N, 2, H, W] flow; with
     return_all=False (the default: flow_matching.py reads [-1] alone) it is the only one.
 
     corr: "ondemand" (the HIP lookup; float32 on the GPU), "volume" (plain torch, any dtype and device) or "auto": on-demand
-    for float32 inputs on the GPU, volume otherwise."""
+    for float32 inputs on the GPU, volume otherwise.
 
-    def __init__(self, name="small", corr="auto"):
+    update: "torch" (the update block as torch modules, any dtype and device), "fused" (FusedUpdate: RAFT-small only, float32
+    on the GPU, forward only, no CPU fallback) or "auto": the fused path for RAFT-small in float32 on the GPU when no gradient
+    is recorded, as the measurement decided (AUTO_UPDATE_IS_FUSED), the torch modules otherwise."""
+
+    def __init__(self, name="small", corr="auto", update="auto"):
         super().__init__()
         if name not in CONFIGS:
             raise ValueError(f"raft RAFT: name is 'small' or 'large', got {name!r}")
         if corr not in ("auto", "ondemand", "volume"):
             raise ValueError(f"raft RAFT: corr is 'auto', 'ondemand' or 'volume', got {corr!r}")
+        if update not in ("auto", "torch", "fused"):
+            raise ValueError(f"raft RAFT: update is 'auto', 'torch' or 'fused', got {update!r}")
+        if update == "fused" and name != "small":
+            raise ValueError(f"raft RAFT: update='fused' is RAFT-small's update block; '{name}' runs update='torch'")
         cfg = CONFIGS[name]
-        self.name, self.corr = name, corr
+        self.name, self.corr, self.update = name, corr, update
         self.corr_levels, self.corr_radius = cfg["corr_levels"], cfg["corr_radius"]
         self.feature_encoder = FeatureEncoder(cfg["block"], cfg["feature_layers"], cfg["feature_norm"])
         self.context_encoder = FeatureEncoder(cfg["block"], cfg["context_layers"], cfg["context_norm"])
@@ -395,6 +587,7 @@ class RAFT(nn.Module):
         recurrent = RecurrentBlock(motion.out_channels + self.context_size, hidden, cfg["gru_kernels"], cfg["gru_paddings"])
         self.update_block = UpdateBlock(motion, recurrent, FlowHead(hidden, cfg["flow_head_hidden"]))
         self.mask_predictor = None if cfg["mask_hidden"] is None else MaskPredictor(hidden, cfg["mask_hidden"])
+        self._fused = FusedUpdate(self.update_block) if name == "small" else None  # (no Module: nothing is registered)
 
     def _ondemand(self, x):
         if self.corr == "volume":
@@ -404,6 +597,15 @@ class RAFT(nn.Module):
             raise RuntimeError(f"raft RAFT: corr='ondemand' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
                                "there is no CPU fallback, corr='volume' is the plain torch form")
         return ok
+
+    def _fused_update(self, x):
+        if self.update == "torch" or self._fused is None:
+            return False
+        ok = x.device.type == "cuda" and x.dtype == torch.float32
+        if self.update == "fused" and not ok:
+            raise RuntimeError(f"raft RAFT: update='fused' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
+                               "there is no CPU fallback, update='torch' is the plain torch form")
+        return ok and (self.update == "fused" or (AUTO_UPDATE_IS_FUSED and not torch.is_grad_enabled()))
 
     def forward(self, image1, image2, num_flow_updates=12, return_all=False):
         N, _, H, W = image1.shape
@@ -416,7 +618,7 @@ class RAFT(nn.Module):
         if h < 16 or w < 16:
             raise ValueError(f"input image H and W should be at least 128, instead got {H} (h) and {W} (w): the feature "
                              "encoder downsamples by 8 and the correlation pyramid by another 8")
-        ondemand = self._ondemand(image1)
+        ondemand, fused = self._ondemand(image1), self._fused_update(image1)
         fmaps = self.feature_encoder(torch.cat([image1, image2], dim=0))
         fmap1, fmap2 = torch.chunk(fmaps, chunks=2, dim=0)
         if ondemand:
@@ -431,6 +633,8 @@ class RAFT(nn.Module):
                                 torch.arange(w, dtype=image1.dtype, device=image1.device), indexing="ij")
         coords0 = torch.stack([xs, ys], dim=0)[None].repeat(N, 1, 1, 1)
         coords1 = coords0.clone()
+        if fused:
+            self._fused.begin(hidden_state, context)
         flows = []
         for it in range(num_flow_updates):
             coords1 = coords1.detach()
@@ -438,7 +642,10 @@ class RAFT(nn.Module):
                 corr_features = corr_lookup(f1cl, pyramid, coords1, self.corr_radius)
             else:
                 corr_features = volume_lookup(pyramid, coords1, self.corr_radius)
-            hidden_state, delta = self.update_block(hidden_state, context, corr_features, coords1 - coords0)
+            if fused:  # (RAFT-small has no mask predictor: the hidden state stays in the workspace)
+                delta = self._fused.step(corr_features, coords1 - coords0)
+            else:
+                hidden_state, delta = self.update_block(hidden_state, context, corr_features, coords1 - coords0)
             coords1 = coords1 + delta
             if return_all or it == num_flow_updates - 1:
                 mask = None if self.mask_predictor is None else self.mask_predictor(hidden_state)
@@ -466,9 +673,9 @@ def _rename(key, table):
     return f"{table.get(head, head)}.{tail}" if tail else table.get(head, head)
 
 
-def raft_small(corr="auto"):
+def raft_small(corr="auto", update="auto"):
     """RAFT-small: bottleneck encoders (128 feature channels), 4 levels at radius 3, one 3 x 3 GRU, bilinear upsampling."""
-    return RAFT("small", corr)
+    return RAFT("small", corr, update)
 
 
 def raft_large(corr="auto"):
@@ -476,5 +683,6 @@ def raft_large(corr="auto"):
     return RAFT("large", corr)
 
 
-__all__ = ["CONFIGS", "CorrPyramid", "RAFT", "TORCHVISION_NAMES", "convex_upsample_torch", "corr_lookup", "corr_pyramid", "raft_large",
-           "raft_small", "stage_info", "upsample_flow", "volume_lookup", "volume_pyramid"]
+__all__ = ["AUTO_UPDATE_IS_FUSED", "CONFIGS", "CorrPyramid", "FusedUpdate", "RAFT", "TORCHVISION_NAMES", "conv2d_cl", "conv_info",
+           "convex_upsample_torch", "corr_lookup", "corr_pyramid", "raft_large", "raft_small", "stage_info", "upsample_flow",
+           "volume_lookup", "volume_pyramid"]

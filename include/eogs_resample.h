@@ -148,6 +148,87 @@ int eogs_raft_stage_info(int* tile_w, int* tile_h, int* max_positions);
  * pointer not 16-byte aligned. */
 int eogs_raft_upsample(int N, int h, int w, int mode, const float* flow, const float* mask, float* out, void* stream);
 
+/* ---- The convolutions of RAFT-small's update block (motion encoder, ConvGRU, flow head): one channel-last convolution on
+ * the exact-fp32 matrix instruction, and the update step composed of eight launches of it. Float32, forward only. The
+ * conventions are those above: no allocation, no waiting, every argument checked before anything touches a device, the
+ * stream last, device pointers 16-byte aligned, no atomics and a fixed order of every sum (bitwise reproducible; a batch
+ * gives the bits of its single images). seg_channels, seg_offsets and params are HOST arrays.
+ *
+ * The convolution: stride 1, zero padding (k - 1) / 2, a cross-correlation as nn.Conv2d's. Its input is the channel
+ * concatenation of nseg <= 3 maps in_i f32[N][h][w][C_i] (no concatenated copy is made), in_i = NULL beyond nseg:
+ *
+ *   v[n][y][x][c] = ((sum over (i, ch, ky, kx) of in_i[n][y + ky - p][x + kx - p][ch] W[c][off_i + ch][ky][kx]) + bias[c]) + add[n][y][x][c]
+ *
+ * with bias and add (f32[N][h][w][Cout]) optional. The sum takes the segments in order, their channels in chunks of eight,
+ * per chunk the taps in row-major order and per tap the chunk's channels ascending, one fused multiply-add per product.
+ * Epilogues:
+ *   EOGS_FLOWNET_EPI_BIAS   out = v
+ *   EOGS_FLOWNET_EPI_RELU   out = v < 0 ? 0 : v (a NaN stays a NaN)
+ *   EOGS_FLOWNET_EPI_GATES  Cout even, aux = h f32[N][h][w][Cout / 2]; out is two maps f32[2][N][h][w][Cout / 2]:
+ *                           out[0] = sigmoid(v[..., :Cout / 2]) (z), out[1] = sigmoid(v[..., Cout / 2:]) * h (r * h)
+ *   EOGS_FLOWNET_EPI_GRU    aux = z f32[N][h][w][Cout]; out holds h and is updated in place: h = (1 - z) h + z tanh(v).
+ *                           out must not be one of the inputs.
+ * Flags: EOGS_FLOWNET_IN0_NCHW << i reads in_i as f32[N][C_i][h][w] (what a torch convolution or the correlation lookup
+ * leaves); EOGS_FLOWNET_OUT_NCHW writes out as f32[N][Cout][h][w] (BIAS and RELU only: the flow head's 128 -> 2 tail writes
+ * delta this way).
+ *
+ * Weights are repacked from torch's f32[cout_n][cin][k][k] by eogs_flownet_conv_pack into the kernel's tap-major layout
+ * (eogs_flownet_conv_pack_bytes): a call fills the columns [cout_off, cout_off + cout_n) of a Cout-wide packing, reading
+ * segment i's channels at seg_offsets[i] of the weight's cin (NULL: the segments are the weight's channels in order and
+ * must sum to cin), so several weight tensors can share one packing and a convolution can be split by input channel.
+ * Padded channel lanes and columns are written as zeros, and the kernel stages zeros for them: nothing uninitialised is
+ * ever multiplied. Once every column has been filled the packing is complete.
+ *
+ * Refused: N, h, w, a segment's channels or Cout below 1 (channels and Cout above 4096, N above 65535, more than 2^31 - 1
+ * elements in a map); k not 1, 3, 5 or 7; nseg outside [1, 3]; segments that do not sum to cin, or lie outside it; columns
+ * outside Cout; an unknown epilogue; unknown flags (a flag of a segment beyond nseg among them); OUT_NCHW with a gate
+ * epilogue; an odd Cout with GATES; aux missing for a gate epilogue or given for another; an input beyond nseg; NULL; a
+ * pointer not 16-byte aligned; a packing too small (EOGS_ERR_WORKSPACE). */
+
+#define EOGS_FLOWNET_MAX_SEGMENTS 3
+#define EOGS_FLOWNET_MAX_KERNEL 7
+#define EOGS_FLOWNET_EPI_BIAS 0
+#define EOGS_FLOWNET_EPI_RELU 1
+#define EOGS_FLOWNET_EPI_GATES 2
+#define EOGS_FLOWNET_EPI_GRU 3
+#define EOGS_FLOWNET_IN0_NCHW 1u
+#define EOGS_FLOWNET_OUT_NCHW 8u
+#define EOGS_FLOWNET_UPDATE_PARAMS 18
+
+/* The kernel's position tile, for tests and probes: a workgroup owns tile_w x tile_h positions of one image. */
+int eogs_flownet_conv_info(int* tile_w, int* tile_h);
+int eogs_flownet_conv_pack_bytes(int k, int nseg, const int* seg_channels, int cout, size_t* bytes);
+int eogs_flownet_conv_pack(int k, int nseg, const int* seg_channels, const int* seg_offsets, int cin, int cout, int cout_off,
+                           int cout_n, const float* weight, void* packed, size_t packed_bytes, void* stream);
+int eogs_flownet_conv(int N, int h, int w, int k, int nseg, const int* seg_channels, const float* in0, const float* in1,
+                      const float* in2, int cout, const void* packed, size_t packed_bytes, const float* bias, const float* add,
+                      const float* aux, float* out, int epilogue, unsigned flags, void* stream);
+
+/* RAFT-small's update block (hidden 96, context 64, correlation 196 = 4 levels at radius 3) over one workspace
+ * (eogs_flownet_update_bytes: packed weights, biases, the hoisted planes, the hidden state and the intermediates;
+ * rounded up to 256 bytes inside, as the pyramid's).
+ *
+ * begin: params are the 18 device pointers weight, bias of convcorr1, convflow1, convflow2, conv (motion encoder), convz,
+ * convr, convq (GRU), conv1, conv2 (flow head) in torch's layouts; hidden f32[N][96][h][w] and context f32[N][64][h][w]
+ * are the context encoder's halves after tanh / relu. It repacks every weight, copies the biases, stores the hidden state
+ * channel-last, and forms the context's share of the three GRU convolutions, which does not change between updates and
+ * is linear under zero padding: with W = [W_h | W_ctx | W_motion | W_flow] along the 242 input channels,
+ *     plane_zr = conv3x3(context, [W_z; W_r]_ctx) + [b_z; b_r]   (192 channels),   plane_q = conv3x3(context, W_q,ctx) + b_q
+ * step: corr f32[N][196][h][w] (the lookup's output) and flow f32[N][2][h][w] are read as they are; eight launches:
+ *     c  = relu(conv1x1(corr) + b)            f1 = relu(conv7x7(flow) + b)       f2 = relu(conv3x3(f1) + b)
+ *     m  = relu(conv3x3([c | f2]) + b)        z, r h = gates(conv3x3([h | m | flow], [W_z; W_r]) + plane_zr)
+ *     h  = (1 - z) h + z tanh(conv3x3([r h | m | flow], W_q) + plane_q)          (in place in the workspace)
+ *     d  = relu(conv3x3(h) + b)               delta f32[N][2][h][w] = conv3x3(d) + b
+ * eogs_flownet_update_hidden_offset: the byte offset of h f32[N][h][w][96] from the workspace's 256-byte aligned base.
+ * Refused: N, h or w below 1; N above 65535; more than 2^31 - 1 elements in a map; NULL (a NULL among params too); a
+ * pointer not 16-byte aligned; a workspace too small (EOGS_ERR_WORKSPACE). */
+int eogs_flownet_update_bytes(int N, int h, int w, size_t* bytes);
+int eogs_flownet_update_hidden_offset(int N, int h, int w, size_t* offset);
+int eogs_flownet_update_begin(int N, int h, int w, const float* const* params, const float* hidden, const float* context, void* ws,
+                              size_t ws_bytes, void* stream);
+int eogs_flownet_update_step(int N, int h, int w, const float* corr, const float* flow, void* ws, size_t ws_bytes, float* delta,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif
