@@ -1,6 +1,7 @@
 """Cases and the float64 oracle of the flow network's update block (eogs2_amd.raft.conv2d_cl / FusedUpdate, the eogs_flownet_*
 entries of include/eogs_resample.h), shared by the CPU test of the oracle itself (tests/test_flownet_cases.py) and the GPU
-tests (tests/test_gpu_flownet.py). Everything is computed from seeds: no fixture, nothing outside the repository.
+tests (tests/test_gpu_flownet.py; tests/test_gpu_flownet_general.py for GENERAL and GATE_CONFIGS, the kernel beyond the update's
+own convolutions). Everything is computed from seeds: no fixture, nothing outside the repository.
 
   conv_oracle     F.conv2d(torch.cat(inputs)) on NCHW views, in the dtype of its inputs (the tests pass float64); with
                   `magnitude=True` |add| + |bias| + conv(|x|, |W|): the M of the error bound
@@ -26,6 +27,32 @@ CONFIGS = (
 )
 SHAPES = ((1, 1, 1), (1, 5, 7), (1, 16, 16), (2, 17, 19))  # (N, h, w); tests add one shape from the kernel's position tile
 STEP_SHAPES = ((1, 16, 16), (2, 17, 19))
+# The kernel beyond the update's eight, in the same form: what each line reaches of csrc/flownet.hip (a chunk is eight input
+# channels, a block sixteen output channels, NB the blocks per workgroup; tests/test_flownet_cases.py holds these claims)
+GENERAL = (
+    # k = 5; NB = 2, the second block with one real column
+    ((3,), 17, 5, False, "none"),
+    # k = 7 over two chunks (the hand-over from a chunk's last tap row to the next chunk's input and first tap row), two
+    # segments; NB = 2, two workgroups along Cout, the last block with two real columns
+    ((8, 8), 50, 7, False, "relu"),
+    # k = 5 over two chunks; seven blocks under NB = 2: the last workgroup's second block is padding throughout
+    ((12,), 112, 5, True, "none"),
+    # three ragged segments (5: one real lane in the chunk's second instruction; 9: a second chunk of one channel; 1);
+    # NB = 3 with 15 padded columns
+    ((5, 9, 1), 33, 3, True, "relu"),
+    # exactly four channels (the boundary at which a chunk's second instruction is skipped), Cout = 1
+    ((4,), 1, 1, False, "none"),
+)
+GENERAL_SHAPES = ((1, 1, 1), (2, 9, 17))  # and the position tile's shape, as above
+LAYOUT_SHAPES = ((2, 9, 17),)             # and the position tile's shape
+# (segments, Cout, k, with add, epilogue): the gate epilogues at the update's sizes and at one small ragged pair
+GATE_CONFIGS = (
+    ((96, 80, 2), 192, 3, True, "gates"),
+    ((96, 80, 2), 96, 3, True, "gru"),
+    ((5, 9, 1), 34, 3, True, "gates"),
+    ((5, 9, 1), 33, 3, True, "gru"),
+)
+CHUNK, BLOCK = 8, 16  # input channels per staged chunk, output channels per block
 HIDDEN, CONTEXT, CORR = 96, 64, 196
 
 
@@ -43,6 +70,20 @@ def conv_case(config, shape, seed):
     bias = torch.randn(cout, generator=g)
     add = torch.randn(N, h, w, cout, generator=g) if with_add else None
     return inputs, weight, bias, add
+
+
+def gate_case(config, shape, seed):
+    """conv_case and the operands of a gate epilogue: (inputs, weight, bias, add, aux, h). GATES: aux = h, tanh(randn) as
+    [N, h, w, Cout / 2]. GRU: aux = z, sigmoid(randn), and h, tanh(randn), what `out` holds before the call, both
+    [N, h, w, Cout]."""
+    segs, cout, k, with_add, epi = config
+    inputs, weight, bias, add = conv_case(config, shape, seed)
+    g = torch.Generator().manual_seed(seed + 1)
+    N, h, w = shape
+    if epi == "gates":
+        hid = torch.tanh(torch.randn(N, h, w, cout // 2, generator=g))
+        return inputs, weight, bias, add, hid, hid
+    return inputs, weight, bias, add, torch.sigmoid(torch.randn(N, h, w, cout, generator=g)), torch.tanh(torch.randn(N, h, w, cout, generator=g))
 
 
 def conv_oracle(inputs, weight, bias, act="none", add=None, magnitude=False):

@@ -34,26 +34,61 @@ def tile_shape():
     return (1, th + 1, 2 * tw + 1)
 
 
-def run_conv(inputs, weight, bias, act="none", add=None):
+EPILOGUES = {"none": "FLOWNET_EPI_BIAS", "relu": "FLOWNET_EPI_RELU", "gates": "FLOWNET_EPI_GATES", "gru": "FLOWNET_EPI_GRU"}
+
+
+def seg_array(chans):
+    return (ctypes.c_int * len(chans))(*chans)
+
+
+def new_packing(dev, chans, cout, k):
+    """A packing of the library's size with every byte 0xFF (a NaN in every float): what a call does not write shows."""
+    from eogs2_amd import _lib
+    from eogs2_amd._host import query_bytes
+
+    size = query_bytes(_lib.get(), "flownet_conv_pack_bytes", k, len(chans), seg_array(chans), cout)
+    return torch.full((size,), 0xFF, dtype=torch.uint8, device=dev)
+
+
+def pack_into(packed, chans, cout, k, weight, cout_off=0, offsets=None):
+    """One eogs_flownet_conv_pack: `weight` [cout_n, cin, k, k] into the columns [cout_off, cout_off + cout_n) of `packed`, its
+    channels read at `offsets` (None: in order)."""
+    from eogs2_amd._host import call
+
+    weight = weight.contiguous()
+    assert weight.shape[2] == weight.shape[3] == k
+    call("eogs_flownet_conv_pack", packed.device, k, len(chans), seg_array(chans), None if offsets is None else seg_array(offsets),
+         weight.shape[1], cout, cout_off, weight.shape[0], weight.data_ptr(), packed.data_ptr(), packed.numel())
+    return packed
+
+
+def run_conv(inputs, weight, bias, act="none", add=None, flags=0, aux=None, out=None, packed=None):
     """The library's two entries with `out` and the packing filled with NaN before the call: what the kernel does not write,
-    or reads without having been given, shows."""
-    from eogs2_amd import _abi, _lib
-    from eogs2_amd._host import call, query_bytes
+    or reads without having been given, shows. `act` names the epilogue ("none", "relu", "gates" with aux = h, "gru" with
+    aux = z and `out` holding h); bit s of `flags` says that inputs[s] is [N, C, h, w], FLOWNET_OUT_NCHW that `out` is;
+    `packed` = (a packing made by the caller, Cout, k) stands in for `weight`; `out` given is written as it is (the caller
+    prefills it), else it is [N, h, w, Cout], [N, Cout, h, w] or the gates' [2, N, h, w, Cout / 2]."""
+    from eogs2_amd import _abi
+    from eogs2_amd._host import call
 
     dev = inputs[0].device
-    N, h, w = inputs[0].shape[:3]
-    chans = [t.shape[3] for t in inputs]
-    cout, k = weight.shape[0], weight.shape[2]
-    seg = (ctypes.c_int * len(chans))(*chans)
-    size = query_bytes(_lib.get(), "flownet_conv_pack_bytes", k, len(chans), seg, cout)
-    packed = torch.full((size,), 0xFF, dtype=torch.uint8, device=dev)  # (all ones: a NaN in every float)
-    out = torch.full((N, h, w, cout), float("nan"), dtype=torch.float32, device=dev)
+    nchw = [bool(flags >> s & 1) for s in range(len(inputs))]
+    N, h, w = (inputs[0].shape[0],) + tuple(inputs[0].shape[2:] if nchw[0] else inputs[0].shape[1:3])
+    chans = [t.shape[1] if f else t.shape[3] for t, f in zip(inputs, nchw)]
+    for t, f, c in zip(inputs, nchw, chans):
+        assert tuple(t.shape) == ((N, c, h, w) if f else (N, h, w, c))
+    if packed is None:
+        cout, k = weight.shape[0], weight.shape[2]
+        packed = pack_into(new_packing(dev, chans, cout, k), chans, cout, k, weight)
+    else:
+        packed, cout, k = packed
+    if out is None:
+        shape = (2, N, h, w, cout // 2) if act == "gates" else (N, cout, h, w) if flags & _abi.FLOWNET_OUT_NCHW else (N, h, w, cout)
+        out = torch.full(shape, float("nan"), dtype=torch.float32, device=dev)
     xs = [t.contiguous() for t in inputs] + [None] * (3 - len(inputs))
-    weight = weight.contiguous()
-    call("eogs_flownet_conv_pack", dev, k, len(chans), seg, None, sum(chans), cout, 0, cout, weight.data_ptr(), packed.data_ptr(), size)
-    call("eogs_flownet_conv", dev, N, h, w, k, len(chans), seg, *(None if x is None else x.data_ptr() for x in xs), cout,
-         packed.data_ptr(), size, None if bias is None else bias.data_ptr(), None if add is None else add.data_ptr(), None,
-         out.data_ptr(), _abi.FLOWNET_EPI_RELU if act == "relu" else _abi.FLOWNET_EPI_BIAS, 0)
+    call("eogs_flownet_conv", dev, N, h, w, k, len(chans), seg_array(chans), *(None if x is None else x.data_ptr() for x in xs), cout,
+         packed.data_ptr(), packed.numel(), None if bias is None else bias.data_ptr(), None if add is None else add.data_ptr(),
+         None if aux is None else aux.data_ptr(), out.data_ptr(), getattr(_abi, EPILOGUES[act]), flags)
     return out
 
 
@@ -62,9 +97,7 @@ def case_on(dev, config, shape, seed):
     return [t.to(dev) for t in inputs], weight.to(dev), bias.to(dev), None if add is None else add.to(dev)
 
 
-@pytest.mark.parametrize("config", fc.CONFIGS, ids=fc.config_id)
-@pytest.mark.parametrize("shape", fc.SHAPES + ("tile",), ids=lambda s: s if isinstance(s, str) else ids(s))
-def test_convolution_against_float64(dev, shape, config):
+def check_against_float64(dev, shape, config):
     """Every element: |hip - f64| <= (K + 2) 2^-24 M with K = k k sum C_i (+ 1 with `add`) and M = |add| + |bias| +
     conv(|x|, |W|) in float64: the standard bound of a length-K float32 fma sum in any fixed order, the bias and the plane.
     ReLU is exact given its argument. The wrapper gives the bits of the entries called by hand, a second run the same bits."""
@@ -89,10 +122,17 @@ def test_convolution_against_float64(dev, shape, config):
 
 
 @pytest.mark.parametrize("config", fc.CONFIGS, ids=fc.config_id)
-def test_convolution_exact_cases(dev, config):
+@pytest.mark.parametrize("shape", fc.SHAPES + ("tile",), ids=lambda s: s if isinstance(s, str) else ids(s))
+def test_convolution_against_float64(dev, shape, config):
+    check_against_float64(dev, shape, config)
+
+
+def check_exact_cases(dev, config, lanes=False):
     """Bit for bit. An all-zero input returns the bias (plus `add`). A single 1.0 at each corner and at the centre, in the
     last channel of every segment, returns bias + the weight's tap at every position of its footprint: the tap orientation
-    (a cross-correlation), the zero padding and the segment offsets. One NaN gives NaN at exactly the k x k footprint."""
+    (a cross-correlation), the zero padding and the segment offsets. One NaN gives NaN at exactly the k x k footprint.
+    With `lanes`, a segment that is no whole number of eight-channel chunks is also given the impulse in its channels 3 and 4,
+    where it has them: the lanes on either side of the boundary between a chunk's two matrix instructions."""
     segs, cout, k, with_add, act = config
     shape = tile_shape()
     N, h, w = shape
@@ -104,8 +144,8 @@ def test_convolution_exact_cases(dev, config):
     assert torch.equal(run_conv(zeros, weight, bias, act, add), fin(plain))
     offset = 0
     for s, C in enumerate(segs):
-        ch = C - 1
-        for (y, x) in ((0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1), (h // 2, w // 2)):
+        chs = sorted({C - 1} | ({c for c in (3, 4) if c < C} if lanes and C % 8 else set()))
+        for ch, (y, x) in ((ch, yx) for ch in chs for yx in ((0, 0), (0, w - 1), (h - 1, 0), (h - 1, w - 1), (h // 2, w // 2))):
             xs = [z.clone() for z in zeros]
             xs[s][0, y, x, ch] = 1.0
             want = bias.expand(N, h, w, cout).clone()
@@ -119,7 +159,7 @@ def test_convolution_exact_cases(dev, config):
             if add is not None:
                 want = want + add
             got = run_conv(xs, weight, bias, act, add)
-            assert torch.equal(got, fin(want)), (s, y, x)
+            assert torch.equal(got, fin(want)), (s, ch, y, x)
             if (y, x) == (h // 2, w // 2):
                 xs[s][0, y, x, ch] = float("nan")
                 nan = torch.isnan(run_conv(xs, weight, bias, act, add))
@@ -129,13 +169,22 @@ def test_convolution_exact_cases(dev, config):
 
 
 @pytest.mark.parametrize("config", fc.CONFIGS, ids=fc.config_id)
-def test_convolution_of_a_batch_is_its_images(dev, config):
-    inputs, weight, bias, add = case_on(dev, config, (2, 17, 19), seed=300)
+def test_convolution_exact_cases(dev, config):
+    check_exact_cases(dev, config)
+
+
+def check_batch_is_its_images(dev, config, shape):
+    inputs, weight, bias, add = case_on(dev, config, shape, seed=300)
     both = run_conv(inputs, weight, bias, config[4], add)
     for n in range(2):
         # (clones: a slice of the batch may start off a 16-byte boundary, which the library refuses)
         one = run_conv([t[n:n + 1].clone() for t in inputs], weight, bias, config[4], None if add is None else add[n:n + 1].clone())
         assert torch.equal(one[0], both[n]), n
+
+
+@pytest.mark.parametrize("config", fc.CONFIGS, ids=fc.config_id)
+def test_convolution_of_a_batch_is_its_images(dev, config):
+    check_batch_is_its_images(dev, config, (2, 17, 19))
 
 
 @pytest.mark.parametrize("shape", fc.STEP_SHAPES, ids=ids)
