@@ -6,6 +6,8 @@ flowmatching/flow_matching.py:76-86), with its correlation looked up ON DEMAND o
   upsample_flow(flow, mask=None)                    convex (mask) or bilinear x 8 upsampling           one launch
   conv2d_cl(inputs, weight, bias, act, add)         channel-last convolution on the fp32 matrix cores  pack + one launch
   FusedUpdate(update_block)                         RAFT-small's update block over that convolution    eight launches per update
+  conv2d_strided_cl(input, weight, ...), finish_cl  the encoders' strided convolution and block tail   pack + one to three launches
+  FusedEncoder(encoder_module)                      one of RAFT-small's two encoders                   one call
   RAFT, raft_small(), raft_large()                  the two published configurations as nn.Modules
   RAFT.load_weights(path_or_state_dict)             a torchvision checkpoint, strict
 
@@ -16,8 +18,11 @@ offset: the on-demand lookup computes (2r+2)^2 dot products per pixel and level 
 them 2 x 2. Memory is linear in n. `corr="volume"` keeps the materialised form in plain torch (matmul, avg_pool2d,
 grid_sample): it is the CPU path and works in any dtype, so a float64 run of the whole network arbitrates the tests.
 
-The encoders (convolutions, norms) are torch modules, and so is the update block (motion encoder, ConvGRU, flow head) under
-`update="torch"`. Under `update="fused"` RAFT-small's update block runs over the eogs_flownet_* entries of the same header:
+The encoders (convolutions, norms) are torch modules under `encoder="torch"`, and so is the update block (motion encoder,
+ConvGRU, flow head) under `update="torch"`. Under `encoder="fused"` RAFT-small's two encoders run over the eogs_flowenc_*
+entries: the same convolution kernel with a stride, the instance norm's statistics summed in double precision by the
+convolution that produces a map and applied by the one that reads it, the bottleneck's residual tail as an epilogue;
+`encoder="auto"` follows tools/raft_encoder_probe.py (profiles/raft_encoder_probe.json; README). Under `update="fused"` RAFT-small's update block runs over the eogs_flownet_* entries of the same header:
 one channel-last convolution kernel on the exact-fp32 matrix instruction with the bias, ReLU, gate and GRU-blend epilogues in
 registers, the context's share of the three GRU convolutions computed once per forward and added as a plane, no torch.cat
 and no layout round trip; the weights stay the torch modules' parameters and are repacked at every forward. `update="auto"`
@@ -39,7 +44,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._abi import (FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_MAX_KERNEL, FLOWNET_MAX_SEGMENTS, FLOWNET_UPDATE_PARAMS,
+from ._abi import (FLOWENC_CONTEXT, FLOWENC_EPI_BIAS, FLOWENC_EPI_RELU, FLOWENC_EPI_RESIDUAL, FLOWENC_FEATURE, FLOWENC_IN_NCHW,
+                   FLOWENC_OUT_NCHW, FLOWENC_PARAMS, FLOWENC_SHORTCUT_NONE, FLOWENC_SHORTCUT_NORM, FLOWENC_SHORTCUT_PLAIN,
+                   FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_MAX_KERNEL, FLOWNET_MAX_SEGMENTS, FLOWNET_UPDATE_PARAMS,
                    RAFT_MASK_CHANNELS, RAFT_MAX_LEVELS, RAFT_MAX_RADIUS, RAFT_NO_STAGE, RAFT_UP_BILINEAR, RAFT_UP_CONVEX)
 from ._host import Workspaces, call, nbytes, on_device, query_bytes
 
@@ -337,6 +344,213 @@ class FusedUpdate:
         return cl.permute(0, 3, 1, 2).contiguous()
 
 
+# ---- the encoders' convolutions (eogs_flowenc_*) ----
+
+def conv2d_strided_cl(input, weight, bias=None, stride=1, act="none", in_norm=None, res=None, stats=False, in_nchw=False,
+                      out_nchw=False):
+    """conv2d(x, weight, bias, stride 1 or 2, padding (k - 1) // 2) of ONE map, k in 1, 3, 7: `input` [N, h, w, Cin]
+    (channel-last; [N, Cin, h, w] with in_nchw), `weight` torch's [Cout, Cin, k, k], `bias` [Cout] or None. With `in_norm`
+    [N, Cin, 2] = (mean, rstd), x = max((input - mean) * rstd, 0), else x = input. act "none" or "relu"; with `res`
+    [N, h', w', Cout] (act must be "relu") the result is relu(res + relu(v)). Returns [N, h', w', Cout] ([N, Cout, h', w'] with
+    out_nchw, act "none" only), h' = ceil(h / stride). stats=True (act "none" only) returns (out, norm): norm [N, Cout, 2] is
+    (mean, rstd) of the stored map per image and channel (include/eogs_resample.h has the statement)."""
+    what = "conv2d_strided_cl"
+    _f32(input, "the input", what)
+    _f32(weight, "the weight", what)
+    if input.ndim != 4 or input.numel() == 0:
+        raise ValueError(f"raft {what}: the input is a non-empty 4-d tensor, got {tuple(input.shape)}")
+    N, h, w, cin = (int(v) for v in (input.shape if not in_nchw else (input.shape[0], input.shape[2], input.shape[3], input.shape[1])))
+    if weight.ndim != 4 or weight.shape[1] != cin or weight.shape[2] != weight.shape[3] or weight.shape[0] < 1:
+        raise ValueError(f"raft {what}: the weight is (Cout, {cin}, k, k), got {tuple(weight.shape)}")
+    cout, k = int(weight.shape[0]), int(weight.shape[2])
+    if k not in (1, 3, 7):
+        raise ValueError(f"raft {what}: the kernel size is 1, 3 or 7, got {k}")
+    if stride not in (1, 2):
+        raise ValueError(f"raft {what}: the stride is 1 or 2, got {stride!r}")
+    if act not in ("none", "relu"):
+        raise ValueError(f"raft {what}: act is 'none' or 'relu', got {act!r}")
+    ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
+    if bias is not None:
+        _f32(bias, "the bias", what)
+        if tuple(bias.shape) != (cout,):
+            raise ValueError(f"raft {what}: the bias is ({cout},), got {tuple(bias.shape)}")
+    if in_norm is not None:
+        _f32(in_norm, "in_norm", what)
+        if tuple(in_norm.shape) != (N, cin, 2):
+            raise ValueError(f"raft {what}: in_norm is {(N, cin, 2)}, got {tuple(in_norm.shape)}")
+    if res is not None:
+        _f32(res, "res", what)
+        if tuple(res.shape) != (N, ho, wo, cout):
+            raise ValueError(f"raft {what}: res is {(N, ho, wo, cout)}, got {tuple(res.shape)}")
+        if act != "relu":
+            raise ValueError(f"raft {what}: res closes a block as relu(res + relu(v)): act must be 'relu'")
+    if (stats or out_nchw) and act != "none":
+        raise ValueError(f"raft {what}: stats and out_nchw go with act='none' only")
+    every = [input, weight] + [t for t in (bias, in_norm, res) if t is not None]
+    for t in every:
+        _on_device(t, what)
+    dev = input.device
+    if any(t.device != dev for t in every):
+        raise RuntimeError(f"raft {what}: the tensors live on different devices")
+    x, wt = _aligned(input), _aligned(weight)
+    b, tn, r = (None if t is None else _aligned(t) for t in (bias, in_norm, res))
+    seg = (ctypes.c_int * 1)(cin)
+    size = query_bytes(_lib.get(), "flownet_conv_pack_bytes", k, 1, seg, cout)
+    packed = Workspaces.bytes(dev, size)
+    call("eogs_flownet_conv_pack", dev, k, 1, seg, None, cin, cout, 0, cout, wt.data_ptr(), packed.data_ptr(), size)
+    out = torch.empty((N, cout, ho, wo) if out_nchw else (N, ho, wo, cout), dtype=torch.float32, device=dev)
+    partials, pbytes = None, 0
+    if stats:
+        rows, nb = ctypes.c_int(), ctypes.c_size_t()
+        abi = _lib.get()
+        abi.check(abi.flowenc_conv_partials(N, ho, wo, cout, ctypes.byref(rows), ctypes.byref(nb)))
+        pbytes = nb.value
+        partials = torch.empty(pbytes // 8, dtype=torch.float64, device=dev)
+    epi = FLOWENC_EPI_RESIDUAL if res is not None else FLOWENC_EPI_RELU if act == "relu" else FLOWENC_EPI_BIAS
+    opt = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    call("eogs_flowenc_conv", dev, N, h, w, cin, cout, k, stride, x.data_ptr(), opt(tn), packed.data_ptr(), size, opt(b), opt(r),
+         out.data_ptr(), opt(partials), pbytes, epi, (FLOWENC_IN_NCHW if in_nchw else 0) | (FLOWENC_OUT_NCHW if out_nchw else 0))
+    if not stats:
+        return out
+    norm = torch.empty((N, cout, 2), dtype=torch.float32, device=dev)
+    call("eogs_flowenc_norm", dev, N, ho, wo, cout, partials.data_ptr(), pbytes, norm.data_ptr())
+    return out, norm
+
+
+def finish_cl(v, norm_v, s=None, norm_s=None):
+    """relu(S + relu((v - mean_v) * rstd_v)) on channel-last maps [N, h, w, C], C a multiple of 4, with norm_v [N, C, 2] =
+    (mean, rstd): S = 0 without `s` (the stem: relu of the normalised map), S = s with `s` alone (a block's input), S =
+    (s - mean_s) * rstd_s with `norm_s` too (the normalised downsample)."""
+    what = "finish_cl"
+    _f32(v, "v", what)
+    _f32(norm_v, "norm_v", what)
+    if v.ndim != 4 or v.numel() == 0 or v.shape[3] % 4:
+        raise ValueError(f"raft {what}: v is a non-empty (N, h, w, C) tensor with C a multiple of 4, got {tuple(v.shape)}")
+    N, h, w, C = (int(x) for x in v.shape)
+    if tuple(norm_v.shape) != (N, C, 2):
+        raise ValueError(f"raft {what}: norm_v is {(N, C, 2)}, got {tuple(norm_v.shape)}")
+    if norm_s is not None and s is None:
+        raise ValueError(f"raft {what}: norm_s normalises s, which is missing")
+    if s is not None:
+        _f32(s, "s", what)
+        if s.shape != v.shape:
+            raise ValueError(f"raft {what}: s is {tuple(v.shape)}, got {tuple(s.shape)}")
+    if norm_s is not None:
+        _f32(norm_s, "norm_s", what)
+        if tuple(norm_s.shape) != (N, C, 2):
+            raise ValueError(f"raft {what}: norm_s is {(N, C, 2)}, got {tuple(norm_s.shape)}")
+    every = [v, norm_v] + [t for t in (s, norm_s) if t is not None]
+    for t in every:
+        _on_device(t, what)
+    dev = v.device
+    if any(t.device != dev for t in every):
+        raise RuntimeError(f"raft {what}: the tensors live on different devices")
+    a, ta = _aligned(v), _aligned(norm_v)
+    b, tb = (None if t is None else _aligned(t) for t in (s, norm_s))
+    out = torch.empty_like(a)
+    mode = FLOWENC_SHORTCUT_NONE if s is None else FLOWENC_SHORTCUT_PLAIN if norm_s is None else FLOWENC_SHORTCUT_NORM
+    call("eogs_flowenc_finish", dev, N, h, w, C, a.data_ptr(), ta.data_ptr(), None if b is None else b.data_ptr(),
+         None if tb is None else tb.data_ptr(), mode, out.data_ptr())
+    return out
+
+
+class FusedEncoder:
+    """One of RAFT-small's two encoders (a `FeatureEncoder` of bottleneck blocks, widths 32, 32, 64, 96, with InstanceNorm2d and
+    a 128-channel head, or without a norm and a 160-channel head) as one call: `fused(image [N, 3, H, W]) -> [N, C, h, w]`,
+    what the module's forward returns. It holds the module, not a copy of its weights: they are repacked at every call, so
+    edited or reloaded weights can never go stale. It is no nn.Module and registers nothing. It keeps its workspace between
+    calls, one per (device, stream, image shape) and at most MAX_WORKSPACES of them: a workspace is 144 MB per image at 1024^2
+    and 575 MB at 2048^2, so a caller whose image sizes vary must not collect one per size; the one least recently made is
+    dropped. Float32 on the GPU, forward only."""
+
+    WIDTHS = (32, 32, 64, 96)
+    MAX_WORKSPACES = 2
+
+    def __init__(self, encoder_module):
+        what = "raft FusedEncoder"
+        if not isinstance(encoder_module, FeatureEncoder):
+            raise TypeError(f"{what}: expected a FeatureEncoder, got {type(encoder_module).__name__}")
+        names, shapes = ["convnormrelu.0"], [(32, 3, 7, 7)]
+        for L in (1, 2, 3):
+            for B in (0, 1):
+                block = getattr(encoder_module, f"layer{L}")[B]
+                if not isinstance(block, BottleneckBlock):
+                    raise ValueError(f"{what}: the fused encoders are RAFT-small's, of bottleneck blocks; layer{L}.{B} is a {type(block).__name__}")
+                cin, cout = self.WIDTHS[L - 1] if B == 0 else self.WIDTHS[L], self.WIDTHS[L]
+                names += [f"layer{L}.{B}.convnormrelu{i}.0" for i in (1, 2, 3)]
+                shapes += [(cout // 4, cin, 1, 1), (cout // 4, cout // 4, 3, 3), (cout, cout // 4, 1, 1)]
+                if B == 0 and L > 1:
+                    if isinstance(block.downsample, nn.Identity):
+                        raise ValueError(f"{what}: layer{L}.0 has no downsample; RAFT-small's halves the map there")
+                    names.append(f"layer{L}.{B}.downsample.0")
+                    shapes.append((cout, cin, 1, 1))
+                elif not isinstance(block.downsample, nn.Identity):
+                    raise ValueError(f"{what}: layer{L}.{B} has a downsample; RAFT-small's has none there")
+        names.append("conv")
+        convs = [encoder_module.get_submodule(n) for n in names]
+        norms = []
+        for n in names[:-1]:
+            unit = encoder_module.get_submodule(n.rsplit(".", 1)[0])
+            norms += [(n, m) for m in list(unit)[1:] if not isinstance(m, nn.ReLU)]
+        normed = bool(norms)
+        for n, m in norms:
+            if not isinstance(m, nn.InstanceNorm2d) or m.affine or m.track_running_stats or m.eps != 1e-5:
+                raise ValueError(f"{what}: the norm is InstanceNorm2d without affine and running statistics, eps 1e-5, or none; "
+                                 f"{n.rsplit('.', 1)[0]} has {m}")
+        if normed and len(norms) != len(names) - 1:
+            raise ValueError(f"{what}: a norm after every convolution but the head, or none; {len(norms)} of {len(names) - 1} have one")
+        shapes.append((128 if normed else 160, 96, 1, 1))
+        got = tuple(tuple(c.weight.shape) for c in convs)
+        strides = tuple(c.stride[0] for c in convs)
+        want_strides = tuple(2 if n in ("convnormrelu.0", "layer2.0.convnormrelu2.0", "layer3.0.convnormrelu2.0", "layer2.0.downsample.0",
+                                        "layer3.0.downsample.0") else 1 for n in names)
+        if got != tuple(shapes) or strides != want_strides or any(c.bias is None for c in convs):
+            raise ValueError(f"{what}: the fused encoders are RAFT-small's (widths 32, 32, 64, 96, a head of 128 with the norm and of "
+                             f"160 without); this encoder's convolutions are {got} with strides {strides}")
+        assert 2 * len(convs) == FLOWENC_PARAMS
+        self._names, self._convs, self.kind, self.channels = tuple(names), convs, FLOWENC_FEATURE if normed else FLOWENC_CONTEXT, shapes[-1][0]
+        self._ws = Workspaces()
+
+    def __getstate__(self):  # a copied or pickled module starts without workspaces
+        return {"_names": self._names, "_convs": self._convs, "kind": self.kind, "channels": self.channels}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._ws = Workspaces()
+
+    def _params(self, dev):
+        out = []
+        for name, c in zip(self._names, self._convs):
+            for p in (c.weight, c.bias):
+                if p.dtype != torch.float32 or p.device != dev:
+                    raise RuntimeError(f"raft FusedEncoder: {name} is {p.dtype} on {p.device}; the fused encoder runs in float32 on "
+                                       f"the image's device ({dev}), there is no CPU fallback")
+                out.append(_aligned(p))
+        return out
+
+    def workspace_bytes(self, N, H, W):
+        return nbytes(_lib.get(), "flowenc_bytes", int(N), int(H), int(W), self.kind)
+
+    def __call__(self, image):
+        what = "FusedEncoder"
+        N, _, H, W = _map(image, "the image", what, 3)
+        _on_device(image, what)
+        dev = image.device
+        params = self._params(dev)
+        size = self.workspace_bytes(N, H, W)
+        ws = self._ws.of((N, H, W), dev, lambda: Workspaces.bytes(dev, size))
+        while len(self._ws) > self.MAX_WORKSPACES:  # (the allocator frees in stream order: a launch in flight keeps its memory)
+            del self._ws[next(k for k, v in self._ws.items() if v is not ws)]
+        x = _aligned(image)
+        h, w = H, W
+        for _ in range(3):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        out = torch.empty((N, self.channels, h, w), dtype=torch.float32, device=dev)
+        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
+        call("eogs_flowenc_run", dev, N, H, W, self.kind, table, x.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr())
+        return out
+
+
 # ---- the materialised form, in plain torch: any dtype, any device ----
 
 def volume_pyramid(fmap1, fmap2, levels):
@@ -552,6 +766,13 @@ TORCHVISION_NAMES = {
 # 5.85 + 0.15 ms against 6.49 ms at 1024^2, 13.79 + 0.33 ms against 17.36 ms at 2048^2.
 AUTO_UPDATE_IS_FUSED = True
 
+# What encoder="auto" runs under the same conditions. It follows tools/raft_encoder_probe.py (profiles/raft_encoder_probe.json):
+# the fused encoders only if, at 1024^2 and at 2048^2, the slowest fused turn of the encoder phase (the feature encoder on the
+# two images, then the context encoder) is faster than the fastest torch turn. Measured
+# (fused median, min - max against torch): 1.80 ms (1.80 - 1.98) against 3.68 ms (3.67 - 3.80) at 1024^2, 5.62 ms (5.59 - 5.66) against
+# 13.65 ms (13.62 - 13.77) at 2048^2; the fused encoders hold 0.43 and 1.72 GB of workspace there and peak HIGHER in memory. RAFT's default stays encoder="torch": "auto" is what an integrator asks for.
+AUTO_ENCODER_IS_FUSED = True
+
 
 class RAFT(nn.Module):
     """RAFT with torchvision's call shape: `model(image1, image2, num_flow_updates=12) -> list of flows`, images [N, 3, H, W]
@@ -563,9 +784,13 @@ class RAFT(nn.Module):
 
     update: "torch" (the update block as torch modules, any dtype and device), "fused" (FusedUpdate: RAFT-small only, float32
     on the GPU, forward only, no CPU fallback) or "auto": the fused path for RAFT-small in float32 on the GPU when no gradient
-    is recorded, as the measurement decided (AUTO_UPDATE_IS_FUSED), the torch modules otherwise."""
+    is recorded, as the measurement decided (AUTO_UPDATE_IS_FUSED), the torch modules otherwise.
 
-    def __init__(self, name="small", corr="auto", update="auto"):
+    encoder: "torch" (the two encoders as torch modules, any dtype and device; the default), "fused" (FusedEncoder: RAFT-small
+    only, float32 on the GPU, forward only, no CPU fallback) or "auto": the fused encoders for RAFT-small in float32 on the
+    GPU when no gradient is recorded and the measurement decided for them (AUTO_ENCODER_IS_FUSED), the torch modules otherwise."""
+
+    def __init__(self, name="small", corr="auto", update="auto", encoder="torch"):
         super().__init__()
         if name not in CONFIGS:
             raise ValueError(f"raft RAFT: name is 'small' or 'large', got {name!r}")
@@ -575,8 +800,12 @@ class RAFT(nn.Module):
             raise ValueError(f"raft RAFT: update is 'auto', 'torch' or 'fused', got {update!r}")
         if update == "fused" and name != "small":
             raise ValueError(f"raft RAFT: update='fused' is RAFT-small's update block; '{name}' runs update='torch'")
+        if encoder not in ("auto", "torch", "fused"):
+            raise ValueError(f"raft RAFT: encoder is 'auto', 'torch' or 'fused', got {encoder!r}")
+        if encoder == "fused" and name != "small":
+            raise ValueError(f"raft RAFT: encoder='fused' is RAFT-small's encoders; '{name}' runs encoder='torch'")
         cfg = CONFIGS[name]
-        self.name, self.corr, self.update = name, corr, update
+        self.name, self.corr, self.update, self.encoder = name, corr, update, encoder
         self.corr_levels, self.corr_radius = cfg["corr_levels"], cfg["corr_radius"]
         self.feature_encoder = FeatureEncoder(cfg["block"], cfg["feature_layers"], cfg["feature_norm"])
         self.context_encoder = FeatureEncoder(cfg["block"], cfg["context_layers"], cfg["context_norm"])
@@ -588,6 +817,7 @@ class RAFT(nn.Module):
         self.update_block = UpdateBlock(motion, recurrent, FlowHead(hidden, cfg["flow_head_hidden"]))
         self.mask_predictor = None if cfg["mask_hidden"] is None else MaskPredictor(hidden, cfg["mask_hidden"])
         self._fused = FusedUpdate(self.update_block) if name == "small" else None  # (no Module: nothing is registered)
+        self._fused_enc = (FusedEncoder(self.feature_encoder), FusedEncoder(self.context_encoder)) if name == "small" else None
 
     def _ondemand(self, x):
         if self.corr == "volume":
@@ -607,6 +837,15 @@ class RAFT(nn.Module):
                                "there is no CPU fallback, update='torch' is the plain torch form")
         return ok and (self.update == "fused" or (AUTO_UPDATE_IS_FUSED and not torch.is_grad_enabled()))
 
+    def _fused_encoder(self, x):
+        if self.encoder == "torch" or self._fused_enc is None:
+            return False
+        ok = x.device.type == "cuda" and x.dtype == torch.float32
+        if self.encoder == "fused" and not ok:
+            raise RuntimeError(f"raft RAFT: encoder='fused' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
+                               "there is no CPU fallback, encoder='torch' is the plain torch form")
+        return ok and (self.encoder == "fused" or (AUTO_ENCODER_IS_FUSED and not torch.is_grad_enabled()))
+
     def forward(self, image1, image2, num_flow_updates=12, return_all=False):
         N, _, H, W = image1.shape
         if image1.shape != image2.shape:
@@ -618,15 +857,16 @@ class RAFT(nn.Module):
         if h < 16 or w < 16:
             raise ValueError(f"input image H and W should be at least 128, instead got {H} (h) and {W} (w): the feature "
                              "encoder downsamples by 8 and the correlation pyramid by another 8")
-        ondemand, fused = self._ondemand(image1), self._fused_update(image1)
-        fmaps = self.feature_encoder(torch.cat([image1, image2], dim=0))
+        ondemand, fused, fused_enc = self._ondemand(image1), self._fused_update(image1), self._fused_encoder(image1)
+        feature_encoder, context_encoder = self._fused_enc if fused_enc else (self.feature_encoder, self.context_encoder)
+        fmaps = feature_encoder(torch.cat([image1, image2], dim=0))
         fmap1, fmap2 = torch.chunk(fmaps, chunks=2, dim=0)
         if ondemand:
             f1cl = corr_pyramid(fmap1, 1)
             pyramid = corr_pyramid(fmap2, self.corr_levels)
         else:
             pyramid = volume_pyramid(fmap1, fmap2, self.corr_levels)
-        context_out = self.context_encoder(image1)
+        context_out = context_encoder(image1)
         hidden_state, context = torch.split(context_out, [self.update_block.hidden_state_size, self.context_size], dim=1)
         hidden_state, context = torch.tanh(hidden_state), F.relu(context)
         ys, xs = torch.meshgrid(torch.arange(h, dtype=image1.dtype, device=image1.device),
@@ -673,16 +913,17 @@ def _rename(key, table):
     return f"{table.get(head, head)}.{tail}" if tail else table.get(head, head)
 
 
-def raft_small(corr="auto", update="auto"):
+def raft_small(corr="auto", update="auto", encoder="torch"):
     """RAFT-small: bottleneck encoders (128 feature channels), 4 levels at radius 3, one 3 x 3 GRU, bilinear upsampling."""
-    return RAFT("small", corr, update)
+    return RAFT("small", corr, update, encoder)
 
 
-def raft_large(corr="auto"):
-    """RAFT-large: residual encoders (256 feature channels), 4 levels at radius 4, 1 x 5 + 5 x 1 GRUs, convex upsampling."""
-    return RAFT("large", corr)
+def raft_large(corr="auto", encoder="torch"):
+    """RAFT-large: residual encoders (256 feature channels), 4 levels at radius 4, 1 x 5 + 5 x 1 GRUs, convex upsampling.
+    Its encoders are torch modules: encoder="fused" is refused."""
+    return RAFT("large", corr, encoder=encoder)
 
 
-__all__ = ["AUTO_UPDATE_IS_FUSED", "CONFIGS", "CorrPyramid", "FusedUpdate", "RAFT", "TORCHVISION_NAMES", "conv2d_cl", "conv_info",
-           "convex_upsample_torch", "corr_lookup", "corr_pyramid", "raft_large", "raft_small", "stage_info", "upsample_flow",
-           "volume_lookup", "volume_pyramid"]
+__all__ = ["AUTO_ENCODER_IS_FUSED", "AUTO_UPDATE_IS_FUSED", "CONFIGS", "CorrPyramid", "FusedEncoder", "FusedUpdate", "RAFT",
+           "TORCHVISION_NAMES", "conv2d_cl", "conv2d_strided_cl", "conv_info", "convex_upsample_torch", "corr_lookup", "corr_pyramid",
+           "finish_cl", "raft_large", "raft_small", "stage_info", "upsample_flow", "volume_lookup", "volume_pyramid"]

@@ -238,6 +238,10 @@ def main(argv=None):
                     help="with --flow-network small: how RAFT's update block runs, eogs2_amd.raft.RAFT(update=...): 'torch' (torch "
                          "modules), 'fused' (the eogs_flownet_* convolutions of include/eogs_resample.h, RAFT-small only) or 'auto' "
                          "(what profiles/raft_update_probe.json measured as faster)")
+    ap.add_argument("--flow-encoder", choices=["torch", "fused", "auto"], default="torch", metavar="HOW",
+                    help="with --flow-network small: how RAFT's two encoders run, eogs2_amd.raft.RAFT(encoder=...): 'torch' (torch "
+                         "modules), 'fused' (the eogs_flowenc_* convolutions of include/eogs_resample.h, RAFT-small only) or 'auto' "
+                         "(what profiles/raft_encoder_probe.json measured as faster)")
     ap.add_argument("--flow-weights", default=None, metavar="PATH",
                     help="with --flow-network: a torchvision RAFT checkpoint of that configuration (raft_small / raft_large state "
                          "dict), loaded strictly by eogs2_amd.raft.RAFT.load_weights; nothing is downloaded")
@@ -407,6 +411,8 @@ def main(argv=None):
         ap.error("--flow-weights needs --flow-network small|large")
     if a.flow_update == "fused" and a.flow_network != "small":
         ap.error("--flow-update fused needs --flow-network small")
+    if a.flow_encoder == "fused" and a.flow_network != "small":
+        ap.error("--flow-encoder fused needs --flow-network small")
     if a.flow_network and (a.size < 121 or a.graph):
         ap.error("--flow-network: RAFT needs images of at least 128 px after rounding up to a multiple of 8 (--size >= 121), and is "
                  "not recorded into a graph here (not with --graph)")
@@ -570,7 +576,7 @@ def main(argv=None):
         if a.flow_network:
             from eogs2_amd import raft
 
-            flow_model = raft.RAFT(a.flow_network, update=a.flow_update).eval().to(dev)
+            flow_model = raft.RAFT(a.flow_network, update=a.flow_update, encoder=a.flow_encoder).eval().to(dev)
             if a.flow_weights:
                 flow_model.load_weights(a.flow_weights)
         warper = performOpticalmatching(True, mode="upscale", device=dev, model_name=a.flow_network or "small", criteria="max_value_flow",

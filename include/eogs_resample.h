@@ -229,6 +229,96 @@ int eogs_flownet_update_begin(int N, int h, int w, const float* const* params, c
 int eogs_flownet_update_step(int N, int h, int w, const float* corr, const float* flow, void* ws, size_t ws_bytes, float* delta,
                              void* stream);
 
+/* ---- RAFT-small's two encoders (bottleneck blocks of 8, 16 and 24 mid channels behind a 7 x 7 stride-2 stem, a 1 x 1 head;
+ * the feature encoder with an instance norm and a ReLU after every convolution, the context encoder with the ReLU alone):
+ * the convolution above with a stride, the producer's norm applied on load, the block's residual tail and the map's
+ * statistics; the kernel that makes (mean, rstd) of them; the pointwise pass that closes a normalised block; and each
+ * encoder as one call. Float32, forward only, RAFT-small only. Every convention above holds: no allocation, no waiting,
+ * every argument checked before anything touches a device, the stream last, device pointers 16-byte aligned, no atomics,
+ * a fixed order of every sum (bitwise reproducible; a batch gives the bits of its single images). params is a HOST array.
+ *
+ * eogs_flowenc_conv: one input map of cin channels, k in {1, 3, 7}, stride s in {1, 2}, zero padding p = (k - 1) / 2, output
+ * h' x w' = ceil(h / s) x ceil(w / s); a cross-correlation as nn.Conv2d's:
+ *
+ *   sum[n][y][x][c] = sum over (ch, ky, kx) of X[n][s y + ky - p][s x + kx - p][ch] W[c][ch][ky][kx]
+ *
+ * in eogs_flownet_conv's order: the channels in chunks of eight, per chunk the taps in row-major order, per tap the chunk's
+ * channels ascending, one fused multiply-add per product. The weights are packed by eogs_flownet_conv_pack with nseg = 1
+ * (eogs_flownet_conv_pack_bytes). The input is in f32[N][h][w][cin], or f32[N][cin][h][w] under EOGS_FLOWENC_IN_NCHW (the
+ * image of the 7 x 7 stem). With in_norm f32[N][cin][2] = (mean, rstd) per image and channel, the value multiplied is
+ *   X = max((in - mean) * rstd, 0)
+ * as two separately rounded float32 operations and a select that keeps a NaN: the producer's instance norm and ReLU,
+ * applied on load (positions outside the map stay zeros: the padding is the normalised map's). Without in_norm, X = in.
+ * Epilogues, with v = sum + bias[c] (bias may be NULL: v = sum):
+ *   EOGS_FLOWENC_EPI_BIAS      out = v
+ *   EOGS_FLOWENC_EPI_RELU      out = v < 0 ? 0 : v (a NaN stays a NaN)
+ *   EOGS_FLOWENC_EPI_RESIDUAL  out = relu(res + relu(v)), res f32[N][h'][w'][cout]: a bottleneck's tail where there is no norm
+ * out is f32[N][h'][w'][cout], or f32[N][cout][h'][w'] under EOGS_FLOWENC_OUT_NCHW (BIAS only: the heads).
+ * With partials given (BIAS only; eogs_flowenc_conv_partials gives rows and bytes: f64[N][rows][cout][2], one row per
+ * workgroup's 16 x 8 tile of output positions), each workgroup also stores per output channel the double-precision sum and
+ * sum of squares of the float32 values it stored, over its valid positions: per lane its rows ascending and per row its four
+ * positions ascending, the four lanes of a channel by the butterfly (offsets 32, 16), the four waves left to right.
+ * Refused: N, h, w, cin or cout below 1 (cin and cout above 4096, N above 65535, more than 2^31 - 1 elements in the input
+ * or the output map); k not 1, 3 or 7; a stride not 1 or 2; an unknown epilogue; unknown flags; OUT_NCHW or partials with an
+ * epilogue other than BIAS; res missing for RESIDUAL or given for another; NULL in, packed or out; a pointer not 16-byte
+ * aligned; a packing or partials too small (EOGS_ERR_WORKSPACE).
+ *
+ * eogs_flowenc_norm: stage 2 of the two-stage sum over the partials of an h x w map of C channels (h, w: the
+ * convolution's OUTPUT size): one workgroup of 256 threads per (channel, image), thread t adds rows t, t + 256, ... in that
+ * order, then the butterfly and the four waves left to right. In double, with n = h w:
+ *   mean = S1 / n,   var = max(S2 / n - mean^2, 0) (biased; a NaN stays a NaN),   rstd = 1 / sqrt(var + 1e-5)
+ * mean and rstd are rounded to float32 once each and written to norm f32[N][C][2]. One launch.
+ * Refused: N, h, w or C below 1 (C above 4096, N above 65535, 2^31 - 1 elements); NULL; a pointer not 16-byte aligned;
+ * partials too small (EOGS_ERR_WORKSPACE).
+ *
+ * eogs_flowenc_finish: one pointwise pass over f32[N][h][w][C], C a multiple of 4:
+ *   out = relu(S + relu((v - mean_v) * rstd_v))        (each a separately rounded float32 operation; a NaN stays a NaN)
+ *   EOGS_FLOWENC_SHORTCUT_NONE   S = 0: out = relu((v - mean_v) * rstd_v), the stem's output; s and norm_s NULL
+ *   EOGS_FLOWENC_SHORTCUT_PLAIN  S = s; norm_s NULL
+ *   EOGS_FLOWENC_SHORTCUT_NORM   S = (s - mean_s) * rstd_s: the normalised 1 x 1 stride-2 downsample, no ReLU
+ * Refused: sizes as above; C no multiple of 4; an unknown shortcut; s or norm_s that does not fit the shortcut; NULL v,
+ * norm_v or out; a pointer not 16-byte aligned.
+ *
+ * eogs_flowenc_run: a whole encoder. kind EOGS_FLOWENC_FEATURE (widths 32, 32, 64, 96 -> 128, an instance norm after
+ * every convolution but the head) or EOGS_FLOWENC_CONTEXT (the same -> 160, no norm). params: the 44 device pointers
+ * weight, bias of the 22 convolutions in module order: convnormrelu; per block of layer1.0, layer1.1, layer2.0, layer2.1,
+ * layer3.0, layer3.1 its convnormrelu1, 2, 3 and, where it has one (layer2.0, layer3.0), its downsample; conv. image
+ * f32[N][3][H][W]; out f32[N][128 or 160][h3][w3] (NCHW) with h1 = ceil(H / 2), h2 = ceil(h1 / 2), h3 = ceil(h2 / 2). The
+ * weights are repacked at every call. A unit is conv -> statistics -> (v - mean) rstd -> ReLU, a block relu(S + y):
+ *   FEATURE  stem: conv, norm, finish(NONE). Block: conv1 (statistics), norm; conv2 normalising conv1's output on load,
+ *            norm; conv3 normalising conv2's on load, norm; with a downsample its conv and norm; finish(PLAIN with the
+ *            block's input, or NORM with the downsample's output). Head: conv (BIAS, OUT_NCHW).
+ *   CONTEXT  stem RELU. Block: conv1 RELU, conv2 RELU, the downsample (BIAS) where there is one, conv3 RESIDUAL with the
+ *            block's input or the downsample's output as res. Head as above. No pointwise pass.
+ * The workspace (eogs_flowenc_bytes; rounded up to 256 bytes inside) holds the packed weights, the maps, the partials and
+ * the norm tables; a call relies on nothing in it that it did not write.
+ * Refused: an unknown kind; N, H or W below 1; N above 65535; more than 2^31 - 1 elements in a map; for FEATURE a final
+ * map of a single position (h3 w3 = 1: torch's instance norm raises there); NULL (a NULL among params too); a pointer not
+ * 16-byte aligned; a workspace too small (EOGS_ERR_WORKSPACE). */
+
+#define EOGS_FLOWENC_EPI_BIAS 0
+#define EOGS_FLOWENC_EPI_RELU 1
+#define EOGS_FLOWENC_EPI_RESIDUAL 2
+#define EOGS_FLOWENC_IN_NCHW 1u
+#define EOGS_FLOWENC_OUT_NCHW 8u
+#define EOGS_FLOWENC_SHORTCUT_NONE 0
+#define EOGS_FLOWENC_SHORTCUT_PLAIN 1
+#define EOGS_FLOWENC_SHORTCUT_NORM 2
+#define EOGS_FLOWENC_FEATURE 0
+#define EOGS_FLOWENC_CONTEXT 1
+#define EOGS_FLOWENC_PARAMS 44
+
+int eogs_flowenc_conv_partials(int N, int h, int w, int cout, int* rows, size_t* bytes);
+int eogs_flowenc_conv(int N, int h, int w, int cin, int cout, int k, int stride, const float* in, const float* in_norm,
+                      const void* packed, size_t packed_bytes, const float* bias, const float* res, float* out, double* partials,
+                      size_t partials_bytes, int epilogue, unsigned flags, void* stream);
+int eogs_flowenc_norm(int N, int h, int w, int C, const double* partials, size_t partials_bytes, float* norm, void* stream);
+int eogs_flowenc_finish(int N, int h, int w, int C, const float* v, const float* norm_v, const float* s, const float* norm_s,
+                        int shortcut, float* out, void* stream);
+int eogs_flowenc_bytes(int N, int H, int W, int kind, size_t* bytes);
+int eogs_flowenc_run(int N, int H, int W, int kind, const float* const* params, const float* image, void* ws, size_t ws_bytes,
+                     float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
