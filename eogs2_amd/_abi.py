@@ -87,6 +87,9 @@ FLOWNET_MAX_SEGMENTS, FLOWNET_MAX_KERNEL = 3, 7  # EOGS_FLOWNET_MAX_*
 FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_EPI_GATES, FLOWNET_EPI_GRU = 0, 1, 2, 3  # EOGS_FLOWNET_EPI_*: the epilogues
 FLOWNET_IN0_NCHW, FLOWNET_OUT_NCHW = 1, 8  # EOGS_FLOWNET_IN0_NCHW (<< i for segment i), _OUT_NCHW: the convolution's flags
 FLOWNET_UPDATE_PARAMS = 18  # EOGS_FLOWNET_UPDATE_PARAMS
+FLOWRECT_EPI_QUARTER = 4  # include/eogs_resample.h EOGS_FLOWRECT_EPI_QUARTER: the rectangular convolution's added epilogue
+FLOWLARGE_PARAMS = 30  # EOGS_FLOWLARGE_PARAMS
+FLOWRECT_TAP_SHAPES = ((1, 1), (3, 3), (5, 5), (7, 7), (1, 5), (5, 1))  # the (kh, kw) eogs_flowrect_conv takes
 FLOWENC_EPI_BIAS, FLOWENC_EPI_RELU, FLOWENC_EPI_RESIDUAL = 0, 1, 2  # EOGS_FLOWENC_EPI_*: the strided convolution's epilogues
 FLOWENC_IN_NCHW, FLOWENC_OUT_NCHW = 1, 8  # EOGS_FLOWENC_IN_NCHW, _OUT_NCHW: its flags
 FLOWENC_SHORTCUT_NONE, FLOWENC_SHORTCUT_PLAIN, FLOWENC_SHORTCUT_NORM = 0, 1, 2  # EOGS_FLOWENC_SHORTCUT_*: eogs_flowenc_finish
@@ -199,6 +202,15 @@ HEADERS = {
         "eogs_flownet_update_hidden_offset": (_i, [_i, _i, _i, C.POINTER(_z)]),
         "eogs_flownet_update_begin": (_i, [_i, _i, _i, C.POINTER(_p), _p, _p, _p, _z, _p]),
         "eogs_flownet_update_step": (_i, [_i, _i, _i, _p, _p, _p, _z, _p, _p]),
+        # the flow network's convolution over kh x kw taps, and RAFT-large's update block and mask predictor composed of it
+        "eogs_flowrect_pack_bytes": (_i, [_i, _i, _i, C.POINTER(_i), _i, C.POINTER(_z)]),
+        "eogs_flowrect_pack": (_i, [_i, _i, _i, C.POINTER(_i), C.POINTER(_i), _i, _i, _i, _i, _p, _p, _z, _p]),
+        "eogs_flowrect_conv": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i), _p, _p, _p, _i, _p, _z, _p, _p, _p, _p, _i, _u, _p]),
+        "eogs_flowlarge_bytes": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_flowlarge_hidden_offset": (_i, [_i, _i, _i, C.POINTER(_z)]),
+        "eogs_flowlarge_begin": (_i, [_i, _i, _i, C.POINTER(_p), _p, _p, _p, _z, _p]),
+        "eogs_flowlarge_step": (_i, [_i, _i, _i, _p, _p, _p, _z, _p, _p]),
+        "eogs_flowlarge_mask": (_i, [_i, _i, _i, _p, _z, _p, _p]),
         "eogs_flowenc_conv_partials": (_i, [_i, _i, _i, _i, C.POINTER(_i), C.POINTER(_z)]),
         "eogs_flowenc_conv": (_i, [_i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _z, _p, _p, _p, _p, _z, _i, _u, _p]),
         "eogs_flowenc_norm": (_i, [_i, _i, _i, _i, _p, _z, _p, _p]),

@@ -14,14 +14,15 @@ static_assert(FNT / 64 * 2 == FT_H && FT_W == 16, "a wave owns two 16-position r
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int fn_ws(int nb) { return nb == 1 ? 16 : 48; }  // packed row stride: 16 or 48 mod 64 floats
-constexpr int fn_tg(int k) { return k <= 3 ? k * k : k; }  // taps per weight stage: all of 3 x 3, else one row
+constexpr int fn_tg(int kh, int kw) { return kh * kw <= 9 ? kh * kw : kw; }  // taps per weight stage: all of up to nine, else one row
+constexpr int fn_tg(int k) { return fn_tg(k, k); }
 
 struct ConvPlan {
   int nb, chunks, ws, cchunks;  // blocks per workgroup, workgroups along Cout, packed row stride, chunks of FCK over all segments
   size_t floats;                // of the packed weights
 };
 
-inline ConvPlan conv_plan(int k, int nseg, const int* C, int cout) {
+inline ConvPlan conv_plan(int kh, int kw, int nseg, const int* C, int cout) {
   ConvPlan p{};
   const int nbt = (cout + 15) / 16;
   // the fewest padded blocks, three per workgroup on a tie
@@ -29,9 +30,10 @@ inline ConvPlan conv_plan(int k, int nseg, const int* C, int cout) {
   p.chunks = (nbt + p.nb - 1) / p.nb;
   p.ws = fn_ws(p.nb);
   for (int s = 0; s < nseg; s++) p.cchunks += (C[s] + FCK - 1) / FCK;
-  p.floats = (size_t)p.cchunks * p.chunks * k * k * FCK * p.ws;
+  p.floats = (size_t)p.cchunks * p.chunks * kh * kw * FCK * p.ws;
   return p;
 }
+inline ConvPlan conv_plan(int k, int nseg, const int* C, int cout) { return conv_plan(k, k, nseg, C, cout); }
 
 struct PackArgs {
   int C[EOGS_FLOWNET_MAX_SEGMENTS], off[EOGS_FLOWNET_MAX_SEGMENTS];
@@ -41,7 +43,7 @@ struct PackArgs {
   float* packed;
 };
 
-// torch's [cout_n][cin][k][k] into [chunk of FCK channels][workgroup along Cout][tap][FCK][ws]: the columns this call owns,
+// torch's [cout_n][cin][kh][kw] (taps = kh kw, row-major) into [chunk of FCK channels][workgroup along Cout][tap][FCK][ws]: the columns this call owns,
 // and zeros in every padded column; padded channel lanes of its columns are zeros
 __global__ __launch_bounds__(256) void flownet_pack_kernel(PackArgs p) {
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < p.total; idx += (int64_t)gridDim.x * 256) {
@@ -70,18 +72,23 @@ __global__ __launch_bounds__(256) void flownet_pack_kernel(PackArgs p) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-inline int check_conv_shape(const char* who, int k, int nseg, const int* C, int cout) {
-  if (k < 1 || k > EOGS_FLOWNET_MAX_KERNEL || k % 2 == 0) return fail(EOGS_ERR_INVALID_ARG, "%s: the kernel size is 1, 3, 5 or 7", who);
+// the taps: a square of 1, 3, 5 or 7, or (with `rect`, the eogs_flowrect_* entries) 1 x 5 or 5 x 1 as well
+inline int check_conv_shape(const char* who, int kh, int kw, bool rect, int nseg, const int* C, int cout) {
+  const bool square = kh == kw && kh >= 1 && kh <= EOGS_FLOWNET_MAX_KERNEL && kh % 2 == 1;
+  if (!rect && !square) return fail(EOGS_ERR_INVALID_ARG, "%s: the kernel size is 1, 3, 5 or 7", who);
+  if (!square && !((kh == 1 && kw == 5) || (kh == 5 && kw == 1)))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: the kernel shape is 1 x 1, 3 x 3, 5 x 5, 7 x 7, 1 x 5 or 5 x 1", who);
   if (nseg < 1 || nseg > EOGS_FLOWNET_MAX_SEGMENTS || !C) return fail(EOGS_ERR_INVALID_ARG, "%s: one to three input segments", who);
   for (int s = 0; s < nseg; s++)
     if (C[s] < 1 || C[s] > 4096) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (a segment has 1 to 4096 channels)", who);
   if (cout < 1 || cout > 4096) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (Cout is 1 to 4096)", who);
   return EOGS_OK;
 }
+inline int check_conv_shape(const char* who, int k, int nseg, const int* C, int cout) { return check_conv_shape(who, k, k, false, nseg, C, cout); }
 
-inline int pack_checked(const char* who, int k, int nseg, const int* C, const int* offsets, int cin, int cout, int cout_off, int cout_n,
-                        const float* weight, void* packed, size_t packed_bytes, hipStream_t s) {
-  const int rc = check_conv_shape(who, k, nseg, C, cout);
+inline int pack_checked(const char* who, int kh, int kw, bool rect, int nseg, const int* C, const int* offsets, int cin, int cout,
+                        int cout_off, int cout_n, const float* weight, void* packed, size_t packed_bytes, hipStream_t s) {
+  const int rc = check_conv_shape(who, kh, kw, rect, nseg, C, cout);
   if (rc != EOGS_OK) return rc;
   int sum = 0;
   for (int i = 0; i < nseg; i++) sum += C[i];
@@ -94,16 +101,20 @@ inline int pack_checked(const char* who, int k, int nseg, const int* C, const in
   if (cout_off < 0 || cout_n < 1 || cout_off > cout - cout_n) return fail(EOGS_ERR_INVALID_ARG, "%s: the columns lie outside Cout", who);
   if (!weight || !packed) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
   if (!aligned16(weight) || !aligned16(packed)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  const ConvPlan pl = conv_plan(k, nseg, C, cout);
+  const ConvPlan pl = conv_plan(kh, kw, nseg, C, cout);
   if (packed_bytes < pl.floats * sizeof(float)) return fail(EOGS_ERR_WORKSPACE, "%s: packed weights too small", who);
   PackArgs p{};
   int o = 0;
   for (int i = 0; i < nseg; i++) { p.C[i] = C[i]; p.off[i] = offsets ? offsets[i] : o; o += C[i]; }
-  p.nseg = nseg; p.taps = k * k; p.cin = cin; p.cout = cout; p.cout_off = cout_off; p.cout_n = cout_n;
+  p.nseg = nseg; p.taps = kh * kw; p.cin = cin; p.cout = cout; p.cout_off = cout_off; p.cout_n = cout_n;
   p.nb = pl.nb; p.chunks = pl.chunks; p.ws = pl.ws; p.total = (int64_t)pl.floats;
   p.weight = weight; p.packed = reinterpret_cast<float*>(packed);
   hipLaunchKernelGGL(flownet_pack_kernel, dim3(capped_blocks(p.total, 256, 2048)), dim3(256), 0, s, p);
   return EOGS_OK;
+}
+inline int pack_checked(const char* who, int k, int nseg, const int* C, const int* offsets, int cin, int cout, int cout_off, int cout_n,
+                        const float* weight, void* packed, size_t packed_bytes, hipStream_t s) {
+  return pack_checked(who, k, k, false, nseg, C, offsets, cin, cout, cout_off, cout_n, weight, packed, packed_bytes, s);
 }
 
 #ifndef RC_TRY

@@ -6,6 +6,8 @@ flowmatching/flow_matching.py:76-86), with its correlation looked up ON DEMAND o
   upsample_flow(flow, mask=None)                    convex (mask) or bilinear x 8 upsampling           one launch
   conv2d_cl(inputs, weight, bias, act, add)         channel-last convolution on the fp32 matrix cores  pack + one launch
   FusedUpdate(update_block)                         RAFT-small's update block over that convolution    eight launches per update
+  conv2d_rect_cl(inputs, weight, bias, act, add)    the same over kh x kw taps (1 x 5, 5 x 1)          pack + one launch
+  FusedUpdateLarge(update_block, mask_predictor)    RAFT-large's update block and mask predictor       eleven launches per update, two per mask
   conv2d_strided_cl(input, weight, ...), finish_cl  the encoders' strided convolution and block tail   pack + one to three launches
   FusedEncoder(encoder_module)                      one of RAFT-small's two encoders                   one call
   RAFT, raft_small(), raft_large()                  the two published configurations as nn.Modules
@@ -26,7 +28,11 @@ convolution that produces a map and applied by the one that reads it, the bottle
 one channel-last convolution kernel on the exact-fp32 matrix instruction with the bias, ReLU, gate and GRU-blend epilogues in
 registers, the context's share of the three GRU convolutions computed once per forward and added as a plane, no torch.cat
 and no layout round trip; the weights stay the torch modules' parameters and are repacked at every forward. `update="auto"`
-follows the measurement of tools/raft_update_probe.py (profiles/raft_update_probe.json; README). Everything here is forward
+follows the measurement of tools/raft_update_probe.py (profiles/raft_update_probe.json; README). Under `update="fused_large"`
+RAFT-large's update block and mask predictor run the same way over the eogs_flowrect_* and eogs_flowlarge_*
+entries of include/eogs_resample.h: the kernel over 1 x 5 and 5 x 1 taps for the two GRUs, the context's share of their six
+convolutions as four planes formed once per forward, the mask head's 0.25 as an epilogue
+(tools/raft_large_update_probe.py, profiles/raft_large_update_probe.json; README). Everything here is forward
 only (the reference runs the network under inference_mode); the HIP operators are float32 and refuse CPU tensors (no CPU
 fallback).
 
@@ -46,7 +52,8 @@ import torch.nn.functional as F
 from . import _lib
 from ._abi import (FLOWENC_CONTEXT, FLOWENC_EPI_BIAS, FLOWENC_EPI_RELU, FLOWENC_EPI_RESIDUAL, FLOWENC_FEATURE, FLOWENC_IN_NCHW,
                    FLOWENC_OUT_NCHW, FLOWENC_PARAMS, FLOWENC_SHORTCUT_NONE, FLOWENC_SHORTCUT_NORM, FLOWENC_SHORTCUT_PLAIN,
-                   FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_MAX_KERNEL, FLOWNET_MAX_SEGMENTS, FLOWNET_UPDATE_PARAMS,
+                   FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_MAX_KERNEL, FLOWNET_MAX_SEGMENTS, FLOWRECT_TAP_SHAPES,
+                   FLOWLARGE_PARAMS, FLOWNET_UPDATE_PARAMS,
                    RAFT_MASK_CHANNELS, RAFT_MAX_LEVELS, RAFT_MAX_RADIUS, RAFT_NO_STAGE, RAFT_UP_BILINEAR, RAFT_UP_CONVEX)
 from ._host import Workspaces, call, nbytes, on_device, query_bytes
 
@@ -206,7 +213,17 @@ def conv2d_cl(inputs, weight, bias=None, act="none", add=None):
     a list of one to three [N, h, w, C_i] tensors whose concatenation along the channels is never formed, `weight` torch's
     [Cout, sum C_i, k, k] with k in 1, 3, 5, 7, `bias` [Cout] or None, `add` [N, h, w, Cout] or None; returns [N, h, w, Cout].
     The weight is repacked at every call (include/eogs_resample.h has the kernel's statement and the order of its sums)."""
-    what = "conv2d_cl"
+    return _conv2d_cl("conv2d_cl", inputs, weight, bias, act, add, rect=False)
+
+
+def conv2d_rect_cl(inputs, weight, bias=None, act="none", add=None):
+    """`conv2d_cl` for a weight of kh x kw taps, torch's [Cout, sum C_i, kh, kw] with (kh, kw) one of (1, 1), (3, 3), (5, 5), (7, 7),
+    (1, 5), (5, 1) (RAFT-large's two GRUs are 1 x 5 and 5 x 1), padding ((kh - 1) // 2, (kw - 1) // 2): the same checks, the same
+    errors, and for a square weight the same bits (include/eogs_resample.h)."""
+    return _conv2d_cl("conv2d_rect_cl", inputs, weight, bias, act, add, rect=True)
+
+
+def _conv2d_cl(what, inputs, weight, bias, act, add, rect):
     if not isinstance(inputs, (list, tuple)):
         raise TypeError(f"raft {what}: inputs is a list of channel-last tensors, got {type(inputs).__name__}")
     if not 1 <= len(inputs) <= FLOWNET_MAX_SEGMENTS:
@@ -218,10 +235,15 @@ def conv2d_cl(inputs, weight, bias=None, act="none", add=None):
     _f32(weight, "the weight", what)
     N, h, w = (int(v) for v in inputs[0].shape[:3])
     chans = [int(t.shape[3]) for t in inputs]
-    if weight.ndim != 4 or weight.shape[1] != sum(chans) or weight.shape[2] != weight.shape[3] or weight.shape[0] < 1:
+    if rect:
+        if weight.ndim != 4 or weight.shape[1] != sum(chans) or weight.shape[0] < 1:
+            raise ValueError(f"raft {what}: the weight is (Cout, {sum(chans)}, kh, kw), got {tuple(weight.shape)}")
+        if tuple(weight.shape[2:]) not in FLOWRECT_TAP_SHAPES:
+            raise ValueError(f"raft {what}: the taps (kh, kw) are one of {FLOWRECT_TAP_SHAPES}, got {tuple(weight.shape[2:])}")
+    elif weight.ndim != 4 or weight.shape[1] != sum(chans) or weight.shape[2] != weight.shape[3] or weight.shape[0] < 1:
         raise ValueError(f"raft {what}: the weight is (Cout, {sum(chans)}, k, k), got {tuple(weight.shape)}")
-    cout, k = int(weight.shape[0]), int(weight.shape[2])
-    if k % 2 == 0 or k > FLOWNET_MAX_KERNEL:
+    cout, k, kw = int(weight.shape[0]), int(weight.shape[2]), int(weight.shape[3])
+    if not rect and (k % 2 == 0 or k > FLOWNET_MAX_KERNEL):
         raise ValueError(f"raft {what}: the kernel size is odd and at most {FLOWNET_MAX_KERNEL}, got {k}")
     if act not in ("none", "relu"):
         raise ValueError(f"raft {what}: act is 'none' or 'relu', got {act!r}")
@@ -242,11 +264,14 @@ def conv2d_cl(inputs, weight, bias=None, act="none", add=None):
     xs = [_aligned(t) for t in inputs] + [None] * (FLOWNET_MAX_SEGMENTS - len(inputs))
     wt, b, a = _aligned(weight), None if bias is None else _aligned(bias), None if add is None else _aligned(add)
     seg = (ctypes.c_int * len(chans))(*chans)
-    size = query_bytes(_lib.get(), "flownet_conv_pack_bytes", k, len(chans), seg, cout)
+    # (the eogs_flowrect_* entries take (kh, kw) where the eogs_flownet_conv* ones take k)
+    taps, pack_bytes, pack, conv = ((k, kw), "flowrect_pack_bytes", "eogs_flowrect_pack", "eogs_flowrect_conv") if rect else \
+        ((k,), "flownet_conv_pack_bytes", "eogs_flownet_conv_pack", "eogs_flownet_conv")
+    size = query_bytes(_lib.get(), pack_bytes, *taps, len(chans), seg, cout)
     packed = Workspaces.bytes(dev, size)
-    call("eogs_flownet_conv_pack", dev, k, len(chans), seg, None, sum(chans), cout, 0, cout, wt.data_ptr(), packed.data_ptr(), size)
+    call(pack, dev, *taps, len(chans), seg, None, sum(chans), cout, 0, cout, wt.data_ptr(), packed.data_ptr(), size)
     out = torch.empty((N, h, w, cout), dtype=torch.float32, device=dev)
-    call("eogs_flownet_conv", dev, N, h, w, k, len(chans), seg, *(None if x is None else x.data_ptr() for x in xs), cout,
+    call(conv, dev, N, h, w, *taps, len(chans), seg, *(None if x is None else x.data_ptr() for x in xs), cout,
          packed.data_ptr(), size, None if b is None else b.data_ptr(), None if a is None else a.data_ptr(), None, out.data_ptr(),
          FLOWNET_EPI_RELU if act == "relu" else FLOWNET_EPI_BIAS, 0)
     return out
@@ -339,6 +364,121 @@ class FusedUpdate:
             raise RuntimeError("raft FusedUpdate.hidden: begin(hidden_state, context) comes first")
         N, h, w, ws = self._state
         off = nbytes(_lib.get(), "flownet_update_hidden_offset", N, h, w)
+        base = (-ws.data_ptr()) % 256  # the library rounds the pointer up to 256 bytes
+        cl = ws[base + off: base + off + 4 * N * h * w * self.HIDDEN].view(torch.float32).view(N, h, w, self.HIDDEN)
+        return cl.permute(0, 3, 1, 2).contiguous()
+
+
+class FusedUpdateLarge:
+    """RAFT-large's `UpdateBlock` and `MaskPredictor` over the convolution kernel (the eogs_flowlarge_* entries of
+    include/eogs_resample.h), with FusedUpdate's call order and one more call:
+
+        fused.begin(hidden_state, context)         once per forward: the NCHW halves of the context encoder after tanh / relu
+        delta = fused.step(corr_features, flow)    once per update: [N, 2, h, w]; the hidden state advances in the workspace
+        mask = fused.mask()                        [N, 576, h, w] of the hidden state as it is now: what upsample_flow takes
+        fused.hidden()                             the hidden state as [N, 128, h, w]
+
+    It holds the two modules, not copies of their weights: `begin` repacks them at every forward. It is no nn.Module and
+    registers no parameter and no buffer. Float32 on the GPU, forward only."""
+
+    NAMES = ("motion_encoder.convcorr1.0", "motion_encoder.convcorr2.0", "motion_encoder.convflow1.0", "motion_encoder.convflow2.0",
+             "motion_encoder.conv.0", "recurrent_block.convgru1.convz", "recurrent_block.convgru1.convr", "recurrent_block.convgru1.convq",
+             "recurrent_block.convgru2.convz", "recurrent_block.convgru2.convr", "recurrent_block.convgru2.convq", "flow_head.conv1",
+             "flow_head.conv2")
+    MASK_NAMES = ("convrelu.0", "conv")
+    SHAPES = ((256, 324, 1, 1), (192, 256, 3, 3), (128, 2, 7, 7), (64, 128, 3, 3), (126, 256, 3, 3), (128, 384, 1, 5), (128, 384, 1, 5),
+              (128, 384, 1, 5), (128, 384, 5, 1), (128, 384, 5, 1), (128, 384, 5, 1), (256, 128, 3, 3), (2, 256, 3, 3),
+              (256, 128, 3, 3), (RAFT_MASK_CHANNELS, 256, 1, 1))
+    HIDDEN, CONTEXT, CORR = 128, 128, 324
+
+    def __init__(self, update_block, mask_predictor):
+        what = "raft FusedUpdateLarge"
+        if not isinstance(update_block, UpdateBlock):
+            raise TypeError(f"{what}: expected an UpdateBlock, got {type(update_block).__name__}")
+        if not isinstance(mask_predictor, MaskPredictor):
+            raise TypeError(f"{what}: expected a MaskPredictor, got {type(mask_predictor).__name__}")
+        if not isinstance(update_block.motion_encoder.convcorr2, nn.Sequential) or not isinstance(update_block.recurrent_block.convgru2, ConvGRU):
+            raise ValueError(f"{what}: the fused update is RAFT-large's (two correlation convolutions, a 1 x 5 and a 5 x 1 GRU); this "
+                             "block has one of them only")
+        convs = [update_block.get_submodule(n) for n in self.NAMES] + [mask_predictor.get_submodule(n) for n in self.MASK_NAMES]
+        got = tuple(tuple(c.weight.shape) for c in convs)
+        if got != self.SHAPES or mask_predictor.multiplier != 0.25:
+            raise ValueError(f"{what}: the fused update is RAFT-large's (two correlation convolutions, a 1 x 5 and a 5 x 1 GRU, a mask "
+                             f"predictor with the multiplier 0.25); this block's convolutions are {got}, the multiplier {mask_predictor.multiplier}")
+        self._names = tuple(f"update_block.{n}" for n in self.NAMES) + tuple(f"mask_predictor.{n}" for n in self.MASK_NAMES)
+        self._convs = convs
+        self._ws = Workspaces()
+        self._state = None
+
+    def __getstate__(self):  # a copied or pickled module starts without workspaces
+        return {"_names": self._names, "_convs": self._convs}
+
+    def __setstate__(self, state):
+        self._names, self._convs, self._ws, self._state = state["_names"], state["_convs"], Workspaces(), None
+
+    def _params(self, dev):
+        out = []
+        for name, c in zip(self._names, self._convs):
+            for p in (c.weight, c.bias):
+                if p.dtype != torch.float32 or p.device != dev:
+                    raise RuntimeError(f"raft FusedUpdateLarge: {name} is {p.dtype} on {p.device}; the fused update runs in float32 on "
+                                       f"the inputs' device ({dev}), there is no CPU fallback")
+                out.append(_aligned(p))
+        return out
+
+    def begin(self, hidden_state, context):
+        what = "FusedUpdateLarge.begin"
+        N, _, h, w = _map(hidden_state, "the hidden state", what, self.HIDDEN)
+        if _map(context, "the context", what, self.CONTEXT) != (N, self.CONTEXT, h, w):
+            raise ValueError(f"raft {what}: the context is {tuple(context.shape)}, the hidden state asks for {(N, self.CONTEXT, h, w)}")
+        _on_device(hidden_state, what)
+        _on_device(context, what)
+        dev = hidden_state.device
+        if context.device != dev:
+            raise RuntimeError(f"raft {what}: the hidden state and the context live on different devices")
+        params = self._params(dev)
+        assert len(params) == FLOWLARGE_PARAMS
+        size = self.workspace_bytes(N, h, w)
+        ws = self._ws.of((N, h, w), dev, lambda: Workspaces.bytes(dev, size))
+        hid, ctx = _aligned(hidden_state), _aligned(context)
+        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
+        call("eogs_flowlarge_begin", dev, N, h, w, table, hid.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws.numel())
+        self._state = (N, h, w, ws)
+
+    @staticmethod
+    def workspace_bytes(N, h, w):
+        return nbytes(_lib.get(), "flowlarge_bytes", int(N), int(h), int(w))
+
+    def step(self, corr_features, flow):
+        what = "FusedUpdateLarge.step"
+        if self._state is None:
+            raise RuntimeError(f"raft {what}: begin(hidden_state, context) comes first")
+        N, h, w, ws = self._state
+        if _map(corr_features, "the correlation features", what, self.CORR) != (N, self.CORR, h, w) or _map(flow, "the flow", what, 2) != (N, 2, h, w):
+            raise ValueError(f"raft {what}: begin was given {(N, h, w)}; the correlation features are {tuple(corr_features.shape)}, "
+                             f"the flow is {tuple(flow.shape)}")
+        _on_device(corr_features, what)
+        _on_device(flow, what)
+        if corr_features.device != ws.device or flow.device != ws.device:
+            raise RuntimeError(f"raft {what}: the tensors and the workspace live on different devices")
+        corr, fl = _aligned(corr_features), _aligned(flow)
+        delta = torch.empty((N, 2, h, w), dtype=torch.float32, device=ws.device)
+        call("eogs_flowlarge_step", ws.device, N, h, w, corr.data_ptr(), fl.data_ptr(), ws.data_ptr(), ws.numel(), delta.data_ptr())
+        return delta
+
+    def mask(self):
+        if self._state is None:
+            raise RuntimeError("raft FusedUpdateLarge.mask: begin(hidden_state, context) comes first")
+        N, h, w, ws = self._state
+        out = torch.empty((N, RAFT_MASK_CHANNELS, h, w), dtype=torch.float32, device=ws.device)
+        call("eogs_flowlarge_mask", ws.device, N, h, w, ws.data_ptr(), ws.numel(), out.data_ptr())
+        return out
+
+    def hidden(self):
+        if self._state is None:
+            raise RuntimeError("raft FusedUpdateLarge.hidden: begin(hidden_state, context) comes first")
+        N, h, w, ws = self._state
+        off = nbytes(_lib.get(), "flowlarge_hidden_offset", N, h, w)
         base = (-ws.data_ptr()) % 256  # the library rounds the pointer up to 256 bytes
         cl = ws[base + off: base + off + 4 * N * h * w * self.HIDDEN].view(torch.float32).view(N, h, w, self.HIDDEN)
         return cl.permute(0, 3, 1, 2).contiguous()
@@ -766,6 +906,13 @@ TORCHVISION_NAMES = {
 # 5.85 + 0.15 ms against 6.49 ms at 1024^2, 13.79 + 0.33 ms against 17.36 ms at 2048^2.
 AUTO_UPDATE_IS_FUSED = True
 
+# RAFT-large's update="auto" runs the torch modules whatever this says: the existing tests take that run as their yardstick. It
+# records the verdict of tools/raft_large_update_probe.py (profiles/raft_large_update_probe.json) by the same rule, so that a
+# later change can flip "auto" on it. Measured (update phase with the mask predictor's call, fused + `begin` against torch):
+# 14.12 + 0.37 ms (slowest turn 14.52) against 15.61 ms (fastest turn 15.60) at 1024^2, 43.50 + 0.96 ms (slowest 44.60) against
+# 48.94 ms (fastest 48.91) at 2048^2: the fused path wins, by 1.08 x and 1.10 x, and peaks 0.18 and 0.74 GB higher in memory.
+AUTO_UPDATE_LARGE_IS_FUSED = True
+
 # What encoder="auto" runs under the same conditions. It follows tools/raft_encoder_probe.py (profiles/raft_encoder_probe.json):
 # the fused encoders only if, at 1024^2 and at 2048^2, the slowest fused turn of the encoder phase (the feature encoder on the
 # two images, then the context encoder) is faster than the fastest torch turn. Measured
@@ -783,8 +930,9 @@ class RAFT(nn.Module):
     for float32 inputs on the GPU, volume otherwise.
 
     update: "torch" (the update block as torch modules, any dtype and device), "fused" (FusedUpdate: RAFT-small only, float32
-    on the GPU, forward only, no CPU fallback) or "auto": the fused path for RAFT-small in float32 on the GPU when no gradient
-    is recorded, as the measurement decided (AUTO_UPDATE_IS_FUSED), the torch modules otherwise.
+    on the GPU, forward only, no CPU fallback), "fused_large" (FusedUpdateLarge: RAFT-large only, its update block and mask
+    predictor, under the same conditions) or "auto": the fused path for RAFT-small in float32 on the GPU when no gradient
+    is recorded, as the measurement decided (AUTO_UPDATE_IS_FUSED), the torch modules otherwise, and for RAFT-large always.
 
     encoder: "torch" (the two encoders as torch modules, any dtype and device; the default), "fused" (FusedEncoder: RAFT-small
     only, float32 on the GPU, forward only, no CPU fallback) or "auto": the fused encoders for RAFT-small in float32 on the
@@ -796,10 +944,12 @@ class RAFT(nn.Module):
             raise ValueError(f"raft RAFT: name is 'small' or 'large', got {name!r}")
         if corr not in ("auto", "ondemand", "volume"):
             raise ValueError(f"raft RAFT: corr is 'auto', 'ondemand' or 'volume', got {corr!r}")
-        if update not in ("auto", "torch", "fused"):
-            raise ValueError(f"raft RAFT: update is 'auto', 'torch' or 'fused', got {update!r}")
+        if update not in ("auto", "torch", "fused", "fused_large"):
+            raise ValueError(f"raft RAFT: update is 'auto', 'torch', 'fused' or 'fused_large', got {update!r}")
         if update == "fused" and name != "small":
-            raise ValueError(f"raft RAFT: update='fused' is RAFT-small's update block; '{name}' runs update='torch'")
+            raise ValueError(f"raft RAFT: update='fused' is RAFT-small's update block; '{name}' runs update='torch' or 'fused_large'")
+        if update == "fused_large" and name != "large":
+            raise ValueError(f"raft RAFT: update='fused_large' is RAFT-large's update block; '{name}' runs update='torch' or 'fused'")
         if encoder not in ("auto", "torch", "fused"):
             raise ValueError(f"raft RAFT: encoder is 'auto', 'torch' or 'fused', got {encoder!r}")
         if encoder == "fused" and name != "small":
@@ -818,6 +968,7 @@ class RAFT(nn.Module):
         self.mask_predictor = None if cfg["mask_hidden"] is None else MaskPredictor(hidden, cfg["mask_hidden"])
         self._fused = FusedUpdate(self.update_block) if name == "small" else None  # (no Module: nothing is registered)
         self._fused_enc = (FusedEncoder(self.feature_encoder), FusedEncoder(self.context_encoder)) if name == "small" else None
+        self._fused_large = FusedUpdateLarge(self.update_block, self.mask_predictor) if name == "large" else None
 
     def _ondemand(self, x):
         if self.corr == "volume":
@@ -829,6 +980,13 @@ class RAFT(nn.Module):
         return ok
 
     def _fused_update(self, x):
+        if self.update == "fused_large":  # (never under "auto": AUTO_UPDATE_LARGE_IS_FUSED)
+            if self._fused_large is None:
+                raise ValueError(f"raft RAFT: update='fused_large' is RAFT-large's update block; '{self.name}' runs update='torch' or 'fused'")
+            if x.device.type != "cuda" or x.dtype != torch.float32:
+                raise RuntimeError(f"raft RAFT: update='fused_large' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
+                                   "there is no CPU fallback, update='torch' is the plain torch form")
+            return True
         if self.update == "torch" or self._fused is None:
             return False
         ok = x.device.type == "cuda" and x.dtype == torch.float32
@@ -873,8 +1031,9 @@ class RAFT(nn.Module):
                                 torch.arange(w, dtype=image1.dtype, device=image1.device), indexing="ij")
         coords0 = torch.stack([xs, ys], dim=0)[None].repeat(N, 1, 1, 1)
         coords1 = coords0.clone()
+        fused_update = self._fused_large if self.update == "fused_large" else self._fused
         if fused:
-            self._fused.begin(hidden_state, context)
+            fused_update.begin(hidden_state, context)
         flows = []
         for it in range(num_flow_updates):
             coords1 = coords1.detach()
@@ -882,13 +1041,16 @@ class RAFT(nn.Module):
                 corr_features = corr_lookup(f1cl, pyramid, coords1, self.corr_radius)
             else:
                 corr_features = volume_lookup(pyramid, coords1, self.corr_radius)
-            if fused:  # (RAFT-small has no mask predictor: the hidden state stays in the workspace)
-                delta = self._fused.step(corr_features, coords1 - coords0)
+            if fused:  # (the hidden state stays in the workspace: RAFT-small has no mask predictor, RAFT-large's reads it there)
+                delta = fused_update.step(corr_features, coords1 - coords0)
             else:
                 hidden_state, delta = self.update_block(hidden_state, context, corr_features, coords1 - coords0)
             coords1 = coords1 + delta
             if return_all or it == num_flow_updates - 1:
-                mask = None if self.mask_predictor is None else self.mask_predictor(hidden_state)
+                if self.mask_predictor is None:
+                    mask = None
+                else:
+                    mask = fused_update.mask() if fused else self.mask_predictor(hidden_state)
                 flow = coords1 - coords0
                 flows.append(upsample_flow(flow, mask) if ondemand else _upsample_torch(flow, mask))
         return flows
@@ -918,12 +1080,14 @@ def raft_small(corr="auto", update="auto", encoder="torch"):
     return RAFT("small", corr, update, encoder)
 
 
-def raft_large(corr="auto", encoder="torch"):
+def raft_large(corr="auto", encoder="torch", update="auto"):
     """RAFT-large: residual encoders (256 feature channels), 4 levels at radius 4, 1 x 5 + 5 x 1 GRUs, convex upsampling.
-    Its encoders are torch modules: encoder="fused" is refused."""
-    return RAFT("large", corr, encoder=encoder)
+    Its encoders are torch modules: encoder="fused" is refused. update: "auto" and "torch" run the update block and the mask
+    predictor as torch modules, "fused_large" over the HIP convolutions (FusedUpdateLarge)."""
+    return RAFT("large", corr, update, encoder)
 
 
-__all__ = ["AUTO_ENCODER_IS_FUSED", "AUTO_UPDATE_IS_FUSED", "CONFIGS", "CorrPyramid", "FusedEncoder", "FusedUpdate", "RAFT",
-           "TORCHVISION_NAMES", "conv2d_cl", "conv2d_strided_cl", "conv_info", "convex_upsample_torch", "corr_lookup", "corr_pyramid",
-           "finish_cl", "raft_large", "raft_small", "stage_info", "upsample_flow", "volume_lookup", "volume_pyramid"]
+__all__ = ["AUTO_ENCODER_IS_FUSED", "AUTO_UPDATE_IS_FUSED", "AUTO_UPDATE_LARGE_IS_FUSED", "CONFIGS", "CorrPyramid", "FusedEncoder",
+           "FusedUpdate", "FusedUpdateLarge", "RAFT", "TORCHVISION_NAMES", "conv2d_cl", "conv2d_rect_cl", "conv2d_strided_cl", "conv_info",
+           "convex_upsample_torch", "corr_lookup", "corr_pyramid", "finish_cl", "raft_large", "raft_small", "stage_info", "upsample_flow",
+           "volume_lookup", "volume_pyramid"]

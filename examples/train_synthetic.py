@@ -234,10 +234,12 @@ def main(argv=None):
                          "only, the max_value_flow criterion will reject the random flows and the image passes unwarped. Needs "
                          "--size of at least 121 (the network sees the size rounded up to a multiple of 8, at least 128); not "
                          "with --graph")
-    ap.add_argument("--flow-update", choices=["auto", "torch", "fused"], default="auto", metavar="HOW",
-                    help="with --flow-network small: how RAFT's update block runs, eogs2_amd.raft.RAFT(update=...): 'torch' (torch "
-                         "modules), 'fused' (the eogs_flownet_* convolutions of include/eogs_resample.h, RAFT-small only) or 'auto' "
-                         "(what profiles/raft_update_probe.json measured as faster)")
+    ap.add_argument("--flow-update", choices=["auto", "torch", "fused", "fused_large"], default="auto", metavar="HOW",
+                    help="with --flow-network: how RAFT's update block runs, eogs2_amd.raft.RAFT(update=...): 'torch' (torch "
+                         "modules), 'fused' (the eogs_flownet_* convolutions of include/eogs_resample.h, RAFT-small only), "
+                         "'fused_large' (RAFT-large's update block and mask predictor over the entries of include/eogs_resample.h, "
+                         "RAFT-large only) or 'auto' (for RAFT-small what profiles/raft_update_probe.json measured as faster; for "
+                         "RAFT-large the torch modules)")
     ap.add_argument("--flow-encoder", choices=["torch", "fused", "auto"], default="torch", metavar="HOW",
                     help="with --flow-network small: how RAFT's two encoders run, eogs2_amd.raft.RAFT(encoder=...): 'torch' (torch "
                          "modules), 'fused' (the eogs_flowenc_* convolutions of include/eogs_resample.h, RAFT-small only) or 'auto' "
@@ -411,6 +413,8 @@ def main(argv=None):
         ap.error("--flow-weights needs --flow-network small|large")
     if a.flow_update == "fused" and a.flow_network != "small":
         ap.error("--flow-update fused needs --flow-network small")
+    if a.flow_update == "fused_large" and a.flow_network != "large":
+        ap.error("--flow-update fused_large needs --flow-network large")
     if a.flow_encoder == "fused" and a.flow_network != "small":
         ap.error("--flow-encoder fused needs --flow-network small")
     if a.flow_network and (a.size < 121 or a.graph):

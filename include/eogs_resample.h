@@ -183,7 +183,10 @@ int eogs_raft_upsample(int N, int h, int w, int mode, const float* flow, const f
  * elements in a map); k not 1, 3, 5 or 7; nseg outside [1, 3]; segments that do not sum to cin, or lie outside it; columns
  * outside Cout; an unknown epilogue; unknown flags (a flag of a segment beyond nseg among them); OUT_NCHW with a gate
  * epilogue; an odd Cout with GATES; aux missing for a gate epilogue or given for another; an input beyond nseg; NULL; a
- * pointer not 16-byte aligned; a packing too small (EOGS_ERR_WORKSPACE). */
+ * pointer not 16-byte aligned; a packing too small (EOGS_ERR_WORKSPACE).
+ *
+ * The same convolution over rectangular taps (1 x 5, 5 x 1) and RAFT-large's update block composed of it: eogs_flowrect_*
+ * and eogs_flowlarge_* below. */
 
 #define EOGS_FLOWNET_MAX_SEGMENTS 3
 #define EOGS_FLOWNET_MAX_KERNEL 7
@@ -228,6 +231,79 @@ int eogs_flownet_update_begin(int N, int h, int w, const float* const* params, c
                               size_t ws_bytes, void* stream);
 int eogs_flownet_update_step(int N, int h, int w, const float* corr, const float* flow, void* ws, size_t ws_bytes, float* delta,
                              void* stream);
+
+/* ---- The convolution over RECTANGULAR taps, and RAFT-large's update block and mask predictor composed of it. RAFT-large (the
+ * reference's default flow network: flowmatching/flow_matching.py, model_name = "large") runs two ConvGRUs per update, one of
+ * 1 x 5 and one of 5 x 1 taps, and predicts the mask of the convex upsampling from the hidden state. What is stated for the
+ * eogs_flownet_* entries above (the convolution, the packing, the epilogues, the conventions) holds here word for word; what
+ * follows is what differs. The entries carry prefixes of their own, eogs_flowrect_ and eogs_flowlarge_. ---- */
+
+/* The three convolution entries of eogs_resample.h with (kh, kw) in place of k: kh x kw taps, stride 1, zero padding
+ * ((kh - 1) / 2, (kw - 1) / 2), a cross-correlation as nn.Conv2d's; the weight is torch's f32[cout_n][cin][kh][kw]:
+ *
+ *   v[n][y][x][c] = ((sum over (i, ch, ky, kx) of in_i[n][y + ky - (kh - 1) / 2][x + kx - (kw - 1) / 2][ch] W[c][off_i + ch][ky][kx]) + bias[c])
+ *                   + add[n][y][x][c]
+ *
+ * The order of the sum is the stated one: the segments in order, their channels in chunks of eight, per chunk the kh kw
+ * taps in row-major order and per tap the chunk's channels ascending, one fused multiply-add per product. The tap shapes are
+ * the four squares 1 x 1, 3 x 3, 5 x 5, 7 x 7 and 1 x 5 and 5 x 1. With kh == kw the three entries give the bits (a packing:
+ * the bytes) of eogs_flownet_conv_pack_bytes, eogs_flownet_conv_pack and eogs_flownet_conv, and a packing made by either
+ * serves the other. Epilogues, flags, the packing by column ranges and the segment offsets are those entries'. One
+ * epilogue is added:
+ *   EOGS_FLOWRECT_EPI_QUARTER  out = 0.25 v (an exact scaling by a power of two; a NaN stays a NaN): the mask predictor's
+ *                             multiplier. No aux. Under EOGS_FLOWNET_OUT_NCHW with Cout = 576 it writes the f32[N][576][h][w]
+ *                             that eogs_raft_upsample takes.
+ *
+ * Refused: N, h, w, a segment's channels or Cout below 1 (channels and Cout above 4096, N above 65535, more than 2^31 - 1
+ * elements in a map); (kh, kw) not one of (1, 1), (3, 3), (5, 5), (7, 7), (1, 5), (5, 1); nseg outside [1, 3]; segments that
+ * do not sum to cin, or lie outside it; columns outside Cout; an unknown epilogue; unknown flags (a flag of a segment beyond
+ * nseg among them); OUT_NCHW with a gate epilogue; an odd Cout with GATES; aux missing for a gate epilogue or given for
+ * another (QUARTER among them); an input beyond nseg; NULL; a pointer not 16-byte aligned; a packing too small
+ * (EOGS_ERR_WORKSPACE). */
+
+#define EOGS_FLOWRECT_EPI_QUARTER 4
+#define EOGS_FLOWLARGE_PARAMS 30
+
+int eogs_flowrect_pack_bytes(int kh, int kw, int nseg, const int* seg_channels, int cout, size_t* bytes);
+int eogs_flowrect_pack(int kh, int kw, int nseg, const int* seg_channels, const int* seg_offsets, int cin, int cout,
+                                int cout_off, int cout_n, const float* weight, void* packed, size_t packed_bytes, void* stream);
+int eogs_flowrect_conv(int N, int h, int w, int kh, int kw, int nseg, const int* seg_channels, const float* in0, const float* in1,
+                           const float* in2, int cout, const void* packed, size_t packed_bytes, const float* bias, const float* add,
+                           const float* aux, float* out, int epilogue, unsigned flags, void* stream);
+
+/* RAFT-large's update block (hidden 128, context 128, correlation 324 = 4 levels at radius 4) and its mask predictor over
+ * one workspace (eogs_flowlarge_bytes: packed weights, biases, the four hoisted planes, the hidden state and the
+ * intermediates; rounded up to 256 bytes inside).
+ *
+ * begin: params are the 30 device pointers weight, bias of convcorr1, convcorr2, convflow1, convflow2, conv (motion encoder),
+ * convgru1.convz, .convr, .convq (1 x 5), convgru2.convz, .convr, .convq (5 x 1), conv1, conv2 (flow head), then the mask
+ * predictor's convrelu.0 and conv, in torch's layouts; hidden f32[N][128][h][w] and context f32[N][128][h][w] are the
+ * context encoder's halves after tanh / relu. It repacks every weight, copies the biases, stores the hidden state
+ * channel-last, and forms the context's share of the six GRU convolutions, which does not change between updates and is
+ * linear under zero padding: with W = [W_h | W_ctx | W_motion | W_flow] along the 384 input channels, per GRU g
+ *     plane_zr_g = conv_g(context, [W_z; W_r]_ctx) + [b_z; b_r]   (256 channels),   plane_q_g = conv_g(context, W_q,ctx) + b_q   (128)
+ * with conv_1 over 1 x 5 taps and conv_2 over 5 x 1: 768 channels in all.
+ * step: corr f32[N][324][h][w] (the lookup's output) and flow f32[N][2][h][w] are read as they are; eleven launches:
+ *     c1 = relu(conv1x1(corr) + b)  (256)       c2 = relu(conv3x3(c1) + b)  (192)
+ *     f1 = relu(conv7x7(flow) + b)  (128)       f2 = relu(conv3x3(f1) + b)  (64)
+ *     m  = relu(conv3x3([c2 | f2]) + b)  (126)
+ *     z, r h = gates(conv1x5([h | m | flow], [W_z; W_r]) + plane_zr_1)
+ *     h  = (1 - z) h + z tanh(conv1x5([r h | m | flow], W_q) + plane_q_1)          (in place in the workspace)
+ *     the same two with convgru2's 5 x 1 weights and planes
+ *     d  = relu(conv3x3(h) + b)  (256)          delta f32[N][2][h][w] = conv3x3(d) + b
+ * mask: reads the hidden state the workspace holds now (after begin, or after the last step); two launches:
+ *     mask f32[N][576][h][w] = 0.25 (conv1x1(relu(conv3x3(h) + b)) + b)
+ * It leaves the hidden state as it is; a step may follow it.
+ * eogs_flowlarge_hidden_offset: the byte offset of h f32[N][h][w][128] from the workspace's 256-byte aligned base.
+ * Refused: N, h or w below 1; N above 65535; more than 2^31 - 1 elements in a map (the mask's 576 channels count); NULL (a
+ * NULL among params too); a pointer not 16-byte aligned; a workspace too small (EOGS_ERR_WORKSPACE). */
+int eogs_flowlarge_bytes(int N, int h, int w, size_t* bytes);
+int eogs_flowlarge_hidden_offset(int N, int h, int w, size_t* offset);
+int eogs_flowlarge_begin(int N, int h, int w, const float* const* params, const float* hidden, const float* context,
+                                    void* ws, size_t ws_bytes, void* stream);
+int eogs_flowlarge_step(int N, int h, int w, const float* corr, const float* flow, void* ws, size_t ws_bytes, float* delta,
+                                   void* stream);
+int eogs_flowlarge_mask(int N, int h, int w, void* ws, size_t ws_bytes, float* mask, void* stream);
 
 /* ---- RAFT-small's two encoders (bottleneck blocks of 8, 16 and 24 mid channels behind a 7 x 7 stride-2 stem, a 1 x 1 head;
  * the feature encoder with an instance norm and a ReLU after every convolution, the context encoder with the ReLU alone):
