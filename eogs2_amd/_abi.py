@@ -95,6 +95,7 @@ FLOWENC_IN_NCHW, FLOWENC_OUT_NCHW = 1, 8  # EOGS_FLOWENC_IN_NCHW, _OUT_NCHW: its
 FLOWENC_SHORTCUT_NONE, FLOWENC_SHORTCUT_PLAIN, FLOWENC_SHORTCUT_NORM = 0, 1, 2  # EOGS_FLOWENC_SHORTCUT_*: eogs_flowenc_finish
 FLOWENC_FEATURE, FLOWENC_CONTEXT = 0, 1  # EOGS_FLOWENC_FEATURE, _CONTEXT: the encoder kinds
 FLOWENC_PARAMS = 44  # EOGS_FLOWENC_PARAMS
+FLOWRES_PARAMS, FLOWRES_BN = 32, 60  # EOGS_FLOWRES_PARAMS, _BN: RAFT-large's encoders, (weight, bias) x 16 and (gamma, beta, mean, var) x 15
 
 _p = C.c_void_p
 _i = C.c_int
@@ -217,6 +218,9 @@ HEADERS = {
         "eogs_flowenc_finish": (_i, [_i, _i, _i, _i, _p, _p, _p, _p, _i, _p, _p]),
         "eogs_flowenc_bytes": (_i, [_i, _i, _i, _i, C.POINTER(_z)]),
         "eogs_flowenc_run": (_i, [_i, _i, _i, _i, C.POINTER(_p), _p, _p, _z, _p, _p]),
+        "eogs_flowres_fold": (_i, [_i, _i, _p, _p, _p, _p, _p, _p, C.c_double, _p, _p, _p]),
+        "eogs_flowres_bytes": (_i, [_i, _i, _i, _i, C.POINTER(_z)]),
+        "eogs_flowres_run": (_i, [_i, _i, _i, _i, C.POINTER(_p), C.POINTER(_p), _p, _p, _z, _p, _p]),
     },
     "eogs_knn.h": {
         "eogs_knn_bytes": (_i, [_i, C.POINTER(_z)]),

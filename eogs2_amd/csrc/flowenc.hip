@@ -421,9 +421,209 @@ int check_enc_shape(const char* who, int N, int H, int W, int kind) {
   return EOGS_OK;
 }
 
+// ---- RAFT-large's encoders (eogs_flowres_*) ----
+
+// a batch norm in eval mode folded into its convolution: one workgroup per output channel, every thread forms the same s
+__global__ __launch_bounds__(256) void flowres_fold_kernel(int per_out, const float* __restrict__ w, const float* __restrict__ b,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           const float* __restrict__ mean, const float* __restrict__ var, double eps,
+                                                           float* __restrict__ w_out, float* __restrict__ b_out) {
+  const int c = blockIdx.x;
+  const float s = (float)((double)gamma[c] / sqrt((double)var[c] + eps));  // (a negative var: NaN)
+  const float* __restrict__ src = w + (int64_t)c * per_out;
+  float* __restrict__ dst = w_out + (int64_t)c * per_out;
+  for (int i = threadIdx.x; i < per_out; i += 256) dst[i] = src[i] * s;
+  if (threadIdx.x == 0) b_out[c] = (float)(((double)b[c] - (double)mean[c]) * (double)s + (double)beta[c]);
+}
+
+int fold_checked(const char* who, int cout, int per_out, const float* w, const float* b, const float* gamma, const float* beta,
+                 const float* mean, const float* var, double eps, float* w_out, float* b_out, hipStream_t s) {
+  if (cout < 1 || per_out < 1) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (cout and per_out must be at least 1)", who);
+  if (cout > 4096) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (a convolution has 1 to 4096 output channels)", who);
+  if ((int64_t)cout * per_out > 0x7FFFFFFFll) return fail(EOGS_ERR_INVALID_ARG, "%s: more than 2^31 - 1 weights", who);
+  if (!w || !b || !gamma || !beta || !mean || !var || !w_out || !b_out) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  if (!aligned16(w) || !aligned16(b) || !aligned16(gamma) || !aligned16(beta) || !aligned16(mean) || !aligned16(var) || !aligned16(w_out) ||
+      !aligned16(b_out))
+    return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  hipLaunchKernelGGL(flowres_fold_kernel, dim3((unsigned)cout), dim3(256), 0, s, per_out, w, b, gamma, beta, mean, var, eps, w_out, b_out);
+  return EOGS_OK;
+}
+
+constexpr int R_WIDTH[4] = {64, 64, 96, 128};  // the stem's and the three layers' channels
+constexpr int R_HEAD = 256;
+constexpr int R_CONVS = EOGS_FLOWRES_PARAMS / 2, R_NORMS = EOGS_FLOWRES_BN / 4;
+static_assert(R_CONVS == 16 && R_NORMS == R_CONVS - 1, "every convolution but the head has a norm");
+
+struct ResPlan {
+  EConv conv[R_CONVS];
+  int h[4], w[4];  // the image, then the maps after the stem, layer2 and layer3
+  float* pw[R_CONVS];
+  size_t pw_bytes[R_CONVS];
+  float *fw[R_NORMS], *fb[R_NORMS];  // CONTEXT: the folded weights and biases
+  float *x, *y, *r1, *r2, *rd, *tab[3];
+  double* partials;
+  size_t partials_bytes, bytes;
+};
+
+inline ResPlan res_plan(void* ws, int N, int H, int W, int kind) {
+  ResPlan p{};
+  const bool normed = kind == EOGS_FLOWENC_FEATURE;
+  p.h[0] = H; p.w[0] = W;
+  for (int i = 1; i < 4; i++) { p.h[i] = (p.h[i - 1] + 1) / 2; p.w[i] = (p.w[i - 1] + 1) / 2; }
+  int i = 0;
+  p.conv[i++] = {3, R_WIDTH[0], 7, 2};
+  for (int b = 0; b < 6; b++) {
+    const int L = b / 2, first = b % 2 == 0, cin = first ? R_WIDTH[L] : R_WIDTH[L + 1], cout = R_WIDTH[L + 1], s = first && L > 0 ? 2 : 1;
+    p.conv[i++] = {cin, cout, 3, s};
+    p.conv[i++] = {cout, cout, 3, 1};
+    if (s == 2) p.conv[i++] = {cin, cout, 1, 2};
+  }
+  p.conv[i++] = {R_WIDTH[3], R_HEAD, 1, 1};
+  char* base = ws ? ws_base(ws) : nullptr;
+  size_t o = 0;
+  for (int j = 0; j < R_CONVS; j++) {
+    const size_t n = conv_plan(p.conv[j].k, 1, &p.conv[j].cin, p.conv[j].cout).floats;
+    p.pw_bytes[j] = n * sizeof(float);
+    o = ws_carve(base, o, p.pw[j], n);
+  }
+  if (!normed)
+    for (int j = 0; j < R_NORMS; j++) {
+      o = ws_carve(base, o, p.fw[j], (size_t)p.conv[j].cout * p.conv[j].cin * p.conv[j].k * p.conv[j].k);
+      o = ws_carve(base, o, p.fb[j], (size_t)p.conv[j].cout);
+    }
+  // a buffer holds the largest map it is ever given: positions fall by four from layer to layer, channels rise by less
+  const size_t P1 = (size_t)N * p.h[1] * p.w[1], P2 = (size_t)N * p.h[2] * p.w[2], P3 = (size_t)N * p.h[3] * p.w[3];
+  auto most = [](size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); };
+  const size_t full = most(P1 * 64, P2 * 96, P3 * 128);
+  o = ws_carve(base, o, p.x, full);
+  o = ws_carve(base, o, p.y, full);
+  o = ws_carve(base, o, p.r1, full);
+  if (normed) o = ws_carve(base, o, p.r2, full);  // (CONTEXT: the second convolution closes the block itself)
+  o = ws_carve(base, o, p.rd, most(0, P2 * 96, P3 * 128));
+  if (normed) {
+    for (int j = 0; j < 3; j++) o = ws_carve(base, o, p.tab[j], (size_t)N * 128 * 2);
+    size_t most_rows = 0;  // (tiny maps: one tile each, the widest map decides)
+    for (int l = 1; l < 4; l++) {
+      const size_t rows = (size_t)tiles_of(p.h[l], p.w[l]) * R_WIDTH[l];
+      if (rows > most_rows) most_rows = rows;
+    }
+    p.partials_bytes = (size_t)N * most_rows * 2 * sizeof(double);
+    o = ws_carve(base, o, p.partials, p.partials_bytes / sizeof(double));
+  }
+  p.bytes = ws_align(o) + 256;
+  return p;
+}
+
+int check_res_shape(const char* who, int N, int H, int W, int kind) {
+  if (kind != EOGS_FLOWENC_FEATURE && kind != EOGS_FLOWENC_CONTEXT) return fail(EOGS_ERR_INVALID_ARG, "%s: the kind is FEATURE or CONTEXT", who);
+  if (N < 1 || H < 1 || W < 1) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (N, H and W must be at least 1)", who);
+  if (N > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: N above 65535", who);
+  const int64_t h1 = (H + 1) / 2, w1 = (W + 1) / 2, h2 = (h1 + 1) / 2, w2 = (w1 + 1) / 2, h3 = (h2 + 1) / 2, w3 = (w2 + 1) / 2;
+  if ((int64_t)N * 3 * H * W > 0x7FFFFFFFll || (int64_t)N * h1 * w1 * R_WIDTH[1] > 0x7FFFFFFFll || (int64_t)N * h2 * w2 * R_WIDTH[2] > 0x7FFFFFFFll ||
+      (int64_t)N * h3 * w3 * R_HEAD > 0x7FFFFFFFll)
+    return fail(EOGS_ERR_INVALID_ARG, "%s: more than 2^31 - 1 elements in a map", who);
+  if (kind == EOGS_FLOWENC_FEATURE && h3 * w3 == 1)
+    return fail(EOGS_ERR_INVALID_ARG, "%s: the feature encoder's last map is a single position, which an instance norm cannot normalise", who);
+  return EOGS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int eogs_flowres_fold(int cout, int per_out, const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
+                      const float* var, double eps, float* w_out, float* b_out, void* stream) {
+  clear_error();
+  hipStream_t s = (hipStream_t)stream;
+  RC_TRY(fold_checked("flowres_fold", cout, per_out, w, b, gamma, beta, mean, var, eps, w_out, b_out, s));
+  LAUNCH_TRY(s, false, "flowres_fold");
+  return EOGS_OK;
+}
+
+int eogs_flowres_bytes(int N, int H, int W, int kind, size_t* bytes) {
+  clear_error();
+  RC_TRY(check_res_shape("flowres_bytes", N, H, W, kind));
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "flowres_bytes: NULL argument");
+  *bytes = res_plan(nullptr, N, H, W, kind).bytes;
+  return EOGS_OK;
+}
+
+int eogs_flowres_run(int N, int H, int W, int kind, const float* const* params, const float* const* bn, const float* image, void* ws,
+                     size_t ws_bytes, float* out, void* stream) {
+  clear_error();
+  const char* who = "flowres_run";
+  RC_TRY(check_res_shape(who, N, H, W, kind));
+  const bool normed = kind == EOGS_FLOWENC_FEATURE;
+  if (normed && bn) return fail(EOGS_ERR_INVALID_ARG, "%s: bn goes with CONTEXT only (FEATURE normalises by instance)", who);
+  if (!normed && !bn) return fail(EOGS_ERR_INVALID_ARG, "%s: CONTEXT takes bn, the batch norms of its convolutions", who);
+  if (!params || !image || !ws || !out) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  for (int i = 0; i < EOGS_FLOWRES_PARAMS; i++) {
+    if (!params[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (!aligned16(params[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  }
+  for (int i = 0; bn && i < EOGS_FLOWRES_BN; i++) {
+    if (!bn[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (!aligned16(bn[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  }
+  if (!aligned16(image) || !aligned16(out)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  ResPlan p = res_plan(ws, N, H, W, kind);
+  if (ws_bytes < p.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  hipStream_t s = (hipStream_t)stream;
+  const int BIAS = EOGS_FLOWENC_EPI_BIAS, RELU = EOGS_FLOWENC_EPI_RELU, RESIDUAL = EOGS_FLOWENC_EPI_RESIDUAL;
+  const float *wsrc[R_CONVS], *bsrc[R_CONVS];  // what a convolution multiplies by and adds: the parameters, or their fold
+  for (int i = 0; i < R_CONVS; i++) {
+    const EConv& c = p.conv[i];
+    wsrc[i] = params[2 * i];
+    bsrc[i] = params[2 * i + 1];
+    if (!normed && i < R_NORMS) {
+      RC_TRY(fold_checked(who, c.cout, c.cin * c.k * c.k, params[2 * i], params[2 * i + 1], bn[4 * i], bn[4 * i + 1], bn[4 * i + 2], bn[4 * i + 3],
+                          1e-5, p.fw[i], p.fb[i], s));
+      wsrc[i] = p.fw[i];
+      bsrc[i] = p.fb[i];
+    }
+    RC_TRY(pack_checked(who, c.k, 1, &c.cin, nullptr, c.cin, c.cout, 0, c.cout, wsrc[i], p.pw[i], p.pw_bytes[i], s));
+  }
+  // one convolution of the table on an h x w map; with `tab` its statistics become that (mean, rstd) table
+  auto conv = [&](int i, int h, int w, const float* in, const float* in_norm, const float* res, float* o, float* tab, int epi, unsigned flags) {
+    const EConv& c = p.conv[i];
+    RC_TRY(enc_conv_checked(who, N, h, w, c.cin, c.cout, c.k, c.s, in, in_norm, p.pw[i], p.pw_bytes[i], bsrc[i], res, o,
+                            tab ? p.partials : nullptr, tab ? p.partials_bytes : 0, epi, flags, s));
+    if (tab) RC_TRY(norm_checked(who, N, (h + c.s - 1) / c.s, (w + c.s - 1) / c.s, c.cout, p.partials, p.partials_bytes, tab, s));
+    return (int)EOGS_OK;
+  };
+  int i = 0, lv = 1;
+  float *x = p.x, *y = p.y;
+  if (normed) {
+    RC_TRY(conv(i++, H, W, image, nullptr, nullptr, p.r2, p.tab[1], BIAS, EOGS_FLOWENC_IN_NCHW));
+    RC_TRY(finish_checked(who, N, p.h[1], p.w[1], R_WIDTH[0], p.r2, p.tab[1], nullptr, nullptr, EOGS_FLOWENC_SHORTCUT_NONE, x, s));
+  } else {
+    RC_TRY(conv(i++, H, W, image, nullptr, nullptr, x, nullptr, RELU, EOGS_FLOWENC_IN_NCHW));
+  }
+  for (int b = 0; b < 6; b++) {
+    const bool down = p.conv[i].s == 2;
+    const int h = p.h[lv], w = p.w[lv], ho = down ? p.h[lv + 1] : h, wo = down ? p.w[lv + 1] : w, cout = p.conv[i].cout;
+    if (normed) {
+      RC_TRY(conv(i, h, w, x, nullptr, nullptr, p.r1, p.tab[0], BIAS, 0u));
+      RC_TRY(conv(i + 1, ho, wo, p.r1, p.tab[0], nullptr, p.r2, p.tab[1], BIAS, 0u));
+      if (down) {
+        RC_TRY(conv(i + 2, h, w, x, nullptr, nullptr, p.rd, p.tab[2], BIAS, 0u));
+        RC_TRY(finish_checked(who, N, ho, wo, cout, p.r2, p.tab[1], p.rd, p.tab[2], EOGS_FLOWENC_SHORTCUT_NORM, y, s));
+      } else {
+        RC_TRY(finish_checked(who, N, ho, wo, cout, p.r2, p.tab[1], x, nullptr, EOGS_FLOWENC_SHORTCUT_PLAIN, y, s));
+      }
+    } else {
+      RC_TRY(conv(i, h, w, x, nullptr, nullptr, p.r1, nullptr, RELU, 0u));
+      if (down) RC_TRY(conv(i + 2, h, w, x, nullptr, nullptr, p.rd, nullptr, BIAS, 0u));
+      RC_TRY(conv(i + 1, ho, wo, p.r1, nullptr, down ? p.rd : x, y, nullptr, RESIDUAL, 0u));
+    }
+    i += down ? 3 : 2;
+    if (down) lv++;
+    float* t = x; x = y; y = t;
+  }
+  RC_TRY(conv(i, p.h[3], p.w[3], x, nullptr, nullptr, out, nullptr, BIAS, EOGS_FLOWENC_OUT_NCHW));
+  LAUNCH_TRY(s, false, who);
+  return EOGS_OK;
+}
 
 int eogs_flowenc_conv_partials(int N, int h, int w, int cout, int* rows, size_t* bytes) {
   clear_error();

@@ -10,6 +10,8 @@ flowmatching/flow_matching.py:76-86), with its correlation looked up ON DEMAND o
   FusedUpdateLarge(update_block, mask_predictor)    RAFT-large's update block and mask predictor       eleven launches per update, two per mask
   conv2d_strided_cl(input, weight, ...), finish_cl  the encoders' strided convolution and block tail   pack + one to three launches
   FusedEncoder(encoder_module)                      one of RAFT-small's two encoders                   one call
+  fold_batchnorm(weight, bias, gamma, beta, ...)    an eval-mode batch norm folded into its convolution one launch
+  FusedEncoderLarge(encoder_module)                 one of RAFT-large's two encoders                   one call
   RAFT, raft_small(), raft_large()                  the two published configurations as nn.Modules
   RAFT.load_weights(path_or_state_dict)             a torchvision checkpoint, strict
 
@@ -24,7 +26,10 @@ The encoders (convolutions, norms) are torch modules under `encoder="torch"`, an
 ConvGRU, flow head) under `update="torch"`. Under `encoder="fused"` RAFT-small's two encoders run over the eogs_flowenc_*
 entries: the same convolution kernel with a stride, the instance norm's statistics summed in double precision by the
 convolution that produces a map and applied by the one that reads it, the bottleneck's residual tail as an epilogue;
-`encoder="auto"` follows tools/raft_encoder_probe.py (profiles/raft_encoder_probe.json; README). Under `update="fused"` RAFT-small's update block runs over the eogs_flownet_* entries of the same header:
+`encoder="auto"` follows tools/raft_encoder_probe.py (profiles/raft_encoder_probe.json; README). Under `encoder="fused_large"`
+RAFT-large's two encoders run over the eogs_flowres_* entries: residual blocks of the same kernels, the context encoder's
+eval-mode batch norms folded into their convolutions at every call (tools/raft_large_encoder_probe.py,
+profiles/raft_large_encoder_probe.json; README). Under `update="fused"` RAFT-small's update block runs over the eogs_flownet_* entries of the same header:
 one channel-last convolution kernel on the exact-fp32 matrix instruction with the bias, ReLU, gate and GRU-blend epilogues in
 registers, the context's share of the three GRU convolutions computed once per forward and added as a plane, no torch.cat
 and no layout round trip; the weights stay the torch modules' parameters and are repacked at every forward. `update="auto"`
@@ -52,6 +57,7 @@ import torch.nn.functional as F
 from . import _lib
 from ._abi import (FLOWENC_CONTEXT, FLOWENC_EPI_BIAS, FLOWENC_EPI_RELU, FLOWENC_EPI_RESIDUAL, FLOWENC_FEATURE, FLOWENC_IN_NCHW,
                    FLOWENC_OUT_NCHW, FLOWENC_PARAMS, FLOWENC_SHORTCUT_NONE, FLOWENC_SHORTCUT_NORM, FLOWENC_SHORTCUT_PLAIN,
+                   FLOWRES_BN, FLOWRES_PARAMS,
                    FLOWNET_EPI_BIAS, FLOWNET_EPI_RELU, FLOWNET_MAX_KERNEL, FLOWNET_MAX_SEGMENTS, FLOWRECT_TAP_SHAPES,
                    FLOWLARGE_PARAMS, FLOWNET_UPDATE_PARAMS,
                    RAFT_MASK_CHANNELS, RAFT_MAX_LEVELS, RAFT_MAX_RADIUS, RAFT_NO_STAGE, RAFT_UP_BILINEAR, RAFT_UP_CONVEX)
@@ -691,6 +697,161 @@ class FusedEncoder:
         return out
 
 
+# ---- RAFT-large's encoders (eogs_flowres_*) ----
+
+def fold_batchnorm(weight, bias, gamma, beta, mean, var, eps=1e-5):
+    """A BatchNorm2d in eval mode folded into the convolution before it: `weight` [Cout, Cin, k, k], `bias`, `gamma`, `beta`,
+    the running `mean` and `var` [Cout]; returns (w', b') with s = float(gamma / sqrt(double(var) + eps)), w' = weight * s in
+    float32 and b' = float((double(bias) - mean) * s + beta), so that conv(x, w', b') is norm(conv(x, weight, bias))
+    (include/eogs_resample.h has the statement). Nothing is read back: a NaN stays a NaN, a negative var gives NaN."""
+    what = "fold_batchnorm"
+    _f32(weight, "the weight", what)
+    if weight.ndim != 4 or weight.numel() == 0:
+        raise ValueError(f"raft {what}: the weight is a non-empty (Cout, Cin, kh, kw) tensor, got {tuple(weight.shape)}")
+    cout = int(weight.shape[0])
+    vectors = (("the bias", bias), ("gamma", gamma), ("beta", beta), ("mean", mean), ("var", var))
+    for name, t in vectors:
+        _f32(t, name, what)
+        if tuple(t.shape) != (cout,):
+            raise ValueError(f"raft {what}: {name} is ({cout},), got {tuple(t.shape)}")
+    eps = float(eps)
+    if not 0.0 <= eps < math.inf:
+        raise ValueError(f"raft {what}: eps is a finite number of at least 0, got {eps!r}")
+    every = [weight] + [t for _, t in vectors]
+    for t in every:
+        _on_device(t, what)
+    dev = weight.device
+    if any(t.device != dev for t in every):
+        raise RuntimeError(f"raft {what}: the tensors live on different devices")
+    wt, b, g, be, m, v = (_aligned(t) for t in every)
+    w_out, b_out = torch.empty_like(wt), torch.empty_like(b)
+    call("eogs_flowres_fold", dev, cout, wt.numel() // cout, wt.data_ptr(), b.data_ptr(), g.data_ptr(), be.data_ptr(), m.data_ptr(),
+         v.data_ptr(), eps, w_out.data_ptr(), b_out.data_ptr())
+    return w_out, b_out
+
+
+class FusedEncoderLarge:
+    """One of RAFT-large's two encoders (a `FeatureEncoder` of residual blocks, widths 64, 64, 96, 128, a 256-channel head, with
+    InstanceNorm2d or with BatchNorm2d in eval mode) as one call: `fused(image [N, 3, H, W]) -> [N, 256, h, w]`, what the
+    module's forward returns. It holds the module, not copies: weights, biases and the batch norms' parameters and running
+    statistics are read at every call (the batch norms are folded and the weights repacked there), so they never go stale.
+    A batch norm in training mode raises: batch statistics are not what this computes. It is no nn.Module and registers
+    nothing. It keeps its workspace between calls, one per (device, stream, image shape) and at most MAX_WORKSPACES of them:
+    a workspace is 302 MB (feature) or 236 MB (context) per image at 1024^2 and 1189 or 916 MB at 2048^2 (eogs_flowres_bytes;
+    the feature encoder of a forward takes two images); the one least recently made is dropped. Float32 on the GPU, forward
+    only."""
+
+    WIDTHS = (64, 64, 96, 128)
+    HEAD = 256
+    MAX_WORKSPACES = 2
+
+    def __init__(self, encoder_module):
+        what = "raft FusedEncoderLarge"
+        if not isinstance(encoder_module, FeatureEncoder):
+            raise TypeError(f"{what}: expected a FeatureEncoder, got {type(encoder_module).__name__}")
+        names, shapes, strides = ["convnormrelu.0"], [(64, 3, 7, 7)], [2]
+        for L in (1, 2, 3):
+            for B in (0, 1):
+                block = getattr(encoder_module, f"layer{L}")[B]
+                if not isinstance(block, ResidualBlock):
+                    raise ValueError(f"{what}: the fused encoders are RAFT-large's, of residual blocks; layer{L}.{B} is a {type(block).__name__}")
+                cin, cout = self.WIDTHS[L - 1] if B == 0 else self.WIDTHS[L], self.WIDTHS[L]
+                down = B == 0 and L > 1
+                names += [f"layer{L}.{B}.convnormrelu1.0", f"layer{L}.{B}.convnormrelu2.0"]
+                shapes += [(cout, cin, 3, 3), (cout, cout, 3, 3)]
+                strides += [2 if down else 1, 1]
+                if down:
+                    if isinstance(block.downsample, nn.Identity):
+                        raise ValueError(f"{what}: layer{L}.0 has no downsample; RAFT-large's halves the map there")
+                    names.append(f"layer{L}.{B}.downsample.0")
+                    shapes.append((cout, cin, 1, 1))
+                    strides.append(2)
+                elif not isinstance(block.downsample, nn.Identity):
+                    raise ValueError(f"{what}: layer{L}.{B} has a downsample; RAFT-large's has none there")
+        names.append("conv")
+        shapes.append((self.HEAD, self.WIDTHS[3], 1, 1))
+        strides.append(1)
+        convs = [encoder_module.get_submodule(n) for n in names]
+        norms = []
+        for n in names[:-1]:
+            unit = n.rsplit(".", 1)[0]
+            found = [m for m in list(encoder_module.get_submodule(unit))[1:] if not isinstance(m, nn.ReLU)]
+            if len(found) != 1:
+                raise ValueError(f"{what}: one norm after every convolution but the head; {unit} has {found if found else 'none'}")
+            norms.append(found[0])
+        instance = isinstance(norms[0], nn.InstanceNorm2d)
+        for n, m in zip(names, norms):
+            if instance:
+                ok = isinstance(m, nn.InstanceNorm2d) and not m.affine and not m.track_running_stats
+            else:
+                ok = type(m) is nn.BatchNorm2d and m.affine and m.track_running_stats
+            if not ok or m.eps != 1e-5:
+                raise ValueError(f"{what}: the norm is InstanceNorm2d without affine and running statistics or BatchNorm2d with both, "
+                                 f"eps 1e-5, the same kind throughout; {n.rsplit('.', 1)[0]} has {m}")
+        got = tuple(tuple(c.weight.shape) for c in convs)
+        got_strides = tuple(c.stride[0] for c in convs)
+        if got != tuple(shapes) or got_strides != tuple(strides) or any(c.bias is None for c in convs):
+            raise ValueError(f"{what}: the fused encoders are RAFT-large's (widths 64, 64, 96, 128, a head of 256); this encoder's "
+                             f"convolutions are {got} with strides {got_strides}")
+        assert 2 * len(convs) == FLOWRES_PARAMS and 4 * len(norms) == FLOWRES_BN
+        self._names, self._convs, self._norms = tuple(names), convs, None if instance else norms
+        self.kind, self.channels = FLOWENC_FEATURE if instance else FLOWENC_CONTEXT, self.HEAD
+        self._ws = Workspaces()
+
+    def __getstate__(self):  # a copied or pickled module starts without workspaces
+        return {"_names": self._names, "_convs": self._convs, "_norms": self._norms, "kind": self.kind, "channels": self.channels}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._ws = Workspaces()
+
+    @staticmethod
+    def _checked(name, p, dev):
+        if p.dtype != torch.float32 or p.device != dev:
+            raise RuntimeError(f"raft FusedEncoderLarge: {name} is {p.dtype} on {p.device}; the fused encoder runs in float32 on "
+                               f"the image's device ({dev}), there is no CPU fallback")
+        return _aligned(p)
+
+    def _params(self, dev):
+        return [self._checked(name, p, dev) for name, c in zip(self._names, self._convs) for p in (c.weight, c.bias)]
+
+    def _bn(self, dev):
+        if self._norms is None:
+            return None
+        out = []
+        for name, m in zip(self._names, self._norms):
+            unit = name.rsplit(".", 1)[0] + ".1"
+            if m.training:
+                raise RuntimeError(f"raft FusedEncoderLarge: {unit} is in training mode; the fused encoder folds the running statistics "
+                                   "(eval mode), batch statistics are not what it computes")
+            out += [self._checked(unit, p, dev) for p in (m.weight, m.bias, m.running_mean, m.running_var)]
+        return out
+
+    def workspace_bytes(self, N, H, W):
+        return nbytes(_lib.get(), "flowres_bytes", int(N), int(H), int(W), self.kind)
+
+    def __call__(self, image):
+        what = "FusedEncoderLarge"
+        N, _, H, W = _map(image, "the image", what, 3)
+        _on_device(image, what)
+        dev = image.device
+        bn = self._bn(dev)
+        params = self._params(dev)
+        size = self.workspace_bytes(N, H, W)
+        ws = self._ws.of((N, H, W), dev, lambda: Workspaces.bytes(dev, size))
+        while len(self._ws) > self.MAX_WORKSPACES:  # (the allocator frees in stream order: a launch in flight keeps its memory)
+            del self._ws[next(k for k, v in self._ws.items() if v is not ws)]
+        x = _aligned(image)
+        h, w = H, W
+        for _ in range(3):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        out = torch.empty((N, self.channels, h, w), dtype=torch.float32, device=dev)
+        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
+        bn_table = None if bn is None else (ctypes.c_void_p * len(bn))(*(p.data_ptr() for p in bn))
+        call("eogs_flowres_run", dev, N, H, W, self.kind, table, bn_table, x.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr())
+        return out
+
+
 # ---- the materialised form, in plain torch: any dtype, any device ----
 
 def volume_pyramid(fmap1, fmap2, levels):
@@ -920,6 +1081,15 @@ AUTO_UPDATE_LARGE_IS_FUSED = True
 # 13.65 ms (13.62 - 13.77) at 2048^2; the fused encoders hold 0.43 and 1.72 GB of workspace there and peak HIGHER in memory. RAFT's default stays encoder="torch": "auto" is what an integrator asks for.
 AUTO_ENCODER_IS_FUSED = True
 
+# RAFT-large's encoder="auto" runs the torch modules whatever this says: the existing tests take that run as their yardstick. It
+# records the verdict of tools/raft_large_encoder_probe.py (profiles/raft_large_encoder_probe.json) by the rule above, so that a
+# later change can flip "auto" on it. Measured (encoder phase, fused median, min - max against torch): 6.73 ms (6.70 - 6.75) against
+# 7.55 ms (7.53 - 7.58) at 1024^2, 25.21 ms (25.19 - 25.23) against 29.43 ms (29.40 - 29.56) at 2048^2: the fused encoders win, by
+# 1.12 x and 1.17 x; the whole forward with update="fused_large" 25.32 against 26.14 ms and 84.16 against 88.48 ms. They hold 0.83
+# and 3.29 GB of workspace there, and one forward peaks at 1.23 against 0.98 GB and 4.73 against 3.85 GB. Not measured:
+# pretrained weights, batches above 1, the kernels under a profiler.
+AUTO_ENCODER_LARGE_IS_FUSED = True
+
 
 class RAFT(nn.Module):
     """RAFT with torchvision's call shape: `model(image1, image2, num_flow_updates=12) -> list of flows`, images [N, 3, H, W]
@@ -935,8 +1105,10 @@ class RAFT(nn.Module):
     is recorded, as the measurement decided (AUTO_UPDATE_IS_FUSED), the torch modules otherwise, and for RAFT-large always.
 
     encoder: "torch" (the two encoders as torch modules, any dtype and device; the default), "fused" (FusedEncoder: RAFT-small
-    only, float32 on the GPU, forward only, no CPU fallback) or "auto": the fused encoders for RAFT-small in float32 on the
-    GPU when no gradient is recorded and the measurement decided for them (AUTO_ENCODER_IS_FUSED), the torch modules otherwise."""
+    only, float32 on the GPU, forward only, no CPU fallback), "fused_large" (FusedEncoderLarge: RAFT-large only, under the same
+    conditions; its context encoder's batch norms must be in eval mode) or "auto": the fused encoders for RAFT-small in float32
+    on the GPU when no gradient is recorded and the measurement decided for them (AUTO_ENCODER_IS_FUSED), the torch modules
+    otherwise, and for RAFT-large always (AUTO_ENCODER_LARGE_IS_FUSED records the measurement)."""
 
     def __init__(self, name="small", corr="auto", update="auto", encoder="torch"):
         super().__init__()
@@ -950,10 +1122,12 @@ class RAFT(nn.Module):
             raise ValueError(f"raft RAFT: update='fused' is RAFT-small's update block; '{name}' runs update='torch' or 'fused_large'")
         if update == "fused_large" and name != "large":
             raise ValueError(f"raft RAFT: update='fused_large' is RAFT-large's update block; '{name}' runs update='torch' or 'fused'")
-        if encoder not in ("auto", "torch", "fused"):
-            raise ValueError(f"raft RAFT: encoder is 'auto', 'torch' or 'fused', got {encoder!r}")
+        if encoder not in ("auto", "torch", "fused", "fused_large"):
+            raise ValueError(f"raft RAFT: encoder is 'auto', 'torch', 'fused' or 'fused_large', got {encoder!r}")
         if encoder == "fused" and name != "small":
-            raise ValueError(f"raft RAFT: encoder='fused' is RAFT-small's encoders; '{name}' runs encoder='torch'")
+            raise ValueError(f"raft RAFT: encoder='fused' is RAFT-small's encoders; '{name}' runs encoder='torch' or 'fused_large'")
+        if encoder == "fused_large" and name != "large":
+            raise ValueError(f"raft RAFT: encoder='fused_large' is RAFT-large's encoders; '{name}' runs encoder='torch' or 'fused'")
         cfg = CONFIGS[name]
         self.name, self.corr, self.update, self.encoder = name, corr, update, encoder
         self.corr_levels, self.corr_radius = cfg["corr_levels"], cfg["corr_radius"]
@@ -969,6 +1143,7 @@ class RAFT(nn.Module):
         self._fused = FusedUpdate(self.update_block) if name == "small" else None  # (no Module: nothing is registered)
         self._fused_enc = (FusedEncoder(self.feature_encoder), FusedEncoder(self.context_encoder)) if name == "small" else None
         self._fused_large = FusedUpdateLarge(self.update_block, self.mask_predictor) if name == "large" else None
+        self._fused_enc_large = (FusedEncoderLarge(self.feature_encoder), FusedEncoderLarge(self.context_encoder)) if name == "large" else None
 
     def _ondemand(self, x):
         if self.corr == "volume":
@@ -996,6 +1171,13 @@ class RAFT(nn.Module):
         return ok and (self.update == "fused" or (AUTO_UPDATE_IS_FUSED and not torch.is_grad_enabled()))
 
     def _fused_encoder(self, x):
+        if self.encoder == "fused_large":  # (never under "auto": AUTO_ENCODER_LARGE_IS_FUSED)
+            if self._fused_enc_large is None:  # (the constructor refuses it; `model.encoder` reassigned afterwards gets here)
+                raise ValueError(f"raft RAFT: encoder='fused_large' is RAFT-large's encoders; '{self.name}' runs encoder='torch' or 'fused'")
+            if x.device.type != "cuda" or x.dtype != torch.float32:
+                raise RuntimeError(f"raft RAFT: encoder='fused_large' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
+                                   "there is no CPU fallback, encoder='torch' is the plain torch form")
+            return True
         if self.encoder == "torch" or self._fused_enc is None:
             return False
         ok = x.device.type == "cuda" and x.dtype == torch.float32
@@ -1016,7 +1198,10 @@ class RAFT(nn.Module):
             raise ValueError(f"input image H and W should be at least 128, instead got {H} (h) and {W} (w): the feature "
                              "encoder downsamples by 8 and the correlation pyramid by another 8")
         ondemand, fused, fused_enc = self._ondemand(image1), self._fused_update(image1), self._fused_encoder(image1)
-        feature_encoder, context_encoder = self._fused_enc if fused_enc else (self.feature_encoder, self.context_encoder)
+        if fused_enc:
+            feature_encoder, context_encoder = self._fused_enc_large if self.encoder == "fused_large" else self._fused_enc
+        else:
+            feature_encoder, context_encoder = self.feature_encoder, self.context_encoder
         fmaps = feature_encoder(torch.cat([image1, image2], dim=0))
         fmap1, fmap2 = torch.chunk(fmaps, chunks=2, dim=0)
         if ondemand:
@@ -1082,12 +1267,14 @@ def raft_small(corr="auto", update="auto", encoder="torch"):
 
 def raft_large(corr="auto", encoder="torch", update="auto"):
     """RAFT-large: residual encoders (256 feature channels), 4 levels at radius 4, 1 x 5 + 5 x 1 GRUs, convex upsampling.
-    Its encoders are torch modules: encoder="fused" is refused. update: "auto" and "torch" run the update block and the mask
-    predictor as torch modules, "fused_large" over the HIP convolutions (FusedUpdateLarge)."""
+    encoder: "torch" and "auto" run the two encoders as torch modules, "fused_large" over the HIP convolutions
+    (FusedEncoderLarge: the model in eval mode); encoder="fused" is RAFT-small's and refused. update: "auto" and "torch" run the
+    update block and the mask predictor as torch modules, "fused_large" over the HIP convolutions (FusedUpdateLarge)."""
     return RAFT("large", corr, update, encoder)
 
 
-__all__ = ["AUTO_ENCODER_IS_FUSED", "AUTO_UPDATE_IS_FUSED", "AUTO_UPDATE_LARGE_IS_FUSED", "CONFIGS", "CorrPyramid", "FusedEncoder",
-           "FusedUpdate", "FusedUpdateLarge", "RAFT", "TORCHVISION_NAMES", "conv2d_cl", "conv2d_rect_cl", "conv2d_strided_cl", "conv_info",
-           "convex_upsample_torch", "corr_lookup", "corr_pyramid", "finish_cl", "raft_large", "raft_small", "stage_info", "upsample_flow",
+__all__ = ["AUTO_ENCODER_IS_FUSED", "AUTO_ENCODER_LARGE_IS_FUSED", "AUTO_UPDATE_IS_FUSED", "AUTO_UPDATE_LARGE_IS_FUSED", "CONFIGS",
+           "CorrPyramid", "FusedEncoder", "FusedEncoderLarge", "FusedUpdate", "FusedUpdateLarge", "RAFT", "TORCHVISION_NAMES", "conv2d_cl",
+           "conv2d_rect_cl", "conv2d_strided_cl", "conv_info", "convex_upsample_torch", "corr_lookup", "corr_pyramid", "finish_cl",
+           "fold_batchnorm", "raft_large", "raft_small", "stage_info", "upsample_flow",
            "volume_lookup", "volume_pyramid"]

@@ -240,10 +240,11 @@ def main(argv=None):
                          "'fused_large' (RAFT-large's update block and mask predictor over the entries of include/eogs_resample.h, "
                          "RAFT-large only) or 'auto' (for RAFT-small what profiles/raft_update_probe.json measured as faster; for "
                          "RAFT-large the torch modules)")
-    ap.add_argument("--flow-encoder", choices=["torch", "fused", "auto"], default="torch", metavar="HOW",
-                    help="with --flow-network small: how RAFT's two encoders run, eogs2_amd.raft.RAFT(encoder=...): 'torch' (torch "
-                         "modules), 'fused' (the eogs_flowenc_* convolutions of include/eogs_resample.h, RAFT-small only) or 'auto' "
-                         "(what profiles/raft_encoder_probe.json measured as faster)")
+    ap.add_argument("--flow-encoder", choices=["torch", "fused", "fused_large", "auto"], default="torch", metavar="HOW",
+                    help="with --flow-network: how RAFT's two encoders run, eogs2_amd.raft.RAFT(encoder=...): 'torch' (torch "
+                         "modules), 'fused' (the eogs_flowenc_* convolutions of include/eogs_resample.h, RAFT-small only), "
+                         "'fused_large' (RAFT-large's residual encoders over the eogs_flowres_* entries, RAFT-large only) or 'auto' "
+                         "(for RAFT-small what profiles/raft_encoder_probe.json measured as faster; for RAFT-large the torch modules)")
     ap.add_argument("--flow-weights", default=None, metavar="PATH",
                     help="with --flow-network: a torchvision RAFT checkpoint of that configuration (raft_small / raft_large state "
                          "dict), loaded strictly by eogs2_amd.raft.RAFT.load_weights; nothing is downloaded")
@@ -417,6 +418,8 @@ def main(argv=None):
         ap.error("--flow-update fused_large needs --flow-network large")
     if a.flow_encoder == "fused" and a.flow_network != "small":
         ap.error("--flow-encoder fused needs --flow-network small")
+    if a.flow_encoder == "fused_large" and a.flow_network != "large":
+        ap.error("--flow-encoder fused_large needs --flow-network large")
     if a.flow_network and (a.size < 121 or a.graph):
         ap.error("--flow-network: RAFT needs images of at least 128 px after rounding up to a multiple of 8 (--size >= 121), and is "
                  "not recorded into a graph here (not with --graph)")

@@ -395,6 +395,52 @@ int eogs_flowenc_bytes(int N, int H, int W, int kind, size_t* bytes);
 int eogs_flowenc_run(int N, int H, int W, int kind, const float* const* params, const float* image, void* ws, size_t ws_bytes,
                      float* out, void* stream);
 
+/* ---- RAFT-large's two encoders (residual blocks of two 3 x 3 convolutions at widths 64, 64, 96, 128 behind a 7 x 7 stride-2
+ * stem, a 1 x 1 head of 256 channels; the feature encoder with an instance norm after every convolution but the head, the
+ * context encoder with a batch norm in eval mode there): eogs_flowenc_conv, eogs_flowenc_norm and eogs_flowenc_finish above,
+ * a kernel that folds an eval-mode batch norm into its convolution, and each encoder as one call. Float32, forward only.
+ * Every convention above holds. params and bn are HOST arrays of device pointers.
+ *
+ * eogs_flowres_fold: a batch norm in eval mode folded into its convolution, one kernel, per output channel c over
+ * per_out = Cin k k weights:
+ *   s[c] = float(gamma[c] / sqrt(double(var[c]) + eps)), computed in double and rounded once
+ *   w'[c, .] = w[c, .] * s[c], one float32 product per weight
+ *   b'[c] = float((double(b[c]) - double(mean[c])) * double(s[c]) + double(beta[c])), where s[c] is the rounded float32 above
+ * w and w_out f32[cout][per_out]; b, gamma, beta, mean, var and b_out f32[cout]. Nothing is read back on the host: a NaN
+ * stays a NaN, a negative var is not refused and gives NaN (in its channel alone).
+ * Refused: cout or per_out below 1 (cout above 4096, more than 2^31 - 1 weights); a NULL pointer; a pointer not 16-byte
+ * aligned.
+ *
+ * eogs_flowres_run: a whole encoder. kind EOGS_FLOWENC_FEATURE (bn must be NULL) or EOGS_FLOWENC_CONTEXT (bn required).
+ * params: the 32 device pointers weight, bias of the 16 convolutions in module order: convnormrelu; per block of layer1.0,
+ * layer1.1, layer2.0, layer2.1, layer3.0, layer3.1 its convnormrelu1 (3 x 3, stride 2 in layer2.0 and layer3.0),
+ * convnormrelu2 (3 x 3) and, where it has one (layer2.0, layer3.0), its downsample (1 x 1, stride 2); conv. bn: the 60 device
+ * pointers gamma, beta, running mean, running var of the 15 convolutions that have a norm, in the same order. image
+ * f32[N][3][H][W]; out f32[N][256][h3][w3] (NCHW) with h1 = ceil(H / 2), h2 = ceil(h1 / 2), h3 = ceil(h2 / 2). The packings
+ * (and the folds) are rebuilt at every call.
+ *   FEATURE  stem: conv (statistics), norm, finish(NONE). Block: conv1(x) -> r1 and its table; conv2 normalising r1 on load
+ *            -> r2 and its table; with a downsample down(x) -> rd and its table; y = finish(r2, table, S) with S = x (PLAIN)
+ *            or rd with its table (NORM): relu(S + relu(norm(r2))), the block's forward. Head: conv (BIAS, OUT_NCHW).
+ *            16 convolutions, 15 norms, 7 pointwise passes.
+ *   CONTEXT  every convolution with a norm is folded by eogs_flowres_fold's kernel with eps 1e-5 into the workspace first.
+ *            Stem RELU. Block: conv1 RELU, the downsample (BIAS) where there is one, conv2 RESIDUAL with the block's input
+ *            or the downsample's output as res. Head as above. 16 convolutions and 15 folds, no pointwise pass.
+ * The workspace (eogs_flowres_bytes; rounded up to 256 bytes inside) holds the packed weights, for CONTEXT the folded ones,
+ * a block's maps at the stem's resolution, the partials and the norm tables; a call relies on nothing in it that it did not
+ * write.
+ * Refused: an unknown kind; N, H or W below 1; N above 65535; more than 2^31 - 1 elements in a map; for FEATURE a final
+ * map of a single position; bn given under FEATURE or missing under CONTEXT; NULL (a NULL among params or bn too); a
+ * pointer not 16-byte aligned; a workspace too small (EOGS_ERR_WORKSPACE). */
+
+#define EOGS_FLOWRES_PARAMS 32
+#define EOGS_FLOWRES_BN 60
+
+int eogs_flowres_fold(int cout, int per_out, const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
+                      const float* var, double eps, float* w_out, float* b_out, void* stream);
+int eogs_flowres_bytes(int N, int H, int W, int kind, size_t* bytes);
+int eogs_flowres_run(int N, int H, int W, int kind, const float* const* params, const float* const* bn, const float* image, void* ws,
+                     size_t ws_bytes, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
