@@ -347,81 +347,7 @@ int finish_checked(const char* who, int N, int h, int w, int C, const float* v, 
   return EOGS_OK;
 }
 
-// ---- the encoders ----
-
-constexpr int E_WIDTH[4] = {32, 32, 64, 96};  // the stem's and the three layers' channels
-constexpr int E_CONVS = EOGS_FLOWENC_PARAMS / 2;
-struct EConv { int cin, cout, k, s; };
-
-struct EncPlan {
-  EConv conv[E_CONVS];
-  int h[4], w[4];  // the image, then the maps after the stem, layer2 and layer3
-  int head;
-  float* pw[E_CONVS];
-  size_t pw_bytes[E_CONVS];
-  float *x, *y, *r1, *r2, *r3, *rd, *tab[4];
-  double* partials;
-  size_t partials_bytes, bytes;
-};
-
-inline EncPlan enc_plan(void* ws, int N, int H, int W, int kind) {
-  EncPlan p{};
-  p.head = kind == EOGS_FLOWENC_FEATURE ? 128 : 160;
-  p.h[0] = H; p.w[0] = W;
-  for (int i = 1; i < 4; i++) { p.h[i] = (p.h[i - 1] + 1) / 2; p.w[i] = (p.w[i - 1] + 1) / 2; }
-  int i = 0;
-  p.conv[i++] = {3, E_WIDTH[0], 7, 2};
-  for (int b = 0; b < 6; b++) {
-    const int L = b / 2, first = b % 2 == 0, cin = first ? E_WIDTH[L] : E_WIDTH[L + 1], cout = E_WIDTH[L + 1], s = first && L > 0 ? 2 : 1;
-    p.conv[i++] = {cin, cout / 4, 1, 1};
-    p.conv[i++] = {cout / 4, cout / 4, 3, s};
-    p.conv[i++] = {cout / 4, cout, 1, 1};
-    if (s == 2) p.conv[i++] = {cin, cout, 1, 2};
-  }
-  p.conv[i++] = {E_WIDTH[3], p.head, 1, 1};
-  char* base = ws ? ws_base(ws) : nullptr;
-  size_t o = 0;
-  for (int j = 0; j < E_CONVS; j++) {
-    const size_t n = conv_plan(p.conv[j].k, 1, &p.conv[j].cin, p.conv[j].cout).floats;
-    p.pw_bytes[j] = n * sizeof(float);
-    o = ws_carve(base, o, p.pw[j], n);
-  }
-  // a buffer holds the largest map it is ever given: positions fall by four from layer to layer, channels rise by less
-  const size_t P1 = (size_t)N * p.h[1] * p.w[1], P2 = (size_t)N * p.h[2] * p.w[2], P3 = (size_t)N * p.h[3] * p.w[3];
-  auto most = [](size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); };
-  const size_t full = most(P1 * 32, P2 * 64, P3 * 96);
-  o = ws_carve(base, o, p.x, full);
-  o = ws_carve(base, o, p.y, full);
-  o = ws_carve(base, o, p.r1, most(P1 * 16, P2 * 24, P3 * 24));  // (layer2's first unit: 16 channels on the stem's positions)
-  o = ws_carve(base, o, p.r2, most(P1 * 8, P2 * 16, P3 * 24));
-  o = ws_carve(base, o, p.r3, full);
-  o = ws_carve(base, o, p.rd, most(0, P2 * 64, P3 * 96));
-  for (int j = 0; j < 4; j++) o = ws_carve(base, o, p.tab[j], (size_t)N * 96 * 2);
-  p.partials_bytes = (size_t)N * tiles_of(p.h[1], p.w[1]) * 32 * 2 * sizeof(double);  // (tiles x channels falls as the maps shrink)
-  {
-    const size_t alt2 = (size_t)N * tiles_of(p.h[2], p.w[2]) * 64 * 2 * sizeof(double), alt3 = (size_t)N * tiles_of(p.h[3], p.w[3]) * 96 * 2 * sizeof(double);
-    if (alt2 > p.partials_bytes) p.partials_bytes = alt2;  // (tiny maps: one tile each, the widest map decides)
-    if (alt3 > p.partials_bytes) p.partials_bytes = alt3;
-  }
-  o = ws_carve(base, o, p.partials, p.partials_bytes / sizeof(double));
-  p.bytes = ws_align(o) + 256;
-  return p;
-}
-
-int check_enc_shape(const char* who, int N, int H, int W, int kind) {
-  if (kind != EOGS_FLOWENC_FEATURE && kind != EOGS_FLOWENC_CONTEXT) return fail(EOGS_ERR_INVALID_ARG, "%s: the kind is FEATURE or CONTEXT", who);
-  if (N < 1 || H < 1 || W < 1) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (N, H and W must be at least 1)", who);
-  if (N > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: N above 65535", who);
-  const int64_t h1 = (H + 1) / 2, w1 = (W + 1) / 2, h2 = (h1 + 1) / 2, w2 = (w1 + 1) / 2, h3 = (h2 + 1) / 2, w3 = (w2 + 1) / 2;
-  if ((int64_t)N * 3 * H * W > 0x7FFFFFFFll || (int64_t)N * h1 * w1 * 32 > 0x7FFFFFFFll || (int64_t)N * h2 * w2 * 64 > 0x7FFFFFFFll ||
-      (int64_t)N * h3 * w3 * 160 > 0x7FFFFFFFll)
-    return fail(EOGS_ERR_INVALID_ARG, "%s: more than 2^31 - 1 elements in a map", who);
-  if (kind == EOGS_FLOWENC_FEATURE && h3 * w3 == 1)
-    return fail(EOGS_ERR_INVALID_ARG, "%s: the feature encoder's last map is a single position, which an instance norm cannot normalise", who);
-  return EOGS_OK;
-}
-
-// ---- RAFT-large's encoders (eogs_flowres_*) ----
+// ---- RAFT-large's batch norms (eogs_flowres_fold) ----
 
 // a batch norm in eval mode folded into its convolution: one workgroup per output channel, every thread forms the same s
 __global__ __launch_bounds__(256) void flowres_fold_kernel(int per_out, const float* __restrict__ w, const float* __restrict__ b,
@@ -449,133 +375,146 @@ int fold_checked(const char* who, int cout, int per_out, const float* w, const f
   return EOGS_OK;
 }
 
-constexpr int R_WIDTH[4] = {64, 64, 96, 128};  // the stem's and the three layers' channels
-constexpr int R_HEAD = 256;
-constexpr int R_CONVS = EOGS_FLOWRES_PARAMS / 2, R_NORMS = EOGS_FLOWRES_BN / 4;
-static_assert(R_CONVS == 16 && R_NORMS == R_CONVS - 1, "every convolution but the head has a norm");
+// ---- the encoders: RAFT-small's (eogs_flowenc_run) and RAFT-large's (eogs_flowres_run) ----
 
-struct ResPlan {
-  EConv conv[R_CONVS];
+// An encoder, stated once: a 7 x 7 stem at stride 2, three layers of two blocks (the first block of layers 2 and 3 halves the
+// map, at its convolution `strided`, and carries a 1 x 1 downsample), a 1 x 1 head. A block is `nblock` convolutions of
+// kernel sizes bk, with cout / mid_div channels between them: RAFT-small's 1-3-1 bottleneck, RAFT-large's 3-3 residual block.
+// FEATURE normalises every map but the head's by instance; CONTEXT has no norm, or (fold) eval-mode batch norms folded first.
+struct EncDesc {
+  int width[4];  // the stem's and the three layers' channels
+  int head[2];   // the head's, by kind
+  int nblock, bk[3], mid_div, strided;
+  bool fold;
+};
+constexpr EncDesc E_SMALL = {{32, 32, 64, 96}, {128, 160}, 3, {1, 3, 1}, 4, 1, false};
+constexpr EncDesc E_LARGE = {{64, 64, 96, 128}, {256, 256}, 2, {3, 3, 0}, 1, 0, true};
+static_assert(EOGS_FLOWENC_FEATURE == 0 && EOGS_FLOWENC_CONTEXT == 1, "head[] is indexed by the kind");
+constexpr int enc_convs(const EncDesc& d) { return 1 + 6 * d.nblock + 2 + 1; }  // stem, blocks, two downsamples, head
+constexpr int E_MAX = enc_convs(E_SMALL);
+static_assert(2 * enc_convs(E_SMALL) == EOGS_FLOWENC_PARAMS && 2 * enc_convs(E_LARGE) == EOGS_FLOWRES_PARAMS && enc_convs(E_LARGE) <= E_MAX,
+              "a description reads exactly the params table of its entry");
+static_assert(4 * (enc_convs(E_LARGE) - 1) == EOGS_FLOWRES_BN, "every convolution but the head has a norm");
+
+struct EConv { int cin, cout, k, s; };
+
+struct EncPlan {
+  EConv conv[E_MAX];
+  int nconv;
   int h[4], w[4];  // the image, then the maps after the stem, layer2 and layer3
-  float* pw[R_CONVS];
-  size_t pw_bytes[R_CONVS];
-  float *fw[R_NORMS], *fb[R_NORMS];  // CONTEXT: the folded weights and biases
-  float *x, *y, *r1, *r2, *rd, *tab[3];
+  float* pw[E_MAX];
+  size_t pw_bytes[E_MAX];
+  float *fw[E_MAX], *fb[E_MAX];  // fold: the folded weights and biases
+  float *x, *y, *r[3], *rd, *tab[4];  // the blocks' ping-pong; block convolution j's map and (mean, rstd) table; the downsample's (tab[nblock])
   double* partials;
   size_t partials_bytes, bytes;
 };
 
-inline ResPlan res_plan(void* ws, int N, int H, int W, int kind) {
-  ResPlan p{};
+inline EncPlan enc_plan(const EncDesc& d, void* ws, int N, int H, int W, int kind) {
+  EncPlan p{};
   const bool normed = kind == EOGS_FLOWENC_FEATURE;
+  const int n = d.nblock;
   p.h[0] = H; p.w[0] = W;
   for (int i = 1; i < 4; i++) { p.h[i] = (p.h[i - 1] + 1) / 2; p.w[i] = (p.w[i - 1] + 1) / 2; }
-  int i = 0;
-  p.conv[i++] = {3, R_WIDTH[0], 7, 2};
+  // The table, in the order eogs_*_run walks it, and with it each scratch buffer's size: the largest map any convolution
+  // (or, for x and y, any block's tail) writes into it. `dst`: that buffer's size; none for the head, which writes `out`.
+  size_t xy = 0, r[3] = {}, rd = 0, rows = 0;  // floats; rows: of (tile, channel) partial sums per image
+  int widest = 0;                               // normalised map, in channels
+  auto grow = [](size_t& a, size_t b) { if (b > a) a = b; };
+  auto put = [&](int cin, int cout, int k, int s, int lv, size_t* dst) {
+    p.conv[p.nconv++] = {cin, cout, k, s};
+    const int lo = lv + (s == 2);
+    if (!dst) return;
+    grow(*dst, (size_t)N * p.h[lo] * p.w[lo] * cout);
+    grow(rows, (size_t)tiles_of(p.h[lo], p.w[lo]) * cout);
+    if (cout > widest) widest = cout;
+  };
+  put(3, d.width[0], 7, 2, 0, normed ? &r[n - 1] : &xy);
+  grow(xy, (size_t)N * p.h[1] * p.w[1] * d.width[0]);
+  int lv = 1;
   for (int b = 0; b < 6; b++) {
-    const int L = b / 2, first = b % 2 == 0, cin = first ? R_WIDTH[L] : R_WIDTH[L + 1], cout = R_WIDTH[L + 1], s = first && L > 0 ? 2 : 1;
-    p.conv[i++] = {cin, cout, 3, s};
-    p.conv[i++] = {cout, cout, 3, 1};
-    if (s == 2) p.conv[i++] = {cin, cout, 1, 2};
+    const int L = b / 2, first = b % 2 == 0, cin = first ? d.width[L] : d.width[L + 1], cout = d.width[L + 1], s = first && L > 0 ? 2 : 1;
+    const int mid = cout / d.mid_div, lo = lv + (s == 2);
+    for (int j = 0; j < n; j++)  // (without a norm the last convolution closes the block itself, into y)
+      put(j ? mid : cin, j < n - 1 ? mid : cout, d.bk[j], j == d.strided ? s : 1, j <= d.strided ? lv : lo, !normed && j == n - 1 ? &xy : &r[j]);
+    if (s == 2) put(cin, cout, 1, 2, lv, &rd);
+    grow(xy, (size_t)N * p.h[lo] * p.w[lo] * cout);
+    lv = lo;
   }
-  p.conv[i++] = {R_WIDTH[3], R_HEAD, 1, 1};
+  put(d.width[3], d.head[kind], 1, 1, 3, nullptr);
   char* base = ws ? ws_base(ws) : nullptr;
   size_t o = 0;
-  for (int j = 0; j < R_CONVS; j++) {
-    const size_t n = conv_plan(p.conv[j].k, 1, &p.conv[j].cin, p.conv[j].cout).floats;
-    p.pw_bytes[j] = n * sizeof(float);
-    o = ws_carve(base, o, p.pw[j], n);
+  for (int j = 0; j < p.nconv; j++) {
+    const EConv& c = p.conv[j];
+    const size_t floats = conv_plan(c.k, 1, &c.cin, c.cout).floats;
+    p.pw_bytes[j] = floats * sizeof(float);
+    o = ws_carve(base, o, p.pw[j], floats);
+    if (d.fold && !normed && j < p.nconv - 1) {
+      o = ws_carve(base, o, p.fw[j], (size_t)c.cout * c.cin * c.k * c.k);
+      o = ws_carve(base, o, p.fb[j], (size_t)c.cout);
+    }
   }
-  if (!normed)
-    for (int j = 0; j < R_NORMS; j++) {
-      o = ws_carve(base, o, p.fw[j], (size_t)p.conv[j].cout * p.conv[j].cin * p.conv[j].k * p.conv[j].k);
-      o = ws_carve(base, o, p.fb[j], (size_t)p.conv[j].cout);
-    }
-  // a buffer holds the largest map it is ever given: positions fall by four from layer to layer, channels rise by less
-  const size_t P1 = (size_t)N * p.h[1] * p.w[1], P2 = (size_t)N * p.h[2] * p.w[2], P3 = (size_t)N * p.h[3] * p.w[3];
-  auto most = [](size_t a, size_t b, size_t c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); };
-  const size_t full = most(P1 * 64, P2 * 96, P3 * 128);
-  o = ws_carve(base, o, p.x, full);
-  o = ws_carve(base, o, p.y, full);
-  o = ws_carve(base, o, p.r1, full);
-  if (normed) o = ws_carve(base, o, p.r2, full);  // (CONTEXT: the second convolution closes the block itself)
-  o = ws_carve(base, o, p.rd, most(0, P2 * 96, P3 * 128));
-  if (normed) {
-    for (int j = 0; j < 3; j++) o = ws_carve(base, o, p.tab[j], (size_t)N * 128 * 2);
-    size_t most_rows = 0;  // (tiny maps: one tile each, the widest map decides)
-    for (int l = 1; l < 4; l++) {
-      const size_t rows = (size_t)tiles_of(p.h[l], p.w[l]) * R_WIDTH[l];
-      if (rows > most_rows) most_rows = rows;
-    }
-    p.partials_bytes = (size_t)N * most_rows * 2 * sizeof(double);
+  o = ws_carve(base, o, p.x, xy);
+  o = ws_carve(base, o, p.y, xy);
+  for (int j = 0; j < n - 1 + normed; j++) o = ws_carve(base, o, p.r[j], r[j]);
+  o = ws_carve(base, o, p.rd, rd);
+  if (normed) {  // every table the same size, the widest map's
+    for (int j = 0; j <= n; j++) o = ws_carve(base, o, p.tab[j], (size_t)N * widest * 2);
+    p.partials_bytes = (size_t)N * rows * 2 * sizeof(double);
     o = ws_carve(base, o, p.partials, p.partials_bytes / sizeof(double));
   }
   p.bytes = ws_align(o) + 256;
   return p;
 }
 
-int check_res_shape(const char* who, int N, int H, int W, int kind) {
+int check_enc_shape(const char* who, const EncDesc& d, int N, int H, int W, int kind) {
   if (kind != EOGS_FLOWENC_FEATURE && kind != EOGS_FLOWENC_CONTEXT) return fail(EOGS_ERR_INVALID_ARG, "%s: the kind is FEATURE or CONTEXT", who);
   if (N < 1 || H < 1 || W < 1) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (N, H and W must be at least 1)", who);
   if (N > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: N above 65535", who);
   const int64_t h1 = (H + 1) / 2, w1 = (W + 1) / 2, h2 = (h1 + 1) / 2, w2 = (w1 + 1) / 2, h3 = (h2 + 1) / 2, w3 = (w2 + 1) / 2;
-  if ((int64_t)N * 3 * H * W > 0x7FFFFFFFll || (int64_t)N * h1 * w1 * R_WIDTH[1] > 0x7FFFFFFFll || (int64_t)N * h2 * w2 * R_WIDTH[2] > 0x7FFFFFFFll ||
-      (int64_t)N * h3 * w3 * R_HEAD > 0x7FFFFFFFll)
+  const int head = d.head[0] > d.head[1] ? d.head[0] : d.head[1];  // (one bound for both kinds)
+  if ((int64_t)N * 3 * H * W > 0x7FFFFFFFll || (int64_t)N * h1 * w1 * d.width[1] > 0x7FFFFFFFll || (int64_t)N * h2 * w2 * d.width[2] > 0x7FFFFFFFll ||
+      (int64_t)N * h3 * w3 * head > 0x7FFFFFFFll)
     return fail(EOGS_ERR_INVALID_ARG, "%s: more than 2^31 - 1 elements in a map", who);
   if (kind == EOGS_FLOWENC_FEATURE && h3 * w3 == 1)
     return fail(EOGS_ERR_INVALID_ARG, "%s: the feature encoder's last map is a single position, which an instance norm cannot normalise", who);
   return EOGS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int eogs_flowres_fold(int cout, int per_out, const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
-                      const float* var, double eps, float* w_out, float* b_out, void* stream) {
-  clear_error();
-  hipStream_t s = (hipStream_t)stream;
-  RC_TRY(fold_checked("flowres_fold", cout, per_out, w, b, gamma, beta, mean, var, eps, w_out, b_out, s));
-  LAUNCH_TRY(s, false, "flowres_fold");
+int enc_bytes(const char* who, const EncDesc& d, int N, int H, int W, int kind, size_t* bytes) {
+  RC_TRY(check_enc_shape(who, d, N, H, W, kind));
+  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  *bytes = enc_plan(d, nullptr, N, H, W, kind).bytes;
   return EOGS_OK;
 }
 
-int eogs_flowres_bytes(int N, int H, int W, int kind, size_t* bytes) {
-  clear_error();
-  RC_TRY(check_res_shape("flowres_bytes", N, H, W, kind));
-  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "flowres_bytes: NULL argument");
-  *bytes = res_plan(nullptr, N, H, W, kind).bytes;
-  return EOGS_OK;
-}
-
-int eogs_flowres_run(int N, int H, int W, int kind, const float* const* params, const float* const* bn, const float* image, void* ws,
-                     size_t ws_bytes, float* out, void* stream) {
-  clear_error();
-  const char* who = "flowres_run";
-  RC_TRY(check_res_shape(who, N, H, W, kind));
-  const bool normed = kind == EOGS_FLOWENC_FEATURE;
-  if (normed && bn) return fail(EOGS_ERR_INVALID_ARG, "%s: bn goes with CONTEXT only (FEATURE normalises by instance)", who);
-  if (!normed && !bn) return fail(EOGS_ERR_INVALID_ARG, "%s: CONTEXT takes bn, the batch norms of its convolutions", who);
+// `bn`: the batch norms of a `fold` description's CONTEXT kind, NULL otherwise
+int enc_run(const char* who, const EncDesc& d, int N, int H, int W, int kind, const float* const* params, const float* const* bn,
+            const float* image, void* ws, size_t ws_bytes, float* out, hipStream_t s) {
+  RC_TRY(check_enc_shape(who, d, N, H, W, kind));
+  const bool normed = kind == EOGS_FLOWENC_FEATURE, fold = d.fold && !normed;
+  const int n = d.nblock, nconv = enc_convs(d);
+  if (d.fold && normed && bn) return fail(EOGS_ERR_INVALID_ARG, "%s: bn goes with CONTEXT only (FEATURE normalises by instance)", who);
+  if (fold && !bn) return fail(EOGS_ERR_INVALID_ARG, "%s: CONTEXT takes bn, the batch norms of its convolutions", who);
   if (!params || !image || !ws || !out) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-  for (int i = 0; i < EOGS_FLOWRES_PARAMS; i++) {
+  for (int i = 0; i < 2 * nconv; i++) {
     if (!params[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
     if (!aligned16(params[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
   }
-  for (int i = 0; bn && i < EOGS_FLOWRES_BN; i++) {
+  for (int i = 0; fold && i < 4 * (nconv - 1); i++) {
     if (!bn[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
     if (!aligned16(bn[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
   }
   if (!aligned16(image) || !aligned16(out)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  ResPlan p = res_plan(ws, N, H, W, kind);
+  const EncPlan p = enc_plan(d, ws, N, H, W, kind);
   if (ws_bytes < p.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
-  hipStream_t s = (hipStream_t)stream;
   const int BIAS = EOGS_FLOWENC_EPI_BIAS, RELU = EOGS_FLOWENC_EPI_RELU, RESIDUAL = EOGS_FLOWENC_EPI_RESIDUAL;
-  const float *wsrc[R_CONVS], *bsrc[R_CONVS];  // what a convolution multiplies by and adds: the parameters, or their fold
-  for (int i = 0; i < R_CONVS; i++) {
+  const float *wsrc[E_MAX], *bsrc[E_MAX];  // what a convolution multiplies by and adds: the parameters, or their fold
+  for (int i = 0; i < nconv; i++) {
     const EConv& c = p.conv[i];
     wsrc[i] = params[2 * i];
     bsrc[i] = params[2 * i + 1];
-    if (!normed && i < R_NORMS) {
+    if (fold && i < nconv - 1) {
       RC_TRY(fold_checked(who, c.cout, c.cin * c.k * c.k, params[2 * i], params[2 * i + 1], bn[4 * i], bn[4 * i + 1], bn[4 * i + 2], bn[4 * i + 3],
                           1e-5, p.fw[i], p.fb[i], s));
       wsrc[i] = p.fw[i];
@@ -594,35 +533,58 @@ int eogs_flowres_run(int N, int H, int W, int kind, const float* const* params, 
   int i = 0, lv = 1;
   float *x = p.x, *y = p.y;
   if (normed) {
-    RC_TRY(conv(i++, H, W, image, nullptr, nullptr, p.r2, p.tab[1], BIAS, EOGS_FLOWENC_IN_NCHW));
-    RC_TRY(finish_checked(who, N, p.h[1], p.w[1], R_WIDTH[0], p.r2, p.tab[1], nullptr, nullptr, EOGS_FLOWENC_SHORTCUT_NONE, x, s));
+    RC_TRY(conv(i++, H, W, image, nullptr, nullptr, p.r[n - 1], p.tab[n - 1], BIAS, EOGS_FLOWENC_IN_NCHW));
+    RC_TRY(finish_checked(who, N, p.h[1], p.w[1], d.width[0], p.r[n - 1], p.tab[n - 1], nullptr, nullptr, EOGS_FLOWENC_SHORTCUT_NONE, x, s));
   } else {
     RC_TRY(conv(i++, H, W, image, nullptr, nullptr, x, nullptr, RELU, EOGS_FLOWENC_IN_NCHW));
   }
   for (int b = 0; b < 6; b++) {
-    const bool down = p.conv[i].s == 2;
-    const int h = p.h[lv], w = p.w[lv], ho = down ? p.h[lv + 1] : h, wo = down ? p.w[lv + 1] : w, cout = p.conv[i].cout;
-    if (normed) {
-      RC_TRY(conv(i, h, w, x, nullptr, nullptr, p.r1, p.tab[0], BIAS, 0u));
-      RC_TRY(conv(i + 1, ho, wo, p.r1, p.tab[0], nullptr, p.r2, p.tab[1], BIAS, 0u));
-      if (down) {
-        RC_TRY(conv(i + 2, h, w, x, nullptr, nullptr, p.rd, p.tab[2], BIAS, 0u));
-        RC_TRY(finish_checked(who, N, ho, wo, cout, p.r2, p.tab[1], p.rd, p.tab[2], EOGS_FLOWENC_SHORTCUT_NORM, y, s));
-      } else {
-        RC_TRY(finish_checked(who, N, ho, wo, cout, p.r2, p.tab[1], x, nullptr, EOGS_FLOWENC_SHORTCUT_PLAIN, y, s));
-      }
-    } else {
-      RC_TRY(conv(i, h, w, x, nullptr, nullptr, p.r1, nullptr, RELU, 0u));
-      if (down) RC_TRY(conv(i + 2, h, w, x, nullptr, nullptr, p.rd, nullptr, BIAS, 0u));
-      RC_TRY(conv(i + 1, ho, wo, p.r1, nullptr, down ? p.rd : x, y, nullptr, RESIDUAL, 0u));
+    const bool down = p.conv[i + d.strided].s == 2;
+    const int h = p.h[lv], w = p.w[lv], ho = down ? p.h[lv + 1] : h, wo = down ? p.w[lv + 1] : w, cout = p.conv[i + n - 1].cout;
+    // the block's convolutions in turn, each reading the one before it (normalised: through its table); the map halves after `strided`
+    const float *in = x, *in_tab = nullptr;
+    for (int j = 0; j < n - 1 + normed; j++) {
+      RC_TRY(conv(i + j, j <= d.strided ? h : ho, j <= d.strided ? w : wo, in, in_tab, nullptr, p.r[j], normed ? p.tab[j] : nullptr, normed ? BIAS : RELU, 0u));
+      in = p.r[j];
+      in_tab = normed ? p.tab[j] : nullptr;
     }
-    i += down ? 3 : 2;
+    if (down) RC_TRY(conv(i + n, h, w, x, nullptr, nullptr, p.rd, normed ? p.tab[n] : nullptr, BIAS, 0u));
+    if (normed)
+      RC_TRY(finish_checked(who, N, ho, wo, cout, in, in_tab, down ? p.rd : x, down ? p.tab[n] : nullptr,
+                            down ? EOGS_FLOWENC_SHORTCUT_NORM : EOGS_FLOWENC_SHORTCUT_PLAIN, y, s));
+    else  // the last convolution closes the block: relu(shortcut + relu(v))
+      RC_TRY(conv(i + n - 1, ho, wo, in, nullptr, down ? p.rd : x, y, nullptr, RESIDUAL, 0u));
+    i += n + down;
     if (down) lv++;
     float* t = x; x = y; y = t;
   }
   RC_TRY(conv(i, p.h[3], p.w[3], x, nullptr, nullptr, out, nullptr, BIAS, EOGS_FLOWENC_OUT_NCHW));
   LAUNCH_TRY(s, false, who);
   return EOGS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int eogs_flowres_fold(int cout, int per_out, const float* w, const float* b, const float* gamma, const float* beta, const float* mean,
+                      const float* var, double eps, float* w_out, float* b_out, void* stream) {
+  clear_error();
+  hipStream_t s = (hipStream_t)stream;
+  RC_TRY(fold_checked("flowres_fold", cout, per_out, w, b, gamma, beta, mean, var, eps, w_out, b_out, s));
+  LAUNCH_TRY(s, false, "flowres_fold");
+  return EOGS_OK;
+}
+
+int eogs_flowres_bytes(int N, int H, int W, int kind, size_t* bytes) {
+  clear_error();
+  return enc_bytes("flowres_bytes", E_LARGE, N, H, W, kind, bytes);
+}
+
+int eogs_flowres_run(int N, int H, int W, int kind, const float* const* params, const float* const* bn, const float* image, void* ws,
+                     size_t ws_bytes, float* out, void* stream) {
+  clear_error();
+  return enc_run("flowres_run", E_LARGE, N, H, W, kind, params, bn, image, ws, ws_bytes, out, (hipStream_t)stream);
 }
 
 int eogs_flowenc_conv_partials(int N, int h, int w, int cout, int* rows, size_t* bytes) {
@@ -666,74 +628,13 @@ int eogs_flowenc_finish(int N, int h, int w, int C, const float* v, const float*
 
 int eogs_flowenc_bytes(int N, int H, int W, int kind, size_t* bytes) {
   clear_error();
-  RC_TRY(check_enc_shape("flowenc_bytes", N, H, W, kind));
-  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "flowenc_bytes: NULL argument");
-  *bytes = enc_plan(nullptr, N, H, W, kind).bytes;
-  return EOGS_OK;
+  return enc_bytes("flowenc_bytes", E_SMALL, N, H, W, kind, bytes);
 }
 
 int eogs_flowenc_run(int N, int H, int W, int kind, const float* const* params, const float* image, void* ws, size_t ws_bytes,
                      float* out, void* stream) {
   clear_error();
-  const char* who = "flowenc_run";
-  RC_TRY(check_enc_shape(who, N, H, W, kind));
-  if (!params || !image || !ws || !out) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-  for (int i = 0; i < EOGS_FLOWENC_PARAMS; i++) {
-    if (!params[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!aligned16(params[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  }
-  if (!aligned16(image) || !aligned16(out)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  EncPlan p = enc_plan(ws, N, H, W, kind);
-  if (ws_bytes < p.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
-  hipStream_t s = (hipStream_t)stream;
-  const bool normed = kind == EOGS_FLOWENC_FEATURE;
-  const int BIAS = EOGS_FLOWENC_EPI_BIAS, RELU = EOGS_FLOWENC_EPI_RELU, RESIDUAL = EOGS_FLOWENC_EPI_RESIDUAL;
-  for (int i = 0; i < E_CONVS; i++) {
-    const EConv& c = p.conv[i];
-    RC_TRY(pack_checked(who, c.k, 1, &c.cin, nullptr, c.cin, c.cout, 0, c.cout, params[2 * i], p.pw[i], p.pw_bytes[i], s));
-  }
-  // one convolution of the table on an h x w map; with `tab` its statistics become that (mean, rstd) table
-  auto conv = [&](int i, int h, int w, const float* in, const float* in_norm, const float* res, float* o, float* tab, int epi, unsigned flags) {
-    const EConv& c = p.conv[i];
-    RC_TRY(enc_conv_checked(who, N, h, w, c.cin, c.cout, c.k, c.s, in, in_norm, p.pw[i], p.pw_bytes[i], params[2 * i + 1], res, o,
-                            tab ? p.partials : nullptr, tab ? p.partials_bytes : 0, epi, flags, s));
-    if (tab) RC_TRY(norm_checked(who, N, (h + c.s - 1) / c.s, (w + c.s - 1) / c.s, c.cout, p.partials, p.partials_bytes, tab, s));
-    return (int)EOGS_OK;
-  };
-  int i = 0, lv = 1;
-  float *x = p.x, *y = p.y;
-  if (normed) {
-    RC_TRY(conv(i++, H, W, image, nullptr, nullptr, p.r3, p.tab[2], BIAS, EOGS_FLOWENC_IN_NCHW));
-    RC_TRY(finish_checked(who, N, p.h[1], p.w[1], E_WIDTH[0], p.r3, p.tab[2], nullptr, nullptr, EOGS_FLOWENC_SHORTCUT_NONE, x, s));
-  } else {
-    RC_TRY(conv(i++, H, W, image, nullptr, nullptr, x, nullptr, RELU, EOGS_FLOWENC_IN_NCHW));
-  }
-  for (int b = 0; b < 6; b++) {
-    const bool down = p.conv[i + 1].s == 2;
-    const int h = p.h[lv], w = p.w[lv], ho = down ? p.h[lv + 1] : h, wo = down ? p.w[lv + 1] : w, cout = p.conv[i + 2].cout;
-    if (normed) {
-      RC_TRY(conv(i, h, w, x, nullptr, nullptr, p.r1, p.tab[0], BIAS, 0u));
-      RC_TRY(conv(i + 1, h, w, p.r1, p.tab[0], nullptr, p.r2, p.tab[1], BIAS, 0u));
-      RC_TRY(conv(i + 2, ho, wo, p.r2, p.tab[1], nullptr, p.r3, p.tab[2], BIAS, 0u));
-      if (down) {
-        RC_TRY(conv(i + 3, h, w, x, nullptr, nullptr, p.rd, p.tab[3], BIAS, 0u));
-        RC_TRY(finish_checked(who, N, ho, wo, cout, p.r3, p.tab[2], p.rd, p.tab[3], EOGS_FLOWENC_SHORTCUT_NORM, y, s));
-      } else {
-        RC_TRY(finish_checked(who, N, ho, wo, cout, p.r3, p.tab[2], x, nullptr, EOGS_FLOWENC_SHORTCUT_PLAIN, y, s));
-      }
-    } else {
-      RC_TRY(conv(i, h, w, x, nullptr, nullptr, p.r1, nullptr, RELU, 0u));
-      RC_TRY(conv(i + 1, h, w, p.r1, nullptr, nullptr, p.r2, nullptr, RELU, 0u));
-      if (down) RC_TRY(conv(i + 3, h, w, x, nullptr, nullptr, p.rd, nullptr, BIAS, 0u));
-      RC_TRY(conv(i + 2, ho, wo, p.r2, nullptr, down ? p.rd : x, y, nullptr, RESIDUAL, 0u));
-    }
-    i += down ? 4 : 3;
-    if (down) lv++;
-    float* t = x; x = y; y = t;
-  }
-  RC_TRY(conv(i, p.h[3], p.w[3], x, nullptr, nullptr, out, nullptr, BIAS, EOGS_FLOWENC_OUT_NCHW));
-  LAUNCH_TRY(s, false, who);
-  return EOGS_OK;
+  return enc_run("flowenc_run", E_SMALL, N, H, W, kind, params, nullptr, image, ws, ws_bytes, out, (hipStream_t)stream);
 }
 
 }  // extern "C"

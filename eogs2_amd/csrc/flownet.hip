@@ -244,138 +244,231 @@ int conv_checked(const char* who, int N, int h, int w, int kh, int kw, bool rect
   return EOGS_OK;
 }
 
-// ---- RAFT-small's update block ----
+// ---- the update block: RAFT-small's, and RAFT-large's with its mask predictor ----
 
-constexpr int U_CORR = 196, U_HID = 96, U_CTX = 64, U_F1 = 64, U_F2 = 32, U_MOT = 80, U_FH = 128;
-constexpr int U_GRU_IN = U_HID + U_CTX + U_MOT + 2;  // convz / convr / convq read [h | context | motion | flow]: 242 channels
-enum { UC_CORR1, UC_FLOW1, UC_FLOW2, UC_CONV, UC_HOIST_ZR, UC_HOIST_Q, UC_GATES, UC_Q, UC_FH1, UC_FH2, UC_COUNT };
+// A convolution of the block. `param`: where its weight stands in the caller's params table, its bias right after it (for a
+// GRU's gates and hoisted z | r plane: convz's weight, convr's two places on; for its q: convq's)
+struct UConv { int kh, kw, nseg, C[3], cout, param; };
+// the block's convolutions by role; a GRU g owns the four from UC_GRU + 4 g
+enum { UC_CORR1, UC_CORR2, UC_FLOW1, UC_FLOW2, UC_CONV, UC_FH1, UC_FH2, UC_MASK1, UC_MASK2, UC_GRU, UC_MAX = UC_GRU + 4 * 2 };
+enum { UG_HOIST_ZR, UG_HOIST_Q, UG_GATES, UG_Q };
 
-struct UConv { int kh, kw, nseg, C[3], cout; };
-constexpr UConv U_CONVS[UC_COUNT] = {
-    {1, 1, 1, {U_CORR, 0, 0}, U_HID},          {7, 7, 1, {2, 0, 0}, U_F1},           {3, 3, 1, {U_F1, 0, 0}, U_F2},
-    {3, 3, 2, {U_HID, U_F2, 0}, U_MOT},        {3, 3, 1, {U_CTX, 0, 0}, 2 * U_HID},  {3, 3, 1, {U_CTX, 0, 0}, U_HID},
-    {3, 3, 3, {U_HID, U_MOT, 2}, 2 * U_HID},   {3, 3, 3, {U_HID, U_MOT, 2}, U_HID},  {3, 3, 1, {U_HID, 0, 0}, U_FH},
-    {3, 3, 1, {U_FH, 0, 0}, 2}};
+// An update block, stated once. RAFT-small's is RAFT-large's without convcorr2, the second GRU and the mask head.
+struct UGru { int kh, kw, param; };  // param: convz's weight; then its bias, convr's pair, convq's pair
+struct UpdateDesc {
+  int corr, hid, ctx, c1, c2, f1, f2, mot, fh, mh, mask;  // the widths; c2 = 0: no convcorr2, mh = mask = 0: no mask head
+  int ngru;
+  UGru gru[2];
+  int p_corr1, p_corr2, p_flow1, p_flow2, p_conv, p_fh1, p_fh2, p_mask1, p_mask2;  // the plain convolutions in params (-1: none)
+  int bound;             // channels the 2^31 - 1 element bound of a map is taken at
+  UConv conv[UC_MAX];    // filled by update_desc from the above; cout = 0: the block has no such convolution
+};
+
+constexpr UpdateDesc update_desc(UpdateDesc d) {
+  d.conv[UC_CORR1] = UConv{1, 1, 1, {d.corr, 0, 0}, d.c1, d.p_corr1};
+  if (d.c2) d.conv[UC_CORR2] = UConv{3, 3, 1, {d.c1, 0, 0}, d.c2, d.p_corr2};
+  d.conv[UC_FLOW1] = UConv{7, 7, 1, {2, 0, 0}, d.f1, d.p_flow1};
+  d.conv[UC_FLOW2] = UConv{3, 3, 1, {d.f1, 0, 0}, d.f2, d.p_flow2};
+  d.conv[UC_CONV] = UConv{3, 3, 2, {d.c2 ? d.c2 : d.c1, d.f2, 0}, d.mot, d.p_conv};
+  d.conv[UC_FH1] = UConv{3, 3, 1, {d.hid, 0, 0}, d.fh, d.p_fh1};
+  d.conv[UC_FH2] = UConv{3, 3, 1, {d.fh, 0, 0}, 2, d.p_fh2};
+  if (d.mh) {
+    d.conv[UC_MASK1] = UConv{3, 3, 1, {d.hid, 0, 0}, d.mh, d.p_mask1};
+    d.conv[UC_MASK2] = UConv{1, 1, 1, {d.mh, 0, 0}, d.mask, d.p_mask2};
+  }
+  // convz / convr / convq read [h | context | motion | flow], split by input channel: the context's share is hoisted out of the steps
+  for (int g = 0; g < d.ngru; g++) {
+    const UGru& r = d.gru[g];
+    UConv* c = d.conv + UC_GRU + 4 * g;
+    c[UG_HOIST_ZR] = UConv{r.kh, r.kw, 1, {d.ctx, 0, 0}, 2 * d.hid, r.param};
+    c[UG_HOIST_Q] = UConv{r.kh, r.kw, 1, {d.ctx, 0, 0}, d.hid, r.param + 4};
+    c[UG_GATES] = UConv{r.kh, r.kw, 3, {d.hid, d.mot, 2}, 2 * d.hid, r.param};
+    c[UG_Q] = UConv{r.kh, r.kw, 3, {d.hid, d.mot, 2}, d.hid, r.param + 4};
+  }
+  return d;
+}
+
+// the length of the params table the description reads: every weight and bias once, none left over (0 where they do not tile it)
+constexpr int update_params(const UpdateDesc& d) {
+  bool used[64] = {};
+  int n = 0;
+  for (int i = 0; i < UC_GRU + 3 * d.ngru; i++) {  // the plain convolutions, then convz, convr and convq of each GRU
+    if (i < UC_GRU && !d.conv[i].cout) continue;
+    const int p = i < UC_GRU ? d.conv[i].param : d.gru[(i - UC_GRU) / 3].param + 2 * ((i - UC_GRU) % 3);
+    if (p < 0 || p % 2 || p >= 64 || used[p]) return 0;
+    used[p] = true;
+    n += 2;
+  }
+  for (int p = 0; p < n; p += 2)
+    if (!used[p]) return 0;
+  return n;
+}
+
+constexpr UpdateDesc U_SMALL = update_desc({
+    /* corr hid ctx */ 196, 96, 64, /* c1 c2 */ 96, 0, /* f1 f2 mot */ 64, 32, 80, /* fh mh mask */ 128, 0, 0,
+    /* one 3 x 3 GRU */ 1, {{3, 3, 8}},
+    /* corr1 corr2 flow1 flow2 conv fh1 fh2 mask1 mask2 */ 0, -1, 2, 4, 6, 14, 16, -1, -1,
+    /* bound: the gates' z | r */ 2 * 96});
+constexpr UpdateDesc U_LARGE = update_desc({
+    /* corr hid ctx */ 324, 128, 128, /* c1 c2 */ 256, 192, /* f1 f2 mot */ 128, 64, 126, /* fh mh mask */ 256, 256, EOGS_RAFT_MASK_CHANNELS,
+    /* a 1 x 5 GRU, then a 5 x 1 one */ 2, {{1, 5, 10}, {5, 1, 16}},
+    /* corr1 corr2 flow1 flow2 conv fh1 fh2 mask1 mask2 */ 0, 2, 4, 6, 8, 22, 24, 26, 28,
+    /* bound: the mask */ EOGS_RAFT_MASK_CHANNELS});
+static_assert(update_params(U_SMALL) == EOGS_FLOWNET_UPDATE_PARAMS && update_params(U_LARGE) == EOGS_FLOWLARGE_PARAMS,
+              "a description reads exactly the params table of its entries");
+static_assert(U_LARGE.c1 == U_LARGE.fh && U_LARGE.c1 == U_LARGE.mh, "convcorr1's output, the flow head's and the mask head's hidden map share one buffer");
 
 struct UpdateLayout {
-  float* pw[UC_COUNT];
-  size_t pw_bytes[UC_COUNT];
-  float* bias[UC_COUNT];  // a convolution's bias, copied at begin (the hoisted ones: convz | convr, and convq; the GRU's two: none)
-  float *plane_zr, *plane_q, *hidden, *corr1, *flow1, *flow2, *motion, *gates, *fh1;
+  float* pw[UC_MAX];
+  size_t pw_bytes[UC_MAX];
+  float* bias[UC_MAX];  // a convolution's bias, copied at begin (the hoisted ones: convz | convr, and convq; a GRU's own two: none)
+  float *plane_zr[2], *plane_q[2], *hidden, *wide, *corr2, *flow1, *flow2, *motion, *gates, *fh1;
   size_t hidden_off, bytes;
 };
 
-inline UpdateLayout update_layout(void* ws, int N, int h, int w) {
+inline UpdateLayout update_layout(const UpdateDesc& d, void* ws, int N, int h, int w) {
   UpdateLayout u{};
   char* base = ws ? ws_base(ws) : nullptr;
   const size_t P = (size_t)N * h * w;
   size_t o = 0;
-  for (int i = 0; i < UC_COUNT; i++) {
-    const size_t n = conv_plan(U_CONVS[i].kh, U_CONVS[i].kw, U_CONVS[i].nseg, U_CONVS[i].C, U_CONVS[i].cout).floats;
+  for (int i = 0; i < UC_MAX; i++) {
+    const UConv& c = d.conv[i];
+    if (!c.cout) continue;
+    const size_t n = conv_plan(c.kh, c.kw, c.nseg, c.C, c.cout).floats;
     u.pw_bytes[i] = n * sizeof(float);
     o = ws_carve(base, o, u.pw[i], n);
   }
-  for (int i = 0; i < UC_COUNT; i++) o = ws_carve(base, o, u.bias[i], (size_t)U_CONVS[i].cout);
-  o = ws_carve(base, o, u.plane_zr, P * 2 * U_HID);
-  o = ws_carve(base, o, u.plane_q, P * U_HID);
+  for (int i = 0; i < UC_MAX; i++)
+    if (d.conv[i].cout) o = ws_carve(base, o, u.bias[i], (size_t)d.conv[i].cout);
+  for (int g = 0; g < d.ngru; g++) {
+    o = ws_carve(base, o, u.plane_zr[g], P * 2 * d.hid);
+    o = ws_carve(base, o, u.plane_q[g], P * d.hid);
+  }
   u.hidden_off = ws_align(o);
-  o = ws_carve(base, o, u.hidden, P * U_HID);
-  o = ws_carve(base, o, u.corr1, P * U_HID);
-  o = ws_carve(base, o, u.flow1, P * U_F1);
-  o = ws_carve(base, o, u.flow2, P * U_F2);
-  o = ws_carve(base, o, u.motion, P * U_MOT);
-  o = ws_carve(base, o, u.gates, P * 2 * U_HID);
-  o = ws_carve(base, o, u.fh1, P * U_FH);
+  o = ws_carve(base, o, u.hidden, P * d.hid);
+  o = ws_carve(base, o, u.wide, P * d.c1);  // convcorr1's output; where the widths agree, then flow_head.conv1's and the mask head's: each dead before the next
+  if (d.c2) o = ws_carve(base, o, u.corr2, P * d.c2);
+  o = ws_carve(base, o, u.flow1, P * d.f1);
+  o = ws_carve(base, o, u.flow2, P * d.f2);
+  o = ws_carve(base, o, u.motion, P * d.mot);
+  o = ws_carve(base, o, u.gates, P * 2 * d.hid);
+  u.fh1 = u.wide;
+  if (d.fh != d.c1) o = ws_carve(base, o, u.fh1, P * d.fh);
   u.bytes = ws_align(o) + 256;
   return u;
 }
 
-int check_update_shape(const char* who, int N, int h, int w) {
+int check_update_shape(const char* who, const UpdateDesc& d, int N, int h, int w) {
   if (N < 1 || h < 1 || w < 1) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (N, h and w must be at least 1)", who);
   if (N > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: N above 65535", who);
-  if ((int64_t)N * h * w * (2 * U_HID) > 0x7FFFFFFFll) return fail(EOGS_ERR_INVALID_ARG, "%s: more than 2^31 - 1 elements in a map", who);
+  if ((int64_t)N * h * w * d.bound > 0x7FFFFFFFll) return fail(EOGS_ERR_INVALID_ARG, "%s: more than 2^31 - 1 elements in a map", who);
   return EOGS_OK;
 }
 
-// one convolution of a step: the table's shape and packing, this call's operands
-int tconv(const char* who, const UConv& c, const float* pw, size_t pw_bytes, int N, int h, int w, const float* in0, const float* in1,
+// one convolution of the table: its shape and packing, this call's operands
+int uconv(const char* who, const UpdateDesc& d, const UpdateLayout& u, int i, int N, int h, int w, const float* in0, const float* in1,
           const float* in2, const float* bias, const float* add, const float* aux, float* out, int epi, unsigned flags, hipStream_t s) {
+  const UConv& c = d.conv[i];
   const float* in[3] = {in0, in1, in2};
-  return conv_checked(who, N, h, w, c.kh, c.kw, true, c.nseg, c.C, in, c.cout, pw, pw_bytes, bias, add, aux, out, epi, flags, s);
-}
-
-int uconv(const char* who, const UpdateLayout& u, int i, int N, int h, int w, const float* in0, const float* in1, const float* in2,
-          const float* bias, const float* add, const float* aux, float* out, int epi, unsigned flags, hipStream_t s) {
-  return tconv(who, U_CONVS[i], u.pw[i], u.pw_bytes[i], N, h, w, in0, in1, in2, bias, add, aux, out, epi, flags, s);
-}
-
-// ---- RAFT-large's update block and mask predictor ----
-
-constexpr int L_CORR = 324, L_HID = 128, L_CTX = 128, L_C1 = 256, L_C2 = 192, L_F1 = 128, L_F2 = 64, L_MOT = 126, L_FH = 256,
-              L_MH = 256, L_MASK = EOGS_RAFT_MASK_CHANNELS;
-constexpr int L_GRU_IN = L_HID + L_CTX + L_MOT + 2;  // [h | context | motion | flow]: 384 channels
-enum { LC_CORR1, LC_CORR2, LC_FLOW1, LC_FLOW2, LC_CONV, LC_HOIST_ZR1, LC_HOIST_Q1, LC_GATES1, LC_Q1, LC_HOIST_ZR2, LC_HOIST_Q2,
-       LC_GATES2, LC_Q2, LC_FH1, LC_FH2, LC_MASK1, LC_MASK2, LC_COUNT };
-constexpr UConv L_CONVS[LC_COUNT] = {
-    {1, 1, 1, {L_CORR, 0, 0}, L_C1},           {3, 3, 1, {L_C1, 0, 0}, L_C2},             {7, 7, 1, {2, 0, 0}, L_F1},
-    {3, 3, 1, {L_F1, 0, 0}, L_F2},             {3, 3, 2, {L_C2, L_F2, 0}, L_MOT},
-    {1, 5, 1, {L_CTX, 0, 0}, 2 * L_HID},       {1, 5, 1, {L_CTX, 0, 0}, L_HID},
-    {1, 5, 3, {L_HID, L_MOT, 2}, 2 * L_HID},   {1, 5, 3, {L_HID, L_MOT, 2}, L_HID},
-    {5, 1, 1, {L_CTX, 0, 0}, 2 * L_HID},       {5, 1, 1, {L_CTX, 0, 0}, L_HID},
-    {5, 1, 3, {L_HID, L_MOT, 2}, 2 * L_HID},   {5, 1, 3, {L_HID, L_MOT, 2}, L_HID},
-    {3, 3, 1, {L_HID, 0, 0}, L_FH},            {3, 3, 1, {L_FH, 0, 0}, 2},
-    {3, 3, 1, {L_HID, 0, 0}, L_MH},            {1, 1, 1, {L_MH, 0, 0}, L_MASK}};
-static_assert(L_C1 == L_FH && L_C1 == L_MH, "convcorr1's output, the flow head's and the mask head's hidden map share one buffer");
-
-struct LargeLayout {
-  float* pw[LC_COUNT];
-  size_t pw_bytes[LC_COUNT];
-  float* bias[LC_COUNT];  // as UpdateLayout's: the hoisted ones hold convz | convr and convq, the GRUs' own none
-  float *plane_zr[2], *plane_q[2], *hidden, *wide, *corr2, *flow1, *flow2, *motion, *gates;
-  size_t hidden_off, bytes;
-};
-
-inline LargeLayout large_layout(void* ws, int N, int h, int w) {
-  LargeLayout u{};
-  char* base = ws ? ws_base(ws) : nullptr;
-  const size_t P = (size_t)N * h * w;
-  size_t o = 0;
-  for (int i = 0; i < LC_COUNT; i++) {
-    const size_t n = conv_plan(L_CONVS[i].kh, L_CONVS[i].kw, L_CONVS[i].nseg, L_CONVS[i].C, L_CONVS[i].cout).floats;
-    u.pw_bytes[i] = n * sizeof(float);
-    o = ws_carve(base, o, u.pw[i], n);
-  }
-  for (int i = 0; i < LC_COUNT; i++) o = ws_carve(base, o, u.bias[i], (size_t)L_CONVS[i].cout);
-  for (int g = 0; g < 2; g++) {
-    o = ws_carve(base, o, u.plane_zr[g], P * 2 * L_HID);
-    o = ws_carve(base, o, u.plane_q[g], P * L_HID);
-  }
-  u.hidden_off = ws_align(o);
-  o = ws_carve(base, o, u.hidden, P * L_HID);
-  o = ws_carve(base, o, u.wide, P * L_C1);  // convcorr1's output, then flow_head.conv1's, then the mask head's: each dead before the next
-  o = ws_carve(base, o, u.corr2, P * L_C2);
-  o = ws_carve(base, o, u.flow1, P * L_F1);
-  o = ws_carve(base, o, u.flow2, P * L_F2);
-  o = ws_carve(base, o, u.motion, P * L_MOT);
-  o = ws_carve(base, o, u.gates, P * 2 * L_HID);
-  u.bytes = ws_align(o) + 256;
-  return u;
-}
-
-int check_large_shape(const char* who, int N, int h, int w) {
-  if (N < 1 || h < 1 || w < 1) return fail(EOGS_ERR_INVALID_ARG, "%s: bad sizes (N, h and w must be at least 1)", who);
-  if (N > 65535) return fail(EOGS_ERR_INVALID_ARG, "%s: N above 65535", who);
-  if ((int64_t)N * h * w * L_MASK > 0x7FFFFFFFll) return fail(EOGS_ERR_INVALID_ARG, "%s: more than 2^31 - 1 elements in a map", who);
-  return EOGS_OK;
-}
-
-int large_conv(const char* who, const LargeLayout& u, int i, int N, int h, int w, const float* in0, const float* in1, const float* in2,
-          const float* bias, const float* add, const float* aux, float* out, int epi, unsigned flags, hipStream_t s) {
-  return tconv(who, L_CONVS[i], u.pw[i], u.pw_bytes[i], N, h, w, in0, in1, in2, bias, add, aux, out, epi, flags, s);
+  return conv_checked(who, N, h, w, c.kh, c.kw, true, c.nseg, c.C, in, c.cout, u.pw[i], u.pw_bytes[i], bias, add, aux, out, epi, flags, s);
 }
 
 void copy_bias(hipStream_t s, int n, const float* src, float* dst) {
   hipLaunchKernelGGL(flownet_copy_kernel, dim3((n + 255) / 256), dim3(256), 0, s, n, src, dst);
+}
+
+// eogs_*_bytes and eogs_*_hidden_offset: one field of the layout
+int update_query(const char* who, const UpdateDesc& d, int N, int h, int w, size_t* out, size_t UpdateLayout::*field) {
+  RC_TRY(check_update_shape(who, d, N, h, w));
+  if (!out) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  *out = update_layout(d, nullptr, N, h, w).*field;
+  return EOGS_OK;
+}
+
+int update_begin(const char* who, const UpdateDesc& d, int N, int h, int w, const float* const* params, const float* hidden,
+                 const float* context, void* ws, size_t ws_bytes, hipStream_t s) {
+  RC_TRY(check_update_shape(who, d, N, h, w));
+  if (!params || !hidden || !context || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  for (int i = 0; i < update_params(d); i++) {
+    if (!params[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (!aligned16(params[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  }
+  if (!aligned16(hidden) || !aligned16(context)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  const UpdateLayout u = update_layout(d, ws, N, h, w);
+  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  for (int i = 0; i < UC_GRU; i++) {  // the plain convolutions: packed whole, the bias copied
+    const UConv& c = d.conv[i];
+    if (!c.cout) continue;
+    int cin = 0;
+    for (int j = 0; j < c.nseg; j++) cin += c.C[j];
+    RC_TRY(pack_checked(who, c.kh, c.kw, true, c.nseg, c.C, nullptr, cin, c.cout, 0, c.cout, params[c.param], u.pw[i], u.pw_bytes[i], s));
+    copy_bias(s, c.cout, params[c.param + 1], u.bias[i]);
+  }
+  const int64_t total = (int64_t)N * h * w * d.hid;
+  hipLaunchKernelGGL(flownet_to_cl_kernel, dim3(capped_blocks(total, 256, 4096)), dim3(256), 0, s, total, d.hid, h * w, hidden, u.hidden);
+  // each GRU's three convolutions split by input channel: the context's (once per forward, here) and the rest (every step)
+  const int gin = d.hid + d.ctx + d.mot + 2, ctx_off[1] = {d.hid}, rest_off[3] = {0, d.hid + d.ctx, d.hid + d.ctx + d.mot};
+  for (int g = 0; g < d.ngru; g++) {
+    const int hzr = UC_GRU + 4 * g + UG_HOIST_ZR, hq = UC_GRU + 4 * g + UG_HOIST_Q, gz = UC_GRU + 4 * g + UG_GATES, gq = UC_GRU + 4 * g + UG_Q;
+    const float* const* p = params + d.gru[g].param;
+    const float *wz = p[0], *bz = p[1], *wr = p[2], *br = p[3], *wq = p[4], *bq = p[5];
+    const int kh = d.gru[g].kh, kw = d.gru[g].kw, H = d.hid;
+    RC_TRY(pack_checked(who, kh, kw, true, 1, d.conv[hzr].C, ctx_off, gin, 2 * H, 0, H, wz, u.pw[hzr], u.pw_bytes[hzr], s));
+    RC_TRY(pack_checked(who, kh, kw, true, 1, d.conv[hzr].C, ctx_off, gin, 2 * H, H, H, wr, u.pw[hzr], u.pw_bytes[hzr], s));
+    RC_TRY(pack_checked(who, kh, kw, true, 1, d.conv[hq].C, ctx_off, gin, H, 0, H, wq, u.pw[hq], u.pw_bytes[hq], s));
+    RC_TRY(pack_checked(who, kh, kw, true, 3, d.conv[gz].C, rest_off, gin, 2 * H, 0, H, wz, u.pw[gz], u.pw_bytes[gz], s));
+    RC_TRY(pack_checked(who, kh, kw, true, 3, d.conv[gz].C, rest_off, gin, 2 * H, H, H, wr, u.pw[gz], u.pw_bytes[gz], s));
+    RC_TRY(pack_checked(who, kh, kw, true, 3, d.conv[gq].C, rest_off, gin, H, 0, H, wq, u.pw[gq], u.pw_bytes[gq], s));
+    copy_bias(s, H, bz, u.bias[hzr]);
+    copy_bias(s, H, br, u.bias[hzr] + H);
+    copy_bias(s, H, bq, u.bias[hq]);
+    // the hoisted planes: conv(context, W[:, context's channels]) + bias, linear under zero padding
+    RC_TRY(uconv(who, d, u, hzr, N, h, w, context, nullptr, nullptr, u.bias[hzr], nullptr, nullptr, u.plane_zr[g], EOGS_FLOWNET_EPI_BIAS, 1u, s));
+    RC_TRY(uconv(who, d, u, hq, N, h, w, context, nullptr, nullptr, u.bias[hq], nullptr, nullptr, u.plane_q[g], EOGS_FLOWNET_EPI_BIAS, 1u, s));
+  }
+  LAUNCH_TRY(s, false, who);
+  return EOGS_OK;
+}
+
+int update_step(const char* who, const UpdateDesc& d, int N, int h, int w, const float* corr, const float* flow, void* ws, size_t ws_bytes,
+                float* delta, hipStream_t s) {
+  RC_TRY(check_update_shape(who, d, N, h, w));
+  if (!corr || !flow || !ws || !delta) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  if (!aligned16(corr) || !aligned16(flow) || !aligned16(delta)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  const UpdateLayout u = update_layout(d, ws, N, h, w);
+  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  const int BIAS = EOGS_FLOWNET_EPI_BIAS, RELU = EOGS_FLOWNET_EPI_RELU;
+  const size_t half = (size_t)N * h * w * d.hid;  // the gates' two maps: z, then r * h
+  // motion encoder (corr and flow are read as NCHW planes)
+  RC_TRY(uconv(who, d, u, UC_CORR1, N, h, w, corr, nullptr, nullptr, u.bias[UC_CORR1], nullptr, nullptr, u.wide, RELU, 1u, s));
+  if (d.c2) RC_TRY(uconv(who, d, u, UC_CORR2, N, h, w, u.wide, nullptr, nullptr, u.bias[UC_CORR2], nullptr, nullptr, u.corr2, RELU, 0u, s));
+  RC_TRY(uconv(who, d, u, UC_FLOW1, N, h, w, flow, nullptr, nullptr, u.bias[UC_FLOW1], nullptr, nullptr, u.flow1, RELU, 1u, s));
+  RC_TRY(uconv(who, d, u, UC_FLOW2, N, h, w, u.flow1, nullptr, nullptr, u.bias[UC_FLOW2], nullptr, nullptr, u.flow2, RELU, 0u, s));
+  RC_TRY(uconv(who, d, u, UC_CONV, N, h, w, d.c2 ? u.corr2 : u.wide, u.flow2, nullptr, u.bias[UC_CONV], nullptr, nullptr, u.motion, RELU, 0u, s));
+  // each GRU in turn over [h | motion | flow], the context's share added as a plane
+  for (int g = 0; g < d.ngru; g++) {
+    const int gz = UC_GRU + 4 * g + UG_GATES, gq = UC_GRU + 4 * g + UG_Q;
+    RC_TRY(uconv(who, d, u, gz, N, h, w, u.hidden, u.motion, flow, nullptr, u.plane_zr[g], u.hidden, u.gates, EOGS_FLOWNET_EPI_GATES, 4u, s));
+    RC_TRY(uconv(who, d, u, gq, N, h, w, u.gates + half, u.motion, flow, nullptr, u.plane_q[g], u.gates, u.hidden, EOGS_FLOWNET_EPI_GRU, 4u, s));
+  }
+  // flow head
+  RC_TRY(uconv(who, d, u, UC_FH1, N, h, w, u.hidden, nullptr, nullptr, u.bias[UC_FH1], nullptr, nullptr, u.fh1, RELU, 0u, s));
+  RC_TRY(uconv(who, d, u, UC_FH2, N, h, w, u.fh1, nullptr, nullptr, u.bias[UC_FH2], nullptr, nullptr, delta, BIAS, EOGS_FLOWNET_OUT_NCHW, s));
+  LAUNCH_TRY(s, false, who);
+  return EOGS_OK;
+}
+
+int update_mask(const char* who, const UpdateDesc& d, int N, int h, int w, void* ws, size_t ws_bytes, float* mask, hipStream_t s) {
+  RC_TRY(check_update_shape(who, d, N, h, w));
+  if (!ws || !mask) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
+  if (!aligned16(mask)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
+  const UpdateLayout u = update_layout(d, ws, N, h, w);
+  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
+  RC_TRY(uconv(who, d, u, UC_MASK1, N, h, w, u.hidden, nullptr, nullptr, u.bias[UC_MASK1], nullptr, nullptr, u.wide, EOGS_FLOWNET_EPI_RELU, 0u, s));
+  RC_TRY(uconv(who, d, u, UC_MASK2, N, h, w, u.wide, nullptr, nullptr, u.bias[UC_MASK2], nullptr, nullptr, mask, EOGS_FLOWRECT_EPI_QUARTER,
+               EOGS_FLOWNET_OUT_NCHW, s));
+  LAUNCH_TRY(s, false, who);
+  return EOGS_OK;
 }
 
 }  // namespace
@@ -450,206 +543,58 @@ int eogs_flowrect_conv(int N, int h, int w, int kh, int kw, int nseg, const int*
   return EOGS_OK;
 }
 
+// RAFT-small's update block. params: weight, bias of convcorr1, convflow1, convflow2, conv, convz, convr, convq, flow_head.conv1,
+// flow_head.conv2 (U_SMALL's positions)
 int eogs_flownet_update_bytes(int N, int h, int w, size_t* bytes) {
   clear_error();
-  RC_TRY(check_update_shape("flownet_update_bytes", N, h, w));
-  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "flownet_update_bytes: NULL argument");
-  *bytes = update_layout(nullptr, N, h, w).bytes;
-  return EOGS_OK;
+  return update_query("flownet_update_bytes", U_SMALL, N, h, w, bytes, &UpdateLayout::bytes);
 }
 
 int eogs_flownet_update_hidden_offset(int N, int h, int w, size_t* offset) {
   clear_error();
-  RC_TRY(check_update_shape("flownet_update_hidden_offset", N, h, w));
-  if (!offset) return fail(EOGS_ERR_INVALID_ARG, "flownet_update_hidden_offset: NULL argument");
-  *offset = update_layout(nullptr, N, h, w).hidden_off;
-  return EOGS_OK;
+  return update_query("flownet_update_hidden_offset", U_SMALL, N, h, w, offset, &UpdateLayout::hidden_off);
 }
 
 int eogs_flownet_update_begin(int N, int h, int w, const float* const* params, const float* hidden, const float* context, void* ws,
                               size_t ws_bytes, void* stream) {
   clear_error();
-  const char* who = "flownet_update_begin";
-  RC_TRY(check_update_shape(who, N, h, w));
-  if (!params || !hidden || !context || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-  for (int i = 0; i < EOGS_FLOWNET_UPDATE_PARAMS; i++) {
-    if (!params[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!aligned16(params[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  }
-  if (!aligned16(hidden) || !aligned16(context)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  const UpdateLayout u = update_layout(ws, N, h, w);
-  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
-  hipStream_t s = (hipStream_t)stream;
-  // params: weight, bias of convcorr1, convflow1, convflow2, conv, convz, convr, convq, flow_head.conv1, flow_head.conv2
-  const float *wz = params[8], *bz = params[9], *wr = params[10], *br = params[11], *wq = params[12], *bq = params[13];
-  const int plain[][2] = {{UC_CORR1, 0}, {UC_FLOW1, 2}, {UC_FLOW2, 4}, {UC_CONV, 6}, {UC_FH1, 14}, {UC_FH2, 16}};
-  for (const auto& pc : plain) {
-    const UConv& c = U_CONVS[pc[0]];
-    int cin = 0;
-    for (int i = 0; i < c.nseg; i++) cin += c.C[i];
-    RC_TRY(pack_checked(who, c.kh, c.nseg, c.C, nullptr, cin, c.cout, 0, c.cout, params[pc[1]], u.pw[pc[0]], u.pw_bytes[pc[0]], s));
-    hipLaunchKernelGGL(flownet_copy_kernel, dim3(1), dim3(256), 0, s, c.cout, params[pc[1] + 1], u.bias[pc[0]]);
-  }
-  // the GRU's three convolutions split by input channel: the context's 64 (once per forward, here) and the rest (every step)
-  const int ctx_off[1] = {U_HID}, rest_off[3] = {0, U_HID + U_CTX, U_HID + U_CTX + U_MOT};
-  const UConv &hz = U_CONVS[UC_HOIST_ZR], &hq = U_CONVS[UC_HOIST_Q], &gz = U_CONVS[UC_GATES], &gq = U_CONVS[UC_Q];
-  RC_TRY(pack_checked(who, 3, hz.nseg, hz.C, ctx_off, U_GRU_IN, hz.cout, 0, U_HID, wz, u.pw[UC_HOIST_ZR], u.pw_bytes[UC_HOIST_ZR], s));
-  RC_TRY(pack_checked(who, 3, hz.nseg, hz.C, ctx_off, U_GRU_IN, hz.cout, U_HID, U_HID, wr, u.pw[UC_HOIST_ZR], u.pw_bytes[UC_HOIST_ZR], s));
-  RC_TRY(pack_checked(who, 3, hq.nseg, hq.C, ctx_off, U_GRU_IN, hq.cout, 0, U_HID, wq, u.pw[UC_HOIST_Q], u.pw_bytes[UC_HOIST_Q], s));
-  RC_TRY(pack_checked(who, 3, gz.nseg, gz.C, rest_off, U_GRU_IN, gz.cout, 0, U_HID, wz, u.pw[UC_GATES], u.pw_bytes[UC_GATES], s));
-  RC_TRY(pack_checked(who, 3, gz.nseg, gz.C, rest_off, U_GRU_IN, gz.cout, U_HID, U_HID, wr, u.pw[UC_GATES], u.pw_bytes[UC_GATES], s));
-  RC_TRY(pack_checked(who, 3, gq.nseg, gq.C, rest_off, U_GRU_IN, gq.cout, 0, U_HID, wq, u.pw[UC_Q], u.pw_bytes[UC_Q], s));
-  hipLaunchKernelGGL(flownet_copy_kernel, dim3(1), dim3(256), 0, s, U_HID, bz, u.bias[UC_HOIST_ZR]);
-  hipLaunchKernelGGL(flownet_copy_kernel, dim3(1), dim3(256), 0, s, U_HID, br, u.bias[UC_HOIST_ZR] + U_HID);
-  hipLaunchKernelGGL(flownet_copy_kernel, dim3(1), dim3(256), 0, s, U_HID, bq, u.bias[UC_HOIST_Q]);
-  const int64_t total = (int64_t)N * h * w * U_HID;
-  hipLaunchKernelGGL(flownet_to_cl_kernel, dim3(capped_blocks(total, 256, 4096)), dim3(256), 0, s, total, U_HID, h * w, hidden, u.hidden);
-  // the hoisted planes: conv3x3(context, W[:, context's channels]) + bias, linear under zero padding
-  RC_TRY(uconv(who, u, UC_HOIST_ZR, N, h, w, context, nullptr, nullptr, u.bias[UC_HOIST_ZR], nullptr, nullptr, u.plane_zr, EOGS_FLOWNET_EPI_BIAS, 1u, s));
-  RC_TRY(uconv(who, u, UC_HOIST_Q, N, h, w, context, nullptr, nullptr, u.bias[UC_HOIST_Q], nullptr, nullptr, u.plane_q, EOGS_FLOWNET_EPI_BIAS, 1u, s));
-  LAUNCH_TRY(s, false, who);
-  return EOGS_OK;
+  return update_begin("flownet_update_begin", U_SMALL, N, h, w, params, hidden, context, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int eogs_flownet_update_step(int N, int h, int w, const float* corr, const float* flow, void* ws, size_t ws_bytes, float* delta,
                              void* stream) {
   clear_error();
-  const char* who = "flownet_update_step";
-  RC_TRY(check_update_shape(who, N, h, w));
-  if (!corr || !flow || !ws || !delta) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-  if (!aligned16(corr) || !aligned16(flow) || !aligned16(delta)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  const UpdateLayout u = update_layout(ws, N, h, w);
-  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
-  hipStream_t s = (hipStream_t)stream;
-  const int BIAS = EOGS_FLOWNET_EPI_BIAS, RELU = EOGS_FLOWNET_EPI_RELU;
-  const size_t half = (size_t)N * h * w * U_HID;  // the gates' two maps: z, then r * h
-  // motion encoder (corr and flow are read as NCHW planes)
-  RC_TRY(uconv(who, u, UC_CORR1, N, h, w, corr, nullptr, nullptr, u.bias[UC_CORR1], nullptr, nullptr, u.corr1, RELU, 1u, s));
-  RC_TRY(uconv(who, u, UC_FLOW1, N, h, w, flow, nullptr, nullptr, u.bias[UC_FLOW1], nullptr, nullptr, u.flow1, RELU, 1u, s));
-  RC_TRY(uconv(who, u, UC_FLOW2, N, h, w, u.flow1, nullptr, nullptr, u.bias[UC_FLOW2], nullptr, nullptr, u.flow2, RELU, 0u, s));
-  RC_TRY(uconv(who, u, UC_CONV, N, h, w, u.corr1, u.flow2, nullptr, u.bias[UC_CONV], nullptr, nullptr, u.motion, RELU, 0u, s));
-  // GRU over [h | motion | flow], the context's share added as a plane
-  RC_TRY(uconv(who, u, UC_GATES, N, h, w, u.hidden, u.motion, flow, nullptr, u.plane_zr, u.hidden, u.gates, EOGS_FLOWNET_EPI_GATES, 4u, s));
-  RC_TRY(uconv(who, u, UC_Q, N, h, w, u.gates + half, u.motion, flow, nullptr, u.plane_q, u.gates, u.hidden, EOGS_FLOWNET_EPI_GRU, 4u, s));
-  // flow head
-  RC_TRY(uconv(who, u, UC_FH1, N, h, w, u.hidden, nullptr, nullptr, u.bias[UC_FH1], nullptr, nullptr, u.fh1, RELU, 0u, s));
-  RC_TRY(uconv(who, u, UC_FH2, N, h, w, u.fh1, nullptr, nullptr, u.bias[UC_FH2], nullptr, nullptr, delta, BIAS, EOGS_FLOWNET_OUT_NCHW, s));
-  LAUNCH_TRY(s, false, who);
-  return EOGS_OK;
+  return update_step("flownet_update_step", U_SMALL, N, h, w, corr, flow, ws, ws_bytes, delta, (hipStream_t)stream);
 }
 
+// RAFT-large's update block and mask predictor. params: weight, bias of convcorr1, convcorr2, convflow1, convflow2, conv,
+// convgru1.{convz, convr, convq}, convgru2.{convz, convr, convq}, flow_head.{conv1, conv2}, mask_predictor.{convrelu.0, conv}
+// (U_LARGE's positions)
 int eogs_flowlarge_bytes(int N, int h, int w, size_t* bytes) {
   clear_error();
-  RC_TRY(check_large_shape("flowlarge_bytes", N, h, w));
-  if (!bytes) return fail(EOGS_ERR_INVALID_ARG, "flowlarge_bytes: NULL argument");
-  *bytes = large_layout(nullptr, N, h, w).bytes;
-  return EOGS_OK;
+  return update_query("flowlarge_bytes", U_LARGE, N, h, w, bytes, &UpdateLayout::bytes);
 }
 
 int eogs_flowlarge_hidden_offset(int N, int h, int w, size_t* offset) {
   clear_error();
-  RC_TRY(check_large_shape("flowlarge_hidden_offset", N, h, w));
-  if (!offset) return fail(EOGS_ERR_INVALID_ARG, "flowlarge_hidden_offset: NULL argument");
-  *offset = large_layout(nullptr, N, h, w).hidden_off;
-  return EOGS_OK;
+  return update_query("flowlarge_hidden_offset", U_LARGE, N, h, w, offset, &UpdateLayout::hidden_off);
 }
 
 int eogs_flowlarge_begin(int N, int h, int w, const float* const* params, const float* hidden, const float* context,
                                     void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  const char* who = "flowlarge_begin";
-  RC_TRY(check_large_shape(who, N, h, w));
-  if (!params || !hidden || !context || !ws) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-  for (int i = 0; i < EOGS_FLOWLARGE_PARAMS; i++) {
-    if (!params[i]) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!aligned16(params[i])) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  }
-  if (!aligned16(hidden) || !aligned16(context)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  const LargeLayout u = large_layout(ws, N, h, w);
-  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
-  hipStream_t s = (hipStream_t)stream;
-  // params: weight, bias of convcorr1, convcorr2, convflow1, convflow2, conv, convgru1.{convz, convr, convq}, convgru2.{convz, convr,
-  // convq}, flow_head.{conv1, conv2}, mask_predictor.{convrelu.0, conv}
-  const int plain[][2] = {{LC_CORR1, 0}, {LC_CORR2, 2}, {LC_FLOW1, 4}, {LC_FLOW2, 6}, {LC_CONV, 8}, {LC_FH1, 22}, {LC_FH2, 24},
-                          {LC_MASK1, 26}, {LC_MASK2, 28}};
-  for (const auto& pc : plain) {
-    const UConv& c = L_CONVS[pc[0]];
-    int cin = 0;
-    for (int i = 0; i < c.nseg; i++) cin += c.C[i];
-    RC_TRY(pack_checked(who, c.kh, c.kw, true, c.nseg, c.C, nullptr, cin, c.cout, 0, c.cout, params[pc[1]], u.pw[pc[0]], u.pw_bytes[pc[0]], s));
-    copy_bias(s, c.cout, params[pc[1] + 1], u.bias[pc[0]]);
-  }
-  const int64_t total = (int64_t)N * h * w * L_HID;
-  hipLaunchKernelGGL(flownet_to_cl_kernel, dim3(capped_blocks(total, 256, 4096)), dim3(256), 0, s, total, L_HID, h * w, hidden, u.hidden);
-  // each GRU's three convolutions split by input channel: the context's 128 (once per forward, here) and the rest (every step)
-  const int ctx_off[1] = {L_HID}, rest_off[3] = {0, L_HID + L_CTX, L_HID + L_CTX + L_MOT};
-  for (int g = 0; g < 2; g++) {
-    const int hzr = g ? LC_HOIST_ZR2 : LC_HOIST_ZR1, hq = g ? LC_HOIST_Q2 : LC_HOIST_Q1, gz = g ? LC_GATES2 : LC_GATES1, gq = g ? LC_Q2 : LC_Q1;
-    const float *wz = params[10 + 6 * g], *bz = params[11 + 6 * g], *wr = params[12 + 6 * g], *br = params[13 + 6 * g],
-                *wq = params[14 + 6 * g], *bq = params[15 + 6 * g];
-    const int kh = L_CONVS[gz].kh, kw = L_CONVS[gz].kw;
-    RC_TRY(pack_checked(who, kh, kw, true, 1, L_CONVS[hzr].C, ctx_off, L_GRU_IN, 2 * L_HID, 0, L_HID, wz, u.pw[hzr], u.pw_bytes[hzr], s));
-    RC_TRY(pack_checked(who, kh, kw, true, 1, L_CONVS[hzr].C, ctx_off, L_GRU_IN, 2 * L_HID, L_HID, L_HID, wr, u.pw[hzr], u.pw_bytes[hzr], s));
-    RC_TRY(pack_checked(who, kh, kw, true, 1, L_CONVS[hq].C, ctx_off, L_GRU_IN, L_HID, 0, L_HID, wq, u.pw[hq], u.pw_bytes[hq], s));
-    RC_TRY(pack_checked(who, kh, kw, true, 3, L_CONVS[gz].C, rest_off, L_GRU_IN, 2 * L_HID, 0, L_HID, wz, u.pw[gz], u.pw_bytes[gz], s));
-    RC_TRY(pack_checked(who, kh, kw, true, 3, L_CONVS[gz].C, rest_off, L_GRU_IN, 2 * L_HID, L_HID, L_HID, wr, u.pw[gz], u.pw_bytes[gz], s));
-    RC_TRY(pack_checked(who, kh, kw, true, 3, L_CONVS[gq].C, rest_off, L_GRU_IN, L_HID, 0, L_HID, wq, u.pw[gq], u.pw_bytes[gq], s));
-    copy_bias(s, L_HID, bz, u.bias[hzr]);
-    copy_bias(s, L_HID, br, u.bias[hzr] + L_HID);
-    copy_bias(s, L_HID, bq, u.bias[hq]);
-    // the hoisted planes: conv(context, W[:, context's channels]) + bias, linear under zero padding
-    RC_TRY(large_conv(who, u, hzr, N, h, w, context, nullptr, nullptr, u.bias[hzr], nullptr, nullptr, u.plane_zr[g], EOGS_FLOWNET_EPI_BIAS, 1u, s));
-    RC_TRY(large_conv(who, u, hq, N, h, w, context, nullptr, nullptr, u.bias[hq], nullptr, nullptr, u.plane_q[g], EOGS_FLOWNET_EPI_BIAS, 1u, s));
-  }
-  LAUNCH_TRY(s, false, who);
-  return EOGS_OK;
+  return update_begin("flowlarge_begin", U_LARGE, N, h, w, params, hidden, context, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int eogs_flowlarge_step(int N, int h, int w, const float* corr, const float* flow, void* ws, size_t ws_bytes, float* delta,
                                    void* stream) {
   clear_error();
-  const char* who = "flowlarge_step";
-  RC_TRY(check_large_shape(who, N, h, w));
-  if (!corr || !flow || !ws || !delta) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-  if (!aligned16(corr) || !aligned16(flow) || !aligned16(delta)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  const LargeLayout u = large_layout(ws, N, h, w);
-  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
-  hipStream_t s = (hipStream_t)stream;
-  const int BIAS = EOGS_FLOWNET_EPI_BIAS, RELU = EOGS_FLOWNET_EPI_RELU;
-  const size_t half = (size_t)N * h * w * L_HID;  // the gates' two maps: z, then r * h
-  // motion encoder (corr and flow are read as NCHW planes)
-  RC_TRY(large_conv(who, u, LC_CORR1, N, h, w, corr, nullptr, nullptr, u.bias[LC_CORR1], nullptr, nullptr, u.wide, RELU, 1u, s));
-  RC_TRY(large_conv(who, u, LC_CORR2, N, h, w, u.wide, nullptr, nullptr, u.bias[LC_CORR2], nullptr, nullptr, u.corr2, RELU, 0u, s));
-  RC_TRY(large_conv(who, u, LC_FLOW1, N, h, w, flow, nullptr, nullptr, u.bias[LC_FLOW1], nullptr, nullptr, u.flow1, RELU, 1u, s));
-  RC_TRY(large_conv(who, u, LC_FLOW2, N, h, w, u.flow1, nullptr, nullptr, u.bias[LC_FLOW2], nullptr, nullptr, u.flow2, RELU, 0u, s));
-  RC_TRY(large_conv(who, u, LC_CONV, N, h, w, u.corr2, u.flow2, nullptr, u.bias[LC_CONV], nullptr, nullptr, u.motion, RELU, 0u, s));
-  // the 1 x 5 GRU, then the 5 x 1 one, each over [h | motion | flow] with the context's share added as a plane
-  for (int g = 0; g < 2; g++) {
-    const int gz = g ? LC_GATES2 : LC_GATES1, gq = g ? LC_Q2 : LC_Q1;
-    RC_TRY(large_conv(who, u, gz, N, h, w, u.hidden, u.motion, flow, nullptr, u.plane_zr[g], u.hidden, u.gates, EOGS_FLOWNET_EPI_GATES, 4u, s));
-    RC_TRY(large_conv(who, u, gq, N, h, w, u.gates + half, u.motion, flow, nullptr, u.plane_q[g], u.gates, u.hidden, EOGS_FLOWNET_EPI_GRU, 4u, s));
-  }
-  // flow head
-  RC_TRY(large_conv(who, u, LC_FH1, N, h, w, u.hidden, nullptr, nullptr, u.bias[LC_FH1], nullptr, nullptr, u.wide, RELU, 0u, s));
-  RC_TRY(large_conv(who, u, LC_FH2, N, h, w, u.wide, nullptr, nullptr, u.bias[LC_FH2], nullptr, nullptr, delta, BIAS, EOGS_FLOWNET_OUT_NCHW, s));
-  LAUNCH_TRY(s, false, who);
-  return EOGS_OK;
+  return update_step("flowlarge_step", U_LARGE, N, h, w, corr, flow, ws, ws_bytes, delta, (hipStream_t)stream);
 }
 
 int eogs_flowlarge_mask(int N, int h, int w, void* ws, size_t ws_bytes, float* mask, void* stream) {
   clear_error();
-  const char* who = "flowlarge_mask";
-  RC_TRY(check_large_shape(who, N, h, w));
-  if (!ws || !mask) return fail(EOGS_ERR_INVALID_ARG, "%s: NULL argument", who);
-  if (!aligned16(mask)) return fail(EOGS_ERR_INVALID_ARG, "%s: a pointer is not 16-byte aligned", who);
-  const LargeLayout u = large_layout(ws, N, h, w);
-  if (ws_bytes < u.bytes) return fail(EOGS_ERR_WORKSPACE, "%s: workspace too small", who);
-  hipStream_t s = (hipStream_t)stream;
-  RC_TRY(large_conv(who, u, LC_MASK1, N, h, w, u.hidden, nullptr, nullptr, u.bias[LC_MASK1], nullptr, nullptr, u.wide, EOGS_FLOWNET_EPI_RELU, 0u, s));
-  RC_TRY(large_conv(who, u, LC_MASK2, N, h, w, u.wide, nullptr, nullptr, u.bias[LC_MASK2], nullptr, nullptr, mask, EOGS_FLOWRECT_EPI_QUARTER,
-               EOGS_FLOWNET_OUT_NCHW, s));
-  LAUNCH_TRY(s, false, who);
-  return EOGS_OK;
+  return update_mask("flowlarge_mask", U_LARGE, N, h, w, ws, ws_bytes, mask, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -37,7 +37,10 @@ follows the measurement of tools/raft_update_probe.py (profiles/raft_update_prob
 RAFT-large's update block and mask predictor run the same way over the eogs_flowrect_* and eogs_flowlarge_*
 entries of include/eogs_resample.h: the kernel over 1 x 5 and 5 x 1 taps for the two GRUs, the context's share of their six
 convolutions as four planes formed once per forward, the mask head's 0.25 as an epilogue
-(tools/raft_large_update_probe.py, profiles/raft_large_update_probe.json; README). Everything here is forward
+(tools/raft_large_update_probe.py, profiles/raft_large_update_probe.json; README). The two sizes share one implementation
+per role: in the library one table-driven update block and one table-driven encoder, each size a description of its widths,
+taps and parameter order (csrc/flownet.hip, csrc/flowenc.hip); here `_FusedUpdate` and `_FusedEncoder`, of which FusedUpdate,
+FusedUpdateLarge, FusedEncoder and FusedEncoderLarge are the tables and the checks of their module trees. Everything here is forward
 only (the reference runs the network under inference_mode); the HIP operators are float32 and refuse CPU tensors (no CPU
 fallback).
 
@@ -283,7 +286,88 @@ def _conv2d_cl(what, inputs, weight, bias, act, add, rect):
     return out
 
 
-class FusedUpdate:
+class _FusedUpdate:
+    """What FusedUpdate and FusedUpdateLarge share: the parameter table, `begin`, `step`, `hidden`, the workspaces and the
+    pickling, driven by the subclass's tables. NAMES and SHAPES: the convolutions in the order of the entries' params table
+    (PARAMS pointers: each one's weight, then its bias); HIDDEN, CONTEXT, CORR: the channels of the three inputs; ENTRIES: the
+    library's entries are eogs_<ENTRIES>_{bytes, hidden_offset, begin, step}. A constructor checks its module tree and hands
+    the convolutions to `_hold`. The messages carry the subclass's own name."""
+
+    NAMES = SHAPES = ()
+    HIDDEN = CONTEXT = CORR = PARAMS = 0
+    ENTRIES = ""
+
+    def _hold(self, names, convs):
+        self._names, self._convs, self._ws, self._state = tuple(names), convs, Workspaces(), None
+
+    def __getstate__(self):  # a copied or pickled module starts without workspaces
+        return {"_names": self._names, "_convs": self._convs}
+
+    def __setstate__(self, state):
+        self._hold(state["_names"], state["_convs"])
+
+    def _params(self, dev):
+        out = []
+        for name, c in zip(self._names, self._convs):
+            for p in (c.weight, c.bias):
+                if p.dtype != torch.float32 or p.device != dev:
+                    raise RuntimeError(f"raft {type(self).__name__}: {name} is {p.dtype} on {p.device}; the fused update runs in float32 on "
+                                       f"the inputs' device ({dev}), there is no CPU fallback")
+                out.append(_aligned(p))
+        return out
+
+    @classmethod
+    def workspace_bytes(cls, N, h, w):
+        return nbytes(_lib.get(), f"{cls.ENTRIES}_bytes", int(N), int(h), int(w))
+
+    def begin(self, hidden_state, context):
+        what = f"{type(self).__name__}.begin"
+        N, _, h, w = _map(hidden_state, "the hidden state", what, self.HIDDEN)
+        if _map(context, "the context", what, self.CONTEXT) != (N, self.CONTEXT, h, w):
+            raise ValueError(f"raft {what}: the context is {tuple(context.shape)}, the hidden state asks for {(N, self.CONTEXT, h, w)}")
+        _on_device(hidden_state, what)
+        _on_device(context, what)
+        dev = hidden_state.device
+        if context.device != dev:
+            raise RuntimeError(f"raft {what}: the hidden state and the context live on different devices")
+        params = self._params(dev)
+        assert len(params) == self.PARAMS
+        size = self.workspace_bytes(N, h, w)
+        ws = self._ws.of((N, h, w), dev, lambda: Workspaces.bytes(dev, size))
+        hid, ctx = _aligned(hidden_state), _aligned(context)
+        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
+        call(f"eogs_{self.ENTRIES}_begin", dev, N, h, w, table, hid.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws.numel())
+        self._state = (N, h, w, ws)
+
+    def _begun(self, what):
+        if self._state is None:
+            raise RuntimeError(f"raft {type(self).__name__}.{what}: begin(hidden_state, context) comes first")
+        return self._state
+
+    def step(self, corr_features, flow):
+        N, h, w, ws = self._begun("step")
+        what = f"{type(self).__name__}.step"
+        if _map(corr_features, "the correlation features", what, self.CORR) != (N, self.CORR, h, w) or _map(flow, "the flow", what, 2) != (N, 2, h, w):
+            raise ValueError(f"raft {what}: begin was given {(N, h, w)}; the correlation features are {tuple(corr_features.shape)}, "
+                             f"the flow is {tuple(flow.shape)}")
+        _on_device(corr_features, what)
+        _on_device(flow, what)
+        if corr_features.device != ws.device or flow.device != ws.device:
+            raise RuntimeError(f"raft {what}: the tensors and the workspace live on different devices")
+        corr, fl = _aligned(corr_features), _aligned(flow)
+        delta = torch.empty((N, 2, h, w), dtype=torch.float32, device=ws.device)
+        call(f"eogs_{self.ENTRIES}_step", ws.device, N, h, w, corr.data_ptr(), fl.data_ptr(), ws.data_ptr(), ws.numel(), delta.data_ptr())
+        return delta
+
+    def hidden(self):
+        N, h, w, ws = self._begun("hidden")
+        off = nbytes(_lib.get(), f"{self.ENTRIES}_hidden_offset", N, h, w)
+        base = (-ws.data_ptr()) % 256  # the library rounds the pointer up to 256 bytes
+        cl = ws[base + off: base + off + 4 * N * h * w * self.HIDDEN].view(torch.float32).view(N, h, w, self.HIDDEN)
+        return cl.permute(0, 3, 1, 2).contiguous()
+
+
+class FusedUpdate(_FusedUpdate):
     """RAFT-small's `UpdateBlock` over the convolution kernel, with the call order of UpdateBlock.forward split in two:
 
         fused.begin(hidden_state, context)         once per forward: the NCHW halves of the context encoder after tanh / relu
@@ -298,7 +382,8 @@ class FusedUpdate:
              "flow_head.conv1", "flow_head.conv2")
     SHAPES = ((96, 196, 1, 1), (64, 2, 7, 7), (32, 64, 3, 3), (80, 128, 3, 3), (96, 242, 3, 3), (96, 242, 3, 3), (96, 242, 3, 3),
               (128, 96, 3, 3), (2, 128, 3, 3))
-    HIDDEN, CONTEXT, CORR = 96, 64, 196
+    HIDDEN, CONTEXT, CORR, PARAMS = 96, 64, 196, FLOWNET_UPDATE_PARAMS
+    ENTRIES = "flownet_update"
 
     def __init__(self, update_block):
         if not isinstance(update_block, UpdateBlock):
@@ -309,73 +394,10 @@ class FusedUpdate:
                 not isinstance(update_block.recurrent_block.convgru2, nn.Identity):
             raise ValueError("raft FusedUpdate: the fused update is RAFT-small's (one 1 x 1 correlation convolution, one 3 x 3 GRU); "
                              f"this block's convolutions are {got}")
-        self._convs = convs
-        self._ws = Workspaces()
-        self._state = None
-
-    def __getstate__(self):  # a copied or pickled module starts without workspaces
-        return {"_convs": self._convs}
-
-    def __setstate__(self, state):
-        self._convs, self._ws, self._state = state["_convs"], Workspaces(), None
-
-    def _params(self, dev):
-        out = []
-        for name, c in zip(self.NAMES, self._convs):
-            for p in (c.weight, c.bias):
-                if p.dtype != torch.float32 or p.device != dev:
-                    raise RuntimeError(f"raft FusedUpdate: {name} is {p.dtype} on {p.device}; the fused update runs in float32 on "
-                                       f"the inputs' device ({dev}), there is no CPU fallback")
-                out.append(_aligned(p))
-        return out
-
-    def begin(self, hidden_state, context):
-        what = "FusedUpdate.begin"
-        N, _, h, w = _map(hidden_state, "the hidden state", what, self.HIDDEN)
-        if _map(context, "the context", what, self.CONTEXT) != (N, self.CONTEXT, h, w):
-            raise ValueError(f"raft {what}: the context is {tuple(context.shape)}, the hidden state asks for {(N, self.CONTEXT, h, w)}")
-        _on_device(hidden_state, what)
-        _on_device(context, what)
-        dev = hidden_state.device
-        if context.device != dev:
-            raise RuntimeError(f"raft {what}: the hidden state and the context live on different devices")
-        params = self._params(dev)
-        assert len(params) == FLOWNET_UPDATE_PARAMS
-        size = nbytes(_lib.get(), "flownet_update_bytes", N, h, w)
-        ws = self._ws.of((N, h, w), dev, lambda: Workspaces.bytes(dev, size))
-        hid, ctx = _aligned(hidden_state), _aligned(context)
-        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
-        call("eogs_flownet_update_begin", dev, N, h, w, table, hid.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws.numel())
-        self._state = (N, h, w, ws)
-
-    def step(self, corr_features, flow):
-        what = "FusedUpdate.step"
-        if self._state is None:
-            raise RuntimeError(f"raft {what}: begin(hidden_state, context) comes first")
-        N, h, w, ws = self._state
-        if _map(corr_features, "the correlation features", what, self.CORR) != (N, self.CORR, h, w) or _map(flow, "the flow", what, 2) != (N, 2, h, w):
-            raise ValueError(f"raft {what}: begin was given {(N, h, w)}; the correlation features are {tuple(corr_features.shape)}, "
-                             f"the flow is {tuple(flow.shape)}")
-        _on_device(corr_features, what)
-        _on_device(flow, what)
-        if corr_features.device != ws.device or flow.device != ws.device:
-            raise RuntimeError(f"raft {what}: the tensors and the workspace live on different devices")
-        corr, fl = _aligned(corr_features), _aligned(flow)
-        delta = torch.empty((N, 2, h, w), dtype=torch.float32, device=ws.device)
-        call("eogs_flownet_update_step", ws.device, N, h, w, corr.data_ptr(), fl.data_ptr(), ws.data_ptr(), ws.numel(), delta.data_ptr())
-        return delta
-
-    def hidden(self):
-        if self._state is None:
-            raise RuntimeError("raft FusedUpdate.hidden: begin(hidden_state, context) comes first")
-        N, h, w, ws = self._state
-        off = nbytes(_lib.get(), "flownet_update_hidden_offset", N, h, w)
-        base = (-ws.data_ptr()) % 256  # the library rounds the pointer up to 256 bytes
-        cl = ws[base + off: base + off + 4 * N * h * w * self.HIDDEN].view(torch.float32).view(N, h, w, self.HIDDEN)
-        return cl.permute(0, 3, 1, 2).contiguous()
+        self._hold(self.NAMES, convs)
 
 
-class FusedUpdateLarge:
+class FusedUpdateLarge(_FusedUpdate):
     """RAFT-large's `UpdateBlock` and `MaskPredictor` over the convolution kernel (the eogs_flowlarge_* entries of
     include/eogs_resample.h), with FusedUpdate's call order and one more call:
 
@@ -395,7 +417,8 @@ class FusedUpdateLarge:
     SHAPES = ((256, 324, 1, 1), (192, 256, 3, 3), (128, 2, 7, 7), (64, 128, 3, 3), (126, 256, 3, 3), (128, 384, 1, 5), (128, 384, 1, 5),
               (128, 384, 1, 5), (128, 384, 5, 1), (128, 384, 5, 1), (128, 384, 5, 1), (256, 128, 3, 3), (2, 256, 3, 3),
               (256, 128, 3, 3), (RAFT_MASK_CHANNELS, 256, 1, 1))
-    HIDDEN, CONTEXT, CORR = 128, 128, 324
+    HIDDEN, CONTEXT, CORR, PARAMS = 128, 128, 324, FLOWLARGE_PARAMS
+    ENTRIES = "flowlarge"
 
     def __init__(self, update_block, mask_predictor):
         what = "raft FusedUpdateLarge"
@@ -411,83 +434,13 @@ class FusedUpdateLarge:
         if got != self.SHAPES or mask_predictor.multiplier != 0.25:
             raise ValueError(f"{what}: the fused update is RAFT-large's (two correlation convolutions, a 1 x 5 and a 5 x 1 GRU, a mask "
                              f"predictor with the multiplier 0.25); this block's convolutions are {got}, the multiplier {mask_predictor.multiplier}")
-        self._names = tuple(f"update_block.{n}" for n in self.NAMES) + tuple(f"mask_predictor.{n}" for n in self.MASK_NAMES)
-        self._convs = convs
-        self._ws = Workspaces()
-        self._state = None
-
-    def __getstate__(self):  # a copied or pickled module starts without workspaces
-        return {"_names": self._names, "_convs": self._convs}
-
-    def __setstate__(self, state):
-        self._names, self._convs, self._ws, self._state = state["_names"], state["_convs"], Workspaces(), None
-
-    def _params(self, dev):
-        out = []
-        for name, c in zip(self._names, self._convs):
-            for p in (c.weight, c.bias):
-                if p.dtype != torch.float32 or p.device != dev:
-                    raise RuntimeError(f"raft FusedUpdateLarge: {name} is {p.dtype} on {p.device}; the fused update runs in float32 on "
-                                       f"the inputs' device ({dev}), there is no CPU fallback")
-                out.append(_aligned(p))
-        return out
-
-    def begin(self, hidden_state, context):
-        what = "FusedUpdateLarge.begin"
-        N, _, h, w = _map(hidden_state, "the hidden state", what, self.HIDDEN)
-        if _map(context, "the context", what, self.CONTEXT) != (N, self.CONTEXT, h, w):
-            raise ValueError(f"raft {what}: the context is {tuple(context.shape)}, the hidden state asks for {(N, self.CONTEXT, h, w)}")
-        _on_device(hidden_state, what)
-        _on_device(context, what)
-        dev = hidden_state.device
-        if context.device != dev:
-            raise RuntimeError(f"raft {what}: the hidden state and the context live on different devices")
-        params = self._params(dev)
-        assert len(params) == FLOWLARGE_PARAMS
-        size = self.workspace_bytes(N, h, w)
-        ws = self._ws.of((N, h, w), dev, lambda: Workspaces.bytes(dev, size))
-        hid, ctx = _aligned(hidden_state), _aligned(context)
-        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
-        call("eogs_flowlarge_begin", dev, N, h, w, table, hid.data_ptr(), ctx.data_ptr(), ws.data_ptr(), ws.numel())
-        self._state = (N, h, w, ws)
-
-    @staticmethod
-    def workspace_bytes(N, h, w):
-        return nbytes(_lib.get(), "flowlarge_bytes", int(N), int(h), int(w))
-
-    def step(self, corr_features, flow):
-        what = "FusedUpdateLarge.step"
-        if self._state is None:
-            raise RuntimeError(f"raft {what}: begin(hidden_state, context) comes first")
-        N, h, w, ws = self._state
-        if _map(corr_features, "the correlation features", what, self.CORR) != (N, self.CORR, h, w) or _map(flow, "the flow", what, 2) != (N, 2, h, w):
-            raise ValueError(f"raft {what}: begin was given {(N, h, w)}; the correlation features are {tuple(corr_features.shape)}, "
-                             f"the flow is {tuple(flow.shape)}")
-        _on_device(corr_features, what)
-        _on_device(flow, what)
-        if corr_features.device != ws.device or flow.device != ws.device:
-            raise RuntimeError(f"raft {what}: the tensors and the workspace live on different devices")
-        corr, fl = _aligned(corr_features), _aligned(flow)
-        delta = torch.empty((N, 2, h, w), dtype=torch.float32, device=ws.device)
-        call("eogs_flowlarge_step", ws.device, N, h, w, corr.data_ptr(), fl.data_ptr(), ws.data_ptr(), ws.numel(), delta.data_ptr())
-        return delta
+        self._hold(tuple(f"update_block.{n}" for n in self.NAMES) + tuple(f"mask_predictor.{n}" for n in self.MASK_NAMES), convs)
 
     def mask(self):
-        if self._state is None:
-            raise RuntimeError("raft FusedUpdateLarge.mask: begin(hidden_state, context) comes first")
-        N, h, w, ws = self._state
+        N, h, w, ws = self._begun("mask")
         out = torch.empty((N, RAFT_MASK_CHANNELS, h, w), dtype=torch.float32, device=ws.device)
         call("eogs_flowlarge_mask", ws.device, N, h, w, ws.data_ptr(), ws.numel(), out.data_ptr())
         return out
-
-    def hidden(self):
-        if self._state is None:
-            raise RuntimeError("raft FusedUpdateLarge.hidden: begin(hidden_state, context) comes first")
-        N, h, w, ws = self._state
-        off = nbytes(_lib.get(), "flowlarge_hidden_offset", N, h, w)
-        base = (-ws.data_ptr()) % 256  # the library rounds the pointer up to 256 bytes
-        cl = ws[base + off: base + off + 4 * N * h * w * self.HIDDEN].view(torch.float32).view(N, h, w, self.HIDDEN)
-        return cl.permute(0, 3, 1, 2).contiguous()
 
 
 # ---- the encoders' convolutions (eogs_flowenc_*) ----
@@ -600,17 +553,66 @@ def finish_cl(v, norm_v, s=None, norm_s=None):
     return out
 
 
-class FusedEncoder:
+class _FusedEncoder:
+    """What FusedEncoder and FusedEncoderLarge share: the call, the parameter table, the workspaces and their eviction, the
+    pickling. ENTRIES: the library's entries are eogs_<ENTRIES>_{bytes, run}. A constructor checks its module tree and sets
+    `_names` and `_convs` (the convolutions in the order of the entry's params table), `kind`, `channels` (of the result) and
+    `_ws`. The messages carry the subclass's own name."""
+
+    MAX_WORKSPACES = 2
+    ENTRIES = ""
+
+    def __getstate__(self):  # a copied or pickled module starts without workspaces
+        return {k: v for k, v in self.__dict__.items() if k != "_ws"}
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._ws = Workspaces()
+
+    def _checked(self, name, p, dev):
+        if p.dtype != torch.float32 or p.device != dev:
+            raise RuntimeError(f"raft {type(self).__name__}: {name} is {p.dtype} on {p.device}; the fused encoder runs in float32 on "
+                               f"the image's device ({dev}), there is no CPU fallback")
+        return _aligned(p)
+
+    def _tables(self, dev):
+        """The tensors behind each pointer table the run entry takes after the kind (None: a NULL table)."""
+        return [[self._checked(name, p, dev) for name, c in zip(self._names, self._convs) for p in (c.weight, c.bias)]]
+
+    def workspace_bytes(self, N, H, W):
+        return nbytes(_lib.get(), f"{self.ENTRIES}_bytes", int(N), int(H), int(W), self.kind)
+
+    def __call__(self, image):
+        what = type(self).__name__
+        N, _, H, W = _map(image, "the image", what, 3)
+        _on_device(image, what)
+        dev = image.device
+        tensors = self._tables(dev)
+        size = self.workspace_bytes(N, H, W)
+        ws = self._ws.of((N, H, W), dev, lambda: Workspaces.bytes(dev, size))
+        while len(self._ws) > self.MAX_WORKSPACES:  # (the allocator frees in stream order: a launch in flight keeps its memory)
+            del self._ws[next(k for k, v in self._ws.items() if v is not ws)]
+        x = _aligned(image)
+        h, w = H, W
+        for _ in range(3):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        out = torch.empty((N, self.channels, h, w), dtype=torch.float32, device=dev)
+        tables = [None if t is None else (ctypes.c_void_p * len(t))(*(p.data_ptr() for p in t)) for t in tensors]
+        call(f"eogs_{self.ENTRIES}_run", dev, N, H, W, self.kind, *tables, x.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr())
+        return out
+
+
+class FusedEncoder(_FusedEncoder):
     """One of RAFT-small's two encoders (a `FeatureEncoder` of bottleneck blocks, widths 32, 32, 64, 96, with InstanceNorm2d and
     a 128-channel head, or without a norm and a 160-channel head) as one call: `fused(image [N, 3, H, W]) -> [N, C, h, w]`,
     what the module's forward returns. It holds the module, not a copy of its weights: they are repacked at every call, so
     edited or reloaded weights can never go stale. It is no nn.Module and registers nothing. It keeps its workspace between
-    calls, one per (device, stream, image shape) and at most MAX_WORKSPACES of them: a workspace is 144 MB per image at 1024^2
-    and 575 MB at 2048^2, so a caller whose image sizes vary must not collect one per size; the one least recently made is
+    calls, one per (device, stream, image shape) and at most MAX_WORKSPACES of them: a workspace is 144 MB (feature) or 109 MB
+    (context, which has no norm tables to keep) per image at 1024^2 and 575 or 437 MB at 2048^2, so a caller whose image sizes vary must not collect one per size; the one least recently made is
     dropped. Float32 on the GPU, forward only."""
 
     WIDTHS = (32, 32, 64, 96)
-    MAX_WORKSPACES = 2
+    ENTRIES = "flowenc"
 
     def __init__(self, encoder_module):
         what = "raft FusedEncoder"
@@ -657,45 +659,6 @@ class FusedEncoder:
         self._names, self._convs, self.kind, self.channels = tuple(names), convs, FLOWENC_FEATURE if normed else FLOWENC_CONTEXT, shapes[-1][0]
         self._ws = Workspaces()
 
-    def __getstate__(self):  # a copied or pickled module starts without workspaces
-        return {"_names": self._names, "_convs": self._convs, "kind": self.kind, "channels": self.channels}
-
-    def __setstate__(self, state):
-        self.__dict__.update(state)
-        self._ws = Workspaces()
-
-    def _params(self, dev):
-        out = []
-        for name, c in zip(self._names, self._convs):
-            for p in (c.weight, c.bias):
-                if p.dtype != torch.float32 or p.device != dev:
-                    raise RuntimeError(f"raft FusedEncoder: {name} is {p.dtype} on {p.device}; the fused encoder runs in float32 on "
-                                       f"the image's device ({dev}), there is no CPU fallback")
-                out.append(_aligned(p))
-        return out
-
-    def workspace_bytes(self, N, H, W):
-        return nbytes(_lib.get(), "flowenc_bytes", int(N), int(H), int(W), self.kind)
-
-    def __call__(self, image):
-        what = "FusedEncoder"
-        N, _, H, W = _map(image, "the image", what, 3)
-        _on_device(image, what)
-        dev = image.device
-        params = self._params(dev)
-        size = self.workspace_bytes(N, H, W)
-        ws = self._ws.of((N, H, W), dev, lambda: Workspaces.bytes(dev, size))
-        while len(self._ws) > self.MAX_WORKSPACES:  # (the allocator frees in stream order: a launch in flight keeps its memory)
-            del self._ws[next(k for k, v in self._ws.items() if v is not ws)]
-        x = _aligned(image)
-        h, w = H, W
-        for _ in range(3):
-            h, w = (h + 1) // 2, (w + 1) // 2
-        out = torch.empty((N, self.channels, h, w), dtype=torch.float32, device=dev)
-        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
-        call("eogs_flowenc_run", dev, N, H, W, self.kind, table, x.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr())
-        return out
-
 
 # ---- RAFT-large's encoders (eogs_flowres_*) ----
 
@@ -730,7 +693,7 @@ def fold_batchnorm(weight, bias, gamma, beta, mean, var, eps=1e-5):
     return w_out, b_out
 
 
-class FusedEncoderLarge:
+class FusedEncoderLarge(_FusedEncoder):
     """One of RAFT-large's two encoders (a `FeatureEncoder` of residual blocks, widths 64, 64, 96, 128, a 256-channel head, with
     InstanceNorm2d or with BatchNorm2d in eval mode) as one call: `fused(image [N, 3, H, W]) -> [N, 256, h, w]`, what the
     module's forward returns. It holds the module, not copies: weights, biases and the batch norms' parameters and running
@@ -743,7 +706,7 @@ class FusedEncoderLarge:
 
     WIDTHS = (64, 64, 96, 128)
     HEAD = 256
-    MAX_WORKSPACES = 2
+    ENTRIES = "flowres"
 
     def __init__(self, encoder_module):
         what = "raft FusedEncoderLarge"
@@ -798,22 +761,9 @@ class FusedEncoderLarge:
         self.kind, self.channels = FLOWENC_FEATURE if instance else FLOWENC_CONTEXT, self.HEAD
         self._ws = Workspaces()
 
-    def __getstate__(self):  # a copied or pickled module starts without workspaces
-        return {"_names": self._names, "_convs": self._convs, "_norms": self._norms, "kind": self.kind, "channels": self.channels}
-
-    def __setstate__(self, state):
-        self.__dict__.update(state)
-        self._ws = Workspaces()
-
-    @staticmethod
-    def _checked(name, p, dev):
-        if p.dtype != torch.float32 or p.device != dev:
-            raise RuntimeError(f"raft FusedEncoderLarge: {name} is {p.dtype} on {p.device}; the fused encoder runs in float32 on "
-                               f"the image's device ({dev}), there is no CPU fallback")
-        return _aligned(p)
-
-    def _params(self, dev):
-        return [self._checked(name, p, dev) for name, c in zip(self._names, self._convs) for p in (c.weight, c.bias)]
+    def _tables(self, dev):  # (the batch norms first: a training-mode one is refused before anything else)
+        bn = self._bn(dev)
+        return super()._tables(dev) + [bn]
 
     def _bn(self, dev):
         if self._norms is None:
@@ -825,30 +775,6 @@ class FusedEncoderLarge:
                 raise RuntimeError(f"raft FusedEncoderLarge: {unit} is in training mode; the fused encoder folds the running statistics "
                                    "(eval mode), batch statistics are not what it computes")
             out += [self._checked(unit, p, dev) for p in (m.weight, m.bias, m.running_mean, m.running_var)]
-        return out
-
-    def workspace_bytes(self, N, H, W):
-        return nbytes(_lib.get(), "flowres_bytes", int(N), int(H), int(W), self.kind)
-
-    def __call__(self, image):
-        what = "FusedEncoderLarge"
-        N, _, H, W = _map(image, "the image", what, 3)
-        _on_device(image, what)
-        dev = image.device
-        bn = self._bn(dev)
-        params = self._params(dev)
-        size = self.workspace_bytes(N, H, W)
-        ws = self._ws.of((N, H, W), dev, lambda: Workspaces.bytes(dev, size))
-        while len(self._ws) > self.MAX_WORKSPACES:  # (the allocator frees in stream order: a launch in flight keeps its memory)
-            del self._ws[next(k for k, v in self._ws.items() if v is not ws)]
-        x = _aligned(image)
-        h, w = H, W
-        for _ in range(3):
-            h, w = (h + 1) // 2, (w + 1) // 2
-        out = torch.empty((N, self.channels, h, w), dtype=torch.float32, device=dev)
-        table = (ctypes.c_void_p * len(params))(*(p.data_ptr() for p in params))
-        bn_table = None if bn is None else (ctypes.c_void_p * len(bn))(*(p.data_ptr() for p in bn))
-        call("eogs_flowres_run", dev, N, H, W, self.kind, table, bn_table, x.data_ptr(), ws.data_ptr(), ws.numel(), out.data_ptr())
         return out
 
 
@@ -1140,10 +1066,15 @@ class RAFT(nn.Module):
         recurrent = RecurrentBlock(motion.out_channels + self.context_size, hidden, cfg["gru_kernels"], cfg["gru_paddings"])
         self.update_block = UpdateBlock(motion, recurrent, FlowHead(hidden, cfg["flow_head_hidden"]))
         self.mask_predictor = None if cfg["mask_hidden"] is None else MaskPredictor(hidden, cfg["mask_hidden"])
-        self._fused = FusedUpdate(self.update_block) if name == "small" else None  # (no Module: nothing is registered)
-        self._fused_enc = (FusedEncoder(self.feature_encoder), FusedEncoder(self.context_encoder)) if name == "small" else None
-        self._fused_large = FusedUpdateLarge(self.update_block, self.mask_predictor) if name == "large" else None
-        self._fused_enc_large = (FusedEncoderLarge(self.feature_encoder), FusedEncoderLarge(self.context_encoder)) if name == "large" else None
+        # this configuration's fused update and pair of fused encoders, under its size's names; the other size's stay None
+        # (no Modules: nothing is registered)
+        self._fused = self._fused_enc = self._fused_large = self._fused_enc_large = None
+        if name == "small":
+            self._fused = FusedUpdate(self.update_block)
+            self._fused_enc = (FusedEncoder(self.feature_encoder), FusedEncoder(self.context_encoder))
+        else:
+            self._fused_large = FusedUpdateLarge(self.update_block, self.mask_predictor)
+            self._fused_enc_large = (FusedEncoderLarge(self.feature_encoder), FusedEncoderLarge(self.context_encoder))
 
     def _ondemand(self, x):
         if self.corr == "volume":
@@ -1154,37 +1085,26 @@ class RAFT(nn.Module):
                                "there is no CPU fallback, corr='volume' is the plain torch form")
         return ok
 
-    def _fused_update(self, x):
-        if self.update == "fused_large":  # (never under "auto": AUTO_UPDATE_LARGE_IS_FUSED)
-            if self._fused_large is None:
-                raise ValueError(f"raft RAFT: update='fused_large' is RAFT-large's update block; '{self.name}' runs update='torch' or 'fused'")
-            if x.device.type != "cuda" or x.dtype != torch.float32:
-                raise RuntimeError(f"raft RAFT: update='fused_large' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
-                                   "there is no CPU fallback, update='torch' is the plain torch form")
-            return True
-        if self.update == "torch" or self._fused is None:
+    def _runs_fused(self, option, noun, auto_is_fused, x):
+        """Whether `option` ("update" or "encoder", RAFT-large's `noun`) runs its fused form on `x`. "fused_large" is never chosen
+        under "auto" (AUTO_UPDATE_LARGE_IS_FUSED, AUTO_ENCODER_LARGE_IS_FUSED); the constructor refuses the other size's value,
+        the option reassigned afterwards gets here."""
+        value = getattr(self, option)
+        if value == "fused_large" and self.name != "large":
+            raise ValueError(f"raft RAFT: {option}='fused_large' is RAFT-large's {noun}; '{self.name}' runs {option}='torch' or 'fused'")
+        if value == "torch" or (value != "fused_large" and self.name != "small"):
             return False
-        ok = x.device.type == "cuda" and x.dtype == torch.float32
-        if self.update == "fused" and not ok:
-            raise RuntimeError(f"raft RAFT: update='fused' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
-                               "there is no CPU fallback, update='torch' is the plain torch form")
-        return ok and (self.update == "fused" or (AUTO_UPDATE_IS_FUSED and not torch.is_grad_enabled()))
+        ok, asked = x.device.type == "cuda" and x.dtype == torch.float32, value in ("fused", "fused_large")
+        if asked and not ok:
+            raise RuntimeError(f"raft RAFT: {option}='{value}' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
+                               f"there is no CPU fallback, {option}='torch' is the plain torch form")
+        return ok and (asked or (auto_is_fused and not torch.is_grad_enabled()))
+
+    def _fused_update(self, x):
+        return self._runs_fused("update", "update block", AUTO_UPDATE_IS_FUSED, x)
 
     def _fused_encoder(self, x):
-        if self.encoder == "fused_large":  # (never under "auto": AUTO_ENCODER_LARGE_IS_FUSED)
-            if self._fused_enc_large is None:  # (the constructor refuses it; `model.encoder` reassigned afterwards gets here)
-                raise ValueError(f"raft RAFT: encoder='fused_large' is RAFT-large's encoders; '{self.name}' runs encoder='torch' or 'fused'")
-            if x.device.type != "cuda" or x.dtype != torch.float32:
-                raise RuntimeError(f"raft RAFT: encoder='fused_large' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
-                                   "there is no CPU fallback, encoder='torch' is the plain torch form")
-            return True
-        if self.encoder == "torch" or self._fused_enc is None:
-            return False
-        ok = x.device.type == "cuda" and x.dtype == torch.float32
-        if self.encoder == "fused" and not ok:
-            raise RuntimeError(f"raft RAFT: encoder='fused' runs in float32 on the GPU only (got {x.dtype} on '{x.device.type}'); "
-                               "there is no CPU fallback, encoder='torch' is the plain torch form")
-        return ok and (self.encoder == "fused" or (AUTO_ENCODER_IS_FUSED and not torch.is_grad_enabled()))
+        return self._runs_fused("encoder", "encoders", AUTO_ENCODER_IS_FUSED, x)
 
     def forward(self, image1, image2, num_flow_updates=12, return_all=False):
         N, _, H, W = image1.shape
@@ -1199,7 +1119,7 @@ class RAFT(nn.Module):
                              "encoder downsamples by 8 and the correlation pyramid by another 8")
         ondemand, fused, fused_enc = self._ondemand(image1), self._fused_update(image1), self._fused_encoder(image1)
         if fused_enc:
-            feature_encoder, context_encoder = self._fused_enc_large if self.encoder == "fused_large" else self._fused_enc
+            feature_encoder, context_encoder = self._fused_enc or self._fused_enc_large
         else:
             feature_encoder, context_encoder = self.feature_encoder, self.context_encoder
         fmaps = feature_encoder(torch.cat([image1, image2], dim=0))
@@ -1216,7 +1136,7 @@ class RAFT(nn.Module):
                                 torch.arange(w, dtype=image1.dtype, device=image1.device), indexing="ij")
         coords0 = torch.stack([xs, ys], dim=0)[None].repeat(N, 1, 1, 1)
         coords1 = coords0.clone()
-        fused_update = self._fused_large if self.update == "fused_large" else self._fused
+        fused_update = self._fused or self._fused_large
         if fused:
             fused_update.begin(hidden_state, context)
         flows = []

@@ -2,7 +2,8 @@
 RAFT(encoder="fused") over eogs2_amd/csrc/flowenc.hip) against the float64 oracle of tests/flowenc_cases.py: every convolution of
 RAFT-small's two encoders per element under the bound of a float32 fma sum, the statistics and the pointwise pass under
 theirs, exact cases bit for bit, a block, an encoder and the whole network against their float64 runs with torch's float32
-modules as the yardstick, and the network behind performOpticalmatching."""
+modules as the yardstick, an encoder bit for bit against its chain written by hand, and the network behind
+performOpticalmatching."""
 import copy
 import ctypes
 
@@ -274,6 +275,22 @@ def fused_block(block, x, norm):
     return raft.conv2d_strided_cl(b, c3.weight, c3.bias, act="relu", res=res)
 
 
+def fused_encoder(enc, image, norm):
+    """A whole encoder over the wrappers, launch for launch what eogs_flowenc_run does: NCHW in and out."""
+    from eogs2_amd import raft
+
+    stem = enc.convnormrelu[0]
+    if norm:
+        r, t = raft.conv2d_strided_cl(image, stem.weight, stem.bias, stride=2, stats=True, in_nchw=True)
+        x = raft.finish_cl(r, t)
+    else:
+        x = raft.conv2d_strided_cl(image, stem.weight, stem.bias, stride=2, act="relu", in_nchw=True)
+    for layer in (enc.layer1, enc.layer2, enc.layer3):
+        for block in layer:
+            x = fused_block(block, x, norm)
+    return raft.conv2d_strided_cl(x, enc.conv.weight, enc.conv.bias, out_nchw=True)
+
+
 def report(name, got, t32, t64, margin=16):
     mine, theirs = float((got.double() - t64).abs().max()), float((t32.double() - t64).abs().max())
     print(f"{name}: |fused - f64| {mine:.3e}, |torch32 - f64| {theirs:.3e}, ratio {mine / max(theirs, 1e-300):.3f}, "
@@ -308,8 +325,9 @@ def test_a_block_against_its_float64_run(dev, kind, where):
 @pytest.mark.parametrize("kind", ["feature", "context"])
 @pytest.mark.parametrize("image", ec.ENCODER_IMAGES, ids=ids)
 def test_an_encoder_against_its_float64_run(dev, image, kind):
-    """FusedEncoder against the torch module in float32 and float64 (the same protocol and margin). The workspace is filled
-    with 0xFF between two calls: a call relies on nothing it did not write, and gives the same bits."""
+    """FusedEncoder against the torch module in float32 and float64 (the same protocol and margin), and bit for bit against the
+    chain written by hand through conv2d_strided_cl and finish_cl. The workspace is filled with 0xFF between two calls: a call
+    relies on nothing it did not write, and gives the same bits."""
     from eogs2_amd import raft
 
     torch.manual_seed(82)
@@ -326,8 +344,10 @@ def test_an_encoder_against_its_float64_run(dev, image, kind):
             ws.fill_(0xFF)
         again = fused(x)
         assert len(fused._ws) == 1
+        by_hand = fused_encoder(enc, x, kind == "feature")
         t32, t64 = enc(x), enc64(x.double())
     assert got.shape == t64.shape and got.is_contiguous() and torch.equal(got, again)
+    assert torch.equal(got, by_hand)
     report(f"encoder {kind} {image}", got, t32, t64)
 
 
